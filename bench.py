@@ -3,16 +3,23 @@
 sampling -> 10-iteration point-to-plane Huber dICP -> loss -> backward -> Adam) on
 synthetic 400x3360 radar scans against 20k-point lidar submaps.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE set) this process is a rank; started
    plainly with --gpus N > 1 it is the launcher: before any GPU call it spawns N fresh rank processes through
    ``python -m torch.distributed.run``, relays rank 0's JSON line and exits non-zero if any rank failed.)
 
-Prints ONE JSON line on rank 0 (contract: task prompt / DESIGN.md §6):
-  value      = whole-job scan-pairs/s, inputs resident in HBM before the timed region
-  roofline   = the brute-force NN kernel against the HBM roofline named by
-               BASELINE.json's north_star (plus the binding fp32 VALU roofline)
-  cpu_baseline = the oracle's CPU port of the same step on the host cores (rank 0, N=1)
+Prints ONE JSON line on rank 0 (contract: DESIGN.md §6):
+  value        = whole-job scan-pairs/s, inputs resident in HBM before the timed region
+  ms_per_step  = milliseconds of one timed step (the slowest rank's wall time / K)
+A plain run does only that: set up, settle + warm up, time K steps, write the outputs (--dump-outputs), print the line.
+With --full the line also carries what takes measurements of its own:
+  roofline     = the brute-force NN kernel against the HBM roofline named by
+                 BASELINE.json's north_star (plus the binding matrix-pipe roofline); per-launch events in the timed steps
+  host_enqueue_ms_per_step, conv_stack, roofline_grid, sparse_scene / dim3 / inference side lines
+  cpu_baseline = the oracle's CPU port of the same step on the host cores (rank 0, N=1), with the GPU-vs-oracle pose parity
+--dump-outputs DIR: what the last timed step returned to its caller, on rank 0, as DIR/<name>.npy (float32): the loss, its
+components, and the model's parameters and gradients after that step's Adam update.  The inputs and the number of steps
+before the last one depend on the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -362,6 +369,30 @@ def pose_parity(model, params, device, pairs=2):
             "pairs": pairs, "iters": ICP_ITERS}
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, model, loss, loss_comp):
+    """--dump-outputs: what the last timed step handed its caller -- train_step's loss and loss components, and the model it
+    updated in place (the parameters after Adam, the gradients the step computed) -- as DIR/<name>.npy in float32.  Returns
+    the bytes written (the model is 1.77 M parameters: 14 MB, under the 64 MB limit with room to spare)."""
+    arrays = {"loss": loss}
+    for k, v in loss_comp.items():
+        arrays["loss_comp." + k] = v
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    arrays = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -375,10 +406,16 @@ def main():
                     help="'polar' = the reference's network_input_type='polar' option (U-Net on the 400x3360 polar image, "
                          "SURVEY 8f.3): a side measurement, not the headline configuration")
     ap.add_argument("--settle", type=int, default=40, help="untimed settling steps before the warm-up (0 = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-grid", action="store_true", help="skip the side measurement of the exact grid NN engine")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the side measurements (sparse scenes, dim 3, inference)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: NN roofline (per-launch events in the timed steps), host "
+                         "enqueue cost, U-Net MFMA rate, grid NN engine, side lines, CPU baseline and pose parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, loss components, parameters and gradients after the "
+                         "update) as DIR/<name>.npy, float32, on rank 0")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-grid", action="store_true", help="(--full) skip the side measurement of the exact grid NN engine")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the pose parity against the CPU restatement")
+    ap.add_argument("--no-side", action="store_true", help="(--full) skip the side measurements (sparse scenes, dim 3, inference)")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N-rank code path whatever N is: a process group is initialised (RCCL for --gpus 1 too), the gradient "
                          "all-reduce(s) and the global min-max all-reduce are issued, the line carries the `ddp` block")
@@ -388,6 +425,8 @@ def main():
     ap.add_argument("--local-minmax", action="store_true",
                     help="(diagnostic) keep the min-max normalisation per rank in a --force-dist / N-rank run: no collective in the forward pass")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(sys.argv[1:], args.gpus))
@@ -463,23 +502,15 @@ def main():
             torch.cuda.synchronize(device)
 
     # Untimed settling before the warm-up proper (a guard against start-up transients: allocator growth,
-    # code-object loading): run until five consecutive steps are within 10 % of the fastest step seen,
-    # at most `--settle` steps.
+    # code-object loading): `--settle` steps (at most 25 with more than one rank), each waited for.  The count is
+    # fixed, not adaptive: every step trains the model, so the state the last timed step starts from -- what
+    # --dump-outputs compares -- must depend on the arguments alone.
     if args.settle > 0:
-        progress("settling (untimed, at most %d steps)" % args.settle)
-        best, streak = float("inf"), 0
-        # (with more than one rank every step holds a collective: all ranks must run the same number of
-        # steps, so the count is fixed there instead of adaptive)
         n_settle = args.settle if not dist_on else min(args.settle, 25)
+        progress("settling (untimed, %d steps)" % n_settle)
         for i in range(n_settle):
-            t_s = time.perf_counter()
             one_step(i)
             torch.cuda.synchronize(device)
-            d_s = time.perf_counter() - t_s
-            best = min(best, d_s)
-            streak = streak + 1 if d_s <= 1.10 * best else 0
-            if not dist_on and i >= 5 and streak >= 5:
-                break
     import gc
     gc.collect()
     gc.freeze()      # keep the collector from re-scanning the long-lived objects inside the timed region
@@ -489,35 +520,46 @@ def main():
     fence()          # (nothing but this fence between the warm-up and the timed steps: an idle GPU drops its clocks)
     progress("timing %d steps" % args.steps)
     cap = args.steps * ICP_ITERS + 8
-    _lib.check(L.mmk_nn_profile_begin(cap))
+    if args.full:
+        _lib.check(L.mmk_nn_profile_begin(cap))        # per-launch events around the NN kernel: the roofline block
+        if sync is not None:
+            sync.timing, sync.exposed = [], []
     if sync is not None:
-        sync.timing, sync.exposed, sync.calls = [], [], 0
-    step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    ms0 = torch.cuda.memory_stats(device)
+        sync.calls = 0
+    step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
+    ms0 = torch.cuda.memory_stats(device) if args.full else None
     t0 = time.perf_counter()
-    step_ev[0].record()
+    if step_ev is not None:
+        step_ev[0].record()
     for i in range(args.steps):
-        loss, _ = one_step(args.warmup + i)
-        step_ev[i + 1].record()
+        loss, loss_comp = one_step(args.warmup + i)
+        if step_ev is not None:
+            step_ev[i + 1].record()
     host_dt = time.perf_counter() - t0        # host-side enqueue time (the GPU may still be running)
     fence()
     dt = time.perf_counter() - t0
-    per_step = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
-    progress("per-step GPU ms: " + " ".join("%.1f" % v for v in per_step))
-    progress("host time of the enqueue loop %.1f ms/step (with the launch queue full: it mostly waits for the GPU)" % (host_dt / args.steps * 1e3))
-    ms1 = torch.cuda.memory_stats(device)
-    progress("allocator during the timed region: %d device mallocs, %d frees, %d retries; reserved %.2f GiB" % (
-        ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0),
-        ms1.get("num_device_free", 0) - ms0.get("num_device_free", 0),
-        ms1.get("num_alloc_retries", 0) - ms0.get("num_alloc_retries", 0),
-        ms1.get("reserved_bytes.all.current", 0) / 2 ** 30))
-    ms = (ctypes.c_float * cap)()
-    n_rec = ctypes.c_int32(0)
-    _lib.check(L.mmk_nn_profile_end(ms, cap, ctypes.byref(n_rec)))
-    nn_ms = np.array(ms[:min(n_rec.value, cap)], dtype=np.float64)
+    if args.dump_outputs is not None and rank == 0:
+        # before anything else runs a step: the model holds what the last timed step left in it
+        n_bytes = dump_outputs(args.dump_outputs, model, loss, loss_comp)
+        progress("outputs of the last timed step: %.1f MB in %s" % (n_bytes / 1e6, args.dump_outputs))
+    nn_ms = None
+    if args.full:
+        per_step = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
+        progress("per-step GPU ms: " + " ".join("%.1f" % v for v in per_step))
+        progress("host time of the enqueue loop %.1f ms/step (with the launch queue full: it mostly waits for the GPU)" % (host_dt / args.steps * 1e3))
+        ms1 = torch.cuda.memory_stats(device)
+        progress("allocator during the timed region: %d device mallocs, %d frees, %d retries; reserved %.2f GiB" % (
+            ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0),
+            ms1.get("num_device_free", 0) - ms0.get("num_device_free", 0),
+            ms1.get("num_alloc_retries", 0) - ms0.get("num_alloc_retries", 0),
+            ms1.get("reserved_bytes.all.current", 0) / 2 ** 30))
+        ms = (ctypes.c_float * cap)()
+        n_rec = ctypes.c_int32(0)
+        _lib.check(L.mmk_nn_profile_end(ms, cap, ctypes.byref(n_rec)))
+        nn_ms = np.array(ms[:min(n_rec.value, cap)], dtype=np.float64)
     ddp_block = None
     if dist_on:
-        # what the process group saw, from the group itself: every rank contributes its own wall time and the mean
+        # what the process group saw, from the group itself: every rank contributes its own wall time and (--full) the mean
         # duration of its gradient all-reduces (events on the stream the collective is ordered on)
         ar_ms = [a.elapsed_time(b) for a, b in (sync.timing or [])]
         ex_ms = [a.elapsed_time(b) for a, b in (sync.exposed or [])]
@@ -532,91 +574,46 @@ def main():
         ddp_block = {"backend": dist.get_backend(), "world_size_seen": dist.get_world_size(), "rank_count_reporting": int(len(rows)),
                      "allreduce_bytes": sync.allreduce_bytes(), "allreduce_calls_per_step": per_step,
                      "overlap": bool(sync.overlap), "bucket_elements": [hi - lo for lo, hi in (sync.buckets_last or [])],
-                     "allreduce_ms": float(np.nanmean(rows[:, 1])), "allreduce_ms_max_over_ranks_and_steps": float(np.nanmax(rows[:, 2])),
-                     "allreduce_exposed_ms": None if np.isnan(rows[:, 3]).all() else float(np.nanmean(rows[:, 3])),
                      "ms_per_step_min_over_ranks": float(rows[:, 0].min()) / args.steps * 1e3,
                      "ms_per_step_max_over_ranks": float(rows[:, 0].max()) / args.steps * 1e3,
                      "devices_visible": torch.cuda.device_count(), "global_minmax": bool(getattr(model, "global_minmax", False)),
                      "note": "fp32 sum all-reduce of the U-Net backward's own gradient block (mm_masking_amd/ddp.py): with overlap in the three "
                              "buckets in which the backward completes it (decoder + final layer, encoder blocks 3-5, encoder blocks 0-2), each "
-                             "on a communication stream behind its own completion event; allreduce_ms = per-step sum of the event times "
-                             "around the collectives (mean over ranks; it includes waiting for the slowest rank), allreduce_exposed_ms = time "
-                             "the step's own stream waits for the communication stream before the optimizer (what the overlap leaves)"}
+                             "on a communication stream behind its own completion event"}
+        if args.full:
+            ddp_block.update({
+                "allreduce_ms": float(np.nanmean(rows[:, 1])), "allreduce_ms_max_over_ranks_and_steps": float(np.nanmax(rows[:, 2])),
+                "allreduce_exposed_ms": None if np.isnan(rows[:, 3]).all() else float(np.nanmean(rows[:, 3])),
+                "note": ddp_block["note"] + "; allreduce_ms = per-step sum of the event times around the collectives (mean over "
+                        "ranks; it includes waiting for the slowest rank), allreduce_exposed_ms = time the step's own stream waits for "
+                        "the communication stream before the optimizer (what the overlap leaves)"})
 
-    # host cost of enqueueing one step, measured with an EMPTY launch queue (synchronise, time the Python call, synchronise):
-    # inside the timed loop the host runs ahead until the queue is full and then waits for the GPU, so the loop's host
-    # time says nothing about the host's own cost
-    host_idle = []
-    for i in range(5):
+    host_ms = None
+    if args.full:
+        # host cost of enqueueing one step, measured with an EMPTY launch queue (synchronise, time the Python call, synchronise):
+        # inside the timed loop the host runs ahead until the queue is full and then waits for the GPU, so the loop's host
+        # time says nothing about the host's own cost
+        host_idle = []
+        for i in range(5):
+            torch.cuda.synchronize(device)
+            t_h = time.perf_counter()
+            one_step(args.warmup + args.steps + i)
+            host_idle.append(time.perf_counter() - t_h)
         torch.cuda.synchronize(device)
-        t_h = time.perf_counter()
-        one_step(args.warmup + args.steps + i)
-        host_idle.append(time.perf_counter() - t_h)
-    torch.cuda.synchronize(device)
-    host_ms = float(np.median(host_idle)) * 1e3
-    progress("host enqueue cost %.1f ms/step (empty queue, median of 5)" % host_ms)
+        host_ms = float(np.median(host_idle)) * 1e3
+        progress("host enqueue cost %.1f ms/step (empty queue, median of 5)" % host_ms)
     progress("timed region done: %.1f ms/step" % (dt / args.steps * 1e3))
-    if len(nn_ms) == args.steps * ICP_ITERS:
+    if nn_ms is not None and len(nn_ms) == args.steps * ICP_ITERS:
         by_it = nn_ms.reshape(args.steps, ICP_ITERS).mean(axis=0) * 1e3
         progress("NN launch us by ICP iteration: " + " ".join("%.0f" % v for v in by_it))
     result = None
     if rank == 0:
-        nn_avg_s = float(nn_ms.mean()) * 1e-3 if len(nn_ms) else float("nan")
-        # frozen pairs (||delta|| < tolerance) skip the NN kernel: price a launch by the pairs that ran
-        active_pairs = float(B)
-        from mm_masking_amd.dICP.ICP import _IcpFunction
-        if _IcpFunction.last_active is not None:
-            act = _IcpFunction.last_active[:ICP_ITERS].float().sum(dim=1)       # (K,): active pairs per launch, last step
-            active_pairs = float(act.mean().item())
-        alg_bytes = nn_algorithmic_bytes(1) * active_pairs
-        achieved = alg_bytes / nn_avg_s / 1e9
-        # source rows a launch actually scans: blocks of 512 all-zero padding rows behind a pair's first zero row take that
-        # row's result instead (csrc/mmk_icp.hip: src_zero_scan_kernel) -- the evaluation count follows the rows scanned
-        scanned = float(N_PAD)
-        if model.ICP_alg.nn_search == "brute":
-            src_pts = trn.prepare_batch(raws[0], params, max_loc_pts=N_PAD)["loc_data"]["filtered_pc"]
-            zero = (src_pts == 0).all(dim=-1)                                     # (B,N)
-            first_zero = torch.where(zero.any(dim=1), zero.float().argmax(dim=1), torch.full((B,), N_PAD, device=device))
-            blk_zero = zero.view(B, N_PAD // 512, 512).all(dim=2)
-            starts = torch.arange(0, N_PAD, 512, device=device).view(1, -1)
-            skipped = blk_zero & (first_zero.view(-1, 1) < starts)
-            scanned = float((N_PAD - 512 * skipped.sum(dim=1)).float().mean().item())
-        evals = active_pairs * scanned * M_PAD       # distance evaluations per launch
-        # HBM bytes per launch from the PMC counters: NOT measured in this run -- read from a committed file that a separate
-        # rocprofv3 --pmc pass over the dICP alone wrote (scripts/pmc_nn.sh -> profiles/r05_nn_traffic.json, FETCH_SIZE and
-        # WRITE_SIZE in passes of their own, FETCH_SIZE doubled per the gfx950 correction); null when no such file exists.
-        # `traffic_source` says so in the line itself.
-        traffic, traffic_source = None, None
-        for name in ("r05_nn_traffic.json", "r04_nn_traffic.json", "r03_nn_traffic.json", "r02_nn_traffic.json"):
-            tr_file = os.path.join(ROOT, "profiles", name)
-            if os.path.exists(tr_file) and model.ICP_alg.nn_search == "brute":
-                tj = json.load(open(tr_file))
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_source = ("committed PMC pass profiles/%s (dICP alone, %s us per launch there, scene density %s); not "
-                                  "collected in this run" % (name, tj.get("avg_launch_us", "?"), tj.get("density", "sparse (round 2)")))
-                break
         valid = valid_scan_points(trn.prepare_batch(raws[0], params, max_loc_pts=N_PAD))
-        # bytes a launch actually reads + writes: the scanned source rows (x,y), the target planes, one (idx, d2) per row
-        alg_bytes_read = active_pairs * (4 * DIM * scanned + 4 * DIM * M_PAD + 8 * N_PAD)
-        if model.ICP_alg.nn_search == "grid":
-            nn_kernel = "grid_nn_kernel<2>"
-        else:
-            nn_kernel = "nn_mfma_kernel<2>"
-        # every pair is one element of a v_mfma_f32_32x32x16_bf16 result tile: 1 024 pairs per instruction, one instruction
-        # per 32 cycles and SIMD (MI355X_MICROARCH.md, cycle constants), 1 024 SIMDs at 2.4 GHz
-        peak_pairs = 1024 * 1024 / 32.0 * 2.4e9
-        binding = {"pipe": "bf16 matrix cores (pair pricing) + fp32 VALU (chunk minima, exact re-scan)",
-                   "pair_evals_per_s": evals / nn_avg_s, "peak_pair_evals_per_s": peak_pairs,
-                   "frac": evals / nn_avg_s / peak_pairs,
-                   "equivalent_dense_bf16_tflops": evals / nn_avg_s * 32 / 1e12,
-                   "note": "16 k-slots (2 x 16 flop) per pair: exact three-way bf16 splits of -2p, t and |t|^2, fp32 accumulation; "
-                           "1.1 vector instructions per 64 pairs beside the MFMAs (profiles/r05_nn_pmc_counters.json; the fp32 VALU "
-                           "kernel of rounds 1-2, removed in round 5, issued 3.3)"}
         result = {
             "metric": "scan-pairs/s (mask-CNN + 10-iter dICP fwd+bwd)", "value": B * world * args.steps / dt,
             "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic", "host_enqueue_ms_per_step": host_ms,
+            "dtype": "bf16", "data": "synthetic",
             "config": {"workload": ("BASELINE configs[2]: train_icp_weights step fwd+bwd, batch=%d per GPU, 10 dICP "
                                     "iters, point-to-plane Huber, dim=2; 400x3360 polar radar -> GO-CFAR + peaks + "
                                     "polar->Cartesian 640x640 -> U-Net (hand-written NHWC bf16 MFMA kernels, fp32 masters) -> dICP (fp32 points, "
@@ -628,30 +625,82 @@ def main():
                        "scene_density": "survey (SURVEY.md 8d: 3 500-5 000 valid scan points of 5 120)",
                        "scan_pts_valid_mean": float(valid.mean()), "scan_pts_valid_min": float(valid.min()),
                        "scan_pts_valid_max": float(valid.max()),
-                       "final_loss": float(loss)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": nn_kernel,
-                         "nn_engine": model.ICP_alg.nn_search, "launches_timed": int(len(nn_ms)),
-                         "avg_launch_us": nn_avg_s * 1e6, "algorithmic_bytes_per_launch": alg_bytes,
-                         "algorithmic_bytes_rows_read_per_launch": alg_bytes_read,
-                         "achieved_rows_read": alg_bytes_read / nn_avg_s / 1e9,
-                         "active_pairs_per_launch": active_pairs, "source_rows_scanned_per_pair": scanned,
-                         "note": "north_star names the HBM roofline; brute force does %.3g distance evaluations per "
-                                 "launch over those bytes (~2.2 kFLOP/B), so what binds is the arithmetic pipe that prices the "
-                                 "pairs, not HBM" % evals,
-                         "binding": binding},
+                       "final_loss": float(loss)}
         }
+        if args.full:
+            nn_avg_s = float(nn_ms.mean()) * 1e-3 if len(nn_ms) else float("nan")
+            # frozen pairs (||delta|| < tolerance) skip the NN kernel: price a launch by the pairs that ran
+            active_pairs = float(B)
+            from mm_masking_amd.dICP.ICP import _IcpFunction
+            if _IcpFunction.last_active is not None:
+                act = _IcpFunction.last_active[:ICP_ITERS].float().sum(dim=1)       # (K,): active pairs per launch, last step
+                active_pairs = float(act.mean().item())
+            alg_bytes = nn_algorithmic_bytes(1) * active_pairs
+            achieved = alg_bytes / nn_avg_s / 1e9
+            # source rows a launch actually scans: blocks of 512 all-zero padding rows behind a pair's first zero row take that
+            # row's result instead (csrc/mmk_icp.hip: src_zero_scan_kernel) -- the evaluation count follows the rows scanned
+            scanned = float(N_PAD)
+            if model.ICP_alg.nn_search == "brute":
+                src_pts = trn.prepare_batch(raws[0], params, max_loc_pts=N_PAD)["loc_data"]["filtered_pc"]
+                zero = (src_pts == 0).all(dim=-1)                                     # (B,N)
+                first_zero = torch.where(zero.any(dim=1), zero.float().argmax(dim=1), torch.full((B,), N_PAD, device=device))
+                blk_zero = zero.view(B, N_PAD // 512, 512).all(dim=2)
+                starts = torch.arange(0, N_PAD, 512, device=device).view(1, -1)
+                skipped = blk_zero & (first_zero.view(-1, 1) < starts)
+                scanned = float((N_PAD - 512 * skipped.sum(dim=1)).float().mean().item())
+            evals = active_pairs * scanned * M_PAD       # distance evaluations per launch
+            # HBM bytes per launch from the PMC counters: NOT measured in this run -- read from a committed file that a separate
+            # rocprofv3 --pmc pass over the dICP alone wrote (scripts/pmc_nn.sh -> profiles/r05_nn_traffic.json, FETCH_SIZE and
+            # WRITE_SIZE in passes of their own, FETCH_SIZE doubled per the gfx950 correction); null when no such file exists.
+            # `traffic_source` says so in the line itself.
+            traffic, traffic_source = None, None
+            for name in ("r05_nn_traffic.json", "r04_nn_traffic.json", "r03_nn_traffic.json", "r02_nn_traffic.json"):
+                tr_file = os.path.join(ROOT, "profiles", name)
+                if os.path.exists(tr_file) and model.ICP_alg.nn_search == "brute":
+                    tj = json.load(open(tr_file))
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    traffic_source = ("committed PMC pass profiles/%s (dICP alone, %s us per launch there, scene density %s); not "
+                                      "collected in this run" % (name, tj.get("avg_launch_us", "?"), tj.get("density", "sparse (round 2)")))
+                    break
+            # bytes a launch actually reads + writes: the scanned source rows (x,y), the target planes, one (idx, d2) per row
+            alg_bytes_read = active_pairs * (4 * DIM * scanned + 4 * DIM * M_PAD + 8 * N_PAD)
+            if model.ICP_alg.nn_search == "grid":
+                nn_kernel = "grid_nn_kernel<2>"
+            else:
+                nn_kernel = "nn_mfma_kernel<2>"
+            # every pair is one element of a v_mfma_f32_32x32x16_bf16 result tile: 1 024 pairs per instruction, one instruction
+            # per 32 cycles and SIMD (MI355X_MICROARCH.md, cycle constants), 1 024 SIMDs at 2.4 GHz
+            peak_pairs = 1024 * 1024 / 32.0 * 2.4e9
+            binding = {"pipe": "bf16 matrix cores (pair pricing) + fp32 VALU (chunk minima, exact re-scan)",
+                       "pair_evals_per_s": evals / nn_avg_s, "peak_pair_evals_per_s": peak_pairs,
+                       "frac": evals / nn_avg_s / peak_pairs,
+                       "equivalent_dense_bf16_tflops": evals / nn_avg_s * 32 / 1e12,
+                       "note": "16 k-slots (2 x 16 flop) per pair: exact three-way bf16 splits of -2p, t and |t|^2, fp32 accumulation; "
+                               "1.1 vector instructions per 64 pairs beside the MFMAs (profiles/r05_nn_pmc_counters.json; the fp32 VALU "
+                               "kernel of rounds 1-2, removed in round 5, issued 3.3)"}
+            result["host_enqueue_ms_per_step"] = host_ms
+            result["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                                  "kernel": nn_kernel,
+                                  "nn_engine": model.ICP_alg.nn_search, "launches_timed": int(len(nn_ms)),
+                                  "avg_launch_us": nn_avg_s * 1e6, "algorithmic_bytes_per_launch": alg_bytes,
+                                  "algorithmic_bytes_rows_read_per_launch": alg_bytes_read,
+                                  "achieved_rows_read": alg_bytes_read / nn_avg_s / 1e9,
+                                  "active_pairs_per_launch": active_pairs, "source_rows_scanned_per_pair": scanned,
+                                  "note": "north_star names the HBM roofline; brute force does %.3g distance evaluations per "
+                                          "launch over those bytes (~2.2 kFLOP/B), so what binds is the arithmetic pipe that prices the "
+                                          "pairs, not HBM" % evals,
+                                  "binding": binding}
         if ddp_block is not None:
             result["ddp"] = ddp_block
-        if world == 1:
+        if args.full and world == 1:
             result["conv_stack"] = conv_stack_rate(model, raws[0], params, device)
             if model.ICP_alg.nn_search == "brute" and not args.no_grid:
                 result["roofline_grid"] = grid_engine_block(model, one_step, args.warmup + args.steps, B, L)
             if not args.no_side and not polar:
                 progress("side measurements: sparse scenes, dim 3, inference")
                 result.update(side_blocks(model, opt, lw, params, device, B))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(params)
             if not args.no_parity:
                 progress("cpu_baseline: pose parity of the GPU dICP vs the CPU restatement")

@@ -4,7 +4,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 REPS=$1; shift
-FLAGS="--steps 20 --warmup 3 --no-side --no-cpu-baseline --no-grid --no-parity"
+FLAGS="--full --steps 20 --warmup 3 --no-side --no-cpu-baseline --no-grid --no-parity"
 for rep in $(seq 1 $REPS); do
   for spec in "$@"; do
     tag=${spec%%:*}; envs=${spec#*:}

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 OTHER=${1:-build_exp/prev}
 TA=${2:-prev}
 TB=${3:-this}
-FLAGS="--steps 20 --warmup 3 --no-side --no-cpu-baseline --no-grid --no-parity"
+FLAGS="--full --steps 20 --warmup 3 --no-side --no-cpu-baseline --no-grid --no-parity"
 for rep in 1 2 3; do
   (cd $OTHER && python3 bench.py $FLAGS 2>/dev/null) > gpurun_out/ab_round_${TA}_$rep.json || exit 1
   python3 bench.py $FLAGS 2>/dev/null > gpurun_out/ab_round_${TB}_$rep.json || exit 1

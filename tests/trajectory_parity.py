@@ -18,6 +18,12 @@ from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
 from oracle import dicp_ref, train_ref, unet_ref
 
 LOSS_FN = {"name": "huber", "metric": 1.0}
+# Intra-op threads of the fp32 CPU side while it runs: 8, the reference's own OMP_NUM_THREADS.  torch's CPU
+# kernels split their sums by the thread count, and with norm_weights=True the oracle's gradient is dominated by a cancellation
+# (DESIGN.md §6c), so its trajectory -- the distance its parameters move -- follows the summation order: on one host 16 threads
+# gave a distance ratio of 0.934 and 8 threads 0.999 against the same (bit-reproducible) HIP run.  A fixed count makes the
+# comparison independent of how many cores the machine running the suite happens to grant.
+ORACLE_THREADS = 8
 
 
 def _thin(batch, raw, stride):
@@ -34,7 +40,16 @@ def _cpu_batch(batch):
             "T_init": batch["transforms"]["T_ml_init"].cpu(), "T_gt": batch["transforms"]["T_ml_gt"].cpu()}
 
 
-def run(dev, steps=30, B=4, stride=8, m_valid=2000, m_pad=2048, n_batches=3, norm_weights=True, seed=4321, first=8000,
+def run(dev, *args, **kw):
+    threads_was = torch.get_num_threads()
+    torch.set_num_threads(ORACLE_THREADS)
+    try:
+        return _run(dev, *args, **kw)
+    finally:
+        torch.set_num_threads(threads_was)
+
+
+def _run(dev, steps=30, B=4, stride=8, m_valid=2000, m_pad=2048, n_batches=3, norm_weights=True, seed=4321, first=8000,
         max_iter=10, log=None):
     params = trn.default_params(dev)
     params.update({"dropout": 0.0, "icp_type": "pt2pl", "icp_loss_fn": LOSS_FN, "max_iter": max_iter,
