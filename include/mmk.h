@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 500 /* 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 501 /* 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -159,6 +159,30 @@ int mmk_bce_mean_fwd(const float *x, const float *target, int64_t n, void *ws, s
                      float *out, void *stream);
 int mmk_bce_mean_bwd(const float *x, const float *target, int64_t n, const float *grad_out,
                      float *grad_x, void *stream);
+
+/* Pose terms against a ground-truth pose (gt_eye=False, :192-200): xi = T_pred T_gt^-1 - I, evaluated as (T_pred - T_gt) T_gt^-1
+ * in fp64 with a general 4x4 inverse per pair (Gauss-Jordan, partial pivoting; poses read from data are not exactly orthonormal);
+ * a singular T_gt gives inf / NaN.  mmk_pose_loss_gt_fwd: out2 = (mean_b |xi[1,0]|, mean_b ||(xi[0,3], xi[1,3])||).
+ * _bwd: grad_T (B,16) = G T_gt^-T, G nonzero only at [1,0] (sign(xi[1,0]) g_rot / B) and [0,3], [1,3] ((x, y) / norm g_trans / B,
+ * zero where the norm is zero); g_rot / g_trans DEVICE scalars (NULL = 0).  T_gt gets no gradient.
+ * mmk_val_metric: out3 = (mean_b ||(xi[1,0], xi[0,3], xi[1,3])||, mean_b |xi[1,0]|, mean_b ||(xi[0,3], xi[1,3])||), the 3-vector
+ *   of eval_validation_loss (:255-273); T_gt NULL = the identity (xi = T_pred - I).
+ * FFT-threshold mask term (:204-207): target = fft > 3 * mean_{H,W}(fft) per image, the mean an ordered fp64 reduction rounded
+ * to fp32 and the threshold the fp32 product 3.0f * mean.  fft is (B, hw), hw >= 4; ws = mmk_fft_threshold_ws_bytes(B) bytes.
+ * mmk_fft_threshold_mask writes the 0/1 target (generate_baseline, :312-316).  mmk_bce_fft_threshold_fwd / _bwd: the BCE of
+ *   mmk_bce_mean_* against that target computed on the fly (no target is written), the same bits as mmk_bce_mean_* on the mask
+ *   mmk_fft_threshold_mask writes; _fwd also writes the B thresholds to thr_out, which _bwd reads.  16-byte aligned buffers. */
+int mmk_pose_loss_gt_fwd(const float *T_pred /*B,16*/, const float *T_gt /*B,16*/, int32_t B, float *out2, void *stream);
+int mmk_pose_loss_gt_bwd(const float *T_pred, const float *T_gt, int32_t B, const float *g_rot, const float *g_trans,
+                         float *grad_T /*B,16*/, void *stream);
+int mmk_val_metric(const float *T_pred /*B,16*/, const float *T_gt /*B,16 or NULL*/, int32_t B, float *out3, void *stream);
+size_t mmk_fft_threshold_ws_bytes(int32_t B);
+int mmk_fft_threshold_mask(const float *fft, int32_t B, int64_t hw, void *ws, size_t ws_bytes, float *mask_out,
+                           void *stream);
+int mmk_bce_fft_threshold_fwd(const float *x, const float *fft, int32_t B, int64_t hw, void *ws, size_t ws_bytes,
+                              float *thr_out /*B*/, float *out, void *stream);
+int mmk_bce_fft_threshold_bwd(const float *x, const float *fft, int32_t B, int64_t hw, const float *thr /*B*/,
+                              const float *grad_out, float *grad_x, void *stream);
 
 /* ------------------------------------------------------------------ radar_utils.py
  * mmk_cfar_mask        <- cfar_mask                      radar_utils.py:29-69
@@ -365,6 +389,11 @@ int mmk_conv3x3_wgrad_unpack_batch(int32_t n, const float *const *src, const int
  * batch-global (mm_masking_amd/icp_weight_policy.py: params["global_minmax"]). */
 int mmk_channel_minmax(const float *x /*B,C,hw*/, int32_t B, int32_t C, int64_t hw, float *part,
                        float *pre /*C*2*/, float *minmax /*C*2 or NULL*/, void *stream);
+/* mmk_channel_meanstd fills pre with (mean, 1 / std) over (B,H,W) per channel, std the unbiased (n - 1) standard deviation of
+ * torch.std: the policy's standardisation (icp_weight_policy.py:156-159).  Two ordered fp64 passes; part: C*2048 doubles of
+ * workspace.  A constant channel gives 1 / std = inf (the reference divides by zero). */
+int mmk_channel_meanstd(const float *x /*B,C,hw*/, int32_t B, int32_t C, int64_t hw, double *part,
+                        float *pre /*C*2*/, void *stream);
 int mmk_conv_first(const float *x, int32_t cin, const float *W, const float *bias, const float *pre,
                    int32_t B, int32_t H, int32_t Wd, float leaky_slope, void *y, void *stream);
 /* dW[8][cin][3][3] and db[8] are WRITTEN (not added to): per-block partial sums into ws, then one ordered reduction --

@@ -136,6 +136,13 @@ def _declare(lib):
         "mmk_bce_ws_bytes": (sz, []),
         "mmk_bce_mean_fwd": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, sz, c_vp, c_vp]),
         "mmk_bce_mean_bwd": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+        "mmk_pose_loss_gt_fwd": (ctypes.c_int, [c_vp, c_vp, i32, c_vp, c_vp]),
+        "mmk_pose_loss_gt_bwd": (ctypes.c_int, [c_vp, c_vp, i32, c_vp, c_vp, c_vp, c_vp]),
+        "mmk_val_metric": (ctypes.c_int, [c_vp, c_vp, i32, c_vp, c_vp]),
+        "mmk_fft_threshold_ws_bytes": (sz, [i32]),
+        "mmk_fft_threshold_mask": (ctypes.c_int, [c_vp, i32, ctypes.c_int64, c_vp, sz, c_vp, c_vp]),
+        "mmk_bce_fft_threshold_fwd": (ctypes.c_int, [c_vp, c_vp, i32, ctypes.c_int64, c_vp, sz, c_vp, c_vp, c_vp]),
+        "mmk_bce_fft_threshold_bwd": (ctypes.c_int, [c_vp, c_vp, i32, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
         "mmk_icp_partials_count": (sz, [P]),
         "mmk_icp_accumulate": (ctypes.c_int, [P] + [c_vp] * 8 + [c_vp]),
         "mmk_icp_solve_update": (ctypes.c_int, [P] + [c_vp] * 7 + [c_vp]),
@@ -157,6 +164,7 @@ def _declare(lib):
         "mmk_conv16x8_bwd_fused": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_float, i32, i32, i32, c_vp, c_vp, c_vp, i32, c_vp]),
         "mmk_conv3x3_pool_fusable": (ctypes.c_int32, [i32, i32, i32, i32, i32]),
         "mmk_channel_minmax": (ctypes.c_int, [c_vp, i32, i32, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
+        "mmk_channel_meanstd": (ctypes.c_int, [c_vp, i32, i32, ctypes.c_int64, c_vp, c_vp, c_vp]),
         "mmk_conv_first": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, i32, i32, i32, f32, c_vp, c_vp]),
         "mmk_conv_first_wgrad_ws_bytes": (sz, [i32]),
         "mmk_conv_first_wgrad": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, i32, i32, i32, c_vp, c_vp, c_vp, sz, c_vp]),

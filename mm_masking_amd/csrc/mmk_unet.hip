@@ -3435,6 +3435,71 @@ __global__ __launch_bounds__(256) void channel_minmax_final_kernel(const float *
     }
 }
 
+// Per-channel mean and unbiased standard deviation over (B,H,W) -> pre[2c] = mean, pre[2c+1] = 1 / std: the standardisation of
+// the policy (icp_weight_policy.py:156-159, torch.mean / torch.std), consumed by the first-layer kernels like the min-max pair.
+// Two passes in fp64 with block partials in a fixed order: the sums, then the squared deviations from the mean, which every block
+// of the second pass reduces from the first pass's partials itself (the same order, so the same mean everywhere).  A constant
+// channel has deviations of exactly zero and gives 1 / 0 = inf, the reference's division by a zero std.
+__device__ __forceinline__ double block_sum256(double s, double *red /*4*/)
+{
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    const double r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ double channel_partials_sum(const double *__restrict__ part, double *red)
+{
+    double s = 0.0;
+    for (int k = threadIdx.x; k < MM_BLOCKS; k += 256) s += part[k];
+    return block_sum256(s, red);
+}
+
+template <bool CENTRED>
+__global__ __launch_bounds__(256) void channel_moment_partial_kernel(const float *__restrict__ x, int B, int C, size_t hw,
+                                                                     double *__restrict__ part /*C*MM_BLOCKS*2*/)
+{
+    __shared__ double red[4];
+    const int c = blockIdx.y;
+    double mean = 0.0;
+    if (CENTRED) mean = channel_partials_sum(part + (size_t)c * MM_BLOCKS * 2, red) / ((double)B * (double)hw);
+    auto term = [mean](float v) {
+        if (!CENTRED) return (double)v;
+        const double d = (double)v - mean;
+        return d * d;
+    };
+    double s = 0.0;
+    const bool vec = (hw & 3) == 0 && ((uintptr_t)x & 15) == 0;
+    for (int b = 0; b < B; ++b) {
+        const float *xc = x + ((size_t)b * C + c) * hw;
+        if (vec) {
+            const float4 *x4 = reinterpret_cast<const float4 *>(xc);
+            for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < hw / 4; q += (size_t)gridDim.x * blockDim.x) {
+                const float4 v = x4[q];
+                s += (term(v.x) + term(v.y)) + (term(v.z) + term(v.w));
+            }
+        } else {
+            for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < hw; q += (size_t)gridDim.x * blockDim.x) s += term(xc[q]);
+        }
+    }
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) part[(size_t)c * MM_BLOCKS * 2 + (CENTRED ? MM_BLOCKS : 0) + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void channel_meanstd_final_kernel(const double *__restrict__ part, size_t n, float *__restrict__ pre)
+{
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    const double sum = channel_partials_sum(part + (size_t)c * MM_BLOCKS * 2, red);
+    const double sq = channel_partials_sum(part + (size_t)c * MM_BLOCKS * 2 + MM_BLOCKS, red);
+    if (threadIdx.x == 0) {
+        pre[2 * c] = (float)(sum / (double)n);
+        pre[2 * c + 1] = (float)(1.0 / sqrt(sq / (double)(n - 1)));
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // nn.BatchNorm2d of the network's batch-norm variant (params["batch_norm"], icp_weight_policy.py:108-113: it
 // follows the ReLU of each convolution), on NHWC bf16 tensors.  Training mode: batch statistics over (B,H,W) per
@@ -3901,6 +3966,19 @@ extern "C" int mmk_channel_minmax(const float *x, int32_t B, int32_t C, int64_t 
     hipLaunchKernelGGL(channel_minmax_partial_kernel, dim3(MM_BLOCKS, C), dim3(256), 0, st, x, B, C, (size_t)hw, part);
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(channel_minmax_final_kernel, dim3(C), dim3(256), 0, st, part, C, pre, minmax);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_channel_meanstd(const float *x, int32_t B, int32_t C, int64_t hw, double *part, float *pre, void *stream)
+{
+    MMK_REQUIRE(x && part && pre && B >= 1 && C >= 1 && C <= 65535 && hw >= 1, "mmk_channel_meanstd: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(channel_moment_partial_kernel<false>, dim3(MM_BLOCKS, C), dim3(256), 0, st, x, B, C, (size_t)hw, part);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(channel_moment_partial_kernel<true>, dim3(MM_BLOCKS, C), dim3(256), 0, st, x, B, C, (size_t)hw, part);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(channel_meanstd_final_kernel, dim3(C), dim3(256), 0, st, (const double *)part, (size_t)B * (size_t)hw, pre);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

@@ -228,6 +228,11 @@ class LearnICPWeightPolicy(nn.Module):
                     # normalised copy of the image
                     net_in = raw_in.contiguous().float()
                     pre = unet_hip.channel_minmax(net_in, global_reduce=self.global_minmax)
+                elif "standardize" in self.normalize_type:
+                    # standardisation folded in the same way: (mean, 1 / std) per channel from two ordered passes, per
+                    # rank under data parallelism (as the reference's torch.mean / torch.std of its own batch)
+                    net_in = raw_in.contiguous().float()
+                    pre = unet_hip.channel_meanstd(net_in)
                 else:
                     net_in, pre = self._normalize_channels(raw_in), None
                 # (the amax normalisation below rides inside the same autograd node)

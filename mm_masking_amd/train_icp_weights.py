@@ -121,8 +121,7 @@ class _BceMeanFn(torch.autograd.Function):
         L = _lib.lib()
         x, t = mask.contiguous().float(), target.contiguous().float()
         if x.shape != t.shape:
-            raise ValueError("Using a target size (%s) that is different to the input size (%s) is deprecated. "
-                             "Please ensure they have the same size." % (tuple(t.shape), tuple(x.shape)))
+            raise _shape_mismatch(x, t)
         key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
         ws = _BCE_WS.get(key)
         if ws is None:
@@ -139,6 +138,85 @@ class _BceMeanFn(torch.autograd.Function):
         gx = torch.empty_like(x)
         _lib.check(_lib.lib().mmk_bce_mean_bwd(_lib.ptr(x), _lib.ptr(t), x.numel(), _lib.ptr(g.contiguous().float()), _lib.ptr(gx),
                                                _lib.stream_ptr(x.device)))
+        return gx, None
+
+
+class _PoseLossGtFn(torch.autograd.Function):
+    """(loss_rot, loss_trans) against a ground-truth pose (gt_eye=False, train_icp_weights.py:192-200) in one launch, the
+    gradient w.r.t. T_pred in another (csrc/mmk_loss.hip): a fp64 4x4 inverse per pair on the device instead of torch.inverse,
+    which synchronises with the host, and ~15 launches of matmul / norm / mean.  T_gt gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, T_pred, T_gt):
+        from . import _lib
+        T = T_pred.contiguous().float()
+        Tg = _lib.dev_f32(T_gt, T.device)
+        if Tg.shape != T.shape:
+            raise ValueError("T_gt %s does not match T_pred %s" % (tuple(Tg.shape), tuple(T.shape)))
+        out = torch.empty(2, dtype=torch.float32, device=T.device)
+        _lib.check(_lib.lib().mmk_pose_loss_gt_fwd(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], _lib.ptr(out), _lib.stream_ptr(T.device)))
+        ctx.save_for_backward(T, Tg)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_rot, g_trans):
+        from . import _lib
+        T, Tg = ctx.saved_tensors
+        gT = torch.empty_like(T)
+        gr = None if g_rot is None else g_rot.contiguous().float()
+        gt = None if g_trans is None else g_trans.contiguous().float()
+        _lib.check(_lib.lib().mmk_pose_loss_gt_bwd(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], _lib.ptr(gr), _lib.ptr(gt), _lib.ptr(gT),
+                                                   _lib.stream_ptr(T.device)))
+        return gT, None
+
+
+def _shape_mismatch(x, t):
+    return ValueError("Using a target size (%s) that is different to the input size (%s) is deprecated. "
+                      "Please ensure they have the same size." % (tuple(t.shape), tuple(x.shape)))
+
+
+def fft_threshold_mask(fft_data):
+    """torch.where(fft > 3 * mean_{H,W}(fft), 1, 0) per image of a fp32 (B,H,W) HIP tensor (train_icp_weights.py:204-206,
+    312-316) in three launches (csrc/mmk_loss.hip)."""
+    from . import _lib
+    L = _lib.lib()
+    f = fft_data.contiguous()
+    B = f.shape[0]
+    ws = torch.empty(int(L.mmk_fft_threshold_ws_bytes(B)), dtype=torch.uint8, device=f.device)
+    out = torch.empty_like(f)
+    _lib.check(L.mmk_fft_threshold_mask(_lib.ptr(f, torch.float32, "fft_data"), B, f.numel() // B, _lib.ptr(ws), ws.numel(),
+                                        _lib.ptr(out), _lib.stream_ptr(f.device)))
+    return out
+
+
+class _BceFftThresholdFn(torch.autograd.Function):
+    """_bce_mean(mask, fft_threshold_mask(fft)) without the target tensor: both passes compute the 0/1 target of each element
+    from fft and its image's threshold (csrc/mmk_loss.hip), the same bits as the two calls."""
+
+    @staticmethod
+    def forward(ctx, mask, fft_data):
+        from . import _lib
+        L = _lib.lib()
+        x, f = mask.contiguous().float(), fft_data.contiguous().float()
+        if x.shape != f.shape:
+            raise _shape_mismatch(x, f)
+        B = f.shape[0]
+        ws = torch.empty(int(L.mmk_fft_threshold_ws_bytes(B)), dtype=torch.uint8, device=x.device)
+        thr = torch.empty(B, dtype=torch.float32, device=x.device)
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        _lib.check(L.mmk_bce_fft_threshold_fwd(_lib.ptr(x), _lib.ptr(f), B, f.numel() // B, _lib.ptr(ws), ws.numel(), _lib.ptr(thr),
+                                               _lib.ptr(out), _lib.stream_ptr(x.device)))
+        ctx.save_for_backward(x, f, thr)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _lib
+        x, f, thr = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        B = f.shape[0]
+        _lib.check(_lib.lib().mmk_bce_fft_threshold_bwd(_lib.ptr(x), _lib.ptr(f), B, f.numel() // B, _lib.ptr(thr),
+                                                        _lib.ptr(g.contiguous().float()), _lib.ptr(gx), _lib.stream_ptr(x.device)))
         return gx, None
 
 
@@ -163,6 +241,9 @@ def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map
 
     if (loss_weights["icp_rot"] > 0.0 or loss_weights["icp_trans"] > 0.0) and gt_eye and T_pred.is_cuda and dt == torch.float32:
         terms["rot"], terms["trans"] = _PoseLossFn.apply(T_pred)          # one launch each way (csrc/mmk_loss.hip)
+    elif (loss_weights["icp_rot"] > 0.0 or loss_weights["icp_trans"] > 0.0) and not gt_eye and T_pred.is_cuda and \
+            dt == torch.float32 and batch_T_gt.dtype == torch.float32:
+        terms["rot"], terms["trans"] = _PoseLossGtFn.apply(T_pred, batch_T_gt)     # no torch.inverse: no host synchronisation
     elif loss_weights["icp_rot"] > 0.0 or loss_weights["icp_trans"] > 0.0:
         eye = _const("eye", dev, dt)
         if gt_eye:
@@ -177,9 +258,12 @@ def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map
             (loss_weights["icp_rot"] <= 0 and loss_weights["icp_trans"] <= 0):
         if loss_weights["fft"] > 0.0:
             fft_data = batch_scan["fft_data"].to(mask.device)
-            mean_azimuth = torch.mean(fft_data, dim=(1, 2), keepdim=True)
-            fft_mask = torch.where(fft_data > 3.0 * mean_azimuth, torch.ones_like(fft_data), torch.zeros_like(fft_data))
-            terms["fft"] = mask_criterion(mask, fft_mask)
+            if mask.is_cuda and mask.dtype == torch.float32 and fft_data.dtype == torch.float32:
+                terms["fft"] = _BceFftThresholdFn.apply(mask, fft_data)     # the target is never written
+            else:
+                mean_azimuth = torch.mean(fft_data, dim=(1, 2), keepdim=True)
+                fft_mask = torch.where(fft_data > 3.0 * mean_azimuth, torch.ones_like(fft_data), torch.zeros_like(fft_data))
+                terms["fft"] = mask_criterion(mask, fft_mask)
         if loss_weights["cfar"] > 0.0:
             terms["cfar"] = mask_criterion(mask, batch_scan["fft_cfar"].to(mask.device))
         if loss_weights["mask_pts"] > 0.0:
@@ -211,7 +295,17 @@ def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map
 
 
 def eval_validation_loss(T_pred, batch_T_gt, gt_eye=True):
-    """train_icp_weights.py:255-273 -> [||(theta,x,y)||, |theta|, ||(x,y)||] batch means."""
+    """train_icp_weights.py:255-273 -> [||(theta,x,y)||, |theta|, ||(x,y)||] batch means.  gt_eye=False on a HIP device:
+    one launch (csrc/mmk_loss.hip) instead of torch.inverse, which synchronises with the host; the result carries no gradient,
+    so a T_pred that needs one (the reference only calls this under no_grad) keeps the PyTorch expression."""
+    if not gt_eye and T_pred.is_cuda and T_pred.dtype == torch.float32 and batch_T_gt.dtype == torch.float32 and \
+            not (torch.is_grad_enabled() and T_pred.requires_grad):
+        from . import _lib
+        T = T_pred.detach().contiguous()
+        Tg = _lib.dev_f32(batch_T_gt, T.device)
+        out = torch.empty(3, dtype=torch.float32, device=T.device)
+        _lib.check(_lib.lib().mmk_val_metric(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], _lib.ptr(out), _lib.stream_ptr(T.device)))
+        return out
     eye = _const("eye", T_pred.device, T_pred.dtype)
     if gt_eye:
         xi_wedge = T_pred - eye
@@ -310,6 +404,8 @@ def generate_baseline(model, iterator, baseline_type="train", device="cpu",
             fft_data = batch_scan["fft_data"].to(device)
             if loss_weights.get("cfar", 0.0) > 0.0:
                 ones_mask = batch_scan["fft_cfar"].to(device)
+            elif loss_weights.get("fft", 0.0) > 0.0 and fft_data.is_cuda and fft_data.dtype == torch.float32:
+                ones_mask = fft_threshold_mask(fft_data)
             elif loss_weights.get("fft", 0.0) > 0.0:
                 mean_azimuth = torch.mean(fft_data, dim=(1, 2), keepdim=True)
                 ones_mask = torch.where(fft_data > 3.0 * mean_azimuth, torch.ones_like(fft_data),

@@ -256,6 +256,17 @@ def channel_minmax(x, process_group=None, global_reduce=False):
     return pre
 
 
+def channel_meanstd(x):
+    """(mean, 1 / std) per channel of fp32 (B,C,H,W) over (B,H,W) -> (C,2) fp32, std unbiased (torch.std): the offset and
+    reciprocal scale of the policy's standardisation (icp_weight_policy.py:156-159).  A constant channel gives inf, the
+    reference's division by a zero std."""
+    B, C, H, W = x.shape
+    part = torch.empty(C * 2048, dtype=torch.float64, device=x.device)
+    pre = torch.empty(C, 2, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().mmk_channel_meanstd(_p(x), B, C, H * W, _p(part), _p(pre), _sp(x.device)))
+    return pre
+
+
 def maxpool2(x):
     B, H, W, C = x.shape
     y = torch.empty(B, H // 2, W // 2, C, dtype=BF16, device=x.device)
