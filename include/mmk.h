@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 501 /* 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 502 /* 0.5.2: mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -96,6 +96,23 @@ int mmk_icp_backward(const mmk_icp_params *p, const float *source, const float *
                      const int32_t *active_hist, const float *grad_T /*B,16*/,
                      float *grad_weight /*B,N*/, float *grad_T_init /*B,16 or NULL*/,
                      void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same sweep, also differentiated in the clouds: grad_source (B,N,3) = dL/dsource, grad_target (B,M,tgt_cols) =
+ * dL/dtarget, each optional (both NULL: bit-identical to mmk_icp_backward).  As in autograd through the unrolled
+ * iterations, the correspondences, the trim gate, the freeze decisions and the non-positive-definite fallback are
+ * constants.  Entries outside the arithmetic are exactly 0: source z for dim 2; target columns dim..2 and the normals for
+ * pt2pt (normal columns >= 3 + dim for pt2pl); targets that were never a correspondent.  The target gradient is a scatter
+ * of up to K*N rows per target, summed as 64-bit fixed point (no float atomics, bit-reproducible; resolution max|row
+ * entry| * 2^(ceil(log2(K*N)) - 62)); a non-finite entry makes that pair's target gradient NaN.  workspace:
+ * mmk_icp_backward_points_workspace_bytes(p, grad_target != NULL) bytes.  Argument errors return MMK_ERR_ARG.         */
+size_t mmk_icp_backward_points_workspace_bytes(const mmk_icp_params *p, int32_t with_target);
+int mmk_icp_backward_points(const mmk_icp_params *p, const float *source, const float *target,
+                            const float *weight, const int32_t *idx_hist, const float *T_hist,
+                            const double *delta_hist, const double *A_hist,
+                            const int32_t *active_hist, const float *grad_T /*B,16*/,
+                            float *grad_weight /*B,N*/, float *grad_T_init /*B,16 or NULL*/,
+                            float *grad_source /*B,N,3 or NULL*/, float *grad_target /*B,M,tgt_cols or NULL*/,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 /* Status of the last mmk_icp_forward call that used `workspace`: the MMK_ICP_STATUS_* bits its kernels raised (0 = clean).
  * Asynchronous like everything else: enqueues a 4-byte copy on `stream` into status_out (a device pointer or pinned host
@@ -250,6 +267,12 @@ int mmk_sample_weights_bwd(const float *grad_weights /*B,N*/, const float *pc, i
                            int32_t N, int32_t pc_cols, int32_t H, int32_t W,
                            int32_t cart_pixel_width, float cart_resolution, float *grad_mask,
                            void *ws, size_t ws_bytes, void *stream);
+/* grad_pc (B,N,pc_cols) = dL/dpc of the same gather: grid_sample's gradient with respect to its grid (taps as in the
+ * forward, out-of-image taps read 0), chained through point_to_cart_idx.  Written whole: columns 0 and 1 carry it; the
+ * other columns and fake points (x==0 && y==0) get 0.  One thread per point, no scatter. */
+int mmk_sample_weights_bwd_pc(const float *grad_weights /*B,N*/, const float *mask /*B,H,W*/, const float *pc,
+                              int32_t B, int32_t N, int32_t pc_cols, int32_t H, int32_t W,
+                              int32_t cart_pixel_width, float cart_resolution, float *grad_pc, void *stream);
 
 /* ---- loader primitives (icp_weight_dataset.py:323-362: PNG rows -> load_radar -> augmentation roll -> polar -> Cartesian)
  * mmk_host_read_rows: HOST function, no GPU call, thread-safe: rows [0,rows) of a raw row-major byte file (header_bytes

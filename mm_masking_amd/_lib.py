@@ -130,6 +130,8 @@ def _declare(lib):
         "mmk_icp_workspace_bytes": (sz, [P]),
         "mmk_icp_forward": (ctypes.c_int, [P] + [c_vp] * 10 + [c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
         "mmk_icp_backward": (ctypes.c_int, [P] + [c_vp] * 11 + [c_vp, sz, c_vp]),
+        "mmk_icp_backward_points_workspace_bytes": (sz, [P, i32]),
+        "mmk_icp_backward_points": (ctypes.c_int, [P] + [c_vp] * 13 + [c_vp, sz, c_vp]),
         "mmk_icp_status": (ctypes.c_int, [P, c_vp, sz, c_vp, c_vp]),
         "mmk_pose_loss_fwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp]),
         "mmk_pose_loss_bwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, c_vp]),
@@ -206,6 +208,7 @@ def _declare(lib):
         "mmk_u8_to_float": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
         "mmk_sample_weights_bwd_ws_bytes": (sz, [i32, i32]),
         "mmk_sample_weights_bwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, f32, c_vp, c_vp, sz, c_vp]),
+        "mmk_sample_weights_bwd_pc": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, i32, f32, c_vp, c_vp]),
         "mmk_weight_stats": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, c_vp, c_vp, c_vp]),
         "mmk_bev_raster": (ctypes.c_int, [c_vp, i32, i32, i32, i32, f32, c_vp, c_vp]),
     }

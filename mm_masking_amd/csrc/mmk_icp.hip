@@ -1266,23 +1266,35 @@ __global__ __launch_bounds__(64) void icp_bwd_pair_kernel(
     }
 }
 
+// Columns of a point's contribution row to the target gradient (PTS): q̄ (dim), then n̄ (dim) for pt2pl; and the columns of
+// their fixed-point sums, padded to a power of two (icp_bwd_target_scatter_kernel).
+__host__ __device__ constexpr int tgt_row_cols(int dim, int type) { return type == MMK_ICP_PT2PL ? 2 * dim : dim; }
+__host__ __device__ constexpr int tgt_acc_cols(int c) { return c <= 2 ? 2 : (c <= 4 ? 4 : 8); }
+
 // I7 backward, per-point part: dL/dweight and the point path of dL/dT_k.
-template <int DIM, int TYPE>
+// PTS (mmk_icp_backward_points): also the adjoints of the clouds -- gsrc (B,N,3, may be NULL) += R_kᵀ p̄ in place (each
+// thread owns its point, iterations are ordered launches), and the point's contribution to its correspondent's target
+// gradient as a row of `rows` ((B,N,tgt_row_cols), may be NULL), with the pair's largest |entry| as float bits in pmax (B)
+// by an INTEGER max (order independent): icp_bwd_target_scatter_kernel adds the rows up after the sweep.
+template <int DIM, int TYPE, bool PTS>
 __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     const float *__restrict__ src, const float *__restrict__ tgt, int tgt_cols,
     const float *__restrict__ weight, const float *__restrict__ Tk, const int32_t *__restrict__ active,
     const int32_t *__restrict__ idx, const double *__restrict__ lam64, const double *__restrict__ delta64, int N,
-    int M, int loss, float k, float k2, float trim2, float *__restrict__ gw, double *__restrict__ pparts)
+    int M, int loss, float k, float k2, float trim2, float *__restrict__ gw, double *__restrict__ pparts,
+    float *__restrict__ gsrc, float *__restrict__ rows, unsigned *__restrict__ pmax)
 {
     constexpr int P = PointTerms<DIM, TYPE>::P;
     constexpr int NR = PointTerms<DIM, TYPE>::NR;
     constexpr int NP = npose(DIM);
+    constexpr int C = tgt_row_cols(DIM, TYPE);
     const int b = blockIdx.y;
     const int i = blockIdx.x * ACC_THREADS + threadIdx.x;
     double acc[NP];
 #pragma unroll
     for (int a = 0; a < NP; ++a) acc[a] = 0.0;
     const bool act = active[b] != 0;
+    unsigned mbits = 0u;
 
     if (act && i < N) {
         float T[16];
@@ -1367,16 +1379,72 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
             for (int c = 0; c < DIM; ++c) acc[r * DIM + c] = (double)pbar[r] * (double)t.s[c];
             acc[DIM * DIM + r] = (double)pbar[r];
         }
+        if constexpr (PTS) {
+            if (gsrc != nullptr) {          // s̄ += R_kᵀ p̄ (the DIM x DIM block of T_k); source z stays 0 in dim 2
+                float *gs = gsrc + ((size_t)b * N + i) * 3;
+#pragma unroll
+                for (int c = 0; c < DIM; ++c) {
+                    float v = T[c] * pbar[0];
+#pragma unroll
+                    for (int r = 1; r < DIM; ++r) v += T[r * 4 + c] * pbar[r];
+                    gs[c] += v;
+                }
+            }
+            if (rows != nullptr) {
+                float q[C];                 // ∂L/∂(correspondent's xyz), then ∂L/∂(its normal) for pt2pl
+                if constexpr (TYPE == MMK_ICP_PT2PT) {
+#pragma unroll
+                    for (int c = 0; c < DIM; ++c) q[c] = ebar[c];               // e = q − p
+                } else {
+                    const float eb = ebar[0];                                   // e = n·(q − p), J = nᵀG
+#pragma unroll
+                    for (int c = 0; c < DIM; ++c) {
+                        q[c] = t.n[c] * eb;
+                        q[DIM + c] = eb * t.ev[c] + Jbar[0][c];
+                    }
+                    if constexpr (DIM == 2) {        // J[2] = ny·px − nx·py
+                        q[DIM + 0] -= t.p[1] * Jbar[0][2];
+                        q[DIM + 1] += t.p[0] * Jbar[0][2];
+                    } else {                         // J[3:6] = p × n: n̄ += J̄rot × p (as p̄ += n × J̄rot above)
+                        const float px = t.p[0], py = t.p[1], pz = t.p[DIM - 1];
+                        const float j3 = Jbar[0][P - 3], j4 = Jbar[0][P - 2], j5 = Jbar[0][P - 1];
+                        q[DIM + 0] += j4 * pz - j5 * py;
+                        q[DIM + 1] += j5 * px - j3 * pz;
+                        q[DIM + DIM - 1] += j3 * py - j4 * px;
+                    }
+                }
+                float *row = rows + ((size_t)b * N + i) * C;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    row[c] = q[c];
+                    mbits = max(mbits, __float_as_uint(fabsf(q[c])));      // (NaN patterns sort above +inf)
+                }
+            }
+        }
     }
 
     __shared__ double red[ACC_THREADS / 64][NP];
+    __shared__ unsigned wmax[ACC_THREADS / 64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if constexpr (PTS) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mbits = max(mbits, __shfl_xor(mbits, off, 64));
+        if (lane == 0) wmax[wv] = mbits;
+    }
 #pragma unroll
     for (int a = 0; a < NP; ++a) {
         double v = wave_sum(acc[a]);
         if (lane == 0) red[wv][a] = v;
     }
     __syncthreads();
+    if constexpr (PTS) {            // one integer max per block into the pair's word
+        if (rows != nullptr && threadIdx.x == 0) {
+            unsigned m = 0u;
+#pragma unroll
+            for (int w = 0; w < ACC_THREADS / 64; ++w) m = max(m, wmax[w]);
+            if (m != 0u) atomicMax(&pmax[b], m);
+        }
+    }
     if (threadIdx.x < NP) {
         double v = 0.0;
 #pragma unroll
@@ -1413,6 +1481,67 @@ __global__ void bwd_final_kernel(const double *__restrict__ Gdir, const double *
         __syncthreads();
     }
     if (lane < 16) out[(size_t)b * 16 + lane] = (float)v;
+}
+
+// ------------------------------------------------------------------------------------------
+// I7 backward, target gradient (mmk_icp_backward_points).  Up to K·N rows of a pair land on one target (every zero-padded
+// source row maps to the same one), so the rows are added as FIXED POINT in 64-bit integers, whose sum does not depend on
+// the order of arrival: entry v becomes llrint(v·scale), scale the power of two with K·N·max|v|·scale < 2^62 (no partial
+// sum can overflow) -- a resolution of max|v|·2^(cnt_bits − 62) per entry, cnt_bits = ceil(log2(K·N)).  A non-finite entry
+// (pmax bits >= +inf) makes the pair's target gradient NaN.
+__device__ __forceinline__ double tgt_fixed_scale(unsigned mbits, int cnt_bits)
+{
+    if (mbits >= 0x7f800000u) return 0.0;
+    if (mbits == 0u) return 1.0;
+    return ldexp(1.0, 62 - cnt_bits - ((int)(mbits >> 23) - 126));      // max|v| < 2^((bits >> 23) − 126), subnormals too
+}
+
+// One thread per (row, column), L = tgt_acc_cols(C) lanes per row, so that an atomic wave-instruction adds 64 / L whole rows
+// (C·8 contiguous bytes each) instead of 64 scattered words.  A wave whose rows all share one target (the hot target) sums
+// them first and adds once per column.  Rows of frozen pairs (never written) and zero entries (zero-weight rows) are skipped.
+template <int C>
+__global__ __launch_bounds__(ACC_THREADS) void icp_bwd_target_scatter_kernel(
+    const float *__restrict__ rows, const int32_t *__restrict__ idx_hist, const int32_t *__restrict__ active_hist,
+    const unsigned *__restrict__ pmax, int B, int N, int M, int cnt_bits, unsigned long long *__restrict__ acc)
+{
+    constexpr int L = tgt_acc_cols(C);
+    const int b = blockIdx.y, k = blockIdx.z;
+    const double scale = tgt_fixed_scale(pmax[b], cnt_bits);
+    if (active_hist[(size_t)k * B + b] == 0 || scale == 0.0) return;       // (uniform over the block)
+    const int t = blockIdx.x * ACC_THREADS + threadIdx.x, i = t / L, c = t % L;
+    const bool valid = i < N;
+    const size_t r = ((size_t)k * B + b) * N + i;
+    const int j = valid ? idx_hist[r] : -1;
+    long long v = 0;
+    if (valid && c < C) v = llrint((double)rows[r * C + c] * scale);
+    const unsigned long long vmask = __ballot(valid);
+    if (vmask == 0ull) return;                                              // (uniform over the wave)
+    unsigned long long *ab = acc + (size_t)b * M * L;
+    const int j0 = __shfl(j, __ffsll(vmask) - 1, 64);
+    if (__ballot(valid && j != j0) == 0ull) {
+#pragma unroll
+        for (int off = 32; off >= L; off >>= 1) v += __shfl_xor(v, off, 64);
+        if ((threadIdx.x & 63) < L && v != 0) atomicAdd(&ab[(size_t)j0 * L + c], (unsigned long long)v);
+    } else if (v != 0) {
+        atomicAdd(&ab[(size_t)j * L + c], (unsigned long long)v);
+    }
+}
+
+// (B,M,L) fixed-point sums -> grad_target (B,M,cols): xyz columns < dim, pt2pl normal columns 3 .. 3 + dim; the rest 0.
+__global__ void icp_bwd_target_final_kernel(const unsigned long long *__restrict__ acc, const unsigned *__restrict__ pmax,
+                                            int cnt_bits, int M, int dim, int C, int L, int cols, float *__restrict__ gtgt)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (j >= M) return;
+    const double scale = tgt_fixed_scale(pmax[b], cnt_bits);
+    const unsigned long long *a = acc + ((size_t)b * M + j) * L;
+    float *out = gtgt + ((size_t)b * M + j) * cols;
+    for (int c = 0; c < cols; ++c) {
+        const int e = c < dim ? c : (C > dim && c >= 3 && c < 3 + dim ? dim + (c - 3) : -1);
+        float v = 0.f;
+        if (e >= 0) v = scale == 0.0 ? __builtin_nanf("") : (float)((double)(long long)a[e] / scale);
+        out[c] = v;
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1553,6 +1682,29 @@ IcpWs carve(const mmk_icp_params *p, void *ws, size_t cap)
     return w;
 }
 
+// Scratch of mmk_icp_backward_points: mmk_icp_backward's (carve above), then the target gradient's parts.
+struct IcpPtsWs {
+    float *rows;                 // (K,B,N,C): every point's contribution row, per iteration
+    unsigned long long *acc;     // (B,M,L): their fixed-point sums
+    unsigned *pmax;              // (B): float bits of the largest |entry| of a pair's rows
+    size_t bytes;
+};
+
+IcpPtsWs carve_points(const mmk_icp_params *p, bool with_target, void *ws, size_t cap)
+{
+    mmk::Arena ar(ws, cap);
+    ar.off = carve(p, nullptr, 0).bytes;
+    IcpPtsWs w{nullptr, nullptr, nullptr, 0};
+    if (with_target) {
+        const int C = tgt_row_cols(p->dim, p->icp_type);
+        w.rows = ar.take<float>((size_t)p->max_iter * p->B * p->N * C);
+        w.acc = ar.take<unsigned long long>((size_t)p->B * p->M * tgt_acc_cols(C));
+        w.pmax = ar.take<unsigned>((size_t)p->B);
+    }
+    w.bytes = mmk::align_up(ar.off, 256);
+    return w;
+}
+
 template <int DIM, int TYPE>
 int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight, float *T_hist,
                 int32_t *idx_hist, double *delta_hist, double *A_hist, int32_t *active_hist, const IcpWs &w,
@@ -1641,13 +1793,19 @@ int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, con
 template <int DIM, int TYPE>
 int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight,
                  const int32_t *idx_hist, const float *T_hist, const double *delta_hist, const double *A_hist,
-                 const int32_t *active_hist, const float *grad_T, float *gw, float *grad_T_init, const IcpWs &w,
-                 hipStream_t st)
+                 const int32_t *active_hist, const float *grad_T, float *gw, float *grad_T_init, float *gsrc, float *gtgt,
+                 const IcpWs &w, const IcpPtsWs &pw, hipStream_t st)
 {
     const int B = p->B, N = p->N, M = p->M;
     const int nblk = (N + ACC_THREADS - 1) / ACC_THREADS;
     const float k = p->loss_k, k2 = p->loss_k * p->loss_k, trim2 = p->trim_dist * p->trim_dist;
+    constexpr int C = tgt_row_cols(DIM, TYPE), L = tgt_acc_cols(C);
     MMK_CHECK_HIP(hipMemsetAsync(gw, 0, sizeof(float) * (size_t)B * N, st));
+    if (gsrc) MMK_CHECK_HIP(hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * N * 3, st));
+    if (gtgt) {
+        MMK_CHECK_HIP(hipMemsetAsync(pw.acc, 0, sizeof(unsigned long long) * (size_t)B * M * L, st));
+        MMK_CHECK_HIP(hipMemsetAsync(pw.pmax, 0, sizeof(unsigned) * (size_t)B, st));
+    }
     hipLaunchKernelGGL(f32_to_f64_kernel, dim3((B * 16 + 255) / 256), dim3(256), 0, st, grad_T, w.G0, B * 16);
     MMK_LAUNCH_CHECK();
     double *Gin = w.G0, *Gout = w.G1;
@@ -1658,9 +1816,16 @@ int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, co
         hipLaunchKernelGGL(icp_bwd_pair_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, Tk,
                            delta_hist + (size_t)it * B * 6, A_hist + (size_t)it * B * 36, act, Gout, w.lam);
         MMK_LAUNCH_CHECK();
-        hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
-                           p->tgt_cols, weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam,
-                           delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, gw, w.partials);
+        if (gsrc || gtgt)
+            hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, true>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
+                               p->tgt_cols, weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam,
+                               delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, gw, w.partials, gsrc,
+                               gtgt ? pw.rows + (size_t)it * B * N * C : static_cast<float *>(nullptr), pw.pmax);
+        else
+            hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, false>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
+                               p->tgt_cols, weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam,
+                               delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, gw, w.partials,
+                               static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<unsigned *>(nullptr));
         MMK_LAUNCH_CHECK();
         nparts = nblk;
         double *t = Gin; Gin = Gout; Gout = t;
@@ -1669,7 +1834,37 @@ int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, co
         hipLaunchKernelGGL(bwd_final_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, grad_T_init);
         MMK_LAUNCH_CHECK();
     }
+    if (gtgt) {
+        int cnt_bits = 0;
+        while (((uint64_t)1 << cnt_bits) < (uint64_t)p->max_iter * (uint64_t)N) ++cnt_bits;
+        const unsigned gx = (unsigned)(((size_t)N * L + ACC_THREADS - 1) / ACC_THREADS);
+        hipLaunchKernelGGL(icp_bwd_target_scatter_kernel<C>, dim3(gx, B, p->max_iter), dim3(ACC_THREADS), 0, st, pw.rows, idx_hist,
+                           active_hist, pw.pmax, B, N, M, cnt_bits, pw.acc);
+        MMK_LAUNCH_CHECK();
+        hipLaunchKernelGGL(icp_bwd_target_final_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, pw.acc, pw.pmax, cnt_bits, M, DIM, C,
+                           L, p->tgt_cols, gtgt);
+        MMK_LAUNCH_CHECK();
+    }
     return MMK_OK;
+}
+
+// mmk_icp_backward and mmk_icp_backward_points (gsrc / gtgt NULL: the former's launches exactly).
+int dispatch_backward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight,
+                      const int32_t *idx_hist, const float *T_hist, const double *delta_hist, const double *A_hist,
+                      const int32_t *active_hist, const float *grad_T, float *gw, float *grad_T_init, float *gsrc,
+                      float *gtgt, const IcpWs &w, const IcpPtsWs &pw, hipStream_t st)
+{
+    if (p->dim == 2 && p->icp_type == MMK_ICP_PT2PT)
+        return run_backward<2, MMK_ICP_PT2PT>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
+                                              grad_T_init, gsrc, gtgt, w, pw, st);
+    if (p->dim == 2)
+        return run_backward<2, MMK_ICP_PT2PL>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
+                                              grad_T_init, gsrc, gtgt, w, pw, st);
+    if (p->icp_type == MMK_ICP_PT2PT)
+        return run_backward<3, MMK_ICP_PT2PT>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
+                                              grad_T_init, gsrc, gtgt, w, pw, st);
+    return run_backward<3, MMK_ICP_PT2PL>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
+                                          grad_T_init, gsrc, gtgt, w, pw, st);
 }
 
 }  // namespace
@@ -1889,12 +2084,33 @@ extern "C" int mmk_icp_backward(const mmk_icp_params *p, const float *source, co
         mmk::set_error("mmk_icp_backward: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
         return MMK_ERR_WORKSPACE;
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (p->dim == 2 && p->icp_type == MMK_ICP_PT2PT)
-        return run_backward<2, MMK_ICP_PT2PT>(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight, grad_T_init, w, st);
-    if (p->dim == 2)
-        return run_backward<2, MMK_ICP_PT2PL>(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight, grad_T_init, w, st);
-    if (p->icp_type == MMK_ICP_PT2PT)
-        return run_backward<3, MMK_ICP_PT2PT>(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight, grad_T_init, w, st);
-    return run_backward<3, MMK_ICP_PT2PL>(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight, grad_T_init, w, st);
+    return dispatch_backward(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight,
+                             grad_T_init, nullptr, nullptr, w, IcpPtsWs{nullptr, nullptr, nullptr, 0}, (hipStream_t)stream);
+}
+
+extern "C" size_t mmk_icp_backward_points_workspace_bytes(const mmk_icp_params *p, int32_t with_target)
+{
+    if (check_params(p) != MMK_OK) return 0;
+    return carve_points(p, with_target != 0, nullptr, 0).bytes;
+}
+
+extern "C" int mmk_icp_backward_points(const mmk_icp_params *p, const float *source, const float *target,
+                                       const float *weight, const int32_t *idx_hist, const float *T_hist,
+                                       const double *delta_hist, const double *A_hist, const int32_t *active_hist,
+                                       const float *grad_T, float *grad_weight, float *grad_T_init, float *grad_source,
+                                       float *grad_target, void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_params(p);
+    if (rc != MMK_OK) return rc;
+    MMK_REQUIRE(p->save_state, "mmk_icp_backward_points: forward must have run with save_state = 1");
+    MMK_REQUIRE(source && target && idx_hist && T_hist && delta_hist && A_hist && active_hist && grad_T && grad_weight,
+                "mmk_icp_backward_points: NULL pointer");
+    MMK_REQUIRE(grad_target == nullptr || p->max_iter <= 65535,
+                "mmk_icp_backward_points: the target gradient needs max_iter <= 65535 (got %d)", p->max_iter);
+    const IcpPtsWs pw = carve_points(p, grad_target != nullptr, workspace, workspace_bytes);
+    MMK_REQUIRE(workspace != nullptr && pw.bytes <= workspace_bytes, "mmk_icp_backward_points: workspace too small (%zu < %zu bytes)",
+                workspace_bytes, pw.bytes);
+    const IcpWs w = carve(p, workspace, workspace_bytes);
+    return dispatch_backward(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight,
+                             grad_T_init, grad_source, grad_target, w, pw, (hipStream_t)stream);
 }

@@ -457,6 +457,7 @@ __global__ __launch_bounds__(256) void polar_to_cart_kernel(const float *__restr
 struct Taps {
     int xi, yi;
     float w00, w01, w10, w11;
+    float wx, wy;        // ix − x0, iy − y0
 };
 
 // cw = cart_pixel_width of point_to_cart_idx: the normalisation is by the Cartesian grid's width
@@ -484,6 +485,8 @@ __device__ __forceinline__ Taps weight_taps(const float *__restrict__ p, int H, 
     t.w01 = (1.0f - wy) * wx;
     t.w10 = wy * (1.0f - wx);
     t.w11 = wy * wx;
+    t.wx = wx;
+    t.wy = wy;
     return t;
 }
 
@@ -575,6 +578,40 @@ __global__ void sample_weights_bwd_store_kernel(int N, int H, int W, const int *
     if (e >= 4 * N) return;
     const int p = pix[(size_t)b * 4 * N + e];
     if (p >= 0) gmask[(size_t)b * H * W + p] = res[(size_t)b * 4 * N + e];
+}
+
+// dL/dpc of the gather: F.grid_sample's gradient with respect to its grid (PyTorch's CPU form: ((ne − nw)·s + (se − sw)·n)·g
+// along x, ((sw − nw)·e + (se − ne)·w)·g along y, times (size − 1) / 2 for align_corners=True), chained through
+// point_to_cart_idx.  One thread per point, which owns its output row: no scatter.  Fake rows get 0 (the reference overwrites
+// their grid in place, radar_utils.py:118-122), and so does every column but x, y.
+__global__ void sample_weights_bwd_pc_kernel(const float *__restrict__ gw, const float *__restrict__ mask,
+                                             const float *__restrict__ pc, int N, int cols, int H, int W, int cw, float cres,
+                                             float *__restrict__ gpc)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (n >= N) return;
+    const float *p = pc + ((size_t)b * N + n) * cols;
+    float *g = gpc + ((size_t)b * N + n) * cols;
+    for (int c = 2; c < cols; ++c) g[c] = 0.0f;
+    if (p[0] == 0.0f && p[1] == 0.0f) {
+        g[0] = 0.0f;
+        g[1] = 0.0f;
+        return;
+    }
+    const Taps t = weight_taps(p, H, W, cw, cres);
+    const float *m = mask + (size_t)b * H * W;
+    auto tap = [&](int yy, int xx) -> float {
+        return (xx >= 0 && xx < W && yy >= 0 && yy < H) ? m[(size_t)yy * W + xx] : 0.0f;
+    };
+    const float nw = tap(t.yi, t.xi), ne = tap(t.yi, t.xi + 1), sw = tap(t.yi + 1, t.xi), se = tap(t.yi + 1, t.xi + 1);
+    const float go = gw[(size_t)b * N + n];
+    const float gix = ((ne - nw) * (1.0f - t.wy) + (se - sw) * t.wy) * go;
+    const float giy = ((sw - nw) * (1.0f - t.wx) + (se - ne) * t.wx) * go;
+    const float ggx = gix * ((float)(W - 1) / 2.0f), ggy = giy * ((float)(H - 1) / 2.0f);
+    // gx = ((y / cres) / (cw − 1)) · 2,  gy = ((−x / cres) / (cw − 1)) · 2
+    g[0] = -(((ggy * 2.0f) / (float)(cw - 1)) / cres);
+    g[1] = ((ggx * 2.0f) / (float)(cw - 1)) / cres;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -853,6 +890,19 @@ extern "C" int mmk_sample_weights_bwd(const float *grad_weights, const float *pc
     hipLaunchKernelGGL(sample_weights_bwd_sum_kernel, grid, dim3(256), 0, st, N, H, W, grad_mask, next, val, pix, res);
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(sample_weights_bwd_store_kernel, grid, dim3(256), 0, st, N, H, W, pix, res, grad_mask);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_sample_weights_bwd_pc(const float *grad_weights, const float *mask, const float *pc, int32_t B, int32_t N,
+                                         int32_t pc_cols, int32_t H, int32_t W, int32_t cart_pixel_width, float cart_resolution,
+                                         float *grad_pc, void *stream)
+{
+    MMK_REQUIRE(grad_weights && mask && pc && grad_pc, "mmk_sample_weights_bwd_pc: NULL pointer");
+    MMK_REQUIRE(B >= 1 && N >= 1 && pc_cols >= 2 && H >= 2 && W >= 2 && cart_pixel_width >= 2,
+                "mmk_sample_weights_bwd_pc: bad shape");
+    hipLaunchKernelGGL(sample_weights_bwd_pc_kernel, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, grad_weights, mask,
+                       pc, N, pc_cols, H, W, cart_pixel_width, cart_resolution, grad_pc);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

@@ -17,6 +17,16 @@ dL/dweight) runs in the HIP kernels of csrc/mmk_icp.hip through the C ABI
 is DESIGN.md §3; upstream dICP's source is absent, so it is OUR spec — see
 "parity unpinned" there.  ``T`` maps source -> target (p_t ~ T p_s) and is
 iterated from ``T_init``.
+
+Differentiable (``differentiable=True``, grad enabled) in ``weight``, ``T_init``,
+``source`` and ``target`` (xyz and, for pt2pl, the normals): ``T`` requires grad
+when any of them does, and each one that does gets its gradient in its own dtype
+and on its own device.  As in autograd through the unrolled iterations, the
+correspondences, the trim gate, the freeze decisions and the non-positive-definite
+fallback are constants.  Entries outside the arithmetic get exactly 0: source z for
+dim 2, target columns dim..2, the normals for pt2pt (columns >= 3 + dim for pt2pl)
+and targets that never were a correspondent.  The clouds' adjoints come from
+``mmk_icp_backward_points``; without them the backward is ``mmk_icp_backward``.
 """
 import ctypes
 import os
@@ -139,14 +149,23 @@ class _IcpFunction(torch.autograd.Function):
         p = ctx.p
         L = _lib.lib()
         dev = src.device
-        ws = _workspace(L.mmk_icp_workspace_bytes(ctypes.byref(p)), dev)
         gT = grad_T.contiguous().float()
         gw = torch.empty(p.B, p.N, dtype=torch.float32, device=dev)
         gT0 = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
-        _lib.check(L.mmk_icp_backward(ctypes.byref(p), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(weight), _lib.ptr(idx),
-                                      _lib.ptr(T_hist), _lib.ptr(delta), _lib.ptr(A), _lib.ptr(active), _lib.ptr(gT),
-                                      _lib.ptr(gw), _lib.ptr(gT0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        return gw, gT0, None, None, None
+        need_src, need_tgt = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        state = [_lib.ptr(t) for t in (src, tgt, weight, idx, T_hist, delta, A, active, gT, gw, gT0)]
+        if not (need_src or need_tgt):
+            ws = _workspace(L.mmk_icp_workspace_bytes(ctypes.byref(p)), dev)
+            _lib.check(L.mmk_icp_backward(ctypes.byref(p), *state, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+            return gw, gT0, None, None, None
+        # the clouds' adjoints: the target's takes per-point rows and fixed-point sums as well (sized per call, not cached)
+        ws = torch.empty(int(L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(p), 1 if need_tgt else 0)),
+                         dtype=torch.uint8, device=dev)
+        gs = torch.empty(p.B, p.N, 3, dtype=torch.float32, device=dev) if need_src else None
+        gt = torch.empty(p.B, p.M, p.tgt_cols, dtype=torch.float32, device=dev) if need_tgt else None
+        _lib.check(L.mmk_icp_backward_points(ctypes.byref(p), *state, _lib.ptr(gs), _lib.ptr(gt), _lib.ptr(ws), ws.numel(),
+                                             _lib.stream_ptr(dev)))
+        return gw, gT0, gs, gt, None
 
 
 class ICP:
@@ -205,8 +224,9 @@ class ICP:
         else:
             raise _lib.MmkError("dICP.ICP needs an MI355X/HIP device: the ICP is a set of HIP kernels with no CPU path")
         out_device = source.device
-        src = _lib.dev_f32(source, dev)
-        tgt = _lib.dev_f32(target, dev)
+        # not detached: autograd undoes the move / cast for the clouds' gradients
+        src = source.to(device=dev, dtype=torch.float32).contiguous()
+        tgt = target.to(device=dev, dtype=torch.float32).contiguous()
         B, N, _ = src.shape
         M = tgt.shape[1]
         if T_init is None:
@@ -217,7 +237,7 @@ class ICP:
         if weight is not None:
             w = weight.to(device=dev, dtype=torch.float32).contiguous()
         need_grad = self.differentiable and torch.is_grad_enabled() and (
-            (w is not None and w.requires_grad) or T0.requires_grad)
+            (w is not None and w.requires_grad) or T0.requires_grad or src.requires_grad or tgt.requires_grad)
         p = self._params(B, N, M, tgt.shape[-1], dim, loss_fn, trim_dist, save_state=need_grad)
         if need_grad:
             if w is None:

@@ -266,7 +266,8 @@ def _polar_to_cart_pair(img_a, img_b, azimuths, radar_resolution, cart_pixel_wid
 class _SampleWeights(torch.autograd.Function):
     """Bilinear gather of the mask at the scan points; backward is the
     scatter-add into the 4 taps (what autograd does for F.grid_sample at
-    radar_utils.py:126)."""
+    radar_utils.py:126) and, when the points require grad, the bilinear slope at
+    each point (mmk_sample_weights_bwd_pc)."""
 
     @staticmethod
     def forward(ctx, mask, pc, cart_resolution, cart_pixel_width=640):
@@ -276,7 +277,7 @@ class _SampleWeights(torch.autograd.Function):
         _lib.check(_lib.lib().mmk_sample_weights_fwd(_lib.ptr(mask, torch.float32, "mask"), _lib.ptr(pc), B, N, cols,
                                                      H, W, int(cart_pixel_width), float(cart_resolution), _lib.ptr(out),
                                                      _lib.stream_ptr(mask.device)))
-        ctx.save_for_backward(pc)
+        ctx.save_for_backward(pc, mask if ctx.needs_input_grad[1] else None)
         ctx.shape = (B, H, W)
         ctx.cres = float(cart_resolution)
         ctx.cw = int(cart_pixel_width)
@@ -284,7 +285,7 @@ class _SampleWeights(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gw):
-        (pc,) = ctx.saved_tensors
+        pc, mask = ctx.saved_tensors
         B, H, W = ctx.shape
         gw = gw.contiguous().float()
         gmask = torch.empty(B, H, W, dtype=torch.float32, device=gw.device)
@@ -292,7 +293,12 @@ class _SampleWeights(torch.autograd.Function):
         ws = _workspace(nb, gw.device)
         _lib.check(_lib.lib().mmk_sample_weights_bwd(_lib.ptr(gw), _lib.ptr(pc), B, pc.shape[1], pc.shape[2], H, W,
                                                      ctx.cw, ctx.cres, _lib.ptr(gmask), _lib.ptr(ws), nb, _lib.stream_ptr(gw.device)))
-        return gmask, None, None, None
+        gpc = None
+        if ctx.needs_input_grad[1]:
+            gpc = torch.empty_like(pc)
+            _lib.check(_lib.lib().mmk_sample_weights_bwd_pc(_lib.ptr(gw), _lib.ptr(mask), _lib.ptr(pc), B, pc.shape[1], pc.shape[2],
+                                                            H, W, ctx.cw, ctx.cres, _lib.ptr(gpc), _lib.stream_ptr(gw.device)))
+        return gmask, gpc, None, None
 
 
 class _WeightStats(torch.autograd.Function):
@@ -328,7 +334,7 @@ def _extract_weights_stats(mask, scan_pc):
     dev = _hip_device(mask)
     m = mask if (mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous()) else \
         mask.to(device=dev, dtype=torch.float32).contiguous()
-    pc = _lib.dev_f32(scan_pc, dev)
+    pc = scan_pc.to(device=dev, dtype=torch.float32).contiguous()      # not detached: differentiable in x, y
     # point_to_cart_idx's defaults (0.2384 m, 640 px) whatever the mask's shape: radar_utils.py:112
     weights = _SampleWeights.apply(m, pc, 0.2384, 640)
     diff_mean_num_non0, st = _WeightStats.apply(weights, pc)
@@ -340,7 +346,9 @@ def _extract_weights_stats(mask, scan_pc):
 def extract_weights(mask, scan_pc):
     """radar_utils.py:108-140 -> (weights (B,N), diff_mean_num_non0, mean_num_non0,
     mean_w, max_w, min_w).  The statistics are the reference's, formed over the real points in one
-    fused pass (no boolean indexing, no host sync)."""
+    fused pass (no boolean indexing, no host sync).  The weights are differentiable in ``mask`` and, as
+    F.grid_sample is in its grid, in the x and y columns of ``scan_pc`` (its other columns and the fake
+    (0, 0) rows get 0); diff_mean_num_non0 is differentiable through the weights."""
     return _extract_weights_stats(mask, scan_pc)[0]
 
 
