@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 502 /* 0.5.2: mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 502 /* 0.5.2: mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -205,6 +205,8 @@ int mmk_bce_fft_threshold_bwd(const float *x, const float *fft, int32_t B, int64
  * mmk_cfar_mask        <- cfar_mask                      radar_utils.py:29-69
  * mmk_extract_peaks    <- extract_pc (+mean_peaks_parallel_fast, pol_2_cart)
  *                                                        radar_utils.py:71-106,167-195
+ * mmk_cfar_mask_bwd, mmk_extract_peaks_bwd <- what autograd does for the two above when
+ *                        the scan / the mask requires grad (both default to diff=True upstream)
  * mmk_polar_to_cart    <- radar_polar_to_cartesian_diff  radar_utils.py:258-336
  * mmk_cart_to_polar    <- radar_cartesian_to_polar       radar_utils.py:338-372
  * mmk_sample_weights_* <- extract_weights (fwd + autograd bwd) radar_utils.py:108-128
@@ -217,6 +219,17 @@ int mmk_cfar_mask(const float *raw, int32_t B, int32_t A, int32_t R, int32_t w2,
                   float b_thresh, int32_t diff, float steep_fact, float *mask,
                   void *stream);
 
+/* grad_raw (B,A,R) = dL/draw of mmk_cfar_mask(diff=1) <- autograd through radar_utils.py:29-69: tanh (:62) and the direct
+ * term, hardshrink's gate (:63, a constant: |0.5 t + 0.5| > 0.99 as the forward decides it), and through the threshold
+ * (:57-58) torch.maximum's winner (:56; an exact tie of the two fp32 window sums gives each window half) into every cell
+ * of the winning window (:47-54, with the slice's clamp at R).  Outside [mincol, maxcol) the threshold is the constant 1000.
+ * The window sums are recomputed with the forward's arithmetic, so gate, winner and ties are the forward's bit for bit.
+ * A gather per cell from ordered fp64 prefix sums: no atomics, bit-reproducible; grad_raw is written whole.
+ * (diff=0 has no gradient: torch.where of constants, :65.) */
+int mmk_cfar_mask_bwd(const float *raw, const float *grad_mask /*B,A,R*/, int32_t B, int32_t A, int32_t R, int32_t w2,
+                      int32_t guard, int32_t mincol, int32_t maxcol, float a_thresh, float b_thresh, float steep_fact,
+                      float *grad_raw /*B,A,R*/, void *stream);
+
 size_t mmk_extract_peaks_workspace_bytes(int32_t B, int32_t A, int32_t R, int32_t max_pts);
 /* Blob-centre extraction.  out_pc (B,max_pts,3) zero padded in the reference's
  * azimuth-major order; out_count int32 (B) = points the reference would return
@@ -226,6 +239,19 @@ int mmk_extract_peaks(const float *mask, int32_t B, int32_t A, int32_t R, float 
                       const float *T_ab, int32_t diff, float steep_fact, int32_t max_pts,
                       float *out_pc, int32_t *out_count, void *workspace,
                       size_t workspace_bytes, void *stream);
+/* grad_mask (B,A,R) = dL/dmask of mmk_extract_peaks given grad_pc (B,max_pts,3) <- autograd through radar_utils.py:74
+ * (res * j * mask), mean_peaks_parallel_fast (:167-185; diff=1: through both factors of each product, z = 1 - tanh;
+ * diff=0: z is the bool (arr == 0), a constant, and the gradient flows through the arr factors), the pair mean (:95),
+ * pol_2_cart (:187-195) and T_ab's rotation (:100).  The set of non-zero markers (nonzero, :88), their order and their
+ * pairing are constants and are placed again exactly as the forward places them.  The unpaired last marker of an odd
+ * count, points at or beyond max_pts and cells that feed no marker get exactly 0.  azimuths, times and T_ab are not
+ * differentiated.  grad_mask is written whole (no memset needed), no atomics, bit-reproducible.
+ * workspace: mmk_extract_peaks_bwd_workspace_bytes(B, A, R, max_pts) bytes. */
+size_t mmk_extract_peaks_bwd_workspace_bytes(int32_t B, int32_t A, int32_t R, int32_t max_pts);
+int mmk_extract_peaks_bwd(const float *mask, int32_t B, int32_t A, int32_t R, float res, const float *azimuths /*B,A*/,
+                          const float *T_ab, int32_t diff, float steep_fact, int32_t max_pts,
+                          const float *grad_pc /*B,max_pts,3*/, float *grad_mask /*B,A,R*/, void *workspace,
+                          size_t workspace_bytes, void *stream);
 
 /* Polar (B,A,R) -> Cartesian (B,W,W) bilinear resample.  range_grid/angle_grid (W,W)
  * are form_cart_range_angle_grid's outputs (radar_utils.py:399-419), built by the host. */

@@ -195,7 +195,10 @@ def _declare(lib):
         "mmk_unet_tensor": (ctypes.c_int, [i32, i32, i32, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i32), ctypes.POINTER(i32),
                                            ctypes.POINTER(i32)]),
         "mmk_cfar_mask": (ctypes.c_int, [c_vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, c_vp, c_vp]),
+        "mmk_cfar_mask_bwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, c_vp, c_vp]),
         "mmk_extract_peaks_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "mmk_extract_peaks_bwd_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "mmk_extract_peaks_bwd": (ctypes.c_int, [c_vp, i32, i32, i32, f32, c_vp, c_vp, i32, f32, i32, c_vp, c_vp, c_vp, sz, c_vp]),
         "mmk_extract_peaks": (ctypes.c_int, [c_vp, i32, i32, i32, f32, c_vp, c_vp, c_vp, i32, f32, i32, c_vp, c_vp,
                                              c_vp, sz, c_vp]),
         "mmk_polar_to_cart": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, f32, i32, i32, c_vp, c_vp]),

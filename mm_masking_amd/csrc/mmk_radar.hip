@@ -733,6 +733,206 @@ PeakWs carve_peaks(int B, int A, int max_pts, void *ws, size_t cap_bytes)
     return w;
 }
 
+// ------------------------------------------------------------------------------------------
+// Backward of R2 cfar_mask(diff=True) with respect to the scan: the derivative autograd takes through
+// radar_utils.py:29-69 (hardshrink's gate and torch.maximum's winner are constants; an exact tie halves).
+//   k_c   = keep_c ? g_c * 0.5 * steep * (1 - t_c^2) : 0          t_c = tanh(steep (x_c - th_c) + 2.5)
+//   gx_i  = k_i - a_th / w2 * ( sum of k_c over the cells c whose LEFT window won and holds i
+//                             + sum of k_c over the cells c whose RIGHT window won and holds i )
+// The adjoint of a windowed sum is a windowed sum: i lies in the left window [c-w2-g, c-g) of the cells
+// c in [i+g+1, i+w2+g+1) and in the right window [c+g+1, c+w2+g+1) of the cells c in [i-w2-g, i-g), so both
+// terms are differences of ordered prefix sums of kL / kR (k of the cells whose left / right window won,
+// half of it in both on a tie).  One block per row, a gather per output cell, no atomics.
+// LDS is the forward's 12 bytes per cell: the fp32 row and ONE fp64 prefix array, used three times over.
+//   1. prefix of x, summed exactly as cfar_mask_kernel sums it -> gate, winner and ties are the forward's;
+//      k and kR stay in registers (NPRE cells per thread), kL overwrites the thread's own cells of the row
+//   2. prefix of kL over the same array -> the left-window term goes to registers; kR overwrites the row
+//   3. prefix of kR over the same array -> the right-window term, and the store
+// All three prefixes are fp64 (a window sum is the difference of two prefixes as long as the row).
+// NPRE >= ceil(R / CFAR_T).
+template <int NPRE>
+__global__ __launch_bounds__(CFAR_T) void cfar_mask_bwd_kernel(const float *__restrict__ raw, const float *__restrict__ gmask,
+                                                               int R, int w2, int guard, int mincol, int maxcol, float a_th,
+                                                               float b_th, float steep, float *__restrict__ graw)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *cs = reinterpret_cast<double *>(smem);                 // R + 1
+    float *row = reinterpret_cast<float *>(cs + (R + 1));          // R
+    __shared__ double wsum[CFAR_T / 64];
+    const size_t base = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * R;
+    float kd[NPRE], kr[NPRE], sl[NPRE];
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+        const int c = threadIdx.x + i * CFAR_T;
+        kd[i] = (c < R) ? gmask[base + c] : 0.0f;                  // the upstream gradient until step 1 turns it into k
+        if (c < R) row[c] = raw[base + c];
+    }
+    __syncthreads();
+    const int L = (R + CFAR_T - 1) / CFAR_T;
+    const int c0 = min(R, (int)threadIdx.x * L), c1 = min(R, c0 + L);
+    auto prefix = [&]() {                                          // cs[c] = sum of row[0..c), as the forward forms it
+        double s = 0.0;
+        for (int c = c0; c < c1; ++c) s += (double)row[c];
+        double tot;
+        double run = block_excl_scan<CFAR_T>(s, wsum, &tot);
+        for (int c = c0; c < c1; ++c) {
+            cs[c] = run;
+            run += (double)row[c];
+        }
+        if (threadIdx.x == CFAR_T - 1) cs[R] = tot;
+        __syncthreads();
+    };
+    prefix();
+    // (in steps 1 and 2 a cell of `row` is touched by its own thread only, while every thread reads windows of cs)
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+        const int c = threadIdx.x + i * CFAR_T;
+        kr[i] = 0.0f;
+        if (c < R) {
+            float th = 1000.0f, left = 0.0f, right = 0.0f, kl = 0.0f;
+            const bool inr = c >= mincol && c < maxcol;
+            if (inr) {
+                left = (float)(cs[c - guard] - cs[c - w2 - guard]);
+                right = (float)(cs[min(R, c + w2 + guard + 1)] - cs[min(R, c + guard + 1)]);
+                const float stat = fmaxf(left, right) / (float)w2;
+                th = a_th * stat + b_th;
+            }
+            const float t = tanhf(steep * (row[c] - th) + 2.5f);
+            const float m = 0.5f * t + 0.5f;
+            const float k = (fabsf(m) > 0.99f) ? ((kd[i] * 0.5f) * (1.0f - t * t)) * steep : 0.0f;
+            kd[i] = k;
+            if (inr) {
+                kl = (left > right) ? k : ((left == right) ? 0.5f * k : 0.0f);
+                kr[i] = (right > left) ? k : ((left == right) ? 0.5f * k : 0.0f);
+            }
+            row[c] = kl;
+        }
+    }
+    __syncthreads();
+    prefix();
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+        const int c = threadIdx.x + i * CFAR_T;
+        sl[i] = 0.0f;
+        if (c < R) {
+            sl[i] = (float)(cs[min(R, c + w2 + guard + 1)] - cs[min(R, c + guard + 1)]);
+            row[c] = kr[i];
+        }
+    }
+    __syncthreads();
+    prefix();
+    const float coef = a_th / (float)w2;
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+        const int c = threadIdx.x + i * CFAR_T;
+        if (c < R) {
+            const float sr = (float)(cs[max(0, c - guard)] - cs[max(0, c - w2 - guard)]);
+            graw[base + c] = kd[i] - coef * (sl[i] + sr);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Backward of R3 + R4 with respect to the mask (radar_utils.py:71-106, :167-185).  The set of non-zero markers,
+// their order and their pairing are constants: count / scan / emit place them exactly as the forward does, then
+//   peaks_bwd_points_kernel   one thread per point: grho = (R_ab^T gp) . (cos phi, sin phi, 0), and grho / 2 is written to
+//                             both markers of the pair; every slot of the marker array is written once (0 for the unpaired
+//                             last marker of an odd count and for the pairs at or beyond max_pts)
+//   peaks_bwd_rows_kernel     one block per row: the row's markers are placed again (the emit kernel's partition and scan)
+//                             and their gv spread over an LDS image of the row; every cell then gathers gv[j-1], gv[j] and
+//                             the neighbouring a, z:  ga_j = gv_j z_{j+1} + gv_{j-1} z_{j-1},
+//                             gz_j = gv_{j-1} a_{j-1} + gv_j a_{j+1},  diff: ga_j -= gz_j steep (1 - tanh^2(steep a_j)),
+//                             gm_j = res j ga_j.  Every cell is written; a cell between two zero gv gets exactly 0.
+__global__ void peaks_bwd_points_kernel(const int32_t *__restrict__ mrow, int cap, const int32_t *__restrict__ total,
+                                        const float *__restrict__ az, const float *__restrict__ T_ab, int A, int max_pts,
+                                        const float *__restrict__ grad_pc, float *__restrict__ gv)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (k >= max_pts) return;
+    const int npts = total[b] / 2;
+    float g = 0.0f;
+    const size_t m = (size_t)b * cap + 2 * k;                       // cap = 2 max_pts: the grid covers every slot
+    if (k < npts) {
+        const float phi = (az[b * A + mrow[m + 1]] + az[b * A + mrow[m]]) / 2.0f;
+        const float *gp = grad_pc + ((size_t)b * max_pts + k) * 3;
+        float gx = gp[0], gy = gp[1];
+        if (T_ab) {
+            const float *T = T_ab + (size_t)b * 16;
+            const float gz = gp[2];
+            const float tx = (T[0] * gx + T[4] * gy) + T[8] * gz;
+            const float ty = (T[1] * gx + T[5] * gy) + T[9] * gz;
+            gx = tx; gy = ty;
+        }
+        g = (gx * cosf(phi) + gy * sinf(phi)) / 2.0f;
+    }
+    gv[m] = g;
+    gv[m + 1] = g;
+}
+
+__global__ __launch_bounds__(RT) void peaks_bwd_rows_kernel(const float *__restrict__ mask, int R, float res, int diff,
+                                                            float steep, const int32_t *__restrict__ row_off, int cap,
+                                                            const float *__restrict__ gv, float *__restrict__ gmask)
+{
+    extern __shared__ __attribute__((aligned(16))) float lrow_dyn[];
+    __shared__ int sm[RT / 64];
+    float *gvr = lrow_dyn + R;                                      // R: gv of the marker stored at column j, else 0
+    const int a = blockIdx.x, b = blockIdx.y, A = gridDim.x;
+    const int rowid = b * A + a;
+    for (int c = threadIdx.x; c < R; c += RT) gvr[c] = 0.0f;
+    const float *mrow = stage_row(mask + (size_t)rowid * R, R, lrow_dyn);
+    const int L = (R - 1 + RT - 1) / RT;
+    const int j0 = min(R - 1, (int)threadIdx.x * L), j1 = min(R - 1, j0 + L);
+    int cnt = 0;
+    for (int j = j0; j < j1; ++j) cnt += (peak_value(mrow, j, R, res, diff, steep) != 0.0f) ? 1 : 0;
+    int tot;
+    int g = row_off[rowid] + block_excl_scan_i(cnt, sm, &tot);
+    if (cnt != 0) {
+        for (int j = j0; j < j1; ++j) {
+            if (peak_value(mrow, j, R, res, diff, steep) != 0.0f) {
+                if (g < cap) gvr[j] = gv[(size_t)b * cap + g];
+                ++g;
+            }
+        }
+    }
+    __syncthreads();
+    float *out = gmask + (size_t)rowid * R;
+    auto aval = [&](int j) -> float { return (res * (float)j) * mrow[j]; };
+    auto zval = [&](float av) -> float { return diff ? 1.0f - tanhf(steep * av) : ((av == 0.0f) ? 1.0f : 0.0f); };
+    for (int j = threadIdx.x; j < R; j += RT) {
+        const float g1 = gvr[j], g0 = (j > 0) ? gvr[j - 1] : 0.0f;  // gvr[R - 1] = 0: no marker is stored there
+        float gm = 0.0f;
+        if (g0 != 0.0f || g1 != 0.0f) {
+            const float ap = (j > 0) ? aval(j - 1) : 0.0f, an = (j + 1 < R) ? aval(j + 1) : 0.0f;
+            float ga = g1 * zval(an) + g0 * zval(ap);
+            if (diff) {
+                const float t = tanhf(steep * aval(j));
+                const float gz = g0 * ap + g1 * an;
+                ga += gz * (-steep * (1.0f - t * t));
+            }
+            gm = (res * (float)j) * ga;
+        }
+        out[j] = gm;
+    }
+}
+
+struct PeakBwdWs {
+    PeakWs f;
+    float *gv;
+    size_t bytes;
+};
+
+PeakBwdWs carve_peaks_bwd(int B, int A, int max_pts, void *ws, size_t cap_bytes)
+{
+    PeakBwdWs w;
+    w.f = carve_peaks(B, A, max_pts, ws, cap_bytes);
+    mmk::Arena ar(ws, cap_bytes);
+    ar.off = w.f.bytes;
+    w.gv = ar.take<float>((size_t)B * w.f.cap);
+    w.bytes = mmk::align_up(ar.off, 256);
+    return w;
+}
+
 }  // namespace
 
 // ================================================================================== C ABI
@@ -799,6 +999,75 @@ extern "C" int mmk_extract_peaks(const float *mask, int32_t B, int32_t A, int32_
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(peaks_pair_kernel, dim3((max_pts + 255) / 256, B), dim3(256), 0, st, w.mval, w.mrow, w.cap,
                        w.total, azimuths, T_ab, A, max_pts, out_pc, out_count);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_cfar_mask_bwd(const float *raw, const float *grad_mask, int32_t B, int32_t A, int32_t R, int32_t w2,
+                                 int32_t guard, int32_t mincol, int32_t maxcol, float a_thresh, float b_thresh,
+                                 float steep_fact, float *grad_raw, void *stream)
+{
+    MMK_REQUIRE(raw && grad_mask && grad_raw, "mmk_cfar_mask_bwd: NULL pointer");
+    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 1, "mmk_cfar_mask_bwd: raw_scans must be 3D with non-empty dims");
+    MMK_REQUIRE(w2 >= 1 && guard >= 0, "mmk_cfar_mask_bwd: bad window (w2=%d guard=%d)", w2, guard);
+    MMK_REQUIRE(mincol >= w2 + guard && maxcol <= R, "mmk_cfar_mask_bwd: column range [%d,%d) outside the row", mincol, maxcol);
+    const size_t smem = (size_t)(R + 1) * sizeof(double) + (size_t)R * sizeof(float);
+    MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask_bwd: R=%d does not fit the 160 KB LDS row buffer", R);
+    hipStream_t st = (hipStream_t)stream;
+    if (R <= 8 * CFAR_T) {
+        hipLaunchKernelGGL(cfar_mask_bwd_kernel<8>, dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard, mincol, maxcol,
+                           a_thresh, b_thresh, steep_fact, grad_raw);
+    } else {
+        // the longest row of the LDS budget: (160 KB - 64) / 12 B = 13 648 cells = 26.7 per thread
+        constexpr int NLONG = 27;
+        static_assert((size_t)NLONG * CFAR_T * 12 >= 160 * 1024, "cfar_mask_bwd_kernel<NLONG> must hold every row the LDS admits");
+        if (smem > 64 * 1024)
+            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)cfar_mask_bwd_kernel<NLONG>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)smem));
+        hipLaunchKernelGGL(cfar_mask_bwd_kernel<NLONG>, dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard, mincol,
+                           maxcol, a_thresh, b_thresh, steep_fact, grad_raw);
+    }
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" size_t mmk_extract_peaks_bwd_workspace_bytes(int32_t B, int32_t A, int32_t R, int32_t max_pts)
+{
+    (void)R;
+    if (B < 1 || A < 1 || max_pts < 1) return 0;
+    return carve_peaks_bwd(B, A, max_pts, nullptr, 0).bytes;
+}
+
+extern "C" int mmk_extract_peaks_bwd(const float *mask, int32_t B, int32_t A, int32_t R, float res, const float *azimuths,
+                                     const float *T_ab, int32_t diff, float steep_fact, int32_t max_pts, const float *grad_pc,
+                                     float *grad_mask, void *workspace, size_t workspace_bytes, void *stream)
+{
+    MMK_REQUIRE(mask && azimuths && grad_pc && grad_mask, "mmk_extract_peaks_bwd: NULL pointer");
+    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 2 && max_pts >= 1, "mmk_extract_peaks_bwd: bad shape");
+    const PeakBwdWs w = carve_peaks_bwd(B, A, max_pts, workspace, workspace_bytes);
+    if (workspace == nullptr || w.bytes > workspace_bytes) {
+        mmk::set_error("mmk_extract_peaks_bwd: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
+        return MMK_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t row_lds = (size_t)R * sizeof(float);
+    MMK_REQUIRE(row_lds <= 64 * 1024 - 64, "mmk_extract_peaks_bwd: R=%d does not fit the LDS row buffer", R);
+    if (2 * row_lds > 64 * 1024)
+        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)peaks_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)(2 * row_lds)));
+    // the forward's own placement: same kernels, same arguments
+    hipLaunchKernelGGL(peaks_count_kernel, dim3(A, B), dim3(RT), row_lds, st, mask, R, res, diff, steep_fact, w.f.row_count);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(peaks_scan_kernel, dim3(B), dim3(RT), 0, st, w.f.row_count, A, w.f.row_off, w.f.total);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(peaks_emit_kernel, dim3(A, B), dim3(RT), row_lds, st, mask, R, res, diff, steep_fact, w.f.row_off, w.f.cap,
+                       w.f.mval, w.f.mrow);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(peaks_bwd_points_kernel, dim3((max_pts + 255) / 256, B), dim3(256), 0, st, w.f.mrow, w.f.cap, w.f.total,
+                       azimuths, T_ab, A, max_pts, grad_pc, w.gv);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(peaks_bwd_rows_kernel, dim3(A, B), dim3(RT), 2 * row_lds, st, mask, R, res, diff, steep_fact, w.f.row_off,
+                       w.f.cap, w.gv, grad_mask);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

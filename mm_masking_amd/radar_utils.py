@@ -174,34 +174,58 @@ def cfar_cols(n_range, res, width=101, minr=2.0, maxr=80.0, guard=5):
     return w2, mincol, maxcol
 
 
-def cfar_mask(raw_scans, res, width=101, minr=2.0, maxr=80.0, guard=5,
-              a_thresh=1.0, b_thresh=0.09, diff=True, steep_fact=10.0):
-    """GO-CFAR mask, radar_utils.py:29-69.  (B,A,R) fp32 -> (B,A,R) fp32."""
-    assert raw_scans.ndim == 3, "raw_scans must be 3D"
-    dev = _hip_device(raw_scans)
-    x = _lib.dev_f32(raw_scans, dev)
+def _cfar_forward(x, w2, guard, mincol, maxcol, a_thresh, b_thresh, diff, steep_fact):
     B, A, R = x.shape
-    w2, mincol, maxcol = cfar_cols(R, res, width, minr, maxr, guard)
     out = torch.empty_like(x)
     _lib.check(_lib.lib().mmk_cfar_mask(_lib.ptr(x), B, A, R, w2, guard, mincol, max(mincol, maxcol),
                                         float(a_thresh), float(b_thresh), 1 if diff else 0, float(steep_fact),
-                                        _lib.ptr(out), _lib.stream_ptr(dev)))
-    return _back(out, raw_scans)
+                                        _lib.ptr(out), _lib.stream_ptr(x.device)))
+    return out
+
+
+class _CfarMask(torch.autograd.Function):
+    """cfar_mask(diff=True) with the gradient autograd takes through radar_utils.py:29-69 (mmk_cfar_mask_bwd): tanh's
+    slope on the cells hardshrink keeps, directly and through the GO-CFAR threshold into the winning window."""
+
+    @staticmethod
+    def forward(ctx, raw_scans, dev, cols, a_thresh, b_thresh, steep_fact):
+        x = _lib.dev_f32(raw_scans, dev)
+        out = _cfar_forward(x, *cols, a_thresh, b_thresh, True, steep_fact)
+        ctx.save_for_backward(x)
+        ctx.args = (cols, float(a_thresh), float(b_thresh), float(steep_fact))
+        ctx.like = (raw_scans.dtype, raw_scans.device)
+        return _back(out, raw_scans)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        (w2, guard, mincol, maxcol), a_thresh, b_thresh, steep_fact = ctx.args
+        B, A, R = x.shape
+        g = _lib.dev_f32(g, x.device)
+        gx = torch.empty_like(x)
+        _lib.check(_lib.lib().mmk_cfar_mask_bwd(_lib.ptr(x), _lib.ptr(g), B, A, R, w2, guard, mincol, max(mincol, maxcol),
+                                                a_thresh, b_thresh, steep_fact, _lib.ptr(gx), _lib.stream_ptr(x.device)))
+        return gx.to(device=ctx.like[1], dtype=ctx.like[0]), None, None, None, None, None
+
+
+def cfar_mask(raw_scans, res, width=101, minr=2.0, maxr=80.0, guard=5,
+              a_thresh=1.0, b_thresh=0.09, diff=True, steep_fact=10.0):
+    """GO-CFAR mask, radar_utils.py:29-69.  (B,A,R) fp32 -> (B,A,R) fp32.  With ``diff=True`` the mask is
+    differentiable in ``raw_scans`` (the gradient comes back in its dtype and on its device); with ``diff=False`` it
+    does not require grad, as upstream (torch.where of constants)."""
+    assert raw_scans.ndim == 3, "raw_scans must be 3D"
+    dev = _hip_device(raw_scans)
+    w2, mincol, maxcol = cfar_cols(raw_scans.shape[2], res, width, minr, maxr, guard)
+    if diff and torch.is_grad_enabled() and raw_scans.requires_grad:
+        return _CfarMask.apply(raw_scans, dev, (w2, guard, mincol, maxcol), a_thresh, b_thresh, steep_fact)
+    x = _lib.dev_f32(raw_scans, dev)
+    return _back(_cfar_forward(x, w2, guard, mincol, maxcol, a_thresh, b_thresh, diff, steep_fact), raw_scans)
 
 
 # ----------------------------------------------------------------------------- R3 + R4
-def extract_pc_padded(thres_mask, res, azimuth_angles, azimuth_times, max_pts, T_ab=None, diff=True,
-                      steep_fact=10.0):
-    """Batched form of ``extract_pc``: zero-padded (B,max_pts,3) cloud in the
-    reference's azimuth-major order plus the per-item point count (int32 (B,)),
-    with no host synchronisation.  This is the layout the dataset hands to the
-    policy (icp_weight_dataset.py:379-381)."""
-    dev = _hip_device(thres_mask)
-    m = _lib.dev_f32(thres_mask, dev)
-    az = _lib.dev_f32(azimuth_angles, dev)
-    tm = _lib.dev_f32(azimuth_times, dev) if azimuth_times is not None else None
-    Tab = _lib.dev_f32(T_ab, dev).reshape(-1, 16) if T_ab is not None else None
+def _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts):
     B, A, R = m.shape
+    dev = m.device
     L = _lib.lib()
     nbytes = L.mmk_extract_peaks_workspace_bytes(B, A, R, int(max_pts))
     ws = _workspace(nbytes, dev)
@@ -213,9 +237,59 @@ def extract_pc_padded(thres_mask, res, azimuth_angles, azimuth_times, max_pts, T
     return pc, cnt
 
 
+class _ExtractPeaks(torch.autograd.Function):
+    """extract_pc_padded with the gradient autograd takes through radar_utils.py:71-106 / :167-185 with respect to the
+    mask (mmk_extract_peaks_bwd).  The marker set, its order and its pairing are constants; so are the azimuths and T_ab."""
+
+    @staticmethod
+    def forward(ctx, thres_mask, m, res, az, tm, Tab, diff, steep_fact, max_pts):
+        pc, cnt = _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts)
+        ctx.save_for_backward(m, az, Tab)
+        ctx.args = (float(res), 1 if diff else 0, float(steep_fact), int(max_pts))
+        ctx.like = (thres_mask.dtype, thres_mask.device)
+        ctx.mark_non_differentiable(cnt)
+        return pc, cnt
+
+    @staticmethod
+    def backward(ctx, gpc, _gcnt):
+        m, az, Tab = ctx.saved_tensors
+        res, diff, steep_fact, max_pts = ctx.args
+        B, A, R = m.shape
+        dev = m.device
+        gpc = _lib.dev_f32(gpc, dev)
+        L = _lib.lib()
+        nbytes = L.mmk_extract_peaks_bwd_workspace_bytes(B, A, R, max_pts)
+        ws = _workspace(nbytes, dev)
+        gm = torch.empty_like(m)
+        _lib.check(L.mmk_extract_peaks_bwd(_lib.ptr(m), B, A, R, res, _lib.ptr(az), _lib.ptr(Tab), diff, steep_fact, max_pts,
+                                           _lib.ptr(gpc), _lib.ptr(gm), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return (gm.to(device=ctx.like[1], dtype=ctx.like[0]),) + (None,) * 8
+
+
+def extract_pc_padded(thres_mask, res, azimuth_angles, azimuth_times, max_pts, T_ab=None, diff=True,
+                      steep_fact=10.0):
+    """Batched form of ``extract_pc``: zero-padded (B,max_pts,3) cloud in the
+    reference's azimuth-major order plus the per-item point count (int32 (B,)),
+    with no host synchronisation.  This is the layout the dataset hands to the
+    policy (icp_weight_dataset.py:379-381).  The cloud is differentiable in
+    ``thres_mask`` for both values of ``diff`` (the gradient comes back in the mask's
+    dtype and on its device); ``azimuth_angles``, ``azimuth_times`` and ``T_ab`` are
+    constants, and the count is a non-differentiable int32 tensor."""
+    dev = _hip_device(thres_mask)
+    m = _lib.dev_f32(thres_mask, dev)
+    az = _lib.dev_f32(azimuth_angles, dev)
+    tm = _lib.dev_f32(azimuth_times, dev) if azimuth_times is not None else None
+    Tab = _lib.dev_f32(T_ab, dev).reshape(-1, 16) if T_ab is not None else None
+    if torch.is_grad_enabled() and thres_mask.requires_grad:
+        return _ExtractPeaks.apply(thres_mask, m, res, az, tm, Tab, diff, steep_fact, max_pts)
+    return _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts)
+
+
 def extract_pc(thres_mask, res, azimuth_angles, azimuth_times, T_ab=None, diff=True, steep_fact=10.0):
     """radar_utils.py:71-106: Python list of ragged (n_i,3) clouds (one host sync
-    to read the counts, as the reference's ``nonzero`` implies)."""
+    to read the counts, as the reference's ``nonzero`` implies).  When ``thres_mask``
+    requires grad the clouds are slices of the padded cloud that keep its graph, so a
+    loss on a list element reaches the mask; the azimuths and ``T_ab`` are constants."""
     B, A, R = thres_mask.shape
     cap = (A * (R - 1) + 1) // 2
     cap = min(cap, 1 << 20)
