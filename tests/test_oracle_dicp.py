@@ -190,3 +190,54 @@ def test_kat_trim_boundary_closed_form(r2, kept):
     want = kat.two_group_delta_y(r2, n1, n2, r1, None, 1.0, 5.0)
     assert abs(d[1] - want) <= 2e-7 * max(1.0, abs(want))
     assert (abs(want - r1) < 1e-7) == (not kept)
+
+
+# ----------------------------------------------------------------------------- gradients through frozen pairs
+import icp_freeze_cases as fc  # noqa: E402
+
+
+def test_freeze_case_builder_conditions_hold():
+    """Every shared case of tests/icp_freeze_cases.py builds: its own assertions (two different freeze iterations, a pair
+    frozen for >= 2 iterations, every ||delta_k|| a factor 2 from the tolerance, non-zero reference gradients per pair; the
+    degenerate pairs inert in the oracle) hold for the inputs as they are today."""
+    for case in fc.CASES:
+        c = fc.frozen_case(*case)
+        assert c["active"].shape == (fc.K, fc.B) and c["margin"] >= 2.0
+    assert fc.frozen_case("pt2pl", "huber", 2)["n_active"].tolist() == [3, 2, 1]
+    fc.frozen_case("pt2pl", "huber", 2, with_weight=False)
+    for case in fc.DEGENERATE_CASES:
+        fc.degenerate_case(*case)
+
+
+def test_oracle_gradient_finite_difference_through_freezes():
+    """Pins the oracle's gradient where pairs freeze (pt2pl / huber / dim 2, tolerance 3e-3: 3 / 2 / 1 active iterations of
+    8): fp64 restatement with the fp32 run's correspondences, autograd against central differences in weights of all three
+    pairs and in T_init entries, and the freeze schedule is the same in every perturbed run (a freeze is a constant)."""
+    c = fc.frozen_case("pt2pl", "huber", 2)
+    src, tgt, w0, T0, G = (torch.from_numpy(a) for a in c["arrays"])
+    fixed = list(c["hist"]["idx"])
+    fixed += [fixed[-1]] * (fc.K - len(fixed))           # the oracle broke off once every pair was frozen
+    want = c["active"]
+    ref = dicp_ref.ICPRef("pt2pl", differentiable=True, max_iterations=fc.K, tolerance=c["tol"])
+
+    def f(wv, Tv):
+        o = ref.icp(src, tgt, T_init=Tv, weight=wv, trim_dist=fc.TRIM, loss_fn=fc.loss_dict("huber"), dim=2,
+                    dtype=torch.float64, fixed_idx=fixed)
+        assert np.array_equal(fc.schedule(o["hist"]), want)
+        return (o["T"] * G.double()).sum()
+
+    w = w0.double().requires_grad_(True)
+    T = T0.double().requires_grad_(True)
+    f(w, T).backward()
+    eps = 1e-6
+
+    def check(x, g, where):
+        xp = x.detach().clone(); xp[where] += eps
+        xm = x.detach().clone(); xm[where] -= eps
+        fd = ((f(xp, T.detach()) - f(xm, T.detach())) if x is w else (f(w.detach(), xp) - f(w.detach(), xm))).item() / (2 * eps)
+        assert abs(fd - g[where].item()) <= 1e-5 * max(1e-3, abs(fd)) + 1e-9, (where, fd, g[where].item())
+
+    for where in ((0, 0), (0, 17), (0, 399), (1, 63), (1, 250), (2, 5), (2, 311)):
+        check(w, w.grad, where)
+    for where in ((0, 0, 3), (0, 1, 0), (1, 1, 3), (1, 0, 1), (2, 1, 0), (2, 0, 3), (2, 1, 1)):
+        check(T, T.grad, where)
