@@ -209,6 +209,8 @@ int mmk_bce_fft_threshold_bwd(const float *x, const float *fft, int32_t B, int64
  *                        the scan / the mask requires grad (both default to diff=True upstream)
  * mmk_polar_to_cart    <- radar_polar_to_cartesian_diff  radar_utils.py:258-336
  * mmk_cart_to_polar    <- radar_cartesian_to_polar       radar_utils.py:338-372
+ * mmk_polar_to_cart_bwd, mmk_cart_to_polar_bwd <- what autograd does for the two above when
+ *                        the image requires grad (both are plain F.grid_sample calls upstream)
  * mmk_sample_weights_* <- extract_weights (fwd + autograd bwd) radar_utils.py:108-128
  * mmk_bev_raster       <- extract_bev_from_pts           radar_utils.py:142-165      */
 
@@ -274,6 +276,36 @@ int mmk_polar_to_cart_pair(const float *polar, const float *polar2, const float 
 int mmk_cart_to_polar(const double *cart, const double *sin_az, const double *cos_az, const double *range_coords,
                       int32_t B, int32_t A, int32_t R, int32_t H, int32_t W, double cart_resolution, double *polar,
                       void *stream);
+
+/* grad_polar (B,A,R) = dL/dpolar of mmk_polar_to_cart given grad_cart (B,W,W) <- autograd through the F.grid_sample at
+ * radar_utils.py:334 and the wrap-row concatenation at :318.  The operator is linear in the image: the sampling grid
+ * (:286-323: wobble search, the u < 0 -> 0 clamp, the + 1 row of interpolate_crossover, the normalisation) depends on the
+ * azimuths and the pixel grid only, which are constants, and is recomputed with the forward's arithmetic bit for bit.
+ * Tap (yk, xk) adds g * w_tap to cell (row(yk), xk); with the crossover rows, padded row 0 folds onto row A - 1 and padded
+ * row A + 1 onto row 0; taps in the zero padding contribute nowhere.
+ * The sums are formed in 64-bit fixed point with integer atomics (per item: scale = the power of two that keeps
+ * 4 W^2 * max|g| below 2^62), so they do not depend on the order of arrival: no float atomics, bit-reproducible, a
+ * resolution of max|g| * 2^(ceil(log2(4 W^2)) - 62) per tap.  grad_polar is written whole (cells no tap reaches get exactly
+ * 0; a non-finite grad_cart makes its item NaN).  ws: mmk_polar_to_cart_bwd_ws_bytes(B, A, R, W) bytes. */
+size_t mmk_polar_to_cart_bwd_ws_bytes(int32_t B, int32_t A, int32_t R, int32_t W);
+int mmk_polar_to_cart_bwd(const float *grad_cart /*B,W,W*/, const float *azimuths /*B,A*/, const float *range_grid,
+                          const float *angle_grid, int32_t B, int32_t A, int32_t R, int32_t W, float radar_resolution,
+                          int32_t interpolate_crossover, int32_t fix_wobble, float *grad_polar /*B,A,R*/, void *ws,
+                          size_t ws_bytes, void *stream);
+
+/* grad_cart (B,H,W) = dL/dcart of mmk_cart_to_polar given grad_polar (B,A,R), fp64 <- autograd through the F.grid_sample
+ * at radar_utils.py:370; the sampling grid (:342-363) is a constant.  sin_az, cos_az and range_coords are the forward's
+ * host-formed arrays; radar_resolution is the spacing of range_coords (it bounds how many samples of one ray can reach one
+ * pixel: ceil(2 sqrt 2 cart_resolution / radar_resolution) + 1).  The four in-image taps of every polar cell receive
+ * g * {(1-wy)(1-wx), (1-wy) wx, wy (1-wx), wy wx}.  Same fixed-point form as mmk_polar_to_cart_bwd, with the count bound
+ * A * (ceil(2 sqrt 2 cart_resolution / radar_resolution) + 1): a resolution of max|g| * 2^(cnt_bits - 62) per tap (2^-49 of
+ * max|g| at 400 x 3360 -> 640 x 640).  The sums are formed in grad_cart itself, which is written whole (pixels no ray touches
+ * get exactly 0).  No float atomics, bit-reproducible.  ws: mmk_cart_to_polar_bwd_ws_bytes(B, A, R, H, W) bytes. */
+size_t mmk_cart_to_polar_bwd_ws_bytes(int32_t B, int32_t A, int32_t R, int32_t H, int32_t W);
+int mmk_cart_to_polar_bwd(const double *grad_polar /*B,A,R*/, const double *sin_az, const double *cos_az,
+                          const double *range_coords, int32_t B, int32_t A, int32_t R, int32_t H, int32_t W,
+                          double radar_resolution, double cart_resolution, double *grad_cart /*B,H,W*/, void *ws,
+                          size_t ws_bytes, void *stream);
 
 /* weights[b,n] = bilinear(mask[b], point n) with zero padding; fake points
  * (x==0 && y==0) get 0.  cart_resolution / cart_pixel_width as point_to_cart_idx

@@ -355,27 +355,17 @@ __global__ __launch_bounds__(256) void cart_to_polar_kernel(const double *__rest
     polar[((size_t)b * A + a) * R + r] = fma(t3, wy * wx, fma(t2, wy * ex, fma(t1, sy1 * wx, t0 * (sy1 * ex))));
 }
 
-// R5 radar_polar_to_cartesian_diff (radar_utils.py:258-336).  One thread per Cartesian
-// pixel; the batch item's azimuth table sits in LDS for the binary search (wobble fix).
-__global__ __launch_bounds__(256) void polar_to_cart_kernel(const float *__restrict__ polar,
-                                                            const float *__restrict__ az,
-                                                            const float *__restrict__ rgrid,
-                                                            const float *__restrict__ agrid, int A, int R, int W,
-                                                            float res, float half_res, int wrap, int fix_wobble,
-                                                            float *__restrict__ cart, const float *__restrict__ polar2,
-                                                            float *__restrict__ cart2)
+// Sampling position of one Cartesian pixel in the (wrap-padded) polar image: radar_utils.py:286-323 and the normalise /
+// denormalise round trip of F.grid_sample(align_corners=True).  Shared by the forward kernel and its adjoint, which therefore
+// see the same taps and weights bit for bit (the library is built with -ffp-contract=off).  `laz`: the item's azimuth table.
+struct PolarTaps {
+    int xi, yi;          // top-left tap: column, row of the padded image
+    float wx, wy;        // ix - x0, iy - y0
+};
+
+__device__ __forceinline__ PolarTaps polar_taps(const float *laz, float rng, float ang, int A, int R, float res, float half_res,
+                                                int wrap, int fix_wobble)
 {
-    extern __shared__ float laz[];
-    const int b = blockIdx.y;
-    for (int i = threadIdx.x; i < A; i += blockDim.x) laz[i] = az[(size_t)b * A + i];
-    __syncthreads();
-    // a block is a 32 x 8 patch of the Cartesian image (compact footprint in the polar one: the taps of
-    // neighbouring lanes share cache lines), not a 256-pixel strip of one row
-    const int tiles_x = (W + 31) >> 5;
-    const int px = (blockIdx.x % tiles_x) * 32 + (threadIdx.x & 31), py = (blockIdx.x / tiles_x) * 8 + (threadIdx.x >> 5);
-    if (px >= W || py >= W) return;
-    const int pix = py * W + px;
-    const float rng = rgrid[pix], ang = agrid[pix];
     float u = (rng - half_res) / res;
     float v;
     if (fix_wobble) {
@@ -409,9 +399,39 @@ __global__ __launch_bounds__(256) void polar_to_cart_kernel(const float *__restr
     const float ix = ((gx + 1.0f) / 2.0f) * (float)(R - 1);
     const float iy = ((gy + 1.0f) / 2.0f) * (float)(rows - 1);
     const float x0 = floorf(ix), y0 = floorf(iy);
-    const float wx = ix - x0, wy = iy - y0;
+    PolarTaps t;
+    t.wx = ix - x0;
+    t.wy = iy - y0;
+    t.xi = (int)x0;
+    t.yi = (int)y0;
+    return t;
+}
+
+// R5 radar_polar_to_cartesian_diff (radar_utils.py:258-336).  One thread per Cartesian
+// pixel; the batch item's azimuth table sits in LDS for the binary search (wobble fix).
+__global__ __launch_bounds__(256) void polar_to_cart_kernel(const float *__restrict__ polar,
+                                                            const float *__restrict__ az,
+                                                            const float *__restrict__ rgrid,
+                                                            const float *__restrict__ agrid, int A, int R, int W,
+                                                            float res, float half_res, int wrap, int fix_wobble,
+                                                            float *__restrict__ cart, const float *__restrict__ polar2,
+                                                            float *__restrict__ cart2)
+{
+    extern __shared__ float laz[];
+    const int b = blockIdx.y;
+    for (int i = threadIdx.x; i < A; i += blockDim.x) laz[i] = az[(size_t)b * A + i];
+    __syncthreads();
+    // a block is a 32 x 8 patch of the Cartesian image (compact footprint in the polar one: the taps of
+    // neighbouring lanes share cache lines), not a 256-pixel strip of one row
+    const int tiles_x = (W + 31) >> 5;
+    const int px = (blockIdx.x % tiles_x) * 32 + (threadIdx.x & 31), py = (blockIdx.x / tiles_x) * 8 + (threadIdx.x >> 5);
+    if (px >= W || py >= W) return;
+    const int pix = py * W + px;
+    const int rows = wrap ? A + 2 : A;
+    const PolarTaps t = polar_taps(laz, rgrid[pix], agrid[pix], A, R, res, half_res, wrap, fix_wobble);
+    const int xi = t.xi, yi = t.yi;
+    const float wx = t.wx, wy = t.wy;
     const float ex = 1.0f - wx, sy = 1.0f - wy;
-    const int xi = (int)x0, yi = (int)y0;
     // The gather is bound by the number of load instructions (64 scattered addresses each), not by bytes: the two taps of a
     // row are neighbours in memory, so each row of each image is ONE 8-byte load (4-byte aligned) instead of two 4-byte ones, all
     // four issued back to back; the zero padding is applied as selects afterwards.  Same products, same order of additions as
@@ -933,6 +953,191 @@ PeakBwdWs carve_peaks_bwd(int B, int A, int max_pts, void *ws, size_t cap_bytes)
     return w;
 }
 
+
+// ------------------------------------------------------------------------------------------
+// Adjoints of the two resamplers with respect to their image.  Both operators are linear in the image, so each adjoint is
+// the scatter of g * w_tap over the forward's taps; the taps are recomputed with the forward's own arithmetic.  Several taps
+// fall on one destination (up to hundreds: every ray's first samples on the four centre pixels), and float atomics would make
+// the sum depend on their order of arrival, so the sums are formed in 64-bit FIXED POINT, as icp_bwd_target_*_kernel forms
+// them (mmk_icp.hip): integer additions commute, the result is the same bit pattern whatever the order.
+//   absmax   the item's largest |g| as float bits (fp64: the high word), by an integer max
+//   scatter  v = llrint(g * w * scale) added to the destination's 64-bit word; scale is the power of two that puts the largest
+//            possible sum, count * max|g|, below 2^62: scale = 2^(62 - cnt_bits - e), max|g| < 2^e, count <= 2^cnt_bits
+//   final    destination = word / scale; a word no tap touched is 0 and gives exactly 0.  A non-finite g makes the item NaN.
+// Resolution: one contribution is rounded to max|g| * 2^(cnt_bits - 62), the sum of n of them to n/2 times that.
+template <typename T>
+__device__ __forceinline__ unsigned abs_bits(T v);
+template <>
+__device__ __forceinline__ unsigned abs_bits<float>(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+template <>
+__device__ __forceinline__ unsigned abs_bits<double>(double v) { return (unsigned)((unsigned long long)__double_as_longlong(v) >> 32) & 0x7fffffffu; }
+
+template <typename T>
+__global__ __launch_bounds__(256) void absmax_bits_kernel(const T *__restrict__ g, size_t n, unsigned *__restrict__ pmax)
+{
+    const int b = blockIdx.y;
+    const T *gb = g + (size_t)b * n;
+    unsigned m = 0u;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = max(m, abs_bits<T>(gb[i]));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+    if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(&pmax[b], m);
+}
+
+// max|g| < 2^e from the bits above; 0.0 = non-finite gradient.  EXPB / BIAS: 23 / 126 for fp32 bits, 20 / 1022 for the high
+// word of an fp64 (subnormals included: their exponent field is 0).  The exponent of the scale is capped so that it stays finite.
+template <typename T>
+__device__ __forceinline__ double fixed_scale(unsigned mbits, int cnt_bits)
+{
+    constexpr bool F = sizeof(T) == 4;
+    if (mbits >= (F ? 0x7f800000u : 0x7ff00000u)) return 0.0;
+    if (mbits == 0u) return 1.0;
+    const int e = (int)(mbits >> (F ? 23 : 20)) - (F ? 126 : 1022);
+    return ldexp(1.0, min(62 - cnt_bits - e, 1000));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fixed_final_kernel(const unsigned long long *acc, const unsigned *__restrict__ pmax,
+                                                          int cnt_bits, size_t n, T *out)
+{
+    // (acc and out may be the same buffer when T is 8 bytes wide: a thread reads its word before it writes it)
+    const int b = blockIdx.y;
+    const double scale = fixed_scale<T>(pmax[b], cnt_bits);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const long long a = (long long)acc[(size_t)b * n + i];
+        out[(size_t)b * n + i] = scale == 0.0 ? (T)__builtin_nan("") : (T)((double)a / scale);
+    }
+}
+
+// Adjoint of R5 (radar_utils.py:258-336).  One thread per Cartesian pixel, the forward's tiling; tap (yk, xk) of the padded
+// image adds g * w to polar cell (row(yk), xk): with the crossover rows, padded row 0 is row A - 1, padded row A + 1 is row 0
+// (the adjoint of the concatenation at :318), every other row yk - 1.  Taps outside the image contribute nowhere.
+__global__ __launch_bounds__(256) void polar_to_cart_bwd_scatter_kernel(const float *__restrict__ gcart, const float *__restrict__ az,
+                                                                        const float *__restrict__ rgrid,
+                                                                        const float *__restrict__ agrid, int A, int R, int W,
+                                                                        float res, float half_res, int wrap, int fix_wobble,
+                                                                        const unsigned *__restrict__ pmax, int cnt_bits,
+                                                                        unsigned long long *__restrict__ acc)
+{
+    extern __shared__ float laz[];
+    const int b = blockIdx.y;
+    for (int i = threadIdx.x; i < A; i += blockDim.x) laz[i] = az[(size_t)b * A + i];
+    __syncthreads();
+    const double scale = fixed_scale<float>(pmax[b], cnt_bits);
+    if (scale == 0.0) return;
+    const int tiles_x = (W + 31) >> 5;
+    const int px = (blockIdx.x % tiles_x) * 32 + (threadIdx.x & 31), py = (blockIdx.x / tiles_x) * 8 + (threadIdx.x >> 5);
+    if (px >= W || py >= W) return;
+    const int pix = py * W + px;
+    const float g = gcart[(size_t)b * W * W + pix];
+    if (g == 0.0f) return;
+    const int rows = wrap ? A + 2 : A;
+    const PolarTaps t = polar_taps(laz, rgrid[pix], agrid[pix], A, R, res, half_res, wrap, fix_wobble);
+    const float ex = 1.0f - t.wx, sy = 1.0f - t.wy;
+    const float w[4] = {sy * ex, sy * t.wx, t.wy * ex, t.wy * t.wx};        // the forward's four products
+    unsigned long long *ab = acc + (size_t)b * A * R;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int yk = t.yi + (q >> 1), xk = t.xi + (q & 1);
+        if (xk < 0 || xk >= R || yk < 0 || yk >= rows) continue;
+        int r = yk;
+        if (wrap) r = (yk == 0) ? (A - 1) : ((yk == A + 1) ? 0 : yk - 1);
+        const long long v = llrint(((double)g * (double)w[q]) * scale);
+        if (v != 0) atomicAdd(&ab[(size_t)r * R + xk], (unsigned long long)v);
+    }
+}
+
+// Adjoint of 8f.3 (radar_utils.py:338-372), fp64.  One thread per polar cell with the forward's arithmetic and its coalesced
+// accesses; a cell whose four taps all lie outside the image does not read its gradient.  Neighbouring samples of a ray are
+// radar_resolution / cart_resolution of a pixel apart (0.25 at the default sizes), so runs of consecutive lanes share their
+// 2 x 2 taps (a ray's coordinates are monotone in the range, so the lanes with one tap corner are contiguous): a segmented
+// wave scan adds up their fixed-point values and the first lane of a run adds once per tap -- at the sensor, where every ray's
+// first samples meet on the four centre pixels, a quarter of the atomics on those addresses.  A thread walking eight cells
+// of a ray and summing in registers was measured too: 2.14 ms against 1.47 ms at B = 32 (its 64-byte-strided reads alone
+// cost 1.0 ms).
+__global__ __launch_bounds__(256) void cart_to_polar_bwd_scatter_kernel(const double *__restrict__ gpolar, const double *__restrict__ sin_az,
+                                                                        const double *__restrict__ cos_az,
+                                                                        const double *__restrict__ range_coords, int A, int R, int H,
+                                                                        int W, double cart_resolution,
+                                                                        const unsigned *__restrict__ pmax, int cnt_bits,
+                                                                        unsigned long long *__restrict__ acc)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int a = blockIdx.y, b = blockIdx.z;
+    const int lane = threadIdx.x & 63;
+    const double scale = fixed_scale<double>(pmax[b], cnt_bits);
+    if (scale == 0.0) return;
+    const bool valid = r < R;
+    const double rc = range_coords[valid ? r : R - 1];
+    const double sx = sin_az[(size_t)b * A + a] * rc, sy = cos_az[(size_t)b * A + a] * rc;
+    double u = sx / cart_resolution, v = -sy / cart_resolution;
+    u = u / (double)(W - 1) * 2.0;
+    v = v / (double)(H - 1) * 2.0;
+    const double ix = ((u + 1.0) / 2.0) * (double)(W - 1), iy = ((v + 1.0) / 2.0) * (double)(H - 1);
+    const double x0 = floor(ix), y0 = floor(iy);
+    const double wx = ix - x0, wy = iy - y0, ex = 1.0 - wx, sy1 = 1.0 - wy;
+    // (a sample far outside the image has no tap in it: clamping keeps the conversion to int defined)
+    const int xi = (int)fmin(fmax(x0, -2.0), (double)W), yi = (int)fmin(fmax(y0, -2.0), (double)H);
+    const bool inimg = xi >= -1 && xi < W && yi >= -1 && yi < H;
+    const double g = (valid && inimg) ? gpolar[((size_t)b * A + a) * R + r] : 0.0;
+    long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    if (g != 0.0) {
+        s0 = llrint((g * (sy1 * ex)) * scale);
+        s1 = llrint((g * (sy1 * wx)) * scale);
+        s2 = llrint((g * (wy * ex)) * scale);
+        s3 = llrint((g * (wy * wx)) * scale);
+    }
+    if (__ballot((s0 | s1 | s2 | s3) != 0) == 0ull) return;                 // (uniform over the wave)
+    const int key = valid ? yi * (W + 4) + xi : -0x7fffffff;
+    const int kprev = __shfl_up(key, 1, 64);
+    const bool head = lane == 0 || kprev != key;
+    const unsigned long long heads = __ballot(head);
+    // first lane of the next run (64 when this run reaches the end of the wave)
+    const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1));
+    const int next_head = later ? lane + 1 + (__ffsll(later) - 1) : 64;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const long long t0 = __shfl_down(s0, off, 64), t1 = __shfl_down(s1, off, 64), t2 = __shfl_down(s2, off, 64),
+                        t3 = __shfl_down(s3, off, 64);
+        if (lane + off < next_head) {
+            s0 += t0; s1 += t1; s2 += t2; s3 += t3;
+        }
+    }
+    if (!head || !valid) return;
+    unsigned long long *ab = acc + (size_t)b * H * W;
+    const bool x0ok = xi >= 0 && xi < W, x1ok = xi + 1 >= 0 && xi + 1 < W;
+    const bool y0ok = yi >= 0 && yi < H, y1ok = yi + 1 >= 0 && yi + 1 < H;
+    if (s0 != 0 && y0ok && x0ok) atomicAdd(&ab[(size_t)yi * W + xi], (unsigned long long)s0);
+    if (s1 != 0 && y0ok && x1ok) atomicAdd(&ab[(size_t)yi * W + xi + 1], (unsigned long long)s1);
+    if (s2 != 0 && y1ok && x0ok) atomicAdd(&ab[(size_t)(yi + 1) * W + xi], (unsigned long long)s2);
+    if (s3 != 0 && y1ok && x1ok) atomicAdd(&ab[(size_t)(yi + 1) * W + xi + 1], (unsigned long long)s3);
+}
+
+int ceil_log2(double x)
+{
+    int bits = 0;
+    while (bits < 62 && (double)(1ull << bits) < x) ++bits;
+    return bits;
+}
+
+struct ResampleBwdWs {
+    unsigned *pmax;
+    unsigned long long *acc;
+    size_t bytes;
+};
+
+ResampleBwdWs carve_resample_bwd(int B, size_t acc_words, void *ws, size_t cap_bytes)
+{
+    mmk::Arena ar(ws, cap_bytes);
+    ResampleBwdWs w;
+    w.pmax = ar.take<unsigned>((size_t)B);
+    w.acc = ar.take<unsigned long long>(acc_words);
+    w.bytes = mmk::align_up(ar.off, 256);
+    return w;
+}
+
+inline int stream_blocks(size_t n) { return (int)std::min<size_t>((n + 2047) / 2048, 2048); }
+
 }  // namespace
 
 // ================================================================================== C ABI
@@ -1097,6 +1302,81 @@ extern "C" int mmk_cart_to_polar(const double *cart, const double *sin_az, const
     MMK_REQUIRE(cart_resolution > 0.0, "mmk_cart_to_polar: cart_resolution must be positive");
     hipLaunchKernelGGL(cart_to_polar_kernel, dim3((R + 255) / 256, A, B), dim3(256), 0, (hipStream_t)stream, cart, sin_az, cos_az,
                        range_coords, A, R, H, W, cart_resolution, polar);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" size_t mmk_polar_to_cart_bwd_ws_bytes(int32_t B, int32_t A, int32_t R, int32_t W)
+{
+    if (B < 1 || A < 2 || R < 2 || W < 1) return 0;
+    return carve_resample_bwd(B, (size_t)B * A * R, nullptr, 0).bytes;
+}
+
+extern "C" int mmk_polar_to_cart_bwd(const float *grad_cart, const float *azimuths, const float *range_grid, const float *angle_grid,
+                                     int32_t B, int32_t A, int32_t R, int32_t W, float radar_resolution,
+                                     int32_t interpolate_crossover, int32_t fix_wobble, float *grad_polar, void *ws,
+                                     size_t ws_bytes, void *stream)
+{
+    MMK_REQUIRE(grad_cart && azimuths && range_grid && angle_grid && grad_polar, "mmk_polar_to_cart_bwd: NULL pointer");
+    MMK_REQUIRE(B >= 1 && B <= 65535 && A >= 2 && R >= 2 && W >= 1 && W <= 16384, "mmk_polar_to_cart_bwd: bad shape");
+    MMK_REQUIRE((size_t)A * 4 <= 64 * 1024, "mmk_polar_to_cart_bwd: too many azimuths (%d)", A);
+    const ResampleBwdWs w = carve_resample_bwd(B, (size_t)B * A * R, ws, ws_bytes);
+    if (ws == nullptr || w.bytes > ws_bytes) {
+        mmk::set_error("mmk_polar_to_cart_bwd: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
+        return MMK_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ncart = (size_t)W * W, npolar = (size_t)A * R;
+    const int cnt_bits = ceil_log2(4.0 * (double)ncart);               // every tap of every pixel on one cell
+    const float half_res = (float)((double)radar_resolution / 2.0);
+    MMK_CHECK_HIP(hipMemsetAsync(w.pmax, 0, sizeof(unsigned) * (size_t)B, st));
+    MMK_CHECK_HIP(hipMemsetAsync(w.acc, 0, sizeof(unsigned long long) * (size_t)B * npolar, st));
+    hipLaunchKernelGGL(absmax_bits_kernel<float>, dim3(stream_blocks(ncart), B), dim3(256), 0, st, grad_cart, ncart, w.pmax);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(polar_to_cart_bwd_scatter_kernel, dim3(((W + 31) / 32) * ((W + 7) / 8), B), dim3(256), (size_t)A * 4, st,
+                       grad_cart, azimuths, range_grid, angle_grid, A, R, W, radar_resolution, half_res,
+                       interpolate_crossover ? 1 : 0, fix_wobble ? 1 : 0, w.pmax, cnt_bits, w.acc);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fixed_final_kernel<float>, dim3(stream_blocks(npolar), B), dim3(256), 0, st, w.acc, w.pmax, cnt_bits, npolar,
+                       grad_polar);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" size_t mmk_cart_to_polar_bwd_ws_bytes(int32_t B, int32_t A, int32_t R, int32_t H, int32_t W)
+{
+    if (B < 1 || A < 1 || R < 1 || H < 2 || W < 2) return 0;
+    return carve_resample_bwd(B, 0, nullptr, 0).bytes;                  // the sums are formed in grad_cart itself
+}
+
+extern "C" int mmk_cart_to_polar_bwd(const double *grad_polar, const double *sin_az, const double *cos_az, const double *range_coords,
+                                     int32_t B, int32_t A, int32_t R, int32_t H, int32_t W, double radar_resolution,
+                                     double cart_resolution, double *grad_cart, void *ws, size_t ws_bytes, void *stream)
+{
+    MMK_REQUIRE(grad_polar && sin_az && cos_az && range_coords && grad_cart, "mmk_cart_to_polar_bwd: NULL pointer");
+    MMK_REQUIRE(B >= 1 && B <= 65535 && A >= 1 && R >= 1 && H >= 2 && W >= 2, "mmk_cart_to_polar_bwd: bad shape");
+    MMK_REQUIRE(A <= 65535, "mmk_cart_to_polar_bwd: too many azimuths (%d)", A);
+    MMK_REQUIRE(cart_resolution > 0.0 && radar_resolution > 0.0, "mmk_cart_to_polar_bwd: resolutions must be positive");
+    const ResampleBwdWs w = carve_resample_bwd(B, 0, ws, ws_bytes);
+    if (ws == nullptr || w.bytes > ws_bytes) {
+        mmk::set_error("mmk_cart_to_polar_bwd: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
+        return MMK_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ncart = (size_t)H * W, npolar = (size_t)A * R;
+    // a ray crosses the 2 x 2 tap neighbourhood of a pixel (diagonal 2 sqrt 2 pixels) in at most this many samples
+    const double per_ray = std::min((double)R, ceil(2.0 * sqrt(2.0) * cart_resolution / radar_resolution) + 1.0);
+    const int cnt_bits = ceil_log2((double)A * per_ray);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(grad_cart);
+    MMK_CHECK_HIP(hipMemsetAsync(w.pmax, 0, sizeof(unsigned) * (size_t)B, st));
+    MMK_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * (size_t)B * ncart, st));
+    hipLaunchKernelGGL(absmax_bits_kernel<double>, dim3(stream_blocks(npolar), B), dim3(256), 0, st, grad_polar, npolar, w.pmax);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cart_to_polar_bwd_scatter_kernel, dim3((R + 255) / 256, A, B), dim3(256), 0, st, grad_polar, sin_az, cos_az,
+                       range_coords, A, R, H, W, cart_resolution, w.pmax, cnt_bits, acc);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fixed_final_kernel<double>, dim3(stream_blocks(ncart), B), dim3(256), 0, st, acc, w.pmax, cnt_bits, ncart,
+                       grad_cart);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

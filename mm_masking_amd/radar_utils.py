@@ -138,30 +138,76 @@ def radar_polar_to_cartesian(*args, **kwargs):
                               "use radar_polar_to_cartesian_diff")
 
 
+def _cart_to_polar_geometry(azimuths, radar_resolution, polar_pixel_shape, dev):
+    """sin / cos of the azimuths and the range coordinates, formed on the host with the reference's own torch CPU calls."""
+    az = azimuths.detach().to(device="cpu", dtype=torch.float64)
+    rc = form_polar_range_grid(polar_resolution=radar_resolution, polar_pixel_shape=polar_pixel_shape, dtype=torch.float64,
+                               device="cpu")[0]
+    return torch.sin(az).to(dev).contiguous(), torch.cos(az).to(dev).contiguous(), rc.contiguous().to(dev)
+
+
+def _cart_to_polar_forward(x, s_az, c_az, rc, cart_resolution):
+    B, H, W = x.shape
+    A, R = s_az.shape[1], rc.shape[0]
+    out = torch.empty(B, A, R, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().mmk_cart_to_polar(_lib.ptr(x), _lib.ptr(s_az), _lib.ptr(c_az), _lib.ptr(rc), B, A, R, H, W,
+                                            float(cart_resolution), _lib.ptr(out), _lib.stream_ptr(x.device)))
+    return out
+
+
+class _CartToPolar(torch.autograd.Function):
+    """radar_cartesian_to_polar with the gradient autograd takes through the F.grid_sample at radar_utils.py:370 with
+    respect to the image (mmk_cart_to_polar_bwd).  The operator is linear in the image; the azimuths and both resolutions
+    are constants."""
+
+    @staticmethod
+    def forward(ctx, cart, dev, s_az, c_az, rc, radar_resolution, cart_resolution):
+        x = cart.detach().to(dev).contiguous()
+        out = _cart_to_polar_forward(x, s_az, c_az, rc, cart_resolution)
+        ctx.save_for_backward(s_az, c_az, rc)
+        ctx.args = (tuple(x.shape), float(radar_resolution), float(cart_resolution))
+        ctx.like = cart.device
+        return _back(out, cart)
+
+    @staticmethod
+    def backward(ctx, g):
+        s_az, c_az, rc = ctx.saved_tensors
+        (B, H, W), radar_resolution, cart_resolution = ctx.args
+        A, R = s_az.shape[1], rc.shape[0]
+        dev = s_az.device
+        g = g.detach().to(device=dev, dtype=torch.float64).contiguous()
+        L = _lib.lib()
+        nbytes = int(L.mmk_cart_to_polar_bwd_ws_bytes(B, A, R, H, W))
+        ws = _workspace(nbytes, dev)
+        gx = torch.empty(B, H, W, dtype=torch.float64, device=dev)
+        _lib.check(L.mmk_cart_to_polar_bwd(_lib.ptr(g), _lib.ptr(s_az), _lib.ptr(c_az), _lib.ptr(rc), B, A, R, H, W,
+                                           radar_resolution, cart_resolution, _lib.ptr(gx), _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_ptr(dev)))
+        return (gx.to(ctx.like),) + (None,) * 6
+
+
 def radar_cartesian_to_polar(cart, azimuths, radar_resolution, cart_resolution=0.2384, polar_pixel_shape=(400, 3360)):
     """radar_utils.py:338-372.  (B,H,W) fp64 + (B,A) -> (B,A,R) fp64, bit-identical to the reference.
     As upstream, only an fp64 image is accepted: the reference casts its sampling grid to double (:370)
-    and ``F.grid_sample`` raises ``RuntimeError`` on the dtype mismatch for anything else — same error here.
+    and ``F.grid_sample`` raises ``RuntimeError`` on the dtype mismatch for anything else — same error here
+    (a caller with an fp32 mask writes ``mask.double()``).
     sin / cos of the azimuths and the range coordinates are formed on the host with the reference's own
-    torch CPU calls (B*A + R numbers); products, divisions and the bilinear gather run in the HIP kernel."""
+    torch CPU calls (B*A + R numbers); products, divisions and the bilinear gather run in the HIP kernel.
+    The result is differentiable in ``cart`` (the gradient comes back in fp64 on its device); the azimuths
+    and the resolutions are constants."""
     if cart.dtype != torch.float64:
         raise RuntimeError("expected scalar type Float but found Double" if cart.dtype == torch.float32 else
                            "expected scalar type %s but found Double" % str(cart.dtype).replace("torch.", "").capitalize())
     dev = _hip_device(cart)
-    x = cart.detach().to(dev).contiguous()
-    B, H, W = x.shape
+    B, H, W = cart.shape
     A, R = int(polar_pixel_shape[0]), int(polar_pixel_shape[1])
     if azimuths.shape != (B, A):
         raise ValueError("azimuths must be (B, %d) (got %s)" % (A, tuple(azimuths.shape)))
-    az = azimuths.detach().to(device="cpu", dtype=torch.float64)
-    rc = form_polar_range_grid(polar_resolution=radar_resolution, polar_pixel_shape=polar_pixel_shape, dtype=torch.float64,
-                               device="cpu")[0]
-    s_az, c_az = torch.sin(az).to(dev).contiguous(), torch.cos(az).to(dev).contiguous()
-    rc = rc.contiguous().to(dev)
-    out = torch.empty(B, A, R, dtype=torch.float64, device=dev)
-    _lib.check(_lib.lib().mmk_cart_to_polar(_lib.ptr(x), _lib.ptr(s_az), _lib.ptr(c_az), _lib.ptr(rc), B, A, R, H, W,
-                                            float(cart_resolution), _lib.ptr(out), _lib.stream_ptr(dev)))
-    return _back(out, cart)
+    s_az, c_az, rc = _cart_to_polar_geometry(azimuths, radar_resolution, polar_pixel_shape, dev)
+    if torch.is_grad_enabled() and cart.requires_grad:
+        return _CartToPolar.apply(cart, dev, s_az, c_az, rc, radar_resolution, cart_resolution)
+    x = cart.detach().to(dev).contiguous()
+    return _back(_cart_to_polar_forward(x, s_az, c_az, rc, cart_resolution), cart)
 
 
 # ----------------------------------------------------------------------------- R2
@@ -300,22 +346,59 @@ def extract_pc(thres_mask, res, azimuth_angles, azimuth_times, T_ab=None, diff=T
 
 
 # ----------------------------------------------------------------------------- R5
+def _polar_to_cart_forward(x, az, W, radar_resolution, interpolate_crossover, fix_wobble):
+    B, A, R = x.shape
+    rg, ag = _device_grids(W, x.device)
+    out = torch.empty(B, W, W, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().mmk_polar_to_cart(_lib.ptr(x), _lib.ptr(az), _lib.ptr(rg), _lib.ptr(ag), B, A, R, W,
+                                            float(radar_resolution), 1 if interpolate_crossover else 0,
+                                            1 if fix_wobble else 0, _lib.ptr(out), _lib.stream_ptr(x.device)))
+    return out
+
+
+class _PolarToCart(torch.autograd.Function):
+    """radar_polar_to_cartesian_diff with the gradient autograd takes through the F.grid_sample at radar_utils.py:334 and
+    the wrap rows of :318 with respect to the polar image (mmk_polar_to_cart_bwd).  The operator is linear in the image;
+    the azimuths, the pixel grid and the resolution are constants."""
+
+    @staticmethod
+    def forward(ctx, fft_data, dev, az, W, radar_resolution, interpolate_crossover, fix_wobble):
+        x = _lib.dev_f32(fft_data, dev)
+        out = _polar_to_cart_forward(x, az, W, radar_resolution, interpolate_crossover, fix_wobble)
+        ctx.save_for_backward(az)
+        ctx.args = (tuple(x.shape), W, float(radar_resolution), 1 if interpolate_crossover else 0, 1 if fix_wobble else 0)
+        ctx.like = (fft_data.dtype, fft_data.device)
+        return _back(out, fft_data)
+
+    @staticmethod
+    def backward(ctx, g):
+        (az,) = ctx.saved_tensors
+        (B, A, R), W, radar_resolution, crossover, wobble = ctx.args
+        dev = az.device
+        g = _lib.dev_f32(g, dev)
+        rg, ag = _device_grids(W, dev)
+        L = _lib.lib()
+        nbytes = int(L.mmk_polar_to_cart_bwd_ws_bytes(B, A, R, W))
+        ws = _workspace(nbytes, dev)
+        gx = torch.empty(B, A, R, dtype=torch.float32, device=dev)
+        _lib.check(L.mmk_polar_to_cart_bwd(_lib.ptr(g), _lib.ptr(az), _lib.ptr(rg), _lib.ptr(ag), B, A, R, W, radar_resolution,
+                                           crossover, wobble, _lib.ptr(gx), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return (gx.to(device=ctx.like[1], dtype=ctx.like[0]),) + (None,) * 6
+
+
 def radar_polar_to_cartesian_diff(fft_data, azimuths, radar_resolution, cart_resolution=0.2384, cart_pixel_width=640,
                                   interpolate_crossover=True, fix_wobble=True):
     """radar_utils.py:258-336.  (B,A,R) + (B,A) -> (B,W,W).  As upstream, the
     pixel grid is built with the default 0.2384 m resolution whatever
-    ``cart_resolution`` says (radar_utils.py:276)."""
+    ``cart_resolution`` says (radar_utils.py:276).  The image is differentiable in ``fft_data`` (the gradient comes
+    back in its dtype and on its device); the azimuths are constants."""
     dev = _hip_device(fft_data)
-    x = _lib.dev_f32(fft_data, dev)
     az = _lib.dev_f32(azimuths, dev)
-    B, A, R = x.shape
     W = int(cart_pixel_width)
-    rg, ag = _device_grids(W, dev)
-    out = torch.empty(B, W, W, dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().mmk_polar_to_cart(_lib.ptr(x), _lib.ptr(az), _lib.ptr(rg), _lib.ptr(ag), B, A, R, W,
-                                            float(radar_resolution), 1 if interpolate_crossover else 0,
-                                            1 if fix_wobble else 0, _lib.ptr(out), _lib.stream_ptr(dev)))
-    return _back(out, fft_data)
+    if torch.is_grad_enabled() and fft_data.requires_grad:
+        return _PolarToCart.apply(fft_data, dev, az, W, radar_resolution, interpolate_crossover, fix_wobble)
+    x = _lib.dev_f32(fft_data, dev)
+    return _back(_polar_to_cart_forward(x, az, W, radar_resolution, interpolate_crossover, fix_wobble), fft_data)
 
 
 def _polar_to_cart_pair(img_a, img_b, azimuths, radar_resolution, cart_pixel_width=640):
