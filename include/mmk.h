@@ -392,7 +392,9 @@ typedef struct {
                               icp_weight_policy.py:106): forward max(v, slope v) instead of ReLU; relu_src
                               epilogues use (src > 0 ? scale : src < 0 or -0.0 ? slope*scale : 0) -- a kept
                               zero is stored as -0.0, a dropped element as +0.0.  0 = ReLU              */
-    float drop_p;          /* forward: inverted dropout with this probability (0 = none)    */
+    float drop_p;          /* forward: inverted dropout with this probability, quantised to thr / 65536 with
+                              thr = round(65536 p): thr = 0 (p < 2^-17) is no dropout, thr = 65536
+                              (p >= 1 - 2^-17) is refused like p >= 1                             */
     uint32_t seed;
     void *pool_y;          /* optional bf16 (B,H/2,W/2,O1): nn.MaxPool2d(2,2) of y1 written by the same
                               pass (forward role, single output; layers for which

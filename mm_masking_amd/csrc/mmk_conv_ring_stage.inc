@@ -90,7 +90,7 @@
             }
 #pragma unroll
             for (int r = 0; r < 8; ++r) v8[r] = fmaxf(__builtin_fmaf(v8[r], dk, bs8[r]), relu_lo);
-            if (a.drop_p > 0.f) {
+            if (dp.thr != 0u) {
                 const unsigned e4 = (unsigned)pix0 * 8u + __umul24((unsigned)lpix8, 8u);
                 bool kp[4];
                 dropout_keep4(a.seed, e4, dp, kp);
@@ -132,7 +132,7 @@
                     for (int hlf = 0; hlf < 2; ++hlf)
                         pq[hlf] = pk_max_i16(cvt_pk_bf16(__builtin_fmaf(acc[m][n][2 * hlf], dk, bs[m][2 * hlf]),
                                                          __builtin_fmaf(acc[m][n][2 * hlf + 1], dk, bs[m][2 * hlf + 1])), relu_pk);
-                    if (a.drop_p > 0.f) {
+                    if (dp.thr != 0u) {
                         unsigned hw0, hw1;
                         dropout_words(a.seed, (unsigned)pix0 * (unsigned)a.COUT + __umul24((unsigned)lane_pix[n], (unsigned)a.COUT) +
                                                   (unsigned)o_e0[m], hw0, hw1);
@@ -152,7 +152,7 @@
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = fmaxf(__builtin_fmaf(acc[m][n][r], dk, bs[m][r]), relu_lo);
-                if (a.drop_p > 0.f) {
+                if (dp.thr != 0u) {
                     bool kp[4];
                     // element index (pixel * COUT + channel) mod 2^32: the tile origin's product is scalar, the
                     // in-tile pixel offset fits 24 bits

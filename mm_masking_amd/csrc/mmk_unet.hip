@@ -351,7 +351,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_kernel(const ConvArgs a,
                                 v[r] = acc[m][n][r] + bs[r];
                                 if (a.relu) v[r] = lk ? act_leaky(v[r], a.slope) : fmaxf(v[r], 0.f);
                             }
-                            if (a.drop_p > 0.f) {
+                            if (dp.thr != 0u) {
                                 float sc[4];
                                 dropout_scale4(a.seed, (unsigned)(p * a.COUT + c0), dp, sc);
 #pragma unroll
@@ -695,7 +695,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_ring_kernel(const ConvAr
     // Inverted dropout's factor 1 / keep rides in the bias addition: v = max(fma(acc, dk, bias dk), 0) (dk > 0 commutes with
     // the ReLU; dk = 1 without dropout, where the fma IS the addition), and the draws then only zero elements -- one
     // multiplication per output value less in kernels that are bound by vector-instruction issue.
-    const float dk = a.drop_p > 0.f ? dp.inv_keep : 1.f;
+    const float dk = dp.inv_keep;
     // both halves thr - 32768 - 1: (that) - draw, saturating, is negative exactly for the draws that are kept (pk_keep_mask)
     const unsigned thr1pk = ((unsigned)(dp.thr_s - 1 < -32768 ? -32768 : dp.thr_s - 1) & 0xffffu) * 0x00010001u;
 #pragma unroll
@@ -1189,7 +1189,7 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
                     const int t1s = (int)dp.thr - 32768 - 1;
                     const unsigned t1 = (unsigned)(t1s < -32768 ? -32768 : t1s) & 0xffffu;
                     const unsigned thr1 = t1 | (t1 << 16);
-                    const bool drop = a.drop_p > 0.f;
+                    const bool drop = dp.thr != 0u;
 #pragma unroll
                     for (int n = 0; n < NT; ++n) {
                         const bool okp = e_row_ok && e_x0 + n * 16 < a.W;
@@ -1250,7 +1250,7 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
                                 v[4 * m + r] = t;
                             }
                         if constexpr (!R_BWD) {
-                            if (a.drop_p > 0.f) {
+                            if (dp.thr != 0u) {
 #pragma unroll
                                 for (int m = 0; m < MT; ++m) {
                                     float sc[4];
@@ -1448,7 +1448,7 @@ int dispatch_conv_deep_plain(const ConvArgs &a, hipStream_t st)
     const bool any_acc = a.o1.accumulate != 0 || (a.o2.C > 0 && a.o2.accumulate != 0);
     const bool both1 = a.o1.relu_src != nullptr && a.o1.accumulate != 0, both2 = a.o2.C > 0 && a.o2.relu_src != nullptr && a.o2.accumulate != 0;
     const int role = (a.relu != 0 && !any_src && !any_acc) ? 1
-                   : ((a.relu == 0 && a.bias == nullptr && a.drop_p == 0.f && !both1 && !both2) ? 2 : 0);
+                   : ((a.relu == 0 && a.bias == nullptr && dropout_params(a.drop_p).thr == 0u && !both1 && !both2) ? 2 : 0);
 #define MMK_DEEP_CASE(M, R)                                                                                                        \
     if (BM == M && role == R) {                                                                                                    \
         if (M <= 64 && a.wpack_mtb == 0 && (narrow ? deep_weights_fit<M, 3>(a.CIN) : deep_weights_fit<M, 5>(a.CIN)))               \
@@ -3584,7 +3584,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16 *__restrict__ 
             const float t = __builtin_fmaf(v[j], affine[2 * (gc * 8 + j)], affine[2 * (gc * 8 + j) + 1]);
             v[j] = (t == 0.f) ? -0.f : t;
         }
-        if (drop_p > 0.f) {
+        if (dp.thr != 0u) {
             float sc[4];
             dropout_scale4(seed, (unsigned)(e * 8), dp, sc);
 #pragma unroll
@@ -3777,7 +3777,7 @@ extern "C" int mmk_conv3x3(const mmk_conv_desc *d, void *stream)
     MMK_REQUIRE(d->C1 % 8 == 0 && d->C2 % 8 == 0 && (d->C2 == 0 || d->x2), "mmk_conv3x3: bad input split %d+%d", d->C1, d->C2);
     MMK_REQUIRE(d->O1 % 8 == 0 && d->O2 % 8 == 0 && (d->O2 == 0 || d->y2), "mmk_conv3x3: bad output split %d+%d", d->O1, d->O2);
     MMK_REQUIRE(chan_ok(cin) && chan_ok(cout), "mmk_conv3x3: unsupported channel counts %d -> %d", cin, cout);
-    MMK_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "mmk_conv3x3: dropout probability out of range");
+    MMK_REQUIRE(dropout_prob_ok(d->drop_p), "mmk_conv3x3: dropout probability %g out of range (it is quantised to thr / 65536, thr <= 65535)", (double)d->drop_p);
     ConvArgs a;
     a.x1 = (const bf16 *)d->x1; a.x2 = (const bf16 *)d->x2; a.C1 = d->C1; a.C2 = d->C2;
     a.wpack = (const bf16 *)d->wpack; a.bias = d->bias;
@@ -3918,7 +3918,7 @@ extern "C" int mmk_bn_apply(const void *a, int64_t npix, int32_t C, const float 
 {
     MMK_REQUIRE(a && affine && y, "mmk_bn_apply: NULL pointer");
     MMK_REQUIRE(npix >= 1 && chan_ok(C), "mmk_bn_apply: bad shape");
-    MMK_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mmk_bn_apply: dropout probability out of range");
+    MMK_REQUIRE(dropout_prob_ok(drop_p), "mmk_bn_apply: dropout probability %g out of range (it is quantised to thr / 65536, thr <= 65535)", (double)drop_p);
     const size_t ngran = (size_t)npix * (C / 8);
     hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)std::min<size_t>((ngran + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16 *)a, ngran, C, affine, drop_p, seed, (bf16 *)y);

@@ -248,6 +248,9 @@ float dropout_scale(float p)
     return thr ? 65536.0f / (float)(65536u - thr) : 1.0f;
 }
 
+// the probabilities the convolution entry accepts (mmk_unet_shared.h: dropout_prob_ok), checked before the first launch
+bool dropout_prob_ok(float p) { return p >= 0.f && p < 1.f && (unsigned)(p * 65536.0f + 0.5f) <= 65535u; }
+
 }  // namespace
 
 extern "C" size_t mmk_unet_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cin)
@@ -299,7 +302,7 @@ extern "C" int mmk_unet_forward(const mmk_unet_desc *d, void *stream)
                 d->B, d->H, d->W, d->cin);
     MMK_REQUIRE(d->workspace_bytes >= p.ws_bytes, "mmk_unet_forward: workspace too small (%zu < %zu bytes)", d->workspace_bytes,
                 p.ws_bytes);
-    MMK_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "mmk_unet_forward: dropout probability out of range");
+    MMK_REQUIRE(dropout_prob_ok(d->drop_p), "mmk_unet_forward: dropout probability %g out of range (it is quantised to thr / 65536, thr <= 65535)", (double)d->drop_p);
     for (int i = 0; i < 2 * NCONV; ++i) MMK_REQUIRE(d->params[i] != nullptr, "mmk_unet_forward: NULL parameter %d", i);
     void *ws = d->workspace;
     const float sl = d->leaky_slope;

@@ -64,6 +64,10 @@ __host__ __device__ inline DropoutParams dropout_params(float p)
     return d;
 }
 
+// What the entry points accept: thr = 65536 (p >= 1 - 2^-17) would drop everything and make 1 / keep infinite.  thr = 0
+// (p < 2^-17) is dropout off on every path: the kernels gate on thr, not on p > 0.
+__host__ __device__ inline bool dropout_prob_ok(float p) { return p >= 0.f && p < 1.f && dropout_params(p).thr <= 65535u; }
+
 // Round 5: every step is a BIJECTION of the 32-bit state.  A 24-bit multiply alone keeps the low 24 bits of its
 // input, so the round-4 chain produced at most 2^24 different draw quadruples whatever the seed and the index: at the group
 // counts of the 640 x 640 layers (2^24.6) 78 % of the groups shared their draws with another group, and group 2^24 + k repeated
@@ -72,6 +76,8 @@ __host__ __device__ inline DropoutParams dropout_params(float p)
 // byte histograms at chi^2 / dof = 1.0, |correlation| <= 5e-4 within a group, between neighbours and between the masks of
 // consecutive layer seeds.
 // the two hash words of the group of 4 consecutive channels starting at element index e4: their four 16-bit halves are the draws
+// (restated on the host in tests/dropout_ref.py, which tests/test_gpu_dropout_masks.py holds every kernel's mask to, bit for
+// bit: the element index is pixel * COUT + channel of the LAYER's tensor, plus ConvArgs::hash_base)
 __device__ __forceinline__ void dropout_words(unsigned seed, unsigned e4, unsigned &h, unsigned &g)
 {
     const unsigned i = e4 >> 2;                       // group number

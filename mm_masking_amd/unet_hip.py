@@ -123,7 +123,8 @@ def wgrad_unpack(dWt, accumulate_into=None):
 def dropout_scale(p):
     """1/keep as the kernels apply it: the drop probability is quantised to 16 bits
     (csrc/mmk_unet.hip: dropout_params), and the scale is the exact inverse of that keep rate."""
-    thr = int(float(p) * 65536.0 + 0.5)
+    f32 = lambda v: ctypes.c_float(v).value          # the threshold is rounded in fp32 there, from the fp32 probability
+    thr = int(f32(f32(float(p)) * 65536.0 + 0.5))
     return 65536.0 / (65536 - thr) if thr else 1.0
 
 

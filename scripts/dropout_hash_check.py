@@ -2,33 +2,20 @@
 a group, between neighbouring groups / pixels / rows and between the masks of consecutive layer seeds, uniformity of the 16-bit
 draws, and -- ADVICE r04 -- how many DISTINCT draw quadruples the real group counts produce (the B = 32, 640 x 640 x 8 layers have
 2^24.6 groups).  numpy only.   python scripts/dropout_hash_check.py [variant ...]     variants: r04 (plain 24-bit multiplies), r05 (state as the addend), r05b (bijective steps: the shipped one)"""
+import os
 import sys
 
 import numpy as np
 
-M32 = np.uint64(0xffffffff)
-M24 = np.uint64(0xffffff)
-
-
-def mul24(a, b):
-    return ((a & M24) * np.uint64(b)) & M32
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from dropout_ref import M32, umul24 as mul24, words  # noqa: E402  (the one restatement of the shipped chain: tests/dropout_ref.py)
 
 
 def draws(idx, seed, variant):
     """(h, g): the two 32-bit words whose halves are the four draws of group `idx`."""
     if variant == "r05b":
-        # every step a bijection of the 32-bit state: lo24 * C + x with C EVEN is lo * (C + 1) + (hi << 24), (C + 1) odd
-        x = (mul24(idx, 0x9E3779) + np.uint64(seed) + (idx & np.uint64(0xff000000))) & M32
-        x ^= x >> np.uint64(13)
-        x = (mul24(x, 0x85EBCA) + x) & M32
-        x ^= x >> np.uint64(11)
-        x = (mul24(x, 0xC2B2AE) + x) & M32
-        x ^= x >> np.uint64(15)
-        y = x ^ np.uint64(0x85ebca6b)
-        y ^= y >> np.uint64(12)
-        y = (mul24(y, 0x7FEB34) + y) & M32
-        y ^= y >> np.uint64(14)
-        return x, y
+        # the shipped chain -- every step a bijection of the 32-bit state: lo24 * C + x with C EVEN is lo * (C + 1) + (hi << 24)
+        return words(seed, idx)
     x = (mul24(idx, 0x9E3779) + np.uint64(seed) + mul24(idx >> np.uint64(24), 0x9E3779)) & M32
     x ^= x >> np.uint64(13)
     if variant == "r04":

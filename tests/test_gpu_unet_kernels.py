@@ -394,12 +394,30 @@ def _nchw(t):
     return t.float().permute(0, 3, 1, 2)
 
 
+class _QB(torch.autograd.Function):
+    """bf16 storage point of a gradient tensor only: identity in forward, rounds the gradient in backward."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).float()
+
+
 def _forced(z_or_y, mine_nhwc, relu, scale=1.0):
     """Forward value := the HIP path's stored tensor; backward := the reference operator's
-    (ReLU mask taken from the stored tensor, as the HIP epilogues do), rounded to bf16."""
+    (ReLU mask taken from the stored tensor, as the HIP epilogues do), rounded to bf16 where the HIP path
+    stores it: the producer kernels apply the dropout factor 1 / keep in fp32 and store bf16(g * scale) on the
+    kept elements, so the gradient is scaled first and rounded then (rounding g and scaling afterwards is the
+    same tensor only for scale = 1, and made this reference differ from the kernels by one bf16 rounding per
+    element at every dropout layer: DESIGN.md 6b)."""
     mine = _nchw(mine_nhwc)
-    y = z_or_y * (mine > 0) * scale if relu else z_or_y
-    return _Q.apply(y + (mine - y).detach())
+    if not relu:
+        return _Q.apply(z_or_y + (mine - z_or_y).detach())
+    y = _QB.apply(z_or_y * (mine > 0)) * scale
+    return mine + (y - y.detach())
 
 
 def _unet_on_hip_activations(model, x, fwd, drop=0.0):
@@ -454,13 +472,16 @@ def test_unet_hip_backward_exact_on_pinned_activations(B, H, W, drop):
     (ref * gsel).sum().backward()
     names = [n for n, _ in model.named_parameters()]
     # bf16 rounding noise of the gradient tensors; a little more on the small odd-sized images, whose
-    # thin levels (down to 1 x 2 pixels) average over few elements, and with dropout, where the worst tensor (a 16-element
-    # bias sum that nearly cancels) moves between 0.011 and 0.050 with the mask's seed (eight seeds, scripts/diag_pinned_bias.py;
-    # the round-4 library gave 0.013-0.036 on the same eight)
-    tol = (0.03 if (H % 32 == 0 and W % 32 == 0) else 0.05) + (0.03 if drop > 0 else 0.0)
-    for n, a, p in zip(names, got, uh.param_list(model)):
-        rel = ((a - p.grad).norm() / (p.grad.norm() + 1e-12)).item()
-        assert rel < tol, (n, rel)
+    # thin levels (down to 1 x 2 pixels) average over few elements.  Dropout adds nothing to it, for weight and bias tensors
+    # alike: with the reference rounding the gradient behind the factor 1 / keep, as the kernels do (_forced), the worst of the
+    # 46 tensors is 0.005-0.010 over eight mask seeds at (3, 64, 160, 0.05) and 0.008 without dropout (scripts/diag_pinned_bias.py,
+    # DESIGN.md 6b).  The +0.03 this bound used to carry under dropout covered the reference's own misplaced rounding.
+    tol = 0.03 if (H % 32 == 0 and W % 32 == 0) else 0.05
+    rels = [(n, p.ndim, ((a - p.grad).norm() / (p.grad.norm() + 1e-12)).item()) for n, a, p in zip(names, got, uh.param_list(model))]
+    print("worst weight tensor %s %.4f, worst bias tensor %s %.4f" % (max((r, n) for n, d, r in rels if d == 4)[::-1] +
+                                                                      max((r, n) for n, d, r in rels if d != 4)[::-1]))
+    for n, _, rel in rels:
+        assert rel < tol, (n, rel, tol)
 
 
 def test_unet_hip_dropout_backward_scale():
