@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 502 /* 0.5.2: mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 502 /* 0.5.2: mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -484,6 +484,29 @@ int mmk_conv_first(const float *x, int32_t cin, const float *W, const float *bia
 size_t mmk_conv_first_wgrad_ws_bytes(int32_t cin);
 int mmk_conv_first_wgrad(const float *x, int32_t cin, const void *g, const float *pre, int32_t B,
                          int32_t H, int32_t Wd, float *dW, float *db, float *ws, size_t ws_bytes, void *stream);
+/* Gradient with respect to the network's input image (nothing upstream to mirror: the reference leaves its
+ * `fft_data...#.requires_grad_(True)` commented out, icp_weight_policy.py:130, and its in-place normalisation :151-159 cannot
+ * be differentiated by autograd).  Two steps:
+ * mmk_conv_first_dgrad: grad_x (B,cin,H,Wd) fp32 is WRITTEN with rscale_c * g_n,
+ *   g_n[b,c,y,x] = sum_co sum_ky,kx g[b, y+1-ky, x+1-kx, co] * W[co][c][ky][kx] over the in-image source pixels
+ *   (g = (B,H,Wd,8) bf16, the gradient mmk_conv_first_wgrad consumes; the bf16 rounding of the input is straight-through;
+ *   pre == NULL: rscale = 1).  Gather form, no float atomics, bit-reproducible.
+ *   ws (may be NULL: no statistics; else x and pre are required): mmk_conv_first_dgrad_ws_bytes(cin) bytes; the same pass then
+ *   sums per channel S1 = sum g_n and S2 = sum g_n * x_n, x_n = (x - offset) * rscale, and with minmax (the raw (min, max) pairs
+ *   of mmk_channel_minmax) counts the elements equal to each extremum -- fp64 block partials added in a fixed order.
+ * mmk_input_norm_bwd: adds the adjoint of the statistics to grad_x in place, from that ws.  MMK_NORM_MINMAX: dL/dmin =
+ *   r * (S2 - S1) and dL/dmax = -r * S2 (r = pre[2c+1]), each shared evenly among the elements equal to the extremum (as
+ *   torch.min / torch.max of a whole tensor do).  MMK_NORM_STANDARDIZE (mmk_channel_meanstd): grad_x = (g_n - S1 / n - x_n * S2 /
+ *   (n - 1)) / sigma, n = B * H * Wd.  MMK_NORM_NONE: nothing to add (no launch).  Argument errors return MMK_ERR_ARG. */
+#define MMK_NORM_NONE 0
+#define MMK_NORM_MINMAX 1
+#define MMK_NORM_STANDARDIZE 2
+size_t mmk_conv_first_dgrad_ws_bytes(int32_t cin);
+int mmk_conv_first_dgrad(const void *g, int32_t cin, const float *W, const float *x /*or NULL*/, const float *pre /*or NULL*/,
+                         const float *minmax /*or NULL*/, int32_t B, int32_t H, int32_t Wd, float *grad_x, void *ws /*or NULL*/,
+                         size_t ws_bytes, void *stream);
+int mmk_input_norm_bwd(float *grad_x, const float *x, int32_t cin, const float *pre, const float *minmax /*MINMAX only*/,
+                       int32_t mode, int32_t B, int32_t H, int32_t Wd, const void *ws, size_t ws_bytes, void *stream);
 
 /* nn.MaxPool2d(2,2) on NHWC bf16 (icp_weight_policy.py:122-123).  _bwd fuses the backward of
  * the preceding Dropout(ReLU(.)): gz = route(gy) * (d > 0 ? scale : 0), d = the pooled tensor's
@@ -587,6 +610,15 @@ int mmk_unet_backward(const mmk_unet_desc *d, const float *gmask, float *const *
 int32_t mmk_unet_grad_bucket(int32_t bucket, int32_t *first_param, int32_t *n_params);
 int mmk_unet_backward_buckets(const mmk_unet_desc *d, const float *gmask, float *const *grads, void *scratch,
                               size_t scratch_bytes, void *const *bucket_events, void *stream);
+/* mmk_unet_backward (bucket_events == NULL) or mmk_unet_backward_buckets, and in the same stream-ordered call the gradient with
+ * respect to the input image: the backward schedule runs unchanged, then mmk_conv_first_dgrad + mmk_input_norm_bwd on the
+ * gradient of the first pre-activation, which is still in scratch (the statistics' workspace is the one the first layer's
+ * weight gradient has just released).  grad_x (B,cin,H,W) fp32 is overwritten.  norm_mode: MMK_NORM_NONE (d->pre, when given,
+ * is a pair of constants), MMK_NORM_MINMAX (d->pre from mmk_channel_minmax of d->x, minmax = its raw (min, max) pairs) or
+ * MMK_NORM_STANDARDIZE (d->pre from mmk_channel_meanstd of d->x).  The gradient through extrema that were reduced over the
+ * ranks of a data-parallel job is out of scope. */
+int mmk_unet_backward_input(const mmk_unet_desc *d, const float *gmask, float *const *grads, float *grad_x, int32_t norm_mode,
+                            const float *minmax, void *scratch, size_t scratch_bytes, void *const *bucket_events, void *stream);
 /* Where an activation lives inside the workspace (tests / diagnostics): id 0..5 first conv output of encoder
  * block i, 6..11 second (post-dropout) output, 12..17 t[i] (block output after pooling), 18 + 5 j + {0..4}:
  * decoder block j's up-sampled input, a1, d1, a2, d2.  NHWC bf16 (B,h,w,c) at byte `offset`. */

@@ -70,6 +70,7 @@ class UNetDesc(ctypes.Structure):
 
 
 FINAL_BWD_WS_FLOATS = 16384        # MMK_FINAL_BWD_WS_FLOATS of include/mmk.h
+NORM_MODES = {None: 0, "none": 0, "minmax": 1, "standardize": 2}      # MMK_NORM_* of include/mmk.h
 ICP_TYPES = {"pt2pt": 0, "pt2pl": 1}
 LOSSES = {None: 0, "none": 0, "l2": 0, "cauchy": 1, "huber": 2}
 NN_METHODS = {"brute": 0, "grid": 1}
@@ -170,6 +171,9 @@ def _declare(lib):
         "mmk_conv_first": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, i32, i32, i32, f32, c_vp, c_vp]),
         "mmk_conv_first_wgrad_ws_bytes": (sz, [i32]),
         "mmk_conv_first_wgrad": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, i32, i32, i32, c_vp, c_vp, c_vp, sz, c_vp]),
+        "mmk_conv_first_dgrad_ws_bytes": (sz, [i32]),
+        "mmk_conv_first_dgrad": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, c_vp, i32, i32, i32, c_vp, c_vp, sz, c_vp]),
+        "mmk_input_norm_bwd": (ctypes.c_int, [c_vp, c_vp, i32, c_vp, c_vp, i32, i32, i32, i32, c_vp, sz, c_vp]),
         "mmk_maxpool2_fwd": (ctypes.c_int, [c_vp, i32, i32, i32, i32, c_vp, c_vp]),
         "mmk_maxpool2_bwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, f32, f32, c_vp, c_vp]),
         "mmk_maxpool2_fwd_arg": (ctypes.c_int, [c_vp, i32, i32, i32, i32, c_vp, c_vp, c_vp]),
@@ -191,6 +195,8 @@ def _declare(lib):
         "mmk_unet_backward": (ctypes.c_int, [ctypes.POINTER(UNetDesc), c_vp, ctypes.POINTER(ctypes.c_void_p), c_vp, sz, c_vp]),
         "mmk_unet_backward_buckets": (ctypes.c_int, [ctypes.POINTER(UNetDesc), c_vp, ctypes.POINTER(ctypes.c_void_p), c_vp, sz,
                                                      ctypes.POINTER(ctypes.c_void_p), c_vp]),
+        "mmk_unet_backward_input": (ctypes.c_int, [ctypes.POINTER(UNetDesc), c_vp, ctypes.POINTER(ctypes.c_void_p), c_vp, i32, c_vp,
+                                                   c_vp, sz, ctypes.POINTER(ctypes.c_void_p), c_vp]),
         "mmk_unet_grad_bucket": (i32, [i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "mmk_unet_tensor": (ctypes.c_int, [i32, i32, i32, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i32), ctypes.POINTER(i32),
                                            ctypes.POINTER(i32)]),

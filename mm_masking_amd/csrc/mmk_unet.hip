@@ -3501,6 +3501,227 @@ __global__ __launch_bounds__(256) void channel_meanstd_final_kernel(const double
 }
 
 // ------------------------------------------------------------------------------------------
+// Data gradient of the first layer: gx[b,c,y,x] = rscale_c * g_n, g_n = sum_co sum_ky,kx g[b, y+1-ky, x+1-kx, co] * W[co][c][ky][kx]
+// over the in-image source pixels (the adjoint of conv_first_kernel with respect to the normalised image; the bf16 rounding of
+// the input is straight-through).  g = (B,H,W,8) bf16, the gradient conv_first_wgrad consumes; gx = fp32 NCHW, overwritten.
+// Gather form: a thread owns its output pixels, fp32 sums in a fixed order, no atomics.
+// MODE != DG_PLAIN (a folded normalisation whose statistics depend on x): the same pass sums S1 = sum g_n and S2 = sum g_n * x_n
+// per channel, x_n = (x - offset) * rscale in fp32, and with DG_MINMAX counts the elements equal to the raw minimum and maximum;
+// fp64, one partial per block and channel, added in block order by conv_first_dgrad_stats_kernel.
+constexpr int DG_BLOCKS = 1024;      // at most this many blocks (and statistic partials) per launch
+constexpr int DG_PLAIN = MMK_NORM_NONE, DG_MINMAX = MMK_NORM_MINMAX, DG_STANDARDIZE = MMK_NORM_STANDARDIZE;   // MODE of the kernels
+
+template <int CIN>
+__device__ __forceinline__ void dgrad_stats_store(const double (&s)[CIN][4], double *red, double *__restrict__ part)
+{
+#pragma unroll
+    for (int c = 0; c < CIN; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double t = block_sum256(s[c][k], red);
+            if (threadIdx.x == 0) part[((size_t)blockIdx.x * CIN + c) * 4 + k] = t;
+        }
+}
+
+// Tiled form (W % 4 == 0): a thread owns 4 adjacent pixels of one row in every input channel.  The three rows of g it needs are
+// fetched one after the other, six 16-byte pixels each (an out-of-image pixel reads the 16-byte zero word: the loads stay
+// unconditional): 18 loads per 4 pixels instead of nine per pixel.  The row loop is not unrolled, so that one unpacked row of g
+// (48 values) is live at a time whatever CIN is.  The weights sit in LDS as [c][ky][kx][co] and are read at wave-uniform
+// addresses (two 16-byte broadcasts per tap); as scalar operands held across the walk, the 72 * CIN of them do not fit the
+// scalar registers and are parked in vector lanes (350 v_readlane per unit in the assembly of that form).
+template <int CIN, int MODE>
+__global__ __launch_bounds__(256) void conv_first_dgrad_x4_kernel(const bf16 *__restrict__ g, const float *__restrict__ Wt,
+                                                                  const float *__restrict__ x, const float *__restrict__ pre,
+                                                                  const float *__restrict__ minmax, int B, int H, int W,
+                                                                  float *__restrict__ gx, double *__restrict__ part)
+{
+    __shared__ double red[4];
+    __shared__ __attribute__((aligned(16))) float wl[CIN * 9 * 8];
+    for (int i = threadIdx.x; i < CIN * 72; i += blockDim.x) {
+        const int co = i & 7, tap = (i >> 3) % 9, c = i / 72;
+        wl[i] = Wt[(co * CIN + c) * 9 + tap];
+    }
+    __syncthreads();
+    const int Wq = W >> 2;
+    const int nu = B * H * Wq;
+    float off[CIN], rs[CIN], mn[CIN], mx[CIN];
+#pragma unroll
+    for (int c = 0; c < CIN; ++c) {
+        off[c] = pre ? pre[2 * c] : 0.f;
+        rs[c] = pre ? pre[2 * c + 1] : 1.f;
+        mn[c] = (MODE == DG_MINMAX) ? minmax[2 * c] : 0.f;
+        mx[c] = (MODE == DG_MINMAX) ? minmax[2 * c + 1] : 0.f;
+    }
+    double st[CIN][4];
+#pragma unroll
+    for (int c = 0; c < CIN; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) st[c][k] = 0.0;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nu; e += gridDim.x * blockDim.x) {
+        asm volatile("" ::: "memory");        // (the weights are re-read from LDS in every round, not kept in registers)
+        const int q = e % Wq, t = e / Wq;
+        const int y0 = t % H, b = t / H;
+        const int x0 = q * 4;
+        const bool lok = x0 > 0, hok = x0 + 4 < W;
+        float acc[CIN][4];
+#pragma unroll
+        for (int c = 0; c < CIN; ++c)
+#pragma unroll
+            for (int px = 0; px < 4; ++px) acc[c][px] = 0.f;
+#pragma unroll 1
+        for (int j = 0; j < 3; ++j) {
+            const int yy = y0 - 1 + j, ky = 2 - j;        // row of g and the tap row through which it reaches output row y0
+            const bool rok = yy >= 0 && yy < H;
+            const u32x4 *row = reinterpret_cast<const u32x4 *>(g + (((size_t)b * H + (rok ? yy : y0)) * W + x0) * 8);
+            float gf[6][8];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const bool ok = rok && (i == 0 ? lok : (i == 5 ? hok : true));
+                unpack8(*(ok ? row + (i - 1) : &g_zero16), gf[i]);
+            }
+            const float *wr = wl + ky * 24;
+#pragma unroll
+            for (int c = 0; c < CIN; ++c)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const float4 wa = *reinterpret_cast<const float4 *>(&wr[(c * 9 + kx) * 8]);
+                    const float4 wb = *reinterpret_cast<const float4 *>(&wr[(c * 9 + kx) * 8 + 4]);
+                    const float wv[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+                    for (int co = 0; co < 8; ++co)
+#pragma unroll
+                        for (int px = 0; px < 4; ++px)
+                            acc[c][px] = __builtin_fmaf(gf[px + 2 - kx][co], wv[co], acc[c][px]);
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) {
+            const size_t idx = (((size_t)b * CIN + c) * H + y0) * W + x0;
+            float4 o;
+            o.x = acc[c][0] * rs[c]; o.y = acc[c][1] * rs[c]; o.z = acc[c][2] * rs[c]; o.w = acc[c][3] * rs[c];
+            *reinterpret_cast<float4 *>(gx + idx) = o;
+            if (MODE != DG_PLAIN) {
+                const float4 xv4 = *reinterpret_cast<const float4 *>(x + idx);
+                const float xv[4] = {xv4.x, xv4.y, xv4.z, xv4.w};
+#pragma unroll
+                for (int px = 0; px < 4; ++px) {
+                    const float xn = (xv[px] - off[c]) * rs[c];
+                    st[c][0] += (double)acc[c][px];
+                    st[c][1] += (double)acc[c][px] * (double)xn;
+                    if (MODE == DG_MINMAX) {
+                        st[c][2] += (xv[px] == mn[c]) ? 1.0 : 0.0;
+                        st[c][3] += (xv[px] == mx[c]) ? 1.0 : 0.0;
+                    }
+                }
+            }
+        }
+    }
+    if (MODE != DG_PLAIN) dgrad_stats_store<CIN>(st, red, part);
+}
+
+// Any width: one thread per pixel, nine conditional 16-byte loads of g.
+template <int CIN, int MODE>
+__global__ __launch_bounds__(256) void conv_first_dgrad_kernel(const bf16 *__restrict__ g, const float *__restrict__ Wt,
+                                                               const float *__restrict__ x, const float *__restrict__ pre,
+                                                               const float *__restrict__ minmax, int B, int H, int W,
+                                                               float *__restrict__ gx, double *__restrict__ part)
+{
+    __shared__ double red[4];
+    const size_t npix = (size_t)B * H * W;
+    float off[CIN], rs[CIN], mn[CIN], mx[CIN];
+#pragma unroll
+    for (int c = 0; c < CIN; ++c) {
+        off[c] = pre ? pre[2 * c] : 0.f;
+        rs[c] = pre ? pre[2 * c + 1] : 1.f;
+        mn[c] = (MODE == DG_MINMAX) ? minmax[2 * c] : 0.f;
+        mx[c] = (MODE == DG_MINMAX) ? minmax[2 * c + 1] : 0.f;
+    }
+    double st[CIN][4];
+#pragma unroll
+    for (int c = 0; c < CIN; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) st[c][k] = 0.0;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (size_t)gridDim.x * blockDim.x) {
+        const int xx = (int)(p % W), yy = (int)((p / W) % H), b = (int)(p / ((size_t)W * H));
+        float acc[CIN];
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) acc[c] = 0.f;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ys = yy + 1 - tap / 3, xs = xx + 1 - tap % 3;
+            if (ys < 0 || ys >= H || xs < 0 || xs >= W) continue;
+            float gf[8];
+            unpack8(*reinterpret_cast<const u32x4 *>(g + (((size_t)b * H + ys) * W + xs) * 8), gf);
+#pragma unroll
+            for (int c = 0; c < CIN; ++c)
+#pragma unroll
+                for (int co = 0; co < 8; ++co) acc[c] = __builtin_fmaf(gf[co], Wt[(co * CIN + c) * 9 + tap], acc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) {
+            const size_t idx = (((size_t)b * CIN + c) * H + yy) * W + xx;
+            gx[idx] = acc[c] * rs[c];
+            if (MODE != DG_PLAIN) {
+                const float xv = x[idx];
+                const float xn = (xv - off[c]) * rs[c];
+                st[c][0] += (double)acc[c];
+                st[c][1] += (double)acc[c] * (double)xn;
+                if (MODE == DG_MINMAX) {
+                    st[c][2] += (xv == mn[c]) ? 1.0 : 0.0;
+                    st[c][3] += (xv == mx[c]) ? 1.0 : 0.0;
+                }
+            }
+        }
+    }
+    if (MODE != DG_PLAIN) dgrad_stats_store<CIN>(st, red, part);
+}
+
+// stats[c][0..3] = (S1, S2, #min, #max): the block partials added in block order.  grid = CIN blocks of 256 threads.
+__global__ __launch_bounds__(256) void conv_first_dgrad_stats_kernel(const double *__restrict__ part, int nblk, int CIN,
+                                                                     double *__restrict__ stats)
+{
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    for (int k = 0; k < 4; ++k) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < nblk; b += 256) s += part[((size_t)b * CIN + c) * 4 + k];
+        s = block_sum256(s, red);
+        if (threadIdx.x == 0) stats[c * 4 + k] = s;
+    }
+}
+
+// Adjoint of the folded normalisation's statistics, added to gx (which holds rscale * g_n) in place; grid = (blocks, B * C).
+// MINMAX: x_n = (x - m) * r, r = 1 / (M - m): dL/dm = r * (S2 - S1) and dL/dM = -r * S2, each shared evenly among the elements
+// equal to the extremum (torch.min / torch.max of a whole tensor); only those elements are rewritten.
+// else (standardisation, sigma unbiased over n): gx = (g_n - S1 / n - x_n * S2 / (n - 1)) / sigma.
+template <bool MINMAX>
+__global__ __launch_bounds__(256) void input_norm_bwd_kernel(float *__restrict__ gx, const float *__restrict__ x,
+                                                             const float *__restrict__ pre, const float *__restrict__ minmax,
+                                                             const double *__restrict__ stats, int C, size_t hw, double n)
+{
+    const int c = blockIdx.y % C;
+    const size_t base = (size_t)blockIdx.y * hw;
+    const double S1 = stats[c * 4], S2 = stats[c * 4 + 1];
+    const float off = pre[2 * c], rs = pre[2 * c + 1];
+    if (MINMAX) {
+        const float mn = minmax[2 * c], mx = minmax[2 * c + 1];
+        const float am = (float)((double)rs * (S2 - S1) / stats[c * 4 + 2]);
+        const float aM = (float)(-(double)rs * S2 / stats[c * 4 + 3]);
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += (size_t)gridDim.x * blockDim.x) {
+            const float xv = x[base + i];
+            const bool lo = xv == mn, hi = xv == mx;
+            if (lo || hi) gx[base + i] += (lo ? am : 0.f) + (hi ? aM : 0.f);
+        }
+    } else {
+        const double a = S1 / n, bq = S2 / (n - 1.0);
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += (size_t)gridDim.x * blockDim.x) {
+            const float xn = (x[base + i] - off) * rs;
+            gx[base + i] = (float)((double)gx[base + i] - (a + (double)xn * bq) * (double)rs);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // nn.BatchNorm2d of the network's batch-norm variant (params["batch_norm"], icp_weight_policy.py:108-113: it
 // follows the ReLU of each convolution), on NHWC bf16 tensors.  Training mode: batch statistics over (B,H,W) per
 // channel, fp32 partial sums per block in a fixed order + an fp64 final sum (deterministic), the running
@@ -4030,6 +4251,89 @@ extern "C" int mmk_conv_first_wgrad(const float *x, int32_t cin, const void *g, 
     }
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(conv_first_wgrad_reduce_kernel, dim3(cin), dim3(320), 0, (hipStream_t)stream, ws, (int)blocks, cin, dW, db);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" size_t mmk_conv_first_dgrad_ws_bytes(int32_t cin)
+{
+    return (size_t)(cin < 1 ? 1 : cin) * 4 * (1 + DG_BLOCKS) * sizeof(double);
+}
+
+namespace {
+template <int CIN, int MODE>
+void launch_first_dgrad(bool tiled, unsigned blocks, hipStream_t st, const bf16 *g, const float *W, const float *x, const float *pre,
+                        const float *minmax, int B, int H, int Wd, float *gx, double *part)
+{
+    if (tiled)
+        hipLaunchKernelGGL((conv_first_dgrad_x4_kernel<CIN, MODE>), dim3(blocks), dim3(256), 0, st, g, W, x, pre, minmax, B, H, Wd, gx,
+                           part);
+    else
+        hipLaunchKernelGGL((conv_first_dgrad_kernel<CIN, MODE>), dim3(blocks), dim3(256), 0, st, g, W, x, pre, minmax, B, H, Wd, gx, part);
+}
+
+template <int CIN, typename... A>
+void launch_first_dgrad_mode(int mode, A... a)
+{
+    if (mode == DG_PLAIN) launch_first_dgrad<CIN, DG_PLAIN>(a...);
+    else if (mode == DG_MINMAX) launch_first_dgrad<CIN, DG_MINMAX>(a...);
+    else launch_first_dgrad<CIN, DG_STANDARDIZE>(a...);
+}
+}  // namespace
+
+extern "C" int mmk_conv_first_dgrad(const void *g, int32_t cin, const float *W, const float *x, const float *pre, const float *minmax,
+                                    int32_t B, int32_t H, int32_t Wd, float *grad_x, void *ws, size_t ws_bytes, void *stream)
+{
+    MMK_REQUIRE(g && W && grad_x, "mmk_conv_first_dgrad: NULL pointer");
+    MMK_REQUIRE(cin >= 1 && cin <= 4 && B >= 1 && H >= 1 && Wd >= 1, "mmk_conv_first_dgrad: bad shape (cin must be 1..4)");
+    MMK_REQUIRE(ws || !minmax, "mmk_conv_first_dgrad: the tie counts of minmax need the statistics workspace");
+    MMK_REQUIRE(!ws || (x && pre), "mmk_conv_first_dgrad: the statistics need x and pre (NULL pointer)");
+    MMK_REQUIRE(!ws || ws_bytes >= mmk_conv_first_dgrad_ws_bytes(cin), "mmk_conv_first_dgrad: workspace too small (%zu < %zu bytes)",
+                ws_bytes, mmk_conv_first_dgrad_ws_bytes(cin));
+    MMK_REQUIRE(((uintptr_t)g & 15) == 0, "mmk_conv_first_dgrad: g must be 16-byte aligned");
+    const int mode = !ws ? DG_PLAIN : (minmax ? DG_MINMAX : DG_STANDARDIZE);
+    const size_t npix = (size_t)B * H * Wd;
+    const bool tiled = Wd % 4 == 0 && npix < (1u << 31) && (((uintptr_t)grad_x | (uintptr_t)x) & 15) == 0;
+    const size_t units = tiled ? (size_t)B * H * (Wd / 4) : npix;
+    const unsigned blocks = (unsigned)std::min<size_t>((units + 255) / 256, DG_BLOCKS);
+    double *stats = static_cast<double *>(ws), *part = stats ? stats + 4 * cin : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const bf16 *gp = (const bf16 *)g;
+    switch (cin) {
+    case 1: launch_first_dgrad_mode<1>(mode, tiled, blocks, st, gp, W, x, pre, minmax, B, H, Wd, grad_x, part); break;
+    case 2: launch_first_dgrad_mode<2>(mode, tiled, blocks, st, gp, W, x, pre, minmax, B, H, Wd, grad_x, part); break;
+    case 3: launch_first_dgrad_mode<3>(mode, tiled, blocks, st, gp, W, x, pre, minmax, B, H, Wd, grad_x, part); break;
+    default: launch_first_dgrad_mode<4>(mode, tiled, blocks, st, gp, W, x, pre, minmax, B, H, Wd, grad_x, part); break;
+    }
+    MMK_LAUNCH_CHECK();
+    if (mode != DG_PLAIN) {
+        hipLaunchKernelGGL(conv_first_dgrad_stats_kernel, dim3(cin), dim3(256), 0, st, (const double *)part, (int)blocks, cin, stats);
+        MMK_LAUNCH_CHECK();
+    }
+    return MMK_OK;
+}
+
+extern "C" int mmk_input_norm_bwd(float *grad_x, const float *x, int32_t cin, const float *pre, const float *minmax, int32_t mode,
+                                  int32_t B, int32_t H, int32_t Wd, const void *ws, size_t ws_bytes, void *stream)
+{
+    MMK_REQUIRE(mode == MMK_NORM_NONE || mode == MMK_NORM_MINMAX || mode == MMK_NORM_STANDARDIZE,
+                "mmk_input_norm_bwd: unknown normalisation mode %d", mode);
+    MMK_REQUIRE(grad_x, "mmk_input_norm_bwd: NULL pointer");
+    MMK_REQUIRE(cin >= 1 && cin <= 4 && B >= 1 && B <= 16383 && H >= 1 && Wd >= 1,
+                "mmk_input_norm_bwd: bad shape (cin must be 1..4, B at most 16383)");
+    if (mode == MMK_NORM_NONE) return MMK_OK;         // nothing depends on statistics of x
+    MMK_REQUIRE(x && pre && ws && (mode != MMK_NORM_MINMAX || minmax), "mmk_input_norm_bwd: NULL pointer");
+    MMK_REQUIRE(ws_bytes >= mmk_conv_first_dgrad_ws_bytes(cin), "mmk_input_norm_bwd: workspace too small (%zu < %zu bytes)", ws_bytes,
+                mmk_conv_first_dgrad_ws_bytes(cin));
+    const size_t hw = (size_t)H * Wd;
+    const dim3 grid((unsigned)std::min<size_t>((hw + 1023) / 1024, 256), (unsigned)(B * cin));
+    const double n = (double)B * (double)hw;
+    if (mode == MMK_NORM_MINMAX)
+        hipLaunchKernelGGL(input_norm_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, grad_x, x, pre, minmax,
+                           (const double *)ws, cin, hw, n);
+    else
+        hipLaunchKernelGGL(input_norm_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, grad_x, x, pre, minmax,
+                           (const double *)ws, cin, hw, n);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

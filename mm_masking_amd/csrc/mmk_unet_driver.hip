@@ -386,8 +386,13 @@ extern "C" int mmk_unet_forward(const mmk_unet_desc *d, void *stream)
 }
 
 namespace {
+struct InputGrad {          // mmk_unet_backward_input: where the gradient of the input image goes, and through which normalisation
+    float *grad_x;
+    int mode;
+    const float *minmax;
+};
 int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const *grads, void *scratch, size_t scratch_bytes,
-                       void *const *bucket_events, void *stream);
+                       void *const *bucket_events, void *stream, const InputGrad *ig = nullptr);
 }
 
 extern "C" int mmk_unet_backward(const mmk_unet_desc *d, const float *gmask, float *const *grads, void *scratch,
@@ -417,9 +422,31 @@ extern "C" int mmk_unet_backward_buckets(const mmk_unet_desc *d, const float *gm
     return unet_backward_impl(d, gmask, grads, scratch, scratch_bytes, bucket_events, stream);
 }
 
+extern "C" int mmk_unet_backward_input(const mmk_unet_desc *d, const float *gmask, float *const *grads, float *grad_x,
+                                       int32_t norm_mode, const float *minmax, void *scratch, size_t scratch_bytes,
+                                       void *const *bucket_events, void *stream)
+{
+    MMK_REQUIRE(d != nullptr, "mmk_unet_backward_input: NULL descriptor");
+    MMK_REQUIRE(grad_x != nullptr, "mmk_unet_backward_input: NULL pointer (grad_x)");
+    MMK_REQUIRE(d->cin >= 1 && d->cin <= 4, "mmk_unet_backward_input: bad shape (cin must be 1..4)");
+    MMK_REQUIRE(norm_mode == MMK_NORM_NONE || norm_mode == MMK_NORM_MINMAX || norm_mode == MMK_NORM_STANDARDIZE,
+                "mmk_unet_backward_input: unknown normalisation mode %d", norm_mode);
+    MMK_REQUIRE(norm_mode == MMK_NORM_NONE || d->pre != nullptr, "mmk_unet_backward_input: normalisation mode %d needs d->pre (NULL pointer)",
+                norm_mode);
+    MMK_REQUIRE(norm_mode != MMK_NORM_MINMAX || minmax != nullptr, "mmk_unet_backward_input: MMK_NORM_MINMAX needs minmax (NULL pointer)");
+    // the statistics go where the first layer's weight gradient kept its partials (it is done with them by then)
+    MMK_REQUIRE(mmk_conv_first_dgrad_ws_bytes(d->cin) <= mmk_conv_first_wgrad_ws_bytes(d->cin),
+                "mmk_unet_backward_input: no room for the statistics in scratch");
+    if (bucket_events)
+        for (int b = 0; b < MMK_UNET_GRAD_BUCKETS; ++b)
+            MMK_REQUIRE(bucket_events[b] != nullptr, "mmk_unet_backward_input: NULL event %d", b);
+    const InputGrad ig = {grad_x, norm_mode, norm_mode == MMK_NORM_MINMAX ? minmax : nullptr};
+    return unet_backward_impl(d, gmask, grads, scratch, scratch_bytes, bucket_events, stream, &ig);
+}
+
 namespace {
 int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const *grads, void *scratch, size_t scratch_bytes,
-                       void *const *bucket_events, void *stream)
+                       void *const *bucket_events, void *stream, const InputGrad *ig)
 {
     MMK_REQUIRE(d != nullptr, "mmk_unet_backward: NULL descriptor");
     MMK_REQUIRE(d->x && d->params && d->workspace && d->mask && gmask && grads && scratch, "mmk_unet_backward: NULL pointer");
@@ -637,6 +664,15 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
         MMK_CHECK_HIP(hipStreamWaitEvent(st, ss->join, 0));
     }
     if (bucket_events) MMK_CHECK_HIP(hipEventRecord((hipEvent_t)bucket_events[2], st));
+    if (ig) {
+        // gradient of the input image, behind everything a data-parallel caller waits for: gz_a[0] is still in scratch, and
+        // the first layer's weight gradient (same stream) is done with its workspace, which holds the statistics now
+        const size_t nws = mmk_conv_first_dgrad_ws_bytes(p.cin);
+        void *sws = ig->mode == MMK_NORM_NONE ? nullptr : at(sc, p.first_ws);
+        MMK_TRY(mmk_conv_first_dgrad(at(sc, p.gz_a[0].off), p.cin, Wk(0), d->x, d->pre, ig->minmax, B, p.H, p.W, ig->grad_x, sws, nws,
+                                     stream));
+        MMK_TRY(mmk_input_norm_bwd(ig->grad_x, d->x, p.cin, d->pre, ig->minmax, ig->mode, B, p.H, p.W, sws, nws, stream));
+    }
     return MMK_OK;
 }
 }  // namespace

@@ -223,26 +223,39 @@ class LearnICPWeightPolicy(nn.Module):
                     raise _lib.MmkError("mask U-Net: unsupported network input %s (1..4 channels, at least 32 x 32)"
                                         % (tuple(raw_in.shape),))
                 self._step += 1
+                # an image that requires grad receives its gradient from the network's autograd node; the statistics of a
+                # folded normalisation are computed outside the graph, so the node is told which ones they are (input_norm)
+                want_gx = torch.is_grad_enabled() and raw_in.requires_grad
+                in_norm = None
                 if "minmax" in self.normalize_type:
                     # min-max normalisation folded into the first layer's loads: one min/max pass, no
                     # normalised copy of the image
                     net_in = raw_in.contiguous().float()
-                    pre = unet_hip.channel_minmax(net_in, global_reduce=self.global_minmax)
+                    if want_gx:
+                        if unet_hip.minmax_is_collective(self.global_minmax):
+                            raise _lib.MmkError("the gradient with respect to the network input through min-max extrema that are "
+                                                "reduced over the ranks is not implemented: set params['global_minmax'] = False "
+                                                "or detach the input")
+                        pre, mm = unet_hip.channel_minmax(net_in, return_minmax=True)
+                        in_norm = ("minmax", mm)
+                    else:
+                        pre = unet_hip.channel_minmax(net_in, global_reduce=self.global_minmax)
                 elif "standardize" in self.normalize_type:
                     # standardisation folded in the same way: (mean, 1 / std) per channel from two ordered passes, per
                     # rank under data parallelism (as the reference's torch.mean / torch.std of its own batch)
                     net_in = raw_in.contiguous().float()
                     pre = unet_hip.channel_meanstd(net_in)
+                    in_norm = ("standardize", None) if want_gx else None
                 else:
                     net_in, pre = self._normalize_channels(raw_in), None
                 # (the amax normalisation below rides inside the same autograd node)
                 if self.batch_norm:        # Conv, ReLU, BN, Conv, ReLU, BN: BatchNorm kernels between the convolutions
                     from . import unet_hip_bn
                     weight_mask = unet_hip_bn.unet_mask(self, net_in, self.training, self._step, norm=self.norm_weights, pre=pre,
-                                                        slope=0.1 if self.leaky else 0.0)
+                                                        slope=0.1 if self.leaky else 0.0, input_norm=in_norm)
                 else:
                     weight_mask = unet_hip.unet_mask(self, net_in, self.training, self._step, norm=self.norm_weights, pre=pre,
-                                                     slope=0.1 if self.leaky else 0.0)
+                                                     slope=0.1 if self.leaky else 0.0, input_norm=in_norm)
                 normalised = self.norm_weights
             else:
                 if raw_in.is_cuda:

@@ -225,6 +225,41 @@ def conv_first_wgrad(x, gz, pre, dW, db):
     _lib.check(L.mmk_conv_first_wgrad(_p(x), cin, _p(gz), _p(pre), B, H, W, _p(dW), _p(db), _p(ws), nb, _sp(x.device)))
 
 
+def conv_first_dgrad(gz, w, x=None, pre=None, minmax=None, stats=False):
+    """Gradient with respect to the first layer's fp32 NCHW input, WRITTEN: rscale_c * g_n, g_n = the transposed 3x3 convolution
+    of gz (B,H,W,8) bf16 with w (8,cin,3,3) fp32 (gather form, no atomics).  ``stats``: the same pass also sums the
+    normalisation's statistics (include/mmk.h: mmk_conv_first_dgrad) from x and pre -- with ``minmax`` (C,2) the tie counts of
+    the raw extrema too -- into the workspace input_norm_bwd() takes.  Returns (grad_x, workspace or None)."""
+    L = _lib.lib()
+    B, H, W, _ = gz.shape
+    cin = w.shape[1]
+    gx = torch.empty(B, cin, H, W, dtype=torch.float32, device=gz.device)
+    ws, nb = None, 0
+    if stats:
+        nb = int(L.mmk_conv_first_dgrad_ws_bytes(cin))
+        ws = torch.empty(nb // 8, dtype=torch.float64, device=gz.device)
+    _lib.check(L.mmk_conv_first_dgrad(_p(gz), cin, _p(w), _p(x), _p(pre), _p(minmax), B, H, W, _p(gx), _p(ws), nb, _sp(gz.device)))
+    return gx, ws
+
+
+def input_norm_bwd(gx, x, pre, mode, minmax, ws):
+    """Adds the adjoint of the folded normalisation's statistics ("minmax": the extrema, shared evenly among tied elements;
+    "standardize": mean and unbiased std) to gx in place, from the workspace conv_first_dgrad(stats=True) filled."""
+    B, cin, H, W = gx.shape
+    _lib.check(_lib.lib().mmk_input_norm_bwd(_p(gx), _p(x), cin, _p(pre), _p(minmax), _lib.NORM_MODES[mode], B, H, W, _p(ws),
+                                             0 if ws is None else ws.numel() * 8, _sp(gx.device)))
+    return gx
+
+
+def first_layer_input_grad(x, gz, w, pre, in_norm):
+    """dL/dx of the network from the gradient of the first pre-activation; ``in_norm`` = (mode, minmax) as unet_mask takes it."""
+    mode, mm = in_norm if in_norm is not None else (None, None)
+    if _lib.NORM_MODES[mode] == 0:
+        return conv_first_dgrad(gz, w, pre=pre)[0]
+    gx, ws = conv_first_dgrad(gz, w, x=x, pre=pre, minmax=mm if mode == "minmax" else None, stats=True)
+    return input_norm_bwd(gx, x, pre, mode, mm, ws)
+
+
 def conv_first(x, w, b, pre=None, slope=0.0):
     """x fp32 (B,cin,H,W) -> bf16 (B,H,W,8), + bias + ReLU (encoder.0.0).  ``pre`` (cin,2): per-channel
     (offset, reciprocal scale) applied to x while loading (see channel_minmax)."""
@@ -237,24 +272,32 @@ def conv_first(x, w, b, pre=None, slope=0.0):
 FORCE_COLLECTIVES = False     # one-rank rehearsal of the N-rank path (bench.py --force-dist): issue the collective at world size 1 too
 
 
-def channel_minmax(x, process_group=None, global_reduce=False):
+def minmax_is_collective(global_reduce, process_group=None):
+    """Whether channel_minmax(global_reduce=...) would reduce the extrema over the ranks (an all-reduce)."""
+    import torch.distributed as dist
+    return bool(global_reduce and dist.is_available() and dist.is_initialized()
+                and (dist.get_world_size(process_group) > 1 or FORCE_COLLECTIVES))
+
+
+def channel_minmax(x, process_group=None, global_reduce=False, return_minmax=False):
     """(min, 1 / (max - min)) per channel of fp32 (B,C,H,W) over (B,H,W) -> (C,2) fp32: the offset and
     reciprocal scale of the policy's min-max normalisation (icp_weight_policy.py:151-155).
     ``global_reduce``: in a data-parallel job the minimum / maximum are reduced over the ranks (one MAX
     all-reduce of 2C floats), so that the normalisation stays global over the whole batch as in the
-    single-process reference."""
+    single-process reference.  ``return_minmax``: (pre, minmax) with the raw (min, max) pairs (C,2) the input
+    gradient's min-max adjoint needs (unet_mask: input_norm); the pairs of this rank, never the reduced ones."""
     B, C, H, W = x.shape
     part = torch.empty(C * 2048, dtype=torch.float32, device=x.device)
     pre = torch.empty(C, 2, dtype=torch.float32, device=x.device)
     import torch.distributed as dist
-    reduce = global_reduce and dist.is_available() and dist.is_initialized() and (dist.get_world_size(process_group) > 1 or FORCE_COLLECTIVES)
-    mm = torch.empty(C, 2, dtype=torch.float32, device=x.device) if reduce else None
+    reduce = minmax_is_collective(global_reduce, process_group)
+    mm = torch.empty(C, 2, dtype=torch.float32, device=x.device) if (reduce or return_minmax) else None
     _lib.check(_lib.lib().mmk_channel_minmax(_p(x), B, C, H * W, _p(part), _p(pre), _p(mm), _sp(x.device)))
     if reduce:
         t = torch.stack((-mm[:, 0], mm[:, 1]), dim=1)            # max(-min) = -min over the ranks
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=process_group)
         pre = torch.stack((-t[:, 0], 1.0 / (t[:, 1] + t[:, 0])), dim=1).contiguous()
-    return pre
+    return (pre, mm) if return_minmax else pre
 
 
 def channel_meanstd(x):
@@ -341,8 +384,9 @@ class _UNet(torch.autograd.Function):
     backward is the hand-scheduled reverse pass (no autograd graph inside)."""
 
     @staticmethod
-    def forward(ctx, x, pre, drop_p, seed, training, norm, slope, *params):
+    def forward(ctx, x, pre, drop_p, seed, training, norm, slope, in_norm, *params):
         dev = x.device
+        ctx.x_dtype, ctx.in_norm = x.dtype, in_norm
         x = x.contiguous().float()
         B, cin, H, W = x.shape
         P = [p.detach() for p in params]
@@ -555,6 +599,11 @@ class _UNet(torch.autograd.Function):
         gz_a0 = conv3x3(gz_d0, pkt(1), 8, relu_src=a0, scale=1.0, slope=sl)
         g_w0, g_b0 = seg(0).view(8, cin0, 3, 3), seg(1)
         conv_first_wgrad(x, gz_a0, ctx.pre, g_w0, g_b0)
+        g_x = None
+        if ctx.needs_input_grad[0]:       # the input image: the first layer's data gradient + the folded normalisation's adjoint
+            g_x = first_layer_input_grad(x, gz_a0, W(0).float().contiguous(), ctx.pre, ctx.in_norm).to(ctx.x_dtype)
+        if dbg is not None:
+            dbg["gz_a0"] = gz_a0
         # ---- assemble parameter gradients in input order
         out = [g_w0, g_b0]
         assert all(part_sets[k] == (2 if k >= 12 else 1) for k in range(1, 22))
@@ -563,7 +612,7 @@ class _UNet(torch.autograd.Function):
             out += [gw, dB[k]]
         out += [g_fw.reshape(1, 8, 1, 1), g_fb]
         out = [g.to(p.dtype) for g, p in zip(out, P)]
-        return (None, None, None, None, None, None, None) + tuple(out)
+        return (g_x, None, None, None, None, None, None, None) + tuple(out)
 
 
 # ----------------------------------------------------------------------------- the network as two C-ABI calls
@@ -589,9 +638,10 @@ class _UNetNative(torch.autograd.Function):
     """The same network through mmk_unet_forward / mmk_unet_backward: one C call per pass."""
 
     @staticmethod
-    def forward(ctx, x, pre, drop_p, seed, training, norm, slope, *params):
+    def forward(ctx, x, pre, drop_p, seed, training, norm, slope, in_norm, *params):
         L = _lib.lib()
         dev = x.device
+        ctx.x_dtype, ctx.in_norm = x.dtype, in_norm
         x = x.contiguous().float()
         B, cin, H, W = x.shape
         P = [p.detach().float().contiguous() for p in params]
@@ -642,21 +692,50 @@ class _UNetNative(torch.autograd.Function):
                           drop_p=p_drop, seed=seed, leaky_slope=slope, norm=norm, workspace=ws.data_ptr(),
                           workspace_bytes=ws.numel(), mask=ctx.mask.data_ptr())
         evs = GRAD_BUCKET_EVENTS
+        ep = None
         if evs is not None:
             # data-parallel step: event b fires when the gradients of bucket b are final (include/mmk.h: mmk_unet_backward_buckets)
             ep = (ctypes.c_void_p * len(evs))(*[ctypes.c_void_p(int(e.cuda_event)) for e in evs])
+        g_x = None
+        if ctx.needs_input_grad[0]:
+            # the same pass, then the first layer's data gradient and the folded normalisation's adjoint (mmk_unet_backward_input)
+            mode, mm = ctx.in_norm if ctx.in_norm is not None else (None, None)
+            g_x = torch.empty(B, cin, H, W, dtype=torch.float32, device=dev)
+            _lib.check(L.mmk_unet_backward_input(ctypes.byref(d), _p(gmask), gp, _p(g_x), _lib.NORM_MODES[mode], _p(mm), _p(scratch),
+                                                 nscratch, ep, _sp(dev)))
+            g_x = g_x.to(ctx.x_dtype)
+        elif evs is not None:
             _lib.check(L.mmk_unet_backward_buckets(ctypes.byref(d), _p(gmask), gp, _p(scratch), nscratch, ep, _sp(dev)))
-            GRAD_BUCKET_PASSES[0] += 1
         else:
             _lib.check(L.mmk_unet_backward(ctypes.byref(d), _p(gmask), gp, _p(scratch), nscratch, _sp(dev)))
+        if evs is not None:
+            GRAD_BUCKET_PASSES[0] += 1
         ctx.ws = None
-        return (None, None, None, None, None, None, None) + tuple(grads)
+        return (g_x, None, None, None, None, None, None, None) + tuple(grads)
 
 
-def unet_mask(module, x, training, seed, norm=False, pre=None, slope=0.0, driver=None):
+def check_input_norm(input_norm, pre):
+    """(mode, minmax) of unet_mask's ``input_norm`` (None: pre is a constant), validated."""
+    if input_norm is None:
+        return None
+    mode, mm = input_norm
+    if mode not in _lib.NORM_MODES:
+        raise _lib.MmkError("input_norm: unknown mode %r (none, minmax, standardize)" % (mode,))
+    if _lib.NORM_MODES[mode] and pre is None:
+        raise _lib.MmkError("input_norm %r needs the (offset, reciprocal scale) pairs in pre" % (mode,))
+    if mode == "minmax" and mm is None:
+        raise _lib.MmkError("input_norm 'minmax' needs the raw (min, max) pairs: channel_minmax(x, return_minmax=True)")
+    return (mode, mm if mode == "minmax" else None)
+
+
+def unet_mask(module, x, training, seed, norm=False, pre=None, slope=0.0, driver=None, input_norm=None):
     """sigmoid mask (B,H,W) fp32 of the module's network on fp32 NCHW input x; ``norm``: divided by its
     per-image maximum (the policy's ``norm_weights``), inside the same autograd node; ``pre`` (C,2): the
     input is (x - pre[c,0]) * pre[c,1], applied by the first layer while it loads x; ``slope`` > 0: the
-    LeakyReLU network.  ``driver``: "native" (default, one C call per pass) or "python" (launch by launch)."""
+    LeakyReLU network.  ``driver``: "native" (default, one C call per pass) or "python" (launch by launch).
+    An x that requires grad receives its gradient from the same node.  ``pre`` is computed outside the graph, so the
+    node has to be told when it depends on x: ``input_norm`` = ("minmax", minmax) with the raw (min, max) pairs of
+    channel_minmax(x, return_minmax=True), or ("standardize", None) for channel_meanstd(x); None: pre is a constant."""
     fn = _UNetNative if (driver or DRIVER) == "native" else _UNet
-    return fn.apply(x, pre, float(module.dropout), int(seed), bool(training), bool(norm), float(slope), *param_list(module))
+    return fn.apply(x, pre, float(module.dropout), int(seed), bool(training), bool(norm), float(slope),
+                    check_input_norm(input_norm, pre), *param_list(module))

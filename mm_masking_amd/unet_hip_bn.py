@@ -74,8 +74,9 @@ def _bn_backward(gd, d, drop_scale, a, stat, affine, gamma, slope, dgamma, dbeta
 
 class _UNetBN(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, pre, drop_p, seed, training, norm, slope, module, *params):
+    def forward(ctx, x, pre, drop_p, seed, training, norm, slope, module, in_norm, *params):
         dev = x.device
+        ctx.x_dtype, ctx.in_norm = x.dtype, in_norm
         x = x.contiguous().float()
         B, cin, H, W = x.shape
         P = [p.detach().float().contiguous() for p in params]
@@ -191,6 +192,8 @@ class _UNetBN(torch.autograd.Function):
             gzA = _bn_backward(g_yA, None, 1.0, aA, sA if ctx.training else None, afA, gA, sl, grads[8 * k + 2], grads[8 * k + 3], acc)
             if k == 0:
                 uh.conv_first_wgrad(x, gzA, ctx.pre, grads[0], grads[1])
+                if ctx.needs_input_grad[0]:        # the input image (unet_hip.first_layer_input_grad)
+                    return uh.first_layer_input_grad(x, gzA, wA, ctx.pre, ctx.in_norm).to(ctx.x_dtype)
                 return None
             wgrad(2 * k, x1, gzA, x2=x2)
             cin_k = wA.shape[1]
@@ -236,7 +239,7 @@ class _UNetBN(torch.autograd.Function):
             g_d = uh.maxpool2_bwd(d_i, g_t, 1.0, 1.0)          # routing + "not dropped" factor; the BN adjoint applies 1/keep
             block_bwd(i, ("e", i), g_d, out=g_skip[i - 1], accumulate_out=True)
             g_t = g_skip[i - 1]
-        block_bwd(0, ("e", 0), g_t)
+        g_x = block_bwd(0, ("e", 0), g_t)
         # ---- conv weight / bias gradients of the 21 3x3 layers
         assert all(part_sets[ci] == (2 if ci >= 12 else 1) for ci in range(1, 22))
         items, idxs = [], []
@@ -249,8 +252,10 @@ class _UNetBN(torch.autograd.Function):
         for gi, gw in zip(idxs, uh.wgrad_unpack_batch(items)):
             grads[gi] = gw
         grads[88] = g_fw.view(1, 8, 1, 1)
-        return (None,) * 8 + tuple(g.to(p.dtype) for g, p in zip(grads, P))
+        return (g_x,) + (None,) * 8 + tuple(g.to(p.dtype) for g, p in zip(grads, P))
 
 
-def unet_mask(module, x, training, seed, norm=False, pre=None, slope=0.0):
-    return _UNetBN.apply(x, pre, float(module.dropout), int(seed), bool(training), bool(norm), float(slope), module, *param_list(module))
+def unet_mask(module, x, training, seed, norm=False, pre=None, slope=0.0, input_norm=None):
+    """unet_hip.unet_mask for the BatchNorm network (``input_norm``: see there)."""
+    return _UNetBN.apply(x, pre, float(module.dropout), int(seed), bool(training), bool(norm), float(slope), module,
+                         uh.check_input_norm(input_norm, pre), *param_list(module))
