@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 502 /* 0.5.2: mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 502 /* 0.5.2: mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -211,6 +211,8 @@ int mmk_bce_fft_threshold_bwd(const float *x, const float *fft, int32_t B, int64
  * mmk_cart_to_polar    <- radar_cartesian_to_polar       radar_utils.py:338-372
  * mmk_polar_to_cart_bwd, mmk_cart_to_polar_bwd <- what autograd does for the two above when
  *                        the image requires grad (both are plain F.grid_sample calls upstream)
+ * mmk_mask_polar_scan (+ _bwd) <- radar_cartesian_to_polar(mask.double(), ...).float() * fft_data, the masked scan of
+ *                        icp_weight_policy.py:266, and what autograd does for it
  * mmk_sample_weights_* <- extract_weights (fwd + autograd bwd) radar_utils.py:108-128
  * mmk_bev_raster       <- extract_bev_from_pts           radar_utils.py:142-165      */
 
@@ -306,6 +308,29 @@ int mmk_cart_to_polar_bwd(const double *grad_polar /*B,A,R*/, const double *sin_
                           const double *range_coords, int32_t B, int32_t A, int32_t R, int32_t H, int32_t W,
                           double radar_resolution, double cart_resolution, double *grad_cart /*B,H,W*/, void *ws,
                           size_t ws_bytes, void *stream);
+
+/* out (B,A,R) = fl32(P) * scan, P = mmk_cart_to_polar of mask_cart (B,H,W) fp32 taken as fp64 (exact) -- the Cartesian mask
+ * applied to the polar scan in one pass: one read of scan and one write per polar cell, no polar image of the mask.  The
+ * blend is mmk_cart_to_polar's fp64 FMA chain rounded to fp32 once, the product one fp32 multiplication: bit-identical to
+ * `radar_cartesian_to_polar(mask.double(), ...).float() * scan`.  A cell without a tap in the image gets +0.0 * scan.
+ * sin_az / cos_az (B,A) and range_coords (R) as for mmk_cart_to_polar. */
+int mmk_mask_polar_scan(const float *scan /*B,A,R*/, const float *mask_cart /*B,H,W*/, const double *sin_az,
+                        const double *cos_az, const double *range_coords, int32_t B, int32_t A, int32_t R, int32_t H,
+                        int32_t W, double cart_resolution, float *out /*B,A,R*/, void *stream);
+
+/* Backward of mmk_mask_polar_scan given grad_out (B,A,R).  grad_scan (B,A,R) = grad_out * fl32(P), P recomputed from the
+ * mask.  grad_mask (B,H,W) = the adjoint of the bilinear gather applied to fl32(grad_out * scan), in the fixed-point form,
+ * with the scale rule and the count bound of mmk_cart_to_polar_bwd on that product widened to fp64, closed by
+ * (float)((double)word / scale): bit-identical to autograd through the composition above.  Pixels no ray touches get exactly
+ * 0; a non-finite product makes its item's grad_mask NaN.  Either of grad_scan / grad_mask may be NULL: that half is not
+ * computed (ws is only needed for grad_mask).  No float atomics, bit-reproducible.
+ * ws: mmk_mask_polar_scan_bwd_ws_bytes(B, A, R, H, W) bytes (one 64-bit word per pixel). */
+size_t mmk_mask_polar_scan_bwd_ws_bytes(int32_t B, int32_t A, int32_t R, int32_t H, int32_t W);
+int mmk_mask_polar_scan_bwd(const float *grad_out /*B,A,R*/, const float *scan /*B,A,R*/, const float *mask_cart /*B,H,W*/,
+                            const double *sin_az, const double *cos_az, const double *range_coords, int32_t B, int32_t A,
+                            int32_t R, int32_t H, int32_t W, double radar_resolution, double cart_resolution,
+                            float *grad_scan /*B,A,R or NULL*/, float *grad_mask /*B,H,W or NULL*/, void *ws, size_t ws_bytes,
+                            void *stream);
 
 /* weights[b,n] = bilinear(mask[b], point n) with zero padding; fake points
  * (x==0 && y==0) get 0.  cart_resolution / cart_pixel_width as point_to_cart_idx

@@ -216,6 +216,10 @@ def _declare(lib):
         "mmk_cart_to_polar_bwd_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
         "mmk_cart_to_polar_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, ctypes.c_double, ctypes.c_double,
                                                  c_vp, c_vp, sz, c_vp]),
+        "mmk_mask_polar_scan": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, ctypes.c_double, c_vp, c_vp]),
+        "mmk_mask_polar_scan_bwd_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
+        "mmk_mask_polar_scan_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, ctypes.c_double,
+                                                   ctypes.c_double, c_vp, c_vp, c_vp, sz, c_vp]),
         "mmk_sample_weights_fwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, f32, c_vp, c_vp]),
         "mmk_host_read_rows": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64, i32, i32, i32, i32, i32, c_vp]),
         "mmk_host_read_rows_batch": (ctypes.c_int, [ctypes.POINTER(ReadJob), i32, i32]),

@@ -330,6 +330,46 @@ __device__ __forceinline__ float tap_polar(const float *__restrict__ img, int A,
 // reference's own library calls: device libm results differ in the last bit); every later operation is an
 // IEEE fp64 operation in the reference's order, the four-tap blend the FMA chain of PyTorch's CPU
 // grid_sample kernel (oracle/nn_search.c: mmk_oracle_blend4_f64) -> bit-identical output.
+// Sampling position of one polar cell in the Cartesian image: radar_utils.py:352-370 and the normalise / denormalise round
+// trip of F.grid_sample(align_corners=True), in the reference's order of operations.  Shared by cart_to_polar_kernel, its
+// adjoint and the mask_polar_scan kernels, which therefore see the same taps and weights bit for bit.
+struct CartTaps {
+    int xi, yi;          // top-left tap: column, row (clamped to [-2, W] / [-2, H]: such a sample has no tap in the image)
+    double wx, wy;       // ix - x0, iy - y0
+    bool inimg;          // at least one of the four taps lies in the image
+};
+
+__device__ __forceinline__ CartTaps cart_taps(double s_az, double c_az, double rc, int H, int W, double cart_resolution)
+{
+    const double sx = s_az * rc, sy = c_az * rc;
+    double u = sx / cart_resolution, v = -sy / cart_resolution;
+    u = u / (double)(W - 1) * 2.0;
+    v = v / (double)(H - 1) * 2.0;
+    const double ix = ((u + 1.0) / 2.0) * (double)(W - 1), iy = ((v + 1.0) / 2.0) * (double)(H - 1);
+    const double x0 = floor(ix), y0 = floor(iy);
+    CartTaps t;
+    t.wx = ix - x0;
+    t.wy = iy - y0;
+    // (a sample far outside the image has no tap in it: clamping keeps the conversion to int defined)
+    t.xi = (int)fmin(fmax(x0, -2.0), (double)W);
+    t.yi = (int)fmin(fmax(y0, -2.0), (double)H);
+    t.inimg = t.xi >= -1 && t.xi < W && t.yi >= -1 && t.yi < H;
+    return t;
+}
+
+// The four-tap blend of PyTorch's CPU grid_sample kernel (oracle/nn_search.c: mmk_oracle_blend4_f64) over an image of T
+// (fp64, or fp32 widened, which is exact); taps outside the image are 0.
+template <typename T>
+__device__ __forceinline__ double cart_blend(const T *__restrict__ img, const CartTaps &t, int H, int W)
+{
+    const double ex = 1.0 - t.wx, sy1 = 1.0 - t.wy;
+    auto tap = [&](int y, int x) -> double {
+        return (x >= 0 && x < W && y >= 0 && y < H) ? (double)img[(size_t)y * W + x] : 0.0;
+    };
+    const double t0 = tap(t.yi, t.xi), t1 = tap(t.yi, t.xi + 1), t2 = tap(t.yi + 1, t.xi), t3 = tap(t.yi + 1, t.xi + 1);
+    return fma(t3, t.wy * t.wx, fma(t2, t.wy * ex, fma(t1, sy1 * t.wx, t0 * (sy1 * ex))));
+}
+
 __global__ __launch_bounds__(256) void cart_to_polar_kernel(const double *__restrict__ cart, const double *__restrict__ sin_az,
                                                             const double *__restrict__ cos_az, const double *__restrict__ range_coords,
                                                             int A, int R, int H, int W, double cart_resolution,
@@ -338,21 +378,25 @@ __global__ __launch_bounds__(256) void cart_to_polar_kernel(const double *__rest
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
     const int a = blockIdx.y, b = blockIdx.z;
-    const double rc = range_coords[r];
-    const double sx = sin_az[(size_t)b * A + a] * rc, sy = cos_az[(size_t)b * A + a] * rc;
-    double u = sx / cart_resolution, v = -sy / cart_resolution;
-    u = u / (double)(W - 1) * 2.0;
-    v = v / (double)(H - 1) * 2.0;
-    const double ix = ((u + 1.0) / 2.0) * (double)(W - 1), iy = ((v + 1.0) / 2.0) * (double)(H - 1);
-    const double x0 = floor(ix), y0 = floor(iy);
-    const double wx = ix - x0, wy = iy - y0, ex = 1.0 - wx, sy1 = 1.0 - wy;
-    const long xi = (long)x0, yi = (long)y0;
-    const double *img = cart + (size_t)b * H * W;
-    auto tap = [&](long y, long x) -> double {
-        return (x >= 0 && x < W && y >= 0 && y < H) ? img[(size_t)y * W + x] : 0.0;
-    };
-    const double t0 = tap(yi, xi), t1 = tap(yi, xi + 1), t2 = tap(yi + 1, xi), t3 = tap(yi + 1, xi + 1);
-    polar[((size_t)b * A + a) * R + r] = fma(t3, wy * wx, fma(t2, wy * ex, fma(t1, sy1 * wx, t0 * (sy1 * ex))));
+    const CartTaps t = cart_taps(sin_az[(size_t)b * A + a], cos_az[(size_t)b * A + a], range_coords[r], H, W, cart_resolution);
+    polar[((size_t)b * A + a) * R + r] = cart_blend(cart + (size_t)b * H * W, t, H, W);
+}
+
+// mask_polar_scan: out = fl32(radar_cartesian_to_polar(mask as fp64)) * scan in one pass -- one read of the scan and one write
+// per polar cell, the mask taps from cache; no polar image of the mask is formed.  The blend is cart_to_polar_kernel's, rounded
+// to fp32 once, then one fp32 multiplication: the composition `radar_cartesian_to_polar(mask.double()).float() * scan` bit for
+// bit.  A cell without a tap in the image blends four zeros and writes +0.0 * scan.
+__global__ __launch_bounds__(256) void mask_polar_scan_kernel(const float *__restrict__ scan, const float *__restrict__ mask,
+                                                              const double *__restrict__ sin_az, const double *__restrict__ cos_az,
+                                                              const double *__restrict__ range_coords, int A, int R, int H, int W,
+                                                              double cart_resolution, float *__restrict__ out)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int a = blockIdx.y, b = blockIdx.z;
+    const CartTaps t = cart_taps(sin_az[(size_t)b * A + a], cos_az[(size_t)b * A + a], range_coords[r], H, W, cart_resolution);
+    const size_t cell = ((size_t)b * A + a) * R + r;
+    out[cell] = (float)cart_blend(mask + (size_t)b * H * W, t, H, W) * scan[cell];
 }
 
 // Sampling position of one Cartesian pixel in the (wrap-padded) polar image: radar_utils.py:286-323 and the normalise /
@@ -1055,37 +1099,20 @@ __global__ __launch_bounds__(256) void polar_to_cart_bwd_scatter_kernel(const fl
 // first samples meet on the four centre pixels, a quarter of the atomics on those addresses.  A thread walking eight cells
 // of a ray and summing in registers was measured too: 2.14 ms against 1.47 ms at B = 32 (its 64-byte-strided reads alone
 // cost 1.0 ms).
-__global__ __launch_bounds__(256) void cart_to_polar_bwd_scatter_kernel(const double *__restrict__ gpolar, const double *__restrict__ sin_az,
-                                                                        const double *__restrict__ cos_az,
-                                                                        const double *__restrict__ range_coords, int A, int R, int H,
-                                                                        int W, double cart_resolution,
-                                                                        const unsigned *__restrict__ pmax, int cnt_bits,
-                                                                        unsigned long long *__restrict__ acc)
+// (the body shared by cart_to_polar_bwd_scatter_kernel and mask_polar_scan_bwd_kernel: `g` is the cell's gradient as fp64, 0.0
+// for a lane past the ray's end or without a tap in the image; every lane of the wave calls it)
+__device__ __forceinline__ void cart_scatter_cell(double g, bool valid, const CartTaps &t, int H, int W, double scale,
+                                                  unsigned long long *__restrict__ ab)
 {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    const int a = blockIdx.y, b = blockIdx.z;
     const int lane = threadIdx.x & 63;
-    const double scale = fixed_scale<double>(pmax[b], cnt_bits);
-    if (scale == 0.0) return;
-    const bool valid = r < R;
-    const double rc = range_coords[valid ? r : R - 1];
-    const double sx = sin_az[(size_t)b * A + a] * rc, sy = cos_az[(size_t)b * A + a] * rc;
-    double u = sx / cart_resolution, v = -sy / cart_resolution;
-    u = u / (double)(W - 1) * 2.0;
-    v = v / (double)(H - 1) * 2.0;
-    const double ix = ((u + 1.0) / 2.0) * (double)(W - 1), iy = ((v + 1.0) / 2.0) * (double)(H - 1);
-    const double x0 = floor(ix), y0 = floor(iy);
-    const double wx = ix - x0, wy = iy - y0, ex = 1.0 - wx, sy1 = 1.0 - wy;
-    // (a sample far outside the image has no tap in it: clamping keeps the conversion to int defined)
-    const int xi = (int)fmin(fmax(x0, -2.0), (double)W), yi = (int)fmin(fmax(y0, -2.0), (double)H);
-    const bool inimg = xi >= -1 && xi < W && yi >= -1 && yi < H;
-    const double g = (valid && inimg) ? gpolar[((size_t)b * A + a) * R + r] : 0.0;
+    const double ex = 1.0 - t.wx, sy1 = 1.0 - t.wy;
+    const int xi = t.xi, yi = t.yi;
     long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
     if (g != 0.0) {
         s0 = llrint((g * (sy1 * ex)) * scale);
-        s1 = llrint((g * (sy1 * wx)) * scale);
-        s2 = llrint((g * (wy * ex)) * scale);
-        s3 = llrint((g * (wy * wx)) * scale);
+        s1 = llrint((g * (sy1 * t.wx)) * scale);
+        s2 = llrint((g * (t.wy * ex)) * scale);
+        s3 = llrint((g * (t.wy * t.wx)) * scale);
     }
     if (__ballot((s0 | s1 | s2 | s3) != 0) == 0ull) return;                 // (uniform over the wave)
     const int key = valid ? yi * (W + 4) + xi : -0x7fffffff;
@@ -1104,13 +1131,84 @@ __global__ __launch_bounds__(256) void cart_to_polar_bwd_scatter_kernel(const do
         }
     }
     if (!head || !valid) return;
-    unsigned long long *ab = acc + (size_t)b * H * W;
     const bool x0ok = xi >= 0 && xi < W, x1ok = xi + 1 >= 0 && xi + 1 < W;
     const bool y0ok = yi >= 0 && yi < H, y1ok = yi + 1 >= 0 && yi + 1 < H;
     if (s0 != 0 && y0ok && x0ok) atomicAdd(&ab[(size_t)yi * W + xi], (unsigned long long)s0);
     if (s1 != 0 && y0ok && x1ok) atomicAdd(&ab[(size_t)yi * W + xi + 1], (unsigned long long)s1);
     if (s2 != 0 && y1ok && x0ok) atomicAdd(&ab[(size_t)(yi + 1) * W + xi], (unsigned long long)s2);
     if (s3 != 0 && y1ok && x1ok) atomicAdd(&ab[(size_t)(yi + 1) * W + xi + 1], (unsigned long long)s3);
+}
+
+__global__ __launch_bounds__(256) void cart_to_polar_bwd_scatter_kernel(const double *__restrict__ gpolar, const double *__restrict__ sin_az,
+                                                                        const double *__restrict__ cos_az,
+                                                                        const double *__restrict__ range_coords, int A, int R, int H,
+                                                                        int W, double cart_resolution,
+                                                                        const unsigned *__restrict__ pmax, int cnt_bits,
+                                                                        unsigned long long *__restrict__ acc)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int a = blockIdx.y, b = blockIdx.z;
+    const double scale = fixed_scale<double>(pmax[b], cnt_bits);
+    if (scale == 0.0) return;
+    const bool valid = r < R;
+    const CartTaps t = cart_taps(sin_az[(size_t)b * A + a], cos_az[(size_t)b * A + a], range_coords[valid ? r : R - 1], H, W,
+                                 cart_resolution);
+    const double g = (valid && t.inimg) ? gpolar[((size_t)b * A + a) * R + r] : 0.0;
+    cart_scatter_cell(g, valid, t, H, W, scale, acc + (size_t)b * H * W);
+}
+
+// Backward of mask_polar_scan.  The gradient that reaches the polar mask is the fp32 product grad_out * scan (what autograd
+// forms behind the .float() of the composition), widened to fp64, which is exact: absmax, scale rule and sums are those of
+// mmk_cart_to_polar_bwd on that image, without the image.
+__global__ __launch_bounds__(256) void mask_polar_scan_absmax_kernel(const float *__restrict__ gout, const float *__restrict__ scan,
+                                                                     size_t n, unsigned *__restrict__ pmax)
+{
+    const int b = blockIdx.y;
+    const float *gb = gout + (size_t)b * n, *sb = scan + (size_t)b * n;
+    unsigned m = 0u;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        m = max(m, abs_bits<double>((double)(gb[i] * sb[i])));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+    if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(&pmax[b], m);
+}
+
+// One thread per polar cell, r fastest.  grad_scan (when asked for) = grad_out * fl32(P) with P recomputed from the mask;
+// grad_mask's sums (when acc is given) by cart_scatter_cell.  pmax / acc are NULL when grad_mask is not wanted.
+__global__ __launch_bounds__(256) void mask_polar_scan_bwd_kernel(const float *__restrict__ gout, const float *__restrict__ scan,
+                                                                  const float *__restrict__ mask, const double *__restrict__ sin_az,
+                                                                  const double *__restrict__ cos_az,
+                                                                  const double *__restrict__ range_coords, int A, int R, int H, int W,
+                                                                  double cart_resolution, float *__restrict__ grad_scan,
+                                                                  const unsigned *__restrict__ pmax, int cnt_bits,
+                                                                  unsigned long long *__restrict__ acc)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int a = blockIdx.y, b = blockIdx.z;
+    const bool valid = r < R;
+    const CartTaps t = cart_taps(sin_az[(size_t)b * A + a], cos_az[(size_t)b * A + a], range_coords[valid ? r : R - 1], H, W,
+                                 cart_resolution);
+    const size_t cell = ((size_t)b * A + a) * R + (valid ? r : R - 1);
+    const float go = gout[cell];
+    if (grad_scan != nullptr && valid) grad_scan[cell] = go * (float)cart_blend(mask + (size_t)b * H * W, t, H, W);
+    if (acc == nullptr) return;
+    const double scale = fixed_scale<double>(pmax[b], cnt_bits);
+    if (scale == 0.0) return;
+    const double g = (valid && t.inimg) ? (double)(go * scan[cell]) : 0.0;
+    cart_scatter_cell(g, valid, t, H, W, scale, acc + (size_t)b * H * W);
+}
+
+// word / scale of an fp64-scaled sum, rounded to fp32 once (the .double() of the composition undone)
+__global__ __launch_bounds__(256) void mask_polar_scan_final_kernel(const unsigned long long *__restrict__ acc,
+                                                                    const unsigned *__restrict__ pmax, int cnt_bits, size_t n,
+                                                                    float *__restrict__ out)
+{
+    const int b = blockIdx.y;
+    const double scale = fixed_scale<double>(pmax[b], cnt_bits);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const long long a = (long long)acc[(size_t)b * n + i];
+        out[(size_t)b * n + i] = scale == 0.0 ? __builtin_nanf("") : (float)((double)a / scale);
+    }
 }
 
 int ceil_log2(double x)
@@ -1377,6 +1475,64 @@ extern "C" int mmk_cart_to_polar_bwd(const double *grad_polar, const double *sin
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(fixed_final_kernel<double>, dim3(stream_blocks(ncart), B), dim3(256), 0, st, acc, w.pmax, cnt_bits, ncart,
                        grad_cart);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_mask_polar_scan(const float *scan, const float *mask_cart, const double *sin_az, const double *cos_az,
+                                   const double *range_coords, int32_t B, int32_t A, int32_t R, int32_t H, int32_t W,
+                                   double cart_resolution, float *out, void *stream)
+{
+    MMK_REQUIRE(scan && mask_cart && sin_az && cos_az && range_coords && out, "mmk_mask_polar_scan: NULL pointer");
+    MMK_REQUIRE(B >= 1 && B <= 65535 && A >= 1 && A <= 65535 && R >= 1 && H >= 2 && W >= 2, "mmk_mask_polar_scan: bad shape");
+    MMK_REQUIRE(cart_resolution > 0.0, "mmk_mask_polar_scan: cart_resolution must be positive");
+    hipLaunchKernelGGL(mask_polar_scan_kernel, dim3((R + 255) / 256, A, B), dim3(256), 0, (hipStream_t)stream, scan, mask_cart,
+                       sin_az, cos_az, range_coords, A, R, H, W, cart_resolution, out);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" size_t mmk_mask_polar_scan_bwd_ws_bytes(int32_t B, int32_t A, int32_t R, int32_t H, int32_t W)
+{
+    if (B < 1 || A < 1 || R < 1 || H < 2 || W < 2) return 0;
+    return carve_resample_bwd(B, (size_t)B * H * W, nullptr, 0).bytes;
+}
+
+extern "C" int mmk_mask_polar_scan_bwd(const float *grad_out, const float *scan, const float *mask_cart, const double *sin_az,
+                                       const double *cos_az, const double *range_coords, int32_t B, int32_t A, int32_t R,
+                                       int32_t H, int32_t W, double radar_resolution, double cart_resolution, float *grad_scan,
+                                       float *grad_mask, void *ws, size_t ws_bytes, void *stream)
+{
+    MMK_REQUIRE(grad_out && scan && mask_cart && sin_az && cos_az && range_coords, "mmk_mask_polar_scan_bwd: NULL pointer");
+    MMK_REQUIRE(B >= 1 && B <= 65535 && A >= 1 && A <= 65535 && R >= 1 && H >= 2 && W >= 2, "mmk_mask_polar_scan_bwd: bad shape");
+    MMK_REQUIRE(cart_resolution > 0.0 && radar_resolution > 0.0, "mmk_mask_polar_scan_bwd: resolutions must be positive");
+    if (!grad_scan && !grad_mask) return MMK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ncart = (size_t)H * W, npolar = (size_t)A * R;
+    const dim3 cells((R + 255) / 256, A, B);
+    if (!grad_mask) {
+        hipLaunchKernelGGL(mask_polar_scan_bwd_kernel, cells, dim3(256), 0, st, grad_out, scan, mask_cart, sin_az, cos_az, range_coords,
+                           A, R, H, W, cart_resolution, grad_scan, (const unsigned *)nullptr, 0, (unsigned long long *)nullptr);
+        MMK_LAUNCH_CHECK();
+        return MMK_OK;
+    }
+    const ResampleBwdWs w = carve_resample_bwd(B, (size_t)B * ncart, ws, ws_bytes);
+    if (ws == nullptr || w.bytes > ws_bytes) {
+        mmk::set_error("mmk_mask_polar_scan_bwd: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
+        return MMK_ERR_WORKSPACE;
+    }
+    // mmk_cart_to_polar_bwd's bound on the taps that meet on one pixel
+    const double per_ray = std::min((double)R, ceil(2.0 * sqrt(2.0) * cart_resolution / radar_resolution) + 1.0);
+    const int cnt_bits = ceil_log2((double)A * per_ray);
+    MMK_CHECK_HIP(hipMemsetAsync(w.pmax, 0, sizeof(unsigned) * (size_t)B, st));
+    MMK_CHECK_HIP(hipMemsetAsync(w.acc, 0, sizeof(unsigned long long) * (size_t)B * ncart, st));
+    hipLaunchKernelGGL(mask_polar_scan_absmax_kernel, dim3(stream_blocks(npolar), B), dim3(256), 0, st, grad_out, scan, npolar, w.pmax);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mask_polar_scan_bwd_kernel, cells, dim3(256), 0, st, grad_out, scan, mask_cart, sin_az, cos_az, range_coords, A,
+                       R, H, W, cart_resolution, grad_scan, w.pmax, cnt_bits, w.acc);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mask_polar_scan_final_kernel, dim3(stream_blocks(ncart), B), dim3(256), 0, st, w.acc, w.pmax, cnt_bits, ncart,
+                       grad_mask);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

@@ -495,13 +495,16 @@ def _bytes_to_unit(u8, device, non_blocking):
     return _unit_lut(u8.device)[u8.long()]
 
 
-def finish_batch(batch, device, network_input_type="cartesian", float_type=torch.float32, polar_res=0.0596, non_blocking=True):
+def finish_batch(batch, device, network_input_type="cartesian", float_type=torch.float32, polar_res=0.0596, non_blocking=True,
+                 keep_polar=False):
     """Device half of the worker-safe loader: a collated batch of ``batched_prepare`` items -> the reference's batch
     dictionary (icp_weight_dataset.py:357-362) with every tensor on ``device``.  bytes / 255 is load_radar's fp32 division
     (radar_utils.py:26) and the CFAR cache's (icp_weight_dataset.py:343), taken from a 256-entry table the host computed
     with that very division (mmk_u8_to_float); the polar -> Cartesian resampling (icp_weight_dataset.py:351-352) is ONE
     batched launch instead of one per item; ``aug_cs`` (native item path) is the augmentation's rotation of the clouds
-    (icp_weight_dataset.py:435-443), applied here as [x y] @ [[c, -s], [s, c]]."""
+    (icp_weight_dataset.py:435-443), applied here as [x y] @ [[c, -s], [s, c]].  ``keep_polar``: ``loc_data`` also carries
+    ``fft_polar`` (the fp32 polar image formed here anyway) and ``azimuths`` (B,A), both on ``device`` -- what the policy's
+    ``mask_target="scan"`` mode reads; the default leaves the dictionary as it was."""
     from . import radar_utils as ru
     device = torch.device(device)
     loc = batch["loc_data"]
@@ -512,6 +515,7 @@ def finish_batch(batch, device, network_input_type="cartesian", float_type=torch
     fft = _bytes_to_unit(loc["fft_u8"], device, non_blocking)
     cfar = _bytes_to_unit(loc["cfar_u8"], device, non_blocking)
     az = to(loc["azimuths"])
+    polar = {"fft_polar": fft, "azimuths": az} if keep_polar else {}
     if network_input_type == "cartesian":
         fft, cfar = ru._polar_to_cart_pair(fft, cfar, az.contiguous(), polar_res)
     raw_pc, filt_pc, map_pc = to(loc["raw_pc"]), to(loc["filtered_pc"]), to(batch["map_data"]["pc"])
@@ -528,7 +532,7 @@ def finish_batch(batch, device, network_input_type="cartesian", float_type=torch
             rot(map_pc, 3)
     stamp = lambda v: v.clone() if torch.is_tensor(v) else v          # noqa: E731  (host tensors: not views of a re-used buffer)
     return {"loc_data": {"raw_pc": raw_pc, "filtered_pc": filt_pc, "fft_data": fft, "fft_cfar": cfar,
-                         "timestamp": stamp(loc["timestamp"])},
+                         "timestamp": stamp(loc["timestamp"]), **polar},
             "map_data": {"pc": map_pc, "timestamp": stamp(batch["map_data"]["timestamp"])},
             "transforms": {k: to(v) for k, v in batch["transforms"].items()}}
 
@@ -550,7 +554,7 @@ class DeviceLoader:
     which the thread mode leaves to the device (tests/test_loader_cpu.py, tests/test_gpu_loader.py)."""
 
     def __init__(self, dataset, batch_size, device, num_workers=4, shuffle=False, drop_last=False, prefetch_factor=2,
-                 persistent_workers=True, mode="threads", passes=1, seed=None):
+                 persistent_workers=True, mode="threads", passes=1, seed=None, keep_polar=False):
         if not getattr(dataset, "batched_prepare", False):
             raise ValueError("DeviceLoader needs a Dataset built with params['batched_prepare'] = True (CPU-only items)")
         if mode not in ("threads", "processes"):
@@ -559,6 +563,7 @@ class DeviceLoader:
             raise ValueError("passes > 1 (several passes over the data in ONE iteration, the pipeline kept full across them) "
                              "is a feature of the thread mode")
         self.passes = int(passes)
+        self.keep_polar = bool(keep_polar)       # finish_batch(keep_polar=...): fft_polar and azimuths for mask_target="scan"
         self.dataset, self.device, self.mode = dataset, torch.device(device), mode
         self.batch_size, self.shuffle, self.drop_last, self.num_workers = int(batch_size), shuffle, drop_last, int(num_workers)
         self.loader = None
@@ -664,7 +669,8 @@ class DeviceLoader:
     def _stage(self, cpu_batch):
         ds = self.dataset
         if self.device.type != "cuda":
-            out = finish_batch(cpu_batch, self.device, ds.network_input_type, ds.float_type, ds.polar_res)
+            out = finish_batch(cpu_batch, self.device, ds.network_input_type, ds.float_type, ds.polar_res,
+                               keep_polar=self.keep_polar)
             if self.loader is None:            # the slot buffers are re-used: hand out copies on a CPU device
                 out = {g: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in d.items()} for g, d in out.items()}
                 self._release()
@@ -672,7 +678,8 @@ class DeviceLoader:
         if self._side is None:
             self._side = torch.cuda.Stream(self.device)
         with torch.cuda.stream(self._side):
-            out = finish_batch(cpu_batch, self.device, ds.network_input_type, ds.float_type, ds.polar_res)
+            out = finish_batch(cpu_batch, self.device, ds.network_input_type, ds.float_type, ds.polar_res,
+                               keep_polar=self.keep_polar)
             ev = torch.cuda.Event()
             ev.record(self._side)
         return out, ev

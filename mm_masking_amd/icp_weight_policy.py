@@ -24,7 +24,8 @@ import torch.nn as nn
 from torch.nn import ModuleList
 
 from .dICP.ICP import ICP
-from .radar_utils import _extract_weights_stats, extract_weights, form_cart_range_angle_grid, form_polar_range_grid
+from .radar_utils import (_extract_weights_stats, cfar_mask, extract_pc_padded, extract_weights, form_cart_range_angle_grid,
+                          form_polar_range_grid, mask_polar_scan)
 
 
 def weights_init(m):
@@ -96,6 +97,13 @@ class LearnICPWeightPolicy(nn.Module):
         self.unet_backend = params.get("unet_backend", "hip")
         if self.unet_backend not in ("hip", "torch"):
             raise ValueError("unet_backend must be 'hip' or 'torch' (got %r)" % (self.unet_backend,))
+        # what the mask acts on.  "weights" (default, the reference's forward): the mask is sampled at the fixed CFAR cloud and
+        # weighs its points in ICP.  "scan": the mask multiplies the polar scan (the reference's comment at
+        # icp_weight_policy.py:266), the cloud is extracted again from the masked scan with the differentiable front end, and
+        # ICP runs unweighted on it -- the mask acts through the points.
+        self.mask_target = params.get("mask_target", "weights")
+        if self.mask_target not in ("weights", "scan"):
+            raise ValueError("mask_target must be 'weights' or 'scan' (got %r)" % (self.mask_target,))
         # data-parallel jobs: reduce the min-max normalisation's extrema over the ranks (one MAX all-reduce of 2C floats), so
         # that it stays global over the whole batch as in the single-process reference (icp_weight_policy.py:151-155).
         # Default: ON whenever the process is a rank of a multi-rank job, so that N ranks x B pairs normalise like one
@@ -112,6 +120,7 @@ class LearnICPWeightPolicy(nn.Module):
         self.min_w = 0.0
         self.mean_w = 0.0
         self.mean_all_pts = 0.0
+        self.mean_scan_pts = 0.0          # scan mode: mean number of points extracted from the masked scan (device tensor)
 
         init_c_num = network_inputs["fft"] + network_inputs["cfar"] + network_inputs["range"]
         enc_channels = [init_c_num, 8, 16, 32, 64, 128, 256]
@@ -209,6 +218,15 @@ class LearnICPWeightPolicy(nn.Module):
         fft_cfar = batch_scan["fft_cfar"].to(self.device)
         scan_pc_raw = batch_scan["raw_pc"].to(self.device)
         map_pc = batch_map["pc"].to(self.device)
+        if self.mask_target == "scan" and not mask_only:
+            from . import _lib
+            for key in (("azimuths",) if self.network_input_type == "polar" else ("fft_polar", "azimuths")):
+                if key not in batch_scan:
+                    raise KeyError("mask_target='scan' needs batch_scan[%r] (prepare_batch with params['mask_target'] = 'scan', "
+                                   "or finish_batch(keep_polar=True))" % key)
+            if torch.device(self.device).type != "cuda":
+                raise _lib.MmkError("mask_target='scan' runs the radar front end in HIP kernels with no CPU path: "
+                                    "params['device'] must be a HIP device")
 
         if override_mask is None:
             raw_in = self._network_input(fft_data, fft_cfar, normalize=False)
@@ -284,6 +302,10 @@ class LearnICPWeightPolicy(nn.Module):
         # points with x != 0 and y != 0, per scan (icp_weight_policy.py:209-212): same fused pass
         self.mean_all_pts = stats[5]
 
+        if self.mask_target == "scan":
+            return self._forward_scan(batch_scan, map_pc, T_init, weight_mask, scan_pc_raw.shape[1]), weight_mask, \
+                diff_mean_num_non0
+
         scan_pc_filt = batch_scan["filtered_pc"].to(self.device)
 
         if self.training and not self.use_ICP_4_train:
@@ -291,6 +313,25 @@ class LearnICPWeightPolicy(nn.Module):
 
         T_est = self.icp(scan_pc_filt, map_pc, T_init, weights)
         return T_est, weight_mask, diff_mean_num_non0
+
+    def _forward_scan(self, batch_scan, map_pc, T_init, weight_mask, max_pts):
+        """mask_target="scan": mask -> masked polar scan -> GO-CFAR -> blob centres -> unweighted ICP, every link with its
+        hand-written backward.  diff=True in training and evaluation alike, so both see the same cloud."""
+        azimuths = batch_scan["azimuths"]
+        if self.network_input_type == "polar":          # the mask is polar already
+            masked = weight_mask * batch_scan["fft_data"].to(self.device)
+        else:
+            # (host azimuths cost no synchronisation: the operator forms their sin / cos on the host)
+            masked = mask_polar_scan(batch_scan["fft_polar"].to(self.device), weight_mask, azimuths, self.res)
+        m = cfar_mask(masked, self.res, a_thresh=self.a_thres, b_thresh=self.b_thres, diff=True)
+        az = azimuths.to(self.device)
+        az_times = batch_scan.get("az_times")
+        az_times = torch.zeros_like(az) if az_times is None else az_times.to(self.device)
+        cloud, cnt = extract_pc_padded(m, self.res, az, az_times, max_pts=max_pts, diff=True)
+        self.mean_scan_pts = cnt.float().mean()
+        if self.training and not self.use_ICP_4_train:
+            return T_init
+        return self.icp(cloud, map_pc, T_init, None)
 
     def icp(self, scan_pc, map_pc, T_init, weights):
         """icp_weight_policy.py:277-288 (loss_fn / trim_dist / dim hard-coded there;

@@ -20,7 +20,7 @@ from . import _lib
 
 __all__ = ["load_pc_from_file", "load_radar", "cfar_mask", "extract_pc", "extract_pc_padded", "extract_weights",
            "extract_bev_from_pts", "mean_peaks_parallel_fast", "pol_2_cart", "radar_polar_to_cartesian",
-           "radar_polar_to_cartesian_diff", "radar_cartesian_to_polar", "point_to_cart_idx",
+           "radar_polar_to_cartesian_diff", "radar_cartesian_to_polar", "mask_polar_scan", "point_to_cart_idx",
            "form_cart_range_angle_grid", "form_polar_range_grid"]
 
 
@@ -208,6 +208,69 @@ def radar_cartesian_to_polar(cart, azimuths, radar_resolution, cart_resolution=0
         return _CartToPolar.apply(cart, dev, s_az, c_az, rc, radar_resolution, cart_resolution)
     x = cart.detach().to(dev).contiguous()
     return _back(_cart_to_polar_forward(x, s_az, c_az, rc, cart_resolution), cart)
+
+
+def _mask_polar_scan_forward(x, m, s_az, c_az, rc, cart_resolution):
+    B, A, R = x.shape
+    out = torch.empty_like(x)
+    _lib.check(_lib.lib().mmk_mask_polar_scan(_lib.ptr(x), _lib.ptr(m), _lib.ptr(s_az), _lib.ptr(c_az), _lib.ptr(rc), B, A, R,
+                                              m.shape[1], m.shape[2], float(cart_resolution), _lib.ptr(out),
+                                              _lib.stream_ptr(x.device)))
+    return out
+
+
+class _MaskPolarScan(torch.autograd.Function):
+    """mask_polar_scan with the gradients autograd takes through ``radar_cartesian_to_polar(mask.double()).float() * scan``
+    (mmk_mask_polar_scan_bwd): grad_scan = g * fl32(P) with P recomputed, grad_mask the fixed-point adjoint of the gather
+    applied to fl32(g * scan).  The azimuths and both resolutions are constants."""
+
+    @staticmethod
+    def forward(ctx, scan, mask, dev, s_az, c_az, rc, radar_resolution, cart_resolution):
+        x, m = _lib.dev_f32(scan, dev), _lib.dev_f32(mask, dev)
+        out = _mask_polar_scan_forward(x, m, s_az, c_az, rc, cart_resolution)
+        ctx.save_for_backward(x, m, s_az, c_az, rc)
+        ctx.args = (float(radar_resolution), float(cart_resolution))
+        ctx.like = ((scan.dtype, scan.device), (mask.dtype, mask.device))
+        return _back(out, scan)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, m, s_az, c_az, rc = ctx.saved_tensors
+        radar_resolution, cart_resolution = ctx.args
+        (B, A, R), (H, W) = x.shape, m.shape[1:]
+        dev = x.device
+        g = _lib.dev_f32(g, dev)
+        want_scan, want_mask = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        L = _lib.lib()
+        ws = _workspace(int(L.mmk_mask_polar_scan_bwd_ws_bytes(B, A, R, H, W)), dev) if want_mask else None
+        gx = torch.empty_like(x) if want_scan else None
+        gm = torch.empty_like(m) if want_mask else None
+        _lib.check(L.mmk_mask_polar_scan_bwd(_lib.ptr(g), _lib.ptr(x), _lib.ptr(m), _lib.ptr(s_az), _lib.ptr(c_az), _lib.ptr(rc),
+                                             B, A, R, H, W, radar_resolution, cart_resolution, _lib.ptr(gx), _lib.ptr(gm),
+                                             _lib.ptr(ws), ws.numel() if want_mask else 0, _lib.stream_ptr(dev)))
+        (sd, sdev), (md, mdev) = ctx.like
+        return (gx.to(device=sdev, dtype=sd) if want_scan else None, gm.to(device=mdev, dtype=md) if want_mask else None) \
+            + (None,) * 6
+
+
+def mask_polar_scan(scan, mask, azimuths, radar_resolution, cart_resolution=0.2384):
+    """The Cartesian mask applied to the polar scan, the masked scan of icp_weight_policy.py:266:
+    ``radar_cartesian_to_polar(mask.double(), azimuths, radar_resolution, cart_resolution, scan.shape[1:]).float() * scan``
+    in one kernel, bit for bit, without the fp64 polar image of the mask.  (B,A,R) scan + (B,H,W) mask + (B,A) azimuths ->
+    (B,A,R) fp32, on the scan's device.  Differentiable in ``scan`` and in ``mask`` (each gradient comes back in its input's
+    dtype and on its device; only the halves that are needed are computed); the azimuths and the resolutions are constants."""
+    assert scan.ndim == 3 and mask.ndim == 3, "scan must be (B,A,R) and mask (B,H,W)"
+    dev = _hip_device(scan)
+    B, A, R = scan.shape
+    if mask.shape[0] != B:
+        raise ValueError("mask must be (%d, H, W) (got %s)" % (B, tuple(mask.shape)))
+    if azimuths.shape != (B, A):
+        raise ValueError("azimuths must be (B, %d) (got %s)" % (A, tuple(azimuths.shape)))
+    s_az, c_az, rc = _cart_to_polar_geometry(azimuths, radar_resolution, (A, R), dev)
+    if torch.is_grad_enabled() and (scan.requires_grad or mask.requires_grad):
+        return _MaskPolarScan.apply(scan, mask, dev, s_az, c_az, rc, radar_resolution, cart_resolution)
+    out = _mask_polar_scan_forward(_lib.dev_f32(scan, dev), _lib.dev_f32(mask, dev), s_az, c_az, rc, cart_resolution)
+    return _back(out, scan)
 
 
 # ----------------------------------------------------------------------------- R2

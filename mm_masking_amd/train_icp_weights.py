@@ -54,7 +54,8 @@ def prepare_batch(raw, params, max_loc_pts=5120, polar_res=0.0596):
     for synthetic input: GO-CFAR -> blob centres -> zero-padded scan cloud, and
     polar -> Cartesian for the FFT and CFAR images (kept polar for a polar network).  ``raw`` holds device tensors
     fft_polar (B,400,3360), azimuths (B,400), az_times (B,400), map_pc (B,M,6),
-    T_init, T_gt.  Returns the reference's dict-of-dicts batch."""
+    T_init, T_gt.  Returns the reference's dict-of-dicts batch; with params["mask_target"] == "scan" its ``loc_data`` also
+    carries fft_polar, azimuths and az_times (what the policy's scan mode reads)."""
     fft = raw["fft_polar"]
     az = raw["azimuths"]
     cfar = ru.cfar_mask(fft, polar_res, a_thresh=params["a_thresh"], b_thresh=params["b_thresh"], diff=False)
@@ -64,6 +65,8 @@ def prepare_batch(raw, params, max_loc_pts=5120, polar_res=0.0596):
     else:                                                               # polar network: images stay (400,3360)
         fft_img, cfar_img = fft, cfar
     loc_data = {"raw_pc": pc, "filtered_pc": pc, "fft_data": fft_img, "fft_cfar": cfar_img, "timestamp": 0}
+    if params.get("mask_target") == "scan":
+        loc_data.update({"fft_polar": fft, "azimuths": az, "az_times": raw["az_times"]})
     map_data = {"pc": raw["map_pc"], "timestamp": 0}
     T_data = {"T_ml_init": raw["T_init"], "T_ml_gt": raw["T_gt"]}
     return {"loc_data": loc_data, "map_data": map_data, "transforms": T_data}

@@ -1,0 +1,117 @@
+"""Timing of mask_polar_scan (the fused kernels) against the composition of the operators it replaces,
+`radar_cartesian_to_polar(mask.double(), ...).float() * scan`, at the bench shape (B = 32, 640 x 640 -> 400 x 3360), forward and
+forward + backward, and of one train_step with params["mask_target"] = "scan" beside the default one.  Device events around
+repeated calls after a warm-up; the two variants alternate within one run and the median over the rounds is reported with
+the spread.  Bytes are the algorithm's, computed from the shapes.  Development tool (GPU box); prints one JSON line.
+
+    python scripts/bench_mask_scan.py [--batch 32] [--rounds 7] [--reps 10] [--out FILE]
+"""
+import argparse
+import json
+import statistics
+import sys
+
+sys.path.insert(0, ".")
+import torch  # noqa: E402
+
+from mm_masking_amd import radar_utils as ru, synthetic  # noqa: E402
+from mm_masking_amd import train_icp_weights as trn  # noqa: E402
+from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy  # noqa: E402
+
+RES = 0.0596
+
+
+def timed(fn, reps):
+    """Milliseconds per call of ``fn`` over ``reps`` calls between two device events."""
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(reps):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / reps
+
+
+def alternate(variants, rounds, reps):
+    """{name: (median ms, min ms, max ms)}: every round times each variant once, in turn."""
+    for fn in variants.values():             # warm-up: code objects, workspaces, the caching allocator
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(timed(fn, reps))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--step-batch", type=int, default=8)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_mask_scan needs a HIP device: a CPU run cannot give a time")
+    dev = torch.device("cuda:0")
+    B, A, R, H = args.batch, 400, 3360, 640
+    g = torch.Generator().manual_seed(1)
+    scan, mask = torch.rand(B, A, R, generator=g).to(dev), torch.rand(B, H, H, generator=g).to(dev)
+    G = torch.randn(B, A, R, generator=g).to(dev)
+    az = torch.sort(torch.rand(B, A, generator=g, dtype=torch.float64) * 6.28, dim=1).values     # host: no sync in the calls
+
+    def fused():
+        return ru.mask_polar_scan(scan, mask, az, RES)
+
+    def composed():
+        return ru.radar_cartesian_to_polar(mask.double(), az, RES).float() * scan
+
+    def with_backward(op, s, m):
+        def run():
+            s.grad = m.grad = None
+            op(s, m).backward(G)
+        return run
+
+    sg, mg = scan.clone().requires_grad_(True), mask.clone().requires_grad_(True)
+    fused_fb = with_backward(lambda s, m: ru.mask_polar_scan(s, m, az, RES), sg, mg)
+    composed_fb = with_backward(lambda s, m: ru.radar_cartesian_to_polar(m.double(), az, RES).float() * s, sg, mg)
+    assert torch.equal(fused(), composed())
+    fused_fb()
+    gs, gm = sg.grad.clone(), mg.grad.clone()
+    composed_fb()
+    assert torch.equal(gs, sg.grad) and torch.equal(gm, mg.grad)
+
+    cells, pix = B * A * R, B * H * H
+    res = {"shape": {"B": B, "A": A, "R": R, "H": H, "W": H},
+           "algorithmic_bytes": {"fused_forward": 8 * cells, "fused_backward": 20 * cells + 20 * pix},
+           "forward_ms": alternate({"fused": fused, "composed": composed}, args.rounds, args.reps),
+           "forward_backward_ms": alternate({"fused": fused_fb, "composed": composed_fb}, args.rounds, args.reps)}
+    del sg, mg, gs, gm, scan, mask, G
+    torch.cuda.empty_cache()
+
+    # one training step in each mode on the same synthetic batch
+    Bs = args.step_batch
+    raw = synthetic.make_batch(list(range(Bs)), device=dev)
+    steps = {}
+    for mode in ("weights", "scan"):
+        params = trn.default_params(dev)
+        params["mask_target"] = mode
+        batch = trn.prepare_batch(raw, params)
+        torch.manual_seed(0)
+        model = LearnICPWeightPolicy(params).to(dev)
+        opt = trn.make_optimizer(model, params)
+        model.train()
+        steps[mode] = (lambda model=model, batch=batch, opt=opt, params=params:
+                       trn.train_step(model, batch, opt, trn.loss_weights_from(params), dev))
+    res["train_step_ms"] = {"B": Bs, **alternate(steps, args.rounds, max(1, args.reps // 3))}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
