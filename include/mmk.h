@@ -207,6 +207,7 @@ int mmk_bce_fft_threshold_bwd(const float *x, const float *fft, int32_t B, int64
  *                                                        radar_utils.py:71-106,167-195
  * mmk_cfar_mask_bwd, mmk_extract_peaks_bwd <- what autograd does for the two above when
  *                        the scan / the mask requires grad (both default to diff=True upstream)
+ * mmk_cfar_mask_p, mmk_cfar_mask_bwd_p <- the same with a_thresh / b_thresh as tensors   radar_utils.py:56
  * mmk_polar_to_cart    <- radar_polar_to_cartesian_diff  radar_utils.py:258-336
  * mmk_cart_to_polar    <- radar_cartesian_to_polar       radar_utils.py:338-372
  * mmk_polar_to_cart_bwd, mmk_cart_to_polar_bwd <- what autograd does for the two above when
@@ -233,6 +234,29 @@ int mmk_cfar_mask(const float *raw, int32_t B, int32_t A, int32_t R, int32_t w2,
 int mmk_cfar_mask_bwd(const float *raw, const float *grad_mask /*B,A,R*/, int32_t B, int32_t A, int32_t R, int32_t w2,
                       int32_t guard, int32_t mincol, int32_t maxcol, float a_thresh, float b_thresh, float steep_fact,
                       float *grad_raw /*B,A,R*/, void *stream);
+
+/* mmk_cfar_mask with the two thresholds of radar_utils.py:56 (thres = a_thresh * stat + b_thresh, plain tensor arithmetic
+ * upstream) read from device memory: one float each for the batch (per_scan = 0) or B floats each, one per scan
+ * (per_scan = 1).  For equal values the mask is mmk_cfar_mask's bit for bit, for both values of diff; no host
+ * synchronisation. */
+int mmk_cfar_mask_p(const float *raw, int32_t B, int32_t A, int32_t R, int32_t w2, int32_t guard, int32_t mincol,
+                    int32_t maxcol, const float *a_thresh, const float *b_thresh, int32_t per_scan, int32_t diff,
+                    float steep_fact, float *mask, void *stream);
+
+/* mmk_cfar_mask_bwd with device thresholds, plus what autograd gives a_thresh and b_thresh when they are tensors that
+ * require grad (radar_utils.py:56: dthres/da = stat, dthres/db = 1, and dL/dthres_c = -k_c on the cells hardshrink keeps
+ * inside [mincol, maxcol); outside, the threshold is the constant 1000):
+ *   grad_a = - sum of k_c stat_c,   grad_b = - sum of k_c      over the batch (per_scan = 0, 1 float each) or over each
+ * scan (per_scan = 1, B floats each).  k_c, stat_c and the gate are those of the same launch's grad_raw, so grad_raw is
+ * mmk_cfar_mask_bwd's bit for bit.  The sums are fp64 in a fixed order (per thread, per row, then over the rows: no atomics),
+ * bit-reproducible, and a scan's pair does not depend on the other scans of the batch.  grad_raw may be NULL (only the
+ * thresholds require grad): the kernel then stops after the pass that forms k.  workspace: mmk_cfar_mask_bwd_p_ws_bytes(B, A)
+ * bytes (one pair of doubles per row). */
+size_t mmk_cfar_mask_bwd_p_ws_bytes(int32_t B, int32_t A);
+int mmk_cfar_mask_bwd_p(const float *raw, const float *grad_mask /*B,A,R*/, int32_t B, int32_t A, int32_t R, int32_t w2,
+                        int32_t guard, int32_t mincol, int32_t maxcol, const float *a_thresh, const float *b_thresh,
+                        int32_t per_scan, float steep_fact, float *grad_raw /*B,A,R; may be NULL*/, float *grad_a,
+                        float *grad_b /*1 or B*/, void *workspace, size_t workspace_bytes, void *stream);
 
 size_t mmk_extract_peaks_workspace_bytes(int32_t B, int32_t A, int32_t R, int32_t max_pts);
 /* Blob-centre extraction.  out_pc (B,max_pts,3) zero padded in the reference's

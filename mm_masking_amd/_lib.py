@@ -202,6 +202,10 @@ def _declare(lib):
                                            ctypes.POINTER(i32)]),
         "mmk_cfar_mask": (ctypes.c_int, [c_vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, c_vp, c_vp]),
         "mmk_cfar_mask_bwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, c_vp, c_vp]),
+        "mmk_cfar_mask_p": (ctypes.c_int, [c_vp, i32, i32, i32, i32, i32, i32, i32, c_vp, c_vp, i32, i32, f32, c_vp, c_vp]),
+        "mmk_cfar_mask_bwd_p_ws_bytes": (sz, [i32, i32]),
+        "mmk_cfar_mask_bwd_p": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, i32, c_vp, c_vp, i32, f32, c_vp, c_vp, c_vp,
+                                               c_vp, sz, c_vp]),
         "mmk_extract_peaks_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "mmk_extract_peaks_bwd_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "mmk_extract_peaks_bwd": (ctypes.c_int, [c_vp, i32, i32, i32, f32, c_vp, c_vp, i32, f32, i32, c_vp, c_vp, c_vp, sz, c_vp]),

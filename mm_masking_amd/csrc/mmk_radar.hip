@@ -65,10 +65,33 @@ __device__ __forceinline__ int block_excl_scan_i(int v, int *sm, int *total)
 // (CFAR_T = 512 threads per row: the 40 KB row buffer admits four blocks per CU, and with 256 threads each that was 16 waves per
 // CU in a launch that is load -> scan -> compute -> store latency from end to end; 32 waves hide twice as much of it)
 constexpr int CFAR_T = 512;
+
+// The two thresholds of radar_utils.py:56, by value (one pair for the launch) or read from device memory (one pair for the
+// batch, stride 0, or one per scan, stride 1; scan = row / A).  Both forms hand the same two floats to the same expression
+// a_th * stat + b_th, so equal values give equal bits.
+struct CfarThVal {
+    static constexpr bool per_row = false, params = false;
+    float a, b;
+    __device__ __forceinline__ int scan_of(int) const { return 0; }
+    __device__ __forceinline__ float a_of(int) const { return a; }
+    __device__ __forceinline__ float b_of(int) const { return b; }
+};
+struct CfarThPtr {
+    static constexpr bool per_row = true, params = true;
+    const float *a, *b;
+    int stride, A;
+    double *part;                                                   // backward only: one (sum k stat, sum k) pair per row
+    __device__ __forceinline__ int scan_of(int row) const { return row / A; }
+    __device__ __forceinline__ float a_of(int scan) const { return a[scan * stride]; }
+    __device__ __forceinline__ float b_of(int scan) const { return b[scan * stride]; }
+};
+
+template <class TH>
 __global__ __launch_bounds__(CFAR_T) void cfar_mask_kernel(const float *__restrict__ raw, int R, int w2, int guard,
-                                                       int mincol, int maxcol, float a_th, float b_th, int diff,
+                                                       int mincol, int maxcol, TH thr, int diff,
                                                        float steep, float *__restrict__ mask)
 {
+    const float a_th = thr.a_of(blockIdx.y), b_th = thr.b_of(blockIdx.y);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *cs = reinterpret_cast<double *>(smem);                 // R + 1
     float *row = reinterpret_cast<float *>(cs + (R + 1));          // R
@@ -115,9 +138,9 @@ __global__ __launch_bounds__(CFAR_T) void cfar_mask_kernel(const float *__restri
 // scans / thresholds / stores the current one from LDS, so that no row's HBM latency is exposed (the one-row-per-block form is a
 // load -> scan -> compute -> store latency chain end to end, at four rows in flight per CU).  Same thread -> cell partition and
 // the same fp64 sums as cfar_mask_kernel: bit-identical masks.  NPRE >= ceil(R / CFAR_T).
-template <int NPRE>
+template <int NPRE, class TH>
 __global__ __launch_bounds__(CFAR_T) void cfar_mask_rows_kernel(const float *__restrict__ raw, int rows, int R, int w2, int guard,
-                                                                int mincol, int maxcol, float a_th, float b_th, int diff,
+                                                                int mincol, int maxcol, TH thr, int diff,
                                                                 float steep, float *__restrict__ mask)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -147,6 +170,7 @@ __global__ __launch_bounds__(CFAR_T) void cfar_mask_rows_kernel(const float *__r
     __syncthreads();
     const int L = (R + CFAR_T - 1) / CFAR_T;
     const int c0 = min(R, (int)threadIdx.x * L), c1 = min(R, c0 + L);
+    float a_th = thr.a_of(thr.scan_of(r)), b_th = thr.b_of(thr.scan_of(r));
     while (true) {
         const int rn = r + gridDim.x;
         fetch(rn < rows ? rn : r);                                  // (unconditional: past the last row the current one again)
@@ -184,6 +208,10 @@ __global__ __launch_bounds__(CFAR_T) void cfar_mask_rows_kernel(const float *__r
         stage();
         __syncthreads();
         r = rn;
+        if (TH::per_row) {
+            a_th = thr.a_of(thr.scan_of(r));
+            b_th = thr.b_of(thr.scan_of(r));
+        }
     }
 }
 
@@ -814,11 +842,19 @@ PeakWs carve_peaks(int B, int A, int max_pts, void *ws, size_t cap_bytes)
 //   3. prefix of kR over the same array -> the right-window term, and the store
 // All three prefixes are fp64 (a window sum is the difference of two prefixes as long as the row).
 // NPRE >= ceil(R / CFAR_T).
-template <int NPRE>
+// With TH::params (device thresholds) the same step 1 also gives the gradients of the two thresholds (th_c = a_th stat_c + b_th, radar_utils.py:56):
+//   ga = - sum of k_c stat_c,  gb = - sum of k_c   over the cells c in [mincol, maxcol) (outside, th is the constant 1000).
+// Each thread adds its cells in fp64 in ascending i, the block adds the 512 pairs in a fixed order (a shuffle tree per
+// wave, then the eight wave totals through 16 doubles of LDS) and writes one pair of doubles per row to `part`;
+// cfar_param_sum_kernel finishes the sum.  No atomics.  graw == nullptr (only the thresholds require grad): the block stops
+// after step 1.
+template <int NPRE, class TH>
 __global__ __launch_bounds__(CFAR_T) void cfar_mask_bwd_kernel(const float *__restrict__ raw, const float *__restrict__ gmask,
-                                                               int R, int w2, int guard, int mincol, int maxcol, float a_th,
-                                                               float b_th, float steep, float *__restrict__ graw)
+                                                               int R, int w2, int guard, int mincol, int maxcol, TH thr,
+                                                               float steep, float *__restrict__ graw)
 {
+    constexpr bool PARAMS = TH::params;
+    const float a_th = thr.a_of(blockIdx.y), b_th = thr.b_of(blockIdx.y);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *cs = reinterpret_cast<double *>(smem);                 // R + 1
     float *row = reinterpret_cast<float *>(cs + (R + 1));          // R
@@ -848,6 +884,7 @@ __global__ __launch_bounds__(CFAR_T) void cfar_mask_bwd_kernel(const float *__re
     };
     prefix();
     // (in steps 1 and 2 a cell of `row` is touched by its own thread only, while every thread reads windows of cs)
+    double pa = 0.0, pb = 0.0;
 #pragma unroll
     for (int i = 0; i < NPRE; ++i) {
         const int c = threadIdx.x + i * CFAR_T;
@@ -868,9 +905,39 @@ __global__ __launch_bounds__(CFAR_T) void cfar_mask_bwd_kernel(const float *__re
             if (inr) {
                 kl = (left > right) ? k : ((left == right) ? 0.5f * k : 0.0f);
                 kr[i] = (right > left) ? k : ((left == right) ? 0.5f * k : 0.0f);
+                if constexpr (PARAMS) {
+                    const float stat = fmaxf(left, right) / (float)w2;     // the threshold's, bit for bit
+                    pa += (double)k * (double)stat;
+                    pb += (double)k;
+                }
             }
             row[c] = kl;
         }
+    }
+    if constexpr (PARAMS) {
+        __shared__ double psum[2 * (CFAR_T / 64)];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            pa += __shfl_down(pa, off, 64);
+            pb += __shfl_down(pb, off, 64);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            psum[2 * (threadIdx.x >> 6)] = pa;
+            psum[2 * (threadIdx.x >> 6) + 1] = pb;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double ta = 0.0, tb = 0.0;
+#pragma unroll
+            for (int w = 0; w < CFAR_T / 64; ++w) {
+                ta += psum[2 * w];
+                tb += psum[2 * w + 1];
+            }
+            const size_t rowid = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+            thr.part[2 * rowid] = ta;
+            thr.part[2 * rowid + 1] = tb;
+        }
+        if (graw == nullptr) return;                               // (uniform over the block)
     }
     __syncthreads();
     prefix();
@@ -893,6 +960,42 @@ __global__ __launch_bounds__(CFAR_T) void cfar_mask_bwd_kernel(const float *__re
             const float sr = (float)(cs[max(0, c - guard)] - cs[max(0, c - w2 - guard)]);
             graw[base + c] = kd[i] - coef * (sl[i] + sr);
         }
+    }
+}
+
+// The row partials of cfar_mask_bwd_kernel<NPRE, CfarThPtr> summed in a fixed order: one block per output (one for shared thresholds, over
+// all B A rows; one per scan otherwise, over its A rows, so that a scan's gradient does not depend on the rest of the
+// batch).  Thread t adds the rows t, t + RT, ... in ascending order, then the same shuffle tree and wave totals.  Writes
+// the negated sums (dth/da = stat, dth/db = 1, dm/dth = -k) as fp32.
+__global__ __launch_bounds__(RT) void cfar_param_sum_kernel(const double *__restrict__ part, int rows_per_out,
+                                                            float *__restrict__ grad_a, float *__restrict__ grad_b)
+{
+    __shared__ double psum[2 * (RT / 64)];
+    const double *src = part + (size_t)blockIdx.x * rows_per_out * 2;
+    double pa = 0.0, pb = 0.0;
+    for (int r = threadIdx.x; r < rows_per_out; r += RT) {
+        pa += src[2 * r];
+        pb += src[2 * r + 1];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        pa += __shfl_down(pa, off, 64);
+        pb += __shfl_down(pb, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        psum[2 * (threadIdx.x >> 6)] = pa;
+        psum[2 * (threadIdx.x >> 6) + 1] = pb;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double ta = 0.0, tb = 0.0;
+#pragma unroll
+        for (int w = 0; w < RT / 64; ++w) {
+            ta += psum[2 * w];
+            tb += psum[2 * w + 1];
+        }
+        grad_a[blockIdx.x] = (float)(0.0 - ta);
+        grad_b[blockIdx.x] = (float)(0.0 - tb);
     }
 }
 
@@ -1250,7 +1353,7 @@ extern "C" int mmk_cfar_mask(const float *raw, int32_t B, int32_t A, int32_t R, 
     const size_t smem = (size_t)(R + 1) * sizeof(double) + (size_t)R * sizeof(float);
     MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask: R=%d does not fit the 160 KB LDS row buffer", R);
     if (smem > 64 * 1024)
-        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)cfar_mask_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)cfar_mask_kernel<CfarThVal>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     const int rows = A * B;
     if (R <= 8 * CFAR_T && smem <= 40 * 1024) {
         // persistent form: four blocks per CU (40 KB of LDS each), each with its next row in registers
@@ -1260,12 +1363,87 @@ extern "C" int mmk_cfar_mask(const float *raw, int32_t B, int32_t A, int32_t R, 
             if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
         }
         const int grid = std::min(rows, 4 * cus);
-        hipLaunchKernelGGL(cfar_mask_rows_kernel<8>, dim3(grid), dim3(CFAR_T), smem, (hipStream_t)stream, raw, rows, R, w2, guard, mincol,
-                           maxcol, a_thresh, b_thresh, diff, steep_fact, mask);
+        hipLaunchKernelGGL((cfar_mask_rows_kernel<8, CfarThVal>), dim3(grid), dim3(CFAR_T), smem, (hipStream_t)stream, raw, rows, R, w2,
+                           guard, mincol, maxcol, CfarThVal{a_thresh, b_thresh}, diff, steep_fact, mask);
     } else {
-        hipLaunchKernelGGL(cfar_mask_kernel, dim3(A, B), dim3(CFAR_T), smem, (hipStream_t)stream, raw, R, w2, guard, mincol,
-                           maxcol, a_thresh, b_thresh, diff, steep_fact, mask);
+        hipLaunchKernelGGL(cfar_mask_kernel<CfarThVal>, dim3(A, B), dim3(CFAR_T), smem, (hipStream_t)stream, raw, R, w2, guard, mincol,
+                           maxcol, CfarThVal{a_thresh, b_thresh}, diff, steep_fact, mask);
     }
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_cfar_mask_p(const float *raw, int32_t B, int32_t A, int32_t R, int32_t w2, int32_t guard, int32_t mincol,
+                               int32_t maxcol, const float *a_thresh, const float *b_thresh, int32_t per_scan, int32_t diff,
+                               float steep_fact, float *mask, void *stream)
+{
+    MMK_REQUIRE(raw && mask, "mmk_cfar_mask_p: NULL pointer");
+    MMK_REQUIRE(a_thresh && b_thresh, "mmk_cfar_mask_p: NULL threshold pointer");
+    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 1, "mmk_cfar_mask_p: raw_scans must be 3D with non-empty dims");
+    MMK_REQUIRE(w2 >= 1 && guard >= 0, "mmk_cfar_mask_p: bad window (w2=%d guard=%d)", w2, guard);
+    MMK_REQUIRE(mincol >= w2 + guard && maxcol <= R, "mmk_cfar_mask_p: column range [%d,%d) outside the row", mincol, maxcol);
+    const size_t smem = (size_t)(R + 1) * sizeof(double) + (size_t)R * sizeof(float);
+    MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask_p: R=%d does not fit the 160 KB LDS row buffer", R);
+    if (smem > 64 * 1024)
+        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)cfar_mask_kernel<CfarThPtr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const CfarThPtr thr{a_thresh, b_thresh, per_scan ? 1 : 0, A, nullptr};
+    const int rows = A * B;
+    if (R <= 8 * CFAR_T && smem <= 40 * 1024) {                     // the same choice of kernel as mmk_cfar_mask
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) {
+            int v = 0;
+            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+        }
+        const int grid = std::min(rows, 4 * cus);
+        hipLaunchKernelGGL((cfar_mask_rows_kernel<8, CfarThPtr>), dim3(grid), dim3(CFAR_T), smem, (hipStream_t)stream, raw, rows, R, w2, guard,
+                           mincol, maxcol, thr, diff, steep_fact, mask);
+    } else {
+        hipLaunchKernelGGL(cfar_mask_kernel<CfarThPtr>, dim3(A, B), dim3(CFAR_T), smem, (hipStream_t)stream, raw, R, w2, guard, mincol,
+                           maxcol, thr, diff, steep_fact, mask);
+    }
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" size_t mmk_cfar_mask_bwd_p_ws_bytes(int32_t B, int32_t A)
+{
+    if (B < 1 || A < 1) return 0;
+    return mmk::align_up((size_t)B * A * 2 * sizeof(double), 256);  // one (sum k stat, sum k) pair per row
+}
+
+extern "C" int mmk_cfar_mask_bwd_p(const float *raw, const float *grad_mask, int32_t B, int32_t A, int32_t R, int32_t w2,
+                                   int32_t guard, int32_t mincol, int32_t maxcol, const float *a_thresh, const float *b_thresh,
+                                   int32_t per_scan, float steep_fact, float *grad_raw, float *grad_a, float *grad_b,
+                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    MMK_REQUIRE(raw && grad_mask && grad_a && grad_b, "mmk_cfar_mask_bwd_p: NULL pointer");
+    MMK_REQUIRE(a_thresh && b_thresh, "mmk_cfar_mask_bwd_p: NULL threshold pointer");
+    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 1, "mmk_cfar_mask_bwd_p: raw_scans must be 3D with non-empty dims");
+    MMK_REQUIRE(w2 >= 1 && guard >= 0, "mmk_cfar_mask_bwd_p: bad window (w2=%d guard=%d)", w2, guard);
+    MMK_REQUIRE(mincol >= w2 + guard && maxcol <= R, "mmk_cfar_mask_bwd_p: column range [%d,%d) outside the row", mincol, maxcol);
+    const size_t smem = (size_t)(R + 1) * sizeof(double) + (size_t)R * sizeof(float);
+    MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask_bwd_p: R=%d does not fit the 160 KB LDS row buffer", R);
+    const size_t need = mmk_cfar_mask_bwd_p_ws_bytes(B, A);
+    if (workspace == nullptr || need > workspace_bytes) {
+        mmk::set_error("mmk_cfar_mask_bwd_p: workspace too small (%zu < %zu)", workspace_bytes, need);
+        return MMK_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    double *part = static_cast<double *>(workspace);
+    const CfarThPtr thr{a_thresh, b_thresh, per_scan ? 1 : 0, A, part};
+    if (R <= 8 * CFAR_T) {
+        hipLaunchKernelGGL((cfar_mask_bwd_kernel<8, CfarThPtr>), dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard, mincol,
+                           maxcol, thr, steep_fact, grad_raw);
+    } else {
+        constexpr int NLONG = 27;                                   // as in mmk_cfar_mask_bwd
+        if (smem > 64 * 1024)
+            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)(cfar_mask_bwd_kernel<NLONG, CfarThPtr>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)smem));
+        hipLaunchKernelGGL((cfar_mask_bwd_kernel<NLONG, CfarThPtr>), dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard,
+                           mincol, maxcol, thr, steep_fact, grad_raw);
+    }
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cfar_param_sum_kernel, dim3(per_scan ? B : 1), dim3(RT), 0, st, part, per_scan ? A : A * B, grad_a, grad_b);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -1318,17 +1496,17 @@ extern "C" int mmk_cfar_mask_bwd(const float *raw, const float *grad_mask, int32
     MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask_bwd: R=%d does not fit the 160 KB LDS row buffer", R);
     hipStream_t st = (hipStream_t)stream;
     if (R <= 8 * CFAR_T) {
-        hipLaunchKernelGGL(cfar_mask_bwd_kernel<8>, dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard, mincol, maxcol,
-                           a_thresh, b_thresh, steep_fact, grad_raw);
+        hipLaunchKernelGGL((cfar_mask_bwd_kernel<8, CfarThVal>), dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard, mincol,
+                           maxcol, CfarThVal{a_thresh, b_thresh}, steep_fact, grad_raw);
     } else {
         // the longest row of the LDS budget: (160 KB - 64) / 12 B = 13 648 cells = 26.7 per thread
         constexpr int NLONG = 27;
         static_assert((size_t)NLONG * CFAR_T * 12 >= 160 * 1024, "cfar_mask_bwd_kernel<NLONG> must hold every row the LDS admits");
         if (smem > 64 * 1024)
-            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)cfar_mask_bwd_kernel<NLONG>, hipFuncAttributeMaxDynamicSharedMemorySize,
+            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)(cfar_mask_bwd_kernel<NLONG, CfarThVal>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                               (int)smem));
-        hipLaunchKernelGGL(cfar_mask_bwd_kernel<NLONG>, dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard, mincol,
-                           maxcol, a_thresh, b_thresh, steep_fact, grad_raw);
+        hipLaunchKernelGGL((cfar_mask_bwd_kernel<NLONG, CfarThVal>), dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard,
+                           mincol, maxcol, CfarThVal{a_thresh, b_thresh}, steep_fact, grad_raw);
     }
     MMK_LAUNCH_CHECK();
     return MMK_OK;

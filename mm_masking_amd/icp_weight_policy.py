@@ -132,6 +132,15 @@ class LearnICPWeightPolicy(nn.Module):
         self.final_layer = nn.Sequential(nn.Conv2d(dec_channels[-1], 1, kernel_size=1), nn.Sigmoid())
         if params["init_weights"]:
             self.apply(weights_init)
+        # params["learn_cfar"] (absent upstream): the two GO-CFAR thresholds of the scan mode's detector become parameters,
+        # trained with the mask through cfar_mask's threshold gradients.  They start from params["a_thresh"] / ["b_thresh"];
+        # the CFAR input channel (computed with diff=False by the dataset / prepare_batch) keeps those fixed values.
+        self.learn_cfar = bool(params.get("learn_cfar", False))
+        if self.learn_cfar:
+            if self.mask_target != "scan":
+                raise ValueError("learn_cfar needs mask_target='scan': the default mode never runs the detector in its forward")
+            self.cfar_a = nn.Parameter(torch.tensor(float(self.a_thres), dtype=torch.float32))
+            self.cfar_b = nn.Parameter(torch.tensor(float(self.b_thres), dtype=torch.float32))
 
     @property
     def global_minmax(self):
@@ -316,14 +325,16 @@ class LearnICPWeightPolicy(nn.Module):
 
     def _forward_scan(self, batch_scan, map_pc, T_init, weight_mask, max_pts):
         """mask_target="scan": mask -> masked polar scan -> GO-CFAR -> blob centres -> unweighted ICP, every link with its
-        hand-written backward.  diff=True in training and evaluation alike, so both see the same cloud."""
+        hand-written backward.  diff=True in training and evaluation alike, so both see the same cloud.  With
+        params["learn_cfar"] the detector reads its thresholds from the parameters cfar_a / cfar_b on the device."""
         azimuths = batch_scan["azimuths"]
         if self.network_input_type == "polar":          # the mask is polar already
             masked = weight_mask * batch_scan["fft_data"].to(self.device)
         else:
             # (host azimuths cost no synchronisation: the operator forms their sin / cos on the host)
             masked = mask_polar_scan(batch_scan["fft_polar"].to(self.device), weight_mask, azimuths, self.res)
-        m = cfar_mask(masked, self.res, a_thresh=self.a_thres, b_thresh=self.b_thres, diff=True)
+        a_th, b_th = (self.cfar_a, self.cfar_b) if self.learn_cfar else (self.a_thres, self.b_thres)
+        m = cfar_mask(masked, self.res, a_thresh=a_th, b_thresh=b_th, diff=True)
         az = azimuths.to(self.device)
         az_times = batch_scan.get("az_times")
         az_times = torch.zeros_like(az) if az_times is None else az_times.to(self.device)

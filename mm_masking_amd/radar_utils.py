@@ -317,14 +317,100 @@ class _CfarMask(torch.autograd.Function):
         return gx.to(device=ctx.like[1], dtype=ctx.like[0]), None, None, None, None, None
 
 
+def _cfar_threshold_sizes(a_thresh, b_thresh, B):
+    """Number of values the kernels read per threshold (1: shared by the batch, B: one per scan) for thresholds of which
+    at least one is a tensor.  Shapes are checked here, before anything touches the device."""
+    n = 1
+    for name, v in (("a_thresh", a_thresh), ("b_thresh", b_thresh)):
+        if not torch.is_tensor(v):
+            continue
+        shape = tuple(v.shape)
+        if shape not in ((), (1,), (B,), (B, 1, 1)):
+            raise ValueError("%s must be a number or a tensor of shape (), (1,), (%d,) or (%d, 1, 1) (got %s)"
+                             % (name, B, B, shape))
+        n = max(n, v.numel())
+    return n
+
+
+def _cfar_threshold_dev(v, n, dev):
+    """A threshold as n contiguous fp32 values on the device; a number or a single value is broadcast there."""
+    if torch.is_tensor(v):
+        t = v.detach().to(device=dev, dtype=torch.float32).reshape(-1)
+        return t.expand(n).contiguous() if t.numel() != n else t.contiguous()
+    return torch.full((n,), float(v), dtype=torch.float32, device=dev)
+
+
+def _cfar_forward_p(x, w2, guard, mincol, maxcol, a, b, diff, steep_fact):
+    B, A, R = x.shape
+    out = torch.empty_like(x)
+    _lib.check(_lib.lib().mmk_cfar_mask_p(_lib.ptr(x), B, A, R, w2, guard, mincol, max(mincol, maxcol), _lib.ptr(a), _lib.ptr(b),
+                                          1 if a.numel() > 1 else 0, 1 if diff else 0, float(steep_fact), _lib.ptr(out),
+                                          _lib.stream_ptr(x.device)))
+    return out
+
+
+class _CfarMaskP(torch.autograd.Function):
+    """cfar_mask(diff=True) with tensor thresholds (mmk_cfar_mask_p / mmk_cfar_mask_bwd_p): the scan's gradient of _CfarMask
+    and the gradients autograd takes through ``thres = a_thresh * stat + b_thresh`` (radar_utils.py:56) with respect to the
+    two thresholds, per scan or summed over the batch as the thresholds' shapes ask."""
+
+    @staticmethod
+    def forward(ctx, raw_scans, a_thresh, b_thresh, dev, cols, steep_fact, n):
+        x = _lib.dev_f32(raw_scans, dev)
+        a, b = _cfar_threshold_dev(a_thresh, n, dev), _cfar_threshold_dev(b_thresh, n, dev)
+        out = _cfar_forward_p(x, *cols, a, b, True, steep_fact)
+        ctx.save_for_backward(x, a, b)
+        ctx.args = (cols, float(steep_fact))
+        ctx.like = [(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else None for t in (raw_scans, a_thresh, b_thresh)]
+        return _back(out, raw_scans)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, a, b = ctx.saved_tensors
+        (w2, guard, mincol, maxcol), steep_fact = ctx.args
+        B, A, R = x.shape
+        dev = x.device
+        g = _lib.dev_f32(g, dev)
+        L = _lib.lib()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None       # NULL: the kernel stops after its first pass
+        ga, gb = torch.empty_like(a), torch.empty_like(b)
+        ws = _workspace(int(L.mmk_cfar_mask_bwd_p_ws_bytes(B, A)), dev)
+        _lib.check(L.mmk_cfar_mask_bwd_p(_lib.ptr(x), _lib.ptr(g), B, A, R, w2, guard, mincol, max(mincol, maxcol), _lib.ptr(a),
+                                         _lib.ptr(b), 1 if a.numel() > 1 else 0, steep_fact, _lib.ptr(gx), _lib.ptr(ga),
+                                         _lib.ptr(gb), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        grads = []
+        for need, like, val in zip(ctx.needs_input_grad[:3], ctx.like, (gx, ga, gb)):
+            if not need:
+                grads.append(None)
+                continue
+            dtype, device, shape = like
+            if val.numel() != int(np.prod(shape)):                          # a single value broadcast over the scans
+                val = val.sum()
+            grads.append(val.reshape(shape).to(device=device, dtype=dtype))
+        return tuple(grads) + (None,) * 4
+
+
 def cfar_mask(raw_scans, res, width=101, minr=2.0, maxr=80.0, guard=5,
               a_thresh=1.0, b_thresh=0.09, diff=True, steep_fact=10.0):
     """GO-CFAR mask, radar_utils.py:29-69.  (B,A,R) fp32 -> (B,A,R) fp32.  With ``diff=True`` the mask is
     differentiable in ``raw_scans`` (the gradient comes back in its dtype and on its device); with ``diff=False`` it
-    does not require grad, as upstream (torch.where of constants)."""
+    does not require grad, as upstream (torch.where of constants).
+
+    ``a_thresh`` and ``b_thresh`` are Python numbers or, as upstream's ``a_thresh * stat + b_thresh`` (:56) allows, tensors of
+    shape (), (1,), (B,) or (B,1,1): one value for the batch or one per scan.  Tensors are read on the device (no host
+    synchronisation; a number mixed with a tensor is broadcast there), and with ``diff=True`` each one that requires grad
+    receives its gradient in its own shape, dtype and on its device.  Any other shape raises ``ValueError``."""
     assert raw_scans.ndim == 3, "raw_scans must be 3D"
+    tensors = torch.is_tensor(a_thresh) or torch.is_tensor(b_thresh)
+    n = _cfar_threshold_sizes(a_thresh, b_thresh, raw_scans.shape[0]) if tensors else 0
     dev = _hip_device(raw_scans)
     w2, mincol, maxcol = cfar_cols(raw_scans.shape[2], res, width, minr, maxr, guard)
+    if tensors:
+        if diff and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (raw_scans, a_thresh, b_thresh)):
+            return _CfarMaskP.apply(raw_scans, a_thresh, b_thresh, dev, (w2, guard, mincol, maxcol), steep_fact, n)
+        x = _lib.dev_f32(raw_scans, dev)
+        a, b = _cfar_threshold_dev(a_thresh, n, dev), _cfar_threshold_dev(b_thresh, n, dev)
+        return _back(_cfar_forward_p(x, w2, guard, mincol, maxcol, a, b, diff, steep_fact), raw_scans)
     if diff and torch.is_grad_enabled() and raw_scans.requires_grad:
         return _CfarMask.apply(raw_scans, dev, (w2, guard, mincol, maxcol), a_thresh, b_thresh, steep_fact)
     x = _lib.dev_f32(raw_scans, dev)
