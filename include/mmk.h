@@ -453,8 +453,18 @@ typedef struct {
                               scan order | (maximum > 0) << 2.  When set, y1 is NOT written (may be NULL): the pooled
                               tensor and the codes are all that the rest of the network and its backward pass
                               (mmk_maxpool2_bwd_arg) read of this layer's output                  */
+    const void *x1_pool_arg; /* optional (NULL: x1 is the input itself).  Set: x1 is a POOLED tensor bf16 (B,H/2,W/2,C1) and the
+                              convolution's input is its max-pool adjoint -- what mmk_maxpool2_bwd_arg(x1_pool_arg, x1, B, H, W,
+                              C1, x1_pool_scale) would have written as a (B,H,W,C1) tensor, bit for bit -- routed by these
+                              arg-max codes (layout: pool_arg) inside the kernel's staging.  ReLU network, C2 = 0, data
+                              gradients with a ReLU source or accumulate target of 32 -> 32 and of the >= 64-channel layers;
+                              other layers are refused                                            */
+    float x1_pool_scale;   /* with x1_pool_arg: the factor of the routed values (dropout's 1 / keep) */
 } mmk_conv_desc;
 
+/* sizeof(mmk_conv_desc) as the library was built: a caller with its own mirror of the struct compares it with its mirror's size
+ * (the struct grows at its end: x1_pool_arg / x1_pool_scale were appended without a change of MMK_VERSION). */
+size_t mmk_conv_desc_bytes(void);
 /* 1 when mmk_conv3x3 can write the 2x2 max-pool of this layer's output itself (pool_y). */
 int32_t mmk_conv3x3_pool_fusable(int32_t cin, int32_t cout, int32_t B, int32_t H, int32_t W);
 
@@ -486,6 +496,16 @@ int mmk_conv3x3_wgrad_partial(const void *x1, const void *x2, int32_t C1, int32_
  * partials holds mmk_conv3x3_wgrad_slices(C, C, C, B, H, W) slices of 9*C*C + C floats. */
 int mmk_conv_bwd_fused(const void *x, const void *g, const void *wpack_t, float scale, int32_t B, int32_t H, int32_t W,
                        int32_t C, void *dx, float *partials, int32_t accumulate, void *stream);
+/* The same (C = 16) and mmk_conv3x3_wgrad_partial (32 -> 32, or channel counts that are multiples of 64) with the output
+ * gradient given as a POOLED gradient gy (B,H/2,W/2,cout) + arg-max codes (mmk_conv_desc.pool_arg layout) + factor: g is the
+ * max-pool adjoint mmk_maxpool2_bwd_arg(arg, gy, B, H, W, cout, pool_scale) would have written, taken through the codes while
+ * staging -- bit-identical to that launch followed by the plain entry point, without the full-resolution tensor. */
+int mmk_conv_bwd_fused_pooled(const void *x, const void *gy, const void *arg, float pool_scale, const void *wpack_t, float scale,
+                              int32_t B, int32_t H, int32_t W, int32_t C, void *dx, float *partials, int32_t accumulate,
+                              void *stream);
+int mmk_conv3x3_wgrad_partial_pooled(const void *x1, const void *x2, int32_t C1, int32_t C2, const void *gy, const void *arg,
+                                     float pool_scale, int32_t cout, int32_t B, int32_t H, int32_t W, float *partials,
+                                     int32_t accumulate, void *stream);
 
 /* The same for the backward of an 8 -> 16 convolution whose data gradient (16 -> 8) takes the layer's input activation x as
  * ReLU source and ADDS its result to what dx holds (first convolution of encoder block 1: the skip gradient is there

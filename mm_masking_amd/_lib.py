@@ -57,7 +57,7 @@ class ConvDesc(ctypes.Structure):
                 ("accumulate2", ctypes.c_int32), ("scale2", ctypes.c_float),
                 ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("relu", ctypes.c_int32),
                 ("leaky_slope", ctypes.c_float), ("drop_p", ctypes.c_float), ("seed", ctypes.c_uint32), ("pool_y", ctypes.c_void_p),
-                ("pool_arg", ctypes.c_void_p)]
+                ("pool_arg", ctypes.c_void_p), ("x1_pool_arg", ctypes.c_void_p), ("x1_pool_scale", ctypes.c_float)]
 
 
 class UNetDesc(ctypes.Structure):
@@ -163,8 +163,11 @@ def _declare(lib):
         "mmk_conv3x3_wgrad_slices": (i32, [i32, i32, i32, i32, i32, i32]),
         "mmk_conv3x3_wgrad_partial": (ctypes.c_int, [c_vp, c_vp, i32, i32, c_vp, i32, i32, i32, i32, c_vp, i32, c_vp]),
         "mmk_conv_bwd_fused": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_float, i32, i32, i32, i32, c_vp, c_vp, i32, c_vp]),
+        "mmk_conv_bwd_fused_pooled": (ctypes.c_int, [c_vp, c_vp, c_vp, f32, c_vp, f32, i32, i32, i32, i32, c_vp, c_vp, i32, c_vp]),
+        "mmk_conv3x3_wgrad_partial_pooled": (ctypes.c_int, [c_vp, c_vp, i32, i32, c_vp, c_vp, f32, i32, i32, i32, i32, c_vp, i32, c_vp]),
         "mmk_conv8x16_bwd_fused": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_float, i32, i32, i32, c_vp, c_vp, i32, c_vp]),
         "mmk_conv16x8_bwd_fused": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_float, i32, i32, i32, c_vp, c_vp, c_vp, i32, c_vp]),
+        "mmk_conv_desc_bytes": (sz, []),
         "mmk_conv3x3_pool_fusable": (ctypes.c_int32, [i32, i32, i32, i32, i32]),
         "mmk_channel_minmax": (ctypes.c_int, [c_vp, i32, i32, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
         "mmk_channel_meanstd": (ctypes.c_int, [c_vp, i32, i32, ctypes.c_int64, c_vp, c_vp, c_vp]),
@@ -256,6 +259,8 @@ def lib():
         except OSError as e:
             raise MmkError("cannot load %s: %s" % (SO_PATH, e)) from e
         EXPORTED = _declare(loaded)
+        if loaded.mmk_conv_desc_bytes() != ctypes.sizeof(ConvDesc):
+            raise MmkError("%s: mmk_conv_desc is %d bytes, the ctypes mirror %d" % (SO_PATH, loaded.mmk_conv_desc_bytes(), ctypes.sizeof(ConvDesc)))
         _lib = loaded
     return _lib
 

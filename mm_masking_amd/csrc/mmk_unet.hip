@@ -464,6 +464,61 @@ __device__ __forceinline__ void lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// ------------------------------------------------------------------------------------------
+// The max-pool adjoint inside its consumers (ReLU network).  maxpool2_bwd_arg_kernel writes a full-resolution gradient of
+// which three of four elements are +0 and the fourth is bf16(float(pooled gradient) * scale), picked by the arg-max codes; the
+// kernels that read that tensor (template parameter POOLG) stage it from the pooled gradient and the codes themselves.  A
+// thread owns POOLED granules instead of full-resolution ones: granule gc of pooled pixel (b, py, px) is
+//   e = ((b * (H/2) + py) * (W/2) + px) * (C/8) + gc,  values gy[8 e .. 8 e + 7],  code word arg[e]
+// (both loads go to zero words outside the pooled image: a zero code word never hits, so the out-of-image halo and the last
+// row / column of an odd-sized level, which floor pooling leaves outside every window, come out as +0), and when the tile is
+// written to LDS the thread writes the up to four pixels (2 py + k / 2, 2 px + k % 2) of the window that lie in the tile.  Tile
+// origins are even, so the windows that cover a tile (with its halo: TH/2 + 2 rows of TW/2 + 2) cover each of its pixels
+// exactly once: a quarter of the loads and staging registers of the full-resolution form.
+// poolg_scale: the routed values, rounded exactly as maxpool2_bwd_arg_kernel rounds them (float * scale -> bf16).
+__device__ __forceinline__ u32x4 poolg_scale(const u32x4 g, float scale)
+{
+    float f[8];
+    unpack8(g, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = f[j] * scale;
+    return pack8(f);
+}
+// poolg_route<K>: the granule of window position K: channel j keeps its value where its nibble of the code word is K | 4 (first
+// maximum at K, and positive), +0 elsewhere.  code ^ (K | 4 in every nibble) has a zero nibble exactly at the hits (the nibbles'
+// top bits are never set); the miss bits of the even / odd channels are moved to the sign bits of the bytes of two words,
+// v_perm_b32 pairs them up per packed bf16 pair and a packed arithmetic shift spreads the signs: three instructions per pair
+// of channels, no per-channel compare.
+template <int K>
+__device__ __forceinline__ u32x4 poolg_route(const u32x4 v, unsigned code)
+{
+    const unsigned x = code ^ ((unsigned)(K | 4) * 0x11111111u);
+    const unsigned t = x | (x >> 1) | (x >> 2);       // bit 0 of a nibble: the channel misses
+    const unsigned te = t << 7, to = t << 3;          // bit 7 of byte j: channel 2 j / 2 j + 1 misses
+    u32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        unsigned m;
+        asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(m) : "v"(0x000f000fu), "v"(__builtin_amdgcn_perm(to, te, 0x040c000cu + (unsigned)j * 0x01000100u)));
+        o[j] = v[j] & ~m;
+    }
+    return o;
+}
+// Writes the window of one pooled granule into an LDS tile: `dst` = where the first pixel of the window would sit in the tile (element
+// pointer, granule offset included), `pitch` / `row` = elements per pixel / per tile row, (r0, c0) = tile coordinates of the
+// window's first pixel (-1 for the windows that straddle the upper / left halo edge), (rows, cols) = the tile's extent.
+__device__ __forceinline__ void poolg_write(bf16 *dst, int pitch, int row, int r0, int c0, int rows, int cols, bool on,
+                                            const u32x4 g, unsigned code, float scale)
+{
+    const u32x4 v = poolg_scale(g, scale);
+    const bool r_lo = on && (unsigned)r0 < (unsigned)rows, r_hi = on && (unsigned)(r0 + 1) < (unsigned)rows;
+    const bool c_lo = (unsigned)c0 < (unsigned)cols, c_hi = (unsigned)(c0 + 1) < (unsigned)cols;
+    if (r_lo && c_lo) *reinterpret_cast<u32x4 *>(dst) = poolg_route<0>(v, code);
+    if (r_lo && c_hi) *reinterpret_cast<u32x4 *>(dst + pitch) = poolg_route<1>(v, code);
+    if (r_hi && c_lo) *reinterpret_cast<u32x4 *>(dst + row) = poolg_route<2>(v, code);
+    if (r_hi && c_hi) *reinterpret_cast<u32x4 *>(dst + row + pitch) = poolg_route<3>(v, code);
+}
+
 // Diagnostic build only (-DMMK_DEEP_STAMPS; scripts/deep_stamps.py): the first 64 blocks record s_memtime at eight points of each
 // of their first MMK_STAMP_STAGES stages, per wave, in LDS, and copy them to a caller's buffer when they exit (conv3x3_ring_kernel:
 // the same per tile, plus every block's start and end on the 100 MHz clock: scripts/ring_stamps.py).  The shipped library
@@ -488,7 +543,8 @@ __device__ unsigned long long *g_deep_stamp_buf = nullptr;
 // POOL: 0 = no pooling; 1 = the output and its 2x2 max-pool (pool_y); 2 = the max-pool and its arg-max codes (pool_y, pool_arg)
 // only: the full-resolution output is not written at all (the backward pass routes the pooled gradient by the codes,
 // maxpool2_bwd_arg_kernel, and nothing else reads the block's pre-pool output)
-template <int CK, int CM, int RD, bool EPI, int POOL = 0, bool C8 = false>
+// POOLG: the input x1 is the max-pool adjoint of a pooled gradient, taken through the codes (poolg_write; ConvArgs::x1_pool_arg)
+template <int CK, int CM, int RD, bool EPI, int POOL = 0, bool C8 = false, bool POOLG = false>
 __global__ __launch_bounds__(CONV_THREADS) void conv3x3_ring_kernel(const ConvArgs a, int total_tiles, int tiles_per_xcd)
 {
     static_assert(!(EPI && POOL), "the pooled output belongs to the forward pass (no epilogue operands)");
@@ -534,7 +590,11 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_ring_kernel(const ConvAr
     // (scripts/ring_stamps.py).  Handing s_setprio 2 to another wave slot every 4 096 cycles narrows that to 59 .. 97 us and moves
     // the launch by nothing, and so does giving blocks 4-24 consecutive tiles each and leaving the balance to the hardware
     // dispatcher (slower): two or more resident blocks already keep the CU as busy as five do, profiles/r05_ring_stamps.txt.)
-    u32x4 rin[RD][RIN];
+    // POOLG: the thread's granules are pooled ones (poolg_write: the windows that cover the halo tile), with their code words
+    constexpr int PHT = TH / 2 + 2, PWT = TW / 2 + 2, NPIN = PHT * PWT * GPP;
+    constexpr int NRIN = POOLG ? (NPIN + CONV_THREADS - 1) / CONV_THREADS : RIN;
+    u32x4 rin[RD][NRIN];
+    unsigned rcd[POOLG ? RD : 1][POOLG ? NRIN : 1];
     // Everything per-lane that does not depend on the tile is worked out once: addresses inside the
     // loop are then "uniform tile origin (scalar unit) + 32-bit lane offset", a handful of VALU
     // instructions per access instead of a 64-bit index computation (the full-resolution layers
@@ -552,6 +612,14 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_ring_kernel(const ConvAr
         g_dx[i] = dx1 - 1;
         in_x2[i] = c >= a.C1;
         in_off[i] = in_x2[i] ? (dy1 * a.W + dx1) * a.C2 + (c - a.C1) : (dy1 * a.W + dx1) * a.C1 + c;
+        if constexpr (POOLG) {      // (pooled row / column from the tile's first pooled pixel, -1 = the window on the halo edge)
+            int gp = tid + i * CONV_THREADS;
+            gp = gp < NPIN ? gp : NPIN - 1;
+            const int pp = gp / GPP;
+            g_dy[i] = pp / PWT - 1;
+            g_dx[i] = pp % PWT - 1;
+            in_off[i] = (g_dy[i] * (a.W >> 1) + g_dx[i]) * a.C1 + (gp % GPP) * 8;
+        }
     }
     // output side: lane (m, n) owns 4 channels from c0 of pixel (2 wv + n/2, 16 (n&1) + lane%16) of the tile
     bool o_cv[MT], o_has_src[MT], o_accm[MT];
@@ -627,11 +695,22 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_ring_kernel(const ConvAr
         if constexpr (POOL) s_pp0[SLOT] = (ld_b * Hp + (ty0_ >> 1)) * Wp + (tx0_ >> 1);                      \
         const long org_ = (long)pix0_ - a.W - 1;                       /* halo origin pixel */               \
         const bf16 *base1_ = a.x1 + org_ * a.C1, *base2_ = a.x2 + org_ * a.C2;                               \
+        if constexpr (POOLG) {                                                                               \
+            const long pe_ = ((long)(ld_b * Hp + (ty0_ >> 1)) * Wp + (tx0_ >> 1)) * a.C1;                    \
+            const bf16 *pb_ = a.x1 + pe_;                                                                    \
+            const unsigned *cb_ = a.x1_pool_arg + (pe_ >> 3);                                                \
+            _Pragma("unroll") for (int i = 0; i < NRIN; ++i) {                                               \
+                const bool ok = (unsigned)((ty0_ >> 1) + g_dy[i]) < (unsigned)Hp && (unsigned)((tx0_ >> 1) + g_dx[i]) < (unsigned)Wp; \
+                rin[SLOT][i] = *(ok ? reinterpret_cast<const u32x4 *>(pb_ + in_off[i]) : &g_zero16);         \
+                rcd[SLOT][i] = *(ok ? cb_ + (in_off[i] >> 3) : reinterpret_cast<const unsigned *>(&g_zero16)); \
+            }                                                                                                \
+        } else {                                                                                             \
         _Pragma("unroll") for (int i = 0; i < RIN; ++i) {                                                    \
             const bool ok = (unsigned)(ty0_ + g_dy[i]) < (unsigned)a.H && (unsigned)(tx0_ + g_dx[i]) < (unsigned)a.W; \
             const bf16 *src = (in_x2[i] ? base2_ : base1_) + in_off[i];                                      \
             const u32x4 *sp = (ok && MMK_RING_DIAG != 2) ? reinterpret_cast<const u32x4 *>(src) : &g_zero16; \
             rin[SLOT][i] = *sp;                                                                              \
+        }                                                                                                    \
         }                                                                                                    \
         /* next tile of the walk (parks on the block's last tile: the ring keeps re-loading it) */           \
         const bool adv_ = ld_left > 0;                                                                       \
@@ -653,9 +732,18 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_ring_kernel(const ConvAr
 #define MMK_RING_STORE(SLOT, BUF)                                                                            \
     {                                                                                                        \
         bf16 *dst_ = in_tile + (BUF) * (HT * WT * PK);                                                       \
+        if constexpr (POOLG) {                                                                               \
+            _Pragma("unroll") for (int i = 0; i < NRIN; ++i) {                                               \
+                const int g = tid + i * CONV_THREADS;                                                        \
+                const int r0 = 2 * g_dy[i] + 1, c0 = 2 * g_dx[i] + 1;                                        \
+                poolg_write(dst_ + (r0 * WT + c0) * PK + (g % GPP) * 8, PK, WT * PK, r0, c0, HT, WT, g < NPIN, \
+                            rin[SLOT][i], rcd[SLOT][i], a.x1_pool_scale);                                    \
+            }                                                                                                \
+        } else {                                                                                             \
         _Pragma("unroll") for (int i = 0; i < RIN; ++i) {                                                    \
             const int g = tid + i * CONV_THREADS;                                                            \
             if (g < NIN) *reinterpret_cast<u32x4 *>(dst_ + (size_t)(g / GPP) * PK + (g % GPP) * 8) = rin[SLOT][i]; \
+        }                                                                                                    \
         }                                                                                                    \
     }
 
@@ -793,7 +881,7 @@ ring_done:;
 #undef MMK_RING_STORE
 }
 
-template <int CK, int CM, int RD, bool EPI, int POOL = 0, bool C8 = false>
+template <int CK, int CM, int RD, bool EPI, int POOL = 0, bool C8 = false, bool POOLG = false>
 int launch_conv_ring(const ConvArgs &a, hipStream_t st)
 {
 #ifdef MMK_DEEP_STAMPS
@@ -807,10 +895,10 @@ int launch_conv_ring(const ConvArgs &a, hipStream_t st)
     MMK_CHECK_HIP(hipGetDevice(&dev));
     if (per_cu[dev & 63] == 0) {
         if (smem > 64 * 1024)
-            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8>,
+            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8, POOLG>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         int nblk = 0;
-        MMK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8>, CONV_THREADS,
+        MMK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8, POOLG>, CONV_THREADS,
                                                                    smem));
         per_cu[dev & 63] = nblk < 1 ? 1 : (nblk > 8 ? 8 : nblk);
     }
@@ -820,7 +908,7 @@ int launch_conv_ring(const ConvArgs &a, hipStream_t st)
     const int per_xcd = (total + 7) / 8;
     int nb = (32 * per_cu[dev & 63]) / groups;                 // blocks per XCD (32 CUs each)
     nb = nb < 1 ? 1 : (nb > per_xcd ? per_xcd : nb);
-    hipLaunchKernelGGL((conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8>), dim3(8 * nb, groups), dim3(CONV_THREADS), smem, st, a, total,
+    hipLaunchKernelGGL((conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8, POOLG>), dim3(8 * nb, groups), dim3(CONV_THREADS), smem, st, a, total,
                        per_xcd);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
@@ -844,6 +932,13 @@ int launch_conv_ring_epi(const ConvArgs &a, hipStream_t st)
     // two slots there, and the registers go to occupancy
     constexpr int RDE = 2;
     const bool epi = a.o1.relu_src || a.o1.accumulate || (a.o2.C > 0 && (a.o2.relu_src || a.o2.accumulate));
+    if (a.x1_pool_arg != nullptr) {     // pooled gradient input: the data gradient of encoder block 2's second convolution
+        if constexpr (CK == 32 && CM == 32) {
+            if (epi && a.pool_y == nullptr) return launch_conv_ring<CK, CM, RDE, true, 0, false, true>(a, st);
+        }
+        mmk::set_error("mmk_conv3x3: x1_pool_arg is not supported for this layer (CIN=%d COUT=%d)", a.CIN, a.COUT);
+        return MMK_ERR_ARG;
+    }
     if (a.pool_y != nullptr) {
         if constexpr (CK == CM && (CK == 16 || CK == 32)) {   // the encoder's second convs below 64 channels
             if (!epi && a.o2.C == 0)
@@ -911,7 +1006,8 @@ struct DeepCfg {
 //     everything, for the LeakyReLU network and other callers of the ABI.
 // SUBW: the packed weights are laid out for blocks of a.wpack_mtb 16-channel tiles (a wider BM); this block's BM channels are a
 // slice of one such group (the tail launches of dispatch_conv_deep's sub-batch split)
-template <int BM, int NT, bool LK = false, bool SUBW = false, int ROLE = 0, bool WRES = false>
+// POOLG: the input x1 is the max-pool adjoint of a pooled gradient, taken through the codes (poolg_write; ConvArgs::x1_pool_arg)
+template <int BM, int NT, bool LK = false, bool SUBW = false, int ROLE = 0, bool WRES = false, bool POOLG = false>
 __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvArgs a, int total_tiles, int tiles_per_xcd)
 {
     using C = DeepCfg<BM, NT>;
@@ -938,7 +1034,12 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
     if (tile >= t_end) return;
 
     constexpr int RWL = WRES ? 0 : RW;          // weight granules a thread prefetches per stage
-    u32x4 rin[RIN], rw[RW];
+    // POOLG: the thread's input granules are pooled ones (poolg_write: the windows that cover the halo tile), with their code words
+    constexpr int PHT = C::TH / 2 + 2, PWT = C::TWD / 2 + 2, NPIN = PHT * PWT * GPP;
+    constexpr int NRIN = POOLG ? (NPIN + DEEP_THREADS - 1) / DEEP_THREADS : RIN;
+    u32x4 rin[NRIN], rw[RW];
+    unsigned rcd[POOLG ? NRIN : 1];
+    const int Hp = a.H >> 1, Wp = a.W >> 1;
     // Per lane and granule, once: position inside the halo tile.  Inside the loop an address is "uniform halo origin of the
     // tile (scalar unit) + 32-bit lane offset": a multiply-add, two compares and a pointer select per 16-byte load instead of a
     // 64-bit index computation (6 quarter-rate multiplies among ~45 instructions per load).
@@ -952,11 +1053,21 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
         g_dx[i] = pix % WT - 1;
         g_c[i] = (g % GPP) * 8;
         g_pix[i] = (pix / WT) * a.W + pix % WT;       // pixel offset from the halo origin (row -1, column -1 of the tile)
+        if constexpr (POOLG) {      // (pooled row / column from the tile's first pooled pixel, -1 = the window on the halo edge)
+            int gp = tid + i * DEEP_THREADS;
+            gp = gp < NPIN ? gp : NPIN - 1;
+            const int pp = gp / GPP;
+            g_dy[i] = pp / PWT - 1;
+            g_dx[i] = pp % PWT - 1;
+            g_c[i] = (gp % GPP) * 8;
+            g_pix[i] = g_dy[i] * Wp + g_dx[i];
+        }
     }
     // the stage a prefetch is for: wave-uniform, set once per stage
     const bf16 *ld_base = nullptr;
     int ld_xc = 0, ld_ty0 = 0, ld_tx0 = 0;
     const u32x4 *ld_w = nullptr;
+    const unsigned *ld_code = nullptr;
     int ld_moff = 0;
     auto set_stage = [&](int t, int chunk) {
         const int b = t / tpi, tr = t - b * tpi;
@@ -969,8 +1080,10 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
         const bf16 *xb = in1 ? a.x1 : a.x2;
         ld_xc = in1 ? a.C1 : a.C2;
         const int cb = in1 ? c0 : c0 - a.C1;
-        const long org = ((long)b * a.H + ld_ty0 - 1) * a.W + ld_tx0 - 1;      // halo origin pixel (may lie outside the image)
+        const long org = POOLG ? ((long)b * Hp + (ld_ty0 >> 1)) * Wp + (ld_tx0 >> 1)      // first pooled pixel of the tile
+                               : ((long)b * a.H + ld_ty0 - 1) * a.W + ld_tx0 - 1;      // halo origin pixel (may lie outside the image)
         ld_base = xb + org * ld_xc + cb;
+        if constexpr (POOLG) ld_code = a.x1_pool_arg + ((org * ld_xc + cb) >> 3);
         if constexpr (SUBW) {
             const int pm = a.wpack_mtb, per = pm / MTB;           // tiles per packed group, kernel groups per packed group
             ld_w = reinterpret_cast<const u32x4 *>(a.wpack + ((size_t)((group / per) * nchunk + chunk)) * NS * pm * 512);
@@ -980,6 +1093,13 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
         }
     };
     auto issue_in = [&](int i) {               // (i: a compile-time constant at every call)
+        if constexpr (POOLG) {
+            const bool ok = (unsigned)((ld_ty0 >> 1) + g_dy[i]) < (unsigned)Hp && (unsigned)((ld_tx0 >> 1) + g_dx[i]) < (unsigned)Wp;
+            const int off = g_pix[i] * ld_xc + g_c[i];          // (negative in the halo above / left of the tile)
+            rin[i] = *(ok ? reinterpret_cast<const u32x4 *>(ld_base + off) : &g_zero16);
+            rcd[i] = *(ok ? ld_code + (off >> 3) : reinterpret_cast<const unsigned *>(&g_zero16));
+            return;
+        }
         const bool ok = (unsigned)(ld_ty0 + g_dy[i]) < (unsigned)a.H && (unsigned)(ld_tx0 + g_dx[i]) < (unsigned)a.W;
         const unsigned off = (unsigned)(g_pix[i] * ld_xc + g_c[i]);
         const u32x4 *sp = ok ? reinterpret_cast<const u32x4 *>(ld_base + off) : &g_zero16;
@@ -992,6 +1112,15 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
         else rw[i] = ld_w[g];
     };
     auto write_in = [&]() {
+        if constexpr (POOLG) {
+#pragma unroll
+            for (int i = 0; i < NRIN; ++i) {
+                const int g = tid + i * DEEP_THREADS;
+                const int r0 = 2 * g_dy[i] + 1, c0 = 2 * g_dx[i] + 1;
+                poolg_write(in_tile + (r0 * WT + c0) * PK + g_c[i], PK, WT * PK, r0, c0, HT, WT, g < NPIN, rin[i], rcd[i], a.x1_pool_scale);
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < RIN; ++i) {
             const int g = tid + i * DEEP_THREADS;
@@ -1055,7 +1184,7 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
     }
     set_stage(tile, 0);
 #pragma unroll
-    for (int i = 0; i < RIN; ++i) issue_in(i);
+    for (int i = 0; i < NRIN; ++i) issue_in(i);
     if constexpr (!WRES) {
 #pragma unroll
         for (int i = 0; i < RW; ++i) issue_w(i);
@@ -1095,9 +1224,9 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
             }
             // this tap's share of the next stage's prefetch: loads s and s + 9 of the thread's RIN + RWL
 #pragma unroll
-            for (int j = s; j < RIN + RWL; j += NS) {
-                if (j < RIN) issue_in(j);
-                else issue_w(j - RIN);
+            for (int j = s; j < NRIN + RWL; j += NS) {
+                if (j < NRIN) issue_in(j);
+                else issue_w(j - NRIN);
             }
             __builtin_amdgcn_sched_barrier(0x38F);       // everything but vector-memory instructions may be scheduled across
         }
@@ -1110,7 +1239,11 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
         // the store to complete).
         auto deliver_and_write = [&]() {
 #pragma unroll
-            for (int i = 0; i < RIN; ++i) asm volatile("" : "+v"(rin[i]));
+            for (int i = 0; i < NRIN; ++i) asm volatile("" : "+v"(rin[i]));
+            if constexpr (POOLG) {
+#pragma unroll
+                for (int i = 0; i < NRIN; ++i) asm volatile("" : "+v"(rcd[i]));
+            }
 #pragma unroll
             for (int i = 0; i < RWL; ++i) asm volatile("" : "+v"(rw[i]));
             MMK_STAMP(4);
@@ -1341,7 +1474,7 @@ __global__ __launch_bounds__(DEEP_THREADS) void conv3x3_deep_kernel(const ConvAr
 #endif
 }
 
-template <int BM, int NT, bool LK = false, bool SUBW = false, int ROLE = 0, bool WRES = false>
+template <int BM, int NT, bool LK = false, bool SUBW = false, int ROLE = 0, bool WRES = false, bool POOLG = false>
 int launch_conv_deep(const ConvArgs &a, hipStream_t st)
 {
     using C = DeepCfg<BM, NT>;
@@ -1349,7 +1482,7 @@ int launch_conv_deep(const ConvArgs &a, hipStream_t st)
     int dev = 0;
     MMK_CHECK_HIP(hipGetDevice(&dev));
     if (!attr_set[dev & 63]) {
-        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_deep_kernel<BM, NT, LK, SUBW, ROLE, WRES>,
+        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_deep_kernel<BM, NT, LK, SUBW, ROLE, WRES, POOLG>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[dev & 63] = true;
     }
@@ -1361,7 +1494,7 @@ int launch_conv_deep(const ConvArgs &a, hipStream_t st)
     const int per_xcd = (total + 7) / 8;
     int nb = 32 / groups;                                    // one 8-wave block per CU, 32 CUs per XCD
     nb = nb < 1 ? 1 : (nb > per_xcd ? per_xcd : nb);
-    hipLaunchKernelGGL((conv3x3_deep_kernel<BM, NT, LK, SUBW, ROLE, WRES>), dim3(8 * nb, groups), dim3(DEEP_THREADS), smem, st, a, total, per_xcd);
+    hipLaunchKernelGGL((conv3x3_deep_kernel<BM, NT, LK, SUBW, ROLE, WRES, POOLG>), dim3(8 * nb, groups), dim3(DEEP_THREADS), smem, st, a, total, per_xcd);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -1449,6 +1582,20 @@ int dispatch_conv_deep_plain(const ConvArgs &a, hipStream_t st)
     const bool both1 = a.o1.relu_src != nullptr && a.o1.accumulate != 0, both2 = a.o2.C > 0 && a.o2.relu_src != nullptr && a.o2.accumulate != 0;
     const int role = (a.relu != 0 && !any_src && !any_acc) ? 1
                    : ((a.relu == 0 && a.bias == nullptr && dropout_params(a.drop_p).thr == 0u && !both1 && !both2) ? 2 : 0);
+    if (a.x1_pool_arg != nullptr) {     // pooled gradient input: the data gradients of the encoder's >= 64-channel second convolutions
+#define MMK_DEEP_CASE(M)                                                                                                          \
+    if (BM == M && role == 2 && a.wpack_mtb == 0) {                                                                                \
+        if (M <= 64 && (narrow ? deep_weights_fit<M, 3>(a.CIN) : deep_weights_fit<M, 5>(a.CIN)))                                   \
+            return narrow ? launch_conv_deep<M, 3, false, false, 2, (M <= 64), true>(a, st)                                        \
+                          : launch_conv_deep<M, 5, false, false, 2, (M <= 64), true>(a, st);                                       \
+        if (M > 64)                                                                                                                \
+            return narrow ? launch_conv_deep<M, 3, false, false, 2, false, true>(a, st) : launch_conv_deep<M, 5, false, false, 2, false, true>(a, st); \
+    }
+        MMK_DEEP_CASE(64); MMK_DEEP_CASE(128);
+#undef MMK_DEEP_CASE
+        mmk::set_error("mmk_conv3x3: x1_pool_arg is not supported for this layer (CIN=%d COUT=%d)", a.CIN, a.COUT);
+        return MMK_ERR_ARG;
+    }
 #define MMK_DEEP_CASE(M, R)                                                                                                        \
     if (BM == M && role == R) {                                                                                                    \
         if (M <= 64 && a.wpack_mtb == 0 && (narrow ? deep_weights_fit<M, 3>(a.CIN) : deep_weights_fit<M, 5>(a.CIN)))               \
@@ -1478,8 +1625,16 @@ int dispatch_conv(const ConvArgs &a, hipStream_t st)
         mmk::set_error("mmk_conv3x3: pool_y is not supported for this layer (see mmk_conv3x3_pool_fusable)");
         return MMK_ERR_ARG;
     }
+    if (a.x1_pool_arg != nullptr && (a.slope > 0.f || a.C2 != 0 || a.H < 2 || a.W < 2)) {
+        mmk::set_error("mmk_conv3x3: x1_pool_arg needs the ReLU network, a single input and H, W >= 2");
+        return MMK_ERR_ARG;
+    }
     if (conv_is_deep(a.CIN, a.COUT)) return dispatch_conv_deep(a, st);
     const int CK = conv_ck(a.CIN), CM = conv_cm(a.CIN, a.COUT);
+    if (a.x1_pool_arg != nullptr && !(a.CIN == 32 && CM == 32 && (size_t)a.B * a.H * a.W * 32 < ((size_t)1 << 31))) {
+        mmk::set_error("mmk_conv3x3: x1_pool_arg is not supported for this layer (CIN=%d COUT=%d)", a.CIN, a.COUT);
+        return MMK_ERR_ARG;
+    }
     const bool fits32 = (size_t)a.B * a.H * a.W * (size_t)std::max(a.CIN, a.COUT) < ((size_t)1 << 31);
     // (the LeakyReLU variant of the network runs the thin layers on the plain pipelined kernel: the ring
     // kernel's straight-line epilogue is tuned for the reference's default configuration)
@@ -1552,9 +1707,12 @@ struct WgradArgs {
     int B, H, W, CIN, COUT;
     float *partials; // [gridDim.x][9 * COUT * CIN + COUT]: per-block partial sums (weights, then bias), plain stores
     int acc_partials;   // add to what `partials` holds (second application of shared weights)
+    const unsigned *g_arg = nullptr;   // POOLG: g is the POOLED gradient (B,H/2,W/2,COUT), routed by these codes, times g_scale
+    float g_scale = 1.f;
 };
 
-template <int CK, int CM, bool G8>
+// POOLG: the output gradient is the max-pool adjoint of a pooled gradient, taken through the codes (poolg_write)
+template <int CK, int CM, bool G8, bool POOLG = false>
 __global__ __launch_bounds__(CONV_THREADS) void conv3x3_wgrad_kernel(const WgradArgs a)
 {
     // G8: the gradient tensor has 8 channels (COUT = 8, CM = 16): its LDS pitch is 8 elements
@@ -1616,7 +1774,12 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_wgrad_kernel(const Wgrad
     constexpr int GPG = GCOLS / 8;
     constexpr int NG = TH * TW * GPG;
     constexpr int RG = (NG + CONV_THREADS - 1) / CONV_THREADS;
-    u32x4 rin[RIN], rg[RG];
+    // POOLG: the thread's granules of g are pooled ones (poolg_write), with their code words
+    constexpr int PWG = TW / 2, NPG = (TH / 2) * PWG * GPG;
+    constexpr int NRG = POOLG ? (NPG + CONV_THREADS - 1) / CONV_THREADS : RG;
+    u32x4 rin[RIN], rg[NRG];
+    unsigned rc[POOLG ? NRG : 1];
+    const int Hp = a.H >> 1, Wp = a.W >> 1;
     auto load_tile = [&](int b, int tyi, int txi) {
         int tv = tid;                       // opaque: per-granule offsets are recomputed, not kept live
         asm volatile("" : "+v"(tv));
@@ -1635,6 +1798,19 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_wgrad_kernel(const Wgrad
             const u32x4 *sp = ok ? reinterpret_cast<const u32x4 *>(src) : &g_zero16;
             rin[i] = *sp;
         }
+        if constexpr (POOLG) {
+#pragma unroll
+            for (int i = 0; i < NRG; ++i) {
+                int gi = tv + i * CONV_THREADS;
+                gi = gi < NPG ? gi : NPG - 1;
+                const int pp = gi / GPG, gc = gi % GPG;
+                const int py = (ty0 >> 1) + pp / PWG, px = (tx0 >> 1) + pp % PWG;
+                const bool ok = py < Hp && px < Wp;
+                const long e = (long)((b * Hp + py) * Wp + px) * (a.COUT >> 3) + ((group * CM) >> 3) + gc;
+                rg[i] = *(ok ? reinterpret_cast<const u32x4 *>(a.g + e * 8) : &g_zero16);
+                rc[i] = *(ok ? a.g_arg + e : reinterpret_cast<const unsigned *>(&g_zero16));
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < RG; ++i) {
             int gi = tv + i * CONV_THREADS;
@@ -1646,6 +1822,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_wgrad_kernel(const Wgrad
             const u32x4 *sp = ok ? reinterpret_cast<const u32x4 *>(a.g + ((long)p * a.COUT + group * CM + gc * 8)) : &g_zero16;
             rg[i] = *sp;
         }
+        }
     };
     auto store_tile = [&]() {
         int tv = tid;
@@ -1655,10 +1832,20 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_wgrad_kernel(const Wgrad
             const int gi = tv + i * CONV_THREADS;
             if (gi < NIN) *reinterpret_cast<u32x4 *>(x_tile + (size_t)(gi / GPP) * PK + (gi % GPP) * 8) = rin[i];
         }
+        if constexpr (POOLG) {
+#pragma unroll
+            for (int i = 0; i < NRG; ++i) {
+                const int gi = tv + i * CONV_THREADS;
+                const int pp = gi / GPG, gc = gi % GPG;
+                const int r0 = 2 * (pp / PWG), c0 = 2 * (pp % PWG);
+                poolg_write(g_tile + (r0 * TW + c0) * PG + gc * 8, PG, TW * PG, r0, c0, TH, TW, gi < NPG, rg[i], rc[i], a.g_scale);
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < RG; ++i) {
             const int gi = tv + i * CONV_THREADS;
             if (gi < NG) *reinterpret_cast<u32x4 *>(g_tile + (size_t)(gi / GPG) * PG + (gi % GPG) * 8) = rg[i];
+        }
         }
     };
 
@@ -1804,7 +1991,7 @@ int wgrad_spatial(int cout, int cin, int B, int H, int W)
     return spatial >= 8 ? (spatial & ~7) : spatial;      // multiple of 8: XCD-contiguous tile walk
 }
 
-template <int CK, int CM, bool G8>
+template <int CK, int CM, bool G8, bool POOLG = false>
 int launch_wgrad(const WgradArgs &a, hipStream_t st)
 {
     const size_t smem = ((size_t)(HT * WT + 8) * wg_pitch(CK) + (size_t)(TH * TW + 8) * wg_pitch(G8 ? 8 : CM)) * sizeof(bf16);
@@ -1814,7 +2001,16 @@ int launch_wgrad(const WgradArgs &a, hipStream_t st)
         return MMK_ERR_HIP;
     }
     const int chunks = a.CIN / CK, groups = (a.COUT + CM - 1) / CM;
-    hipLaunchKernelGGL((conv3x3_wgrad_kernel<CK, CM, G8>), dim3(spatial, chunks, groups), dim3(CONV_THREADS), smem, st, a);
+    if constexpr (POOLG) {      // (the attribute is per instantiation; wgrad_spatial set it for the plain one)
+        static bool attr_set[64] = {};
+        int dev = 0;
+        MMK_CHECK_HIP(hipGetDevice(&dev));
+        if (smem > 64 * 1024 && !attr_set[dev & 63]) {
+            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_wgrad_kernel<CK, CM, G8, POOLG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            attr_set[dev & 63] = true;
+        }
+    }
+    hipLaunchKernelGGL((conv3x3_wgrad_kernel<CK, CM, G8, POOLG>), dim3(spatial, chunks, groups), dim3(CONV_THREADS), smem, st, a);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -1848,9 +2044,12 @@ struct BwdFusedArgs {
     int B, H, W;
     float *partials;         // [gridDim.x][9*CG*CX + CG] partial sums of the weight / bias gradient
     int acc_partials;
+    const unsigned *g_arg = nullptr;   // POOLG: g is the POOLED gradient (B,H/2,W/2,CG), routed by these codes, times g_scale
+    float g_scale = 1.f;
 };
 
-template <int CX, int CG>
+// POOLG: the output gradient is the max-pool adjoint of a pooled gradient, taken through the codes (poolg_write)
+template <int CX, int CG, bool POOLG = false>
 __global__ __launch_bounds__(CONV_THREADS) void conv_bwd_fused_kernel(const BwdFusedArgs a)
 {
     static_assert((CX == 8 || CX == 16) && (CG == 8 || CG == 16), "thin layers");
@@ -1920,7 +2119,12 @@ __global__ __launch_bounds__(CONV_THREADS) void conv_bwd_fused_kernel(const BwdF
     // register prefetch of the next tile's operands while the current one is consumed; every load is unconditional
     constexpr int NX = HT * WT * GX, NG = HT * WT * GG;
     constexpr int RX = (NX + CONV_THREADS - 1) / CONV_THREADS, RG = (NG + CONV_THREADS - 1) / CONV_THREADS;
-    u32x4 rx[RX], rg[RG];
+    // POOLG: the thread's granules of g are pooled ones (poolg_write), with their code words
+    constexpr int PH = TH / 2 + 2, PW = TW / 2 + 2, NPG = PH * PW * GG;
+    constexpr int NRG = POOLG ? (NPG + CONV_THREADS - 1) / CONV_THREADS : RG;
+    u32x4 rx[RX], rg[NRG];
+    unsigned rc[POOLG ? NRG : 1];
+    const int Hp = a.H >> 1, Wp = a.W >> 1;
     auto load_tile = [&](int b, int tyi, int txi) {
         int tv = tid;
         asm volatile("" : "+v"(tv));
@@ -1937,14 +2141,28 @@ __global__ __launch_bounds__(CONV_THREADS) void conv_bwd_fused_kernel(const BwdF
             const bf16 *src = split ? (half ? a.x2 : a.x) + po * 8 : a.x + po * CX + half * 8;
             rx[i] = *(ok ? reinterpret_cast<const u32x4 *>(src) : &g_zero16);
         }
+        if constexpr (POOLG) {
 #pragma unroll
-        for (int i = 0; i < RG; ++i) {
-            int gi = tv + i * CONV_THREADS;
-            gi = gi < NG ? gi : NG - 1;
-            const int pix = gi / GG, gc = gi % GG;
-            const int dy = pix / WT - 1, dx = pix % WT - 1;
-            const bool ok = (unsigned)(ty0 + dy) < (unsigned)a.H && (unsigned)(tx0 + dx) < (unsigned)a.W;
-            rg[i] = *(ok ? reinterpret_cast<const u32x4 *>(a.g + (long)(pix0 + dy * a.W + dx) * CG + gc * 8) : &g_zero16);
+            for (int i = 0; i < NRG; ++i) {
+                int gi = tv + i * CONV_THREADS;
+                gi = gi < NPG ? gi : NPG - 1;
+                const int pp = gi / GG, gc = gi % GG;
+                const int py = (ty0 >> 1) + pp / PW - 1, px = (tx0 >> 1) + pp % PW - 1;
+                const bool ok = (unsigned)py < (unsigned)Hp && (unsigned)px < (unsigned)Wp;
+                const long e = (long)((b * Hp + py) * Wp + px) * GG + gc;
+                rg[i] = *(ok ? reinterpret_cast<const u32x4 *>(a.g + e * 8) : &g_zero16);
+                rc[i] = *(ok ? a.g_arg + e : reinterpret_cast<const unsigned *>(&g_zero16));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < RG; ++i) {
+                int gi = tv + i * CONV_THREADS;
+                gi = gi < NG ? gi : NG - 1;
+                const int pix = gi / GG, gc = gi % GG;
+                const int dy = pix / WT - 1, dx = pix % WT - 1;
+                const bool ok = (unsigned)(ty0 + dy) < (unsigned)a.H && (unsigned)(tx0 + dx) < (unsigned)a.W;
+                rg[i] = *(ok ? reinterpret_cast<const u32x4 *>(a.g + (long)(pix0 + dy * a.W + dx) * CG + gc * 8) : &g_zero16);
+            }
         }
     };
     auto store_tile = [&]() {          // (pitch = channel count: granule gi of a tile sits at element 8 gi)
@@ -1955,10 +2173,20 @@ __global__ __launch_bounds__(CONV_THREADS) void conv_bwd_fused_kernel(const BwdF
             const int gi = tv + i * CONV_THREADS;
             if (gi < NX) *reinterpret_cast<u32x4 *>(x_tile + (size_t)gi * 8) = rx[i];
         }
+        if constexpr (POOLG) {
 #pragma unroll
-        for (int i = 0; i < RG; ++i) {
-            const int gi = tv + i * CONV_THREADS;
-            if (gi < NG) *reinterpret_cast<u32x4 *>(g_tile + (size_t)gi * 8) = rg[i];
+            for (int i = 0; i < NRG; ++i) {
+                const int gi = tv + i * CONV_THREADS;
+                const int pp = gi / GG, gc = gi % GG;
+                const int r0 = 2 * (pp / PW) - 1, c0 = 2 * (pp % PW) - 1;
+                poolg_write(g_tile + (r0 * WT + c0) * CG + gc * 8, CG, WT * CG, r0, c0, HT, WT, gi < NPG, rg[i], rc[i], a.g_scale);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < RG; ++i) {
+                const int gi = tv + i * CONV_THREADS;
+                if (gi < NG) *reinterpret_cast<u32x4 *>(g_tile + (size_t)gi * 8) = rg[i];
+            }
         }
     };
 
@@ -2067,7 +2295,11 @@ __global__ __launch_bounds__(CONV_THREADS) void conv_bwd_fused_kernel(const BwdF
 #pragma unroll
         for (int i = 0; i < RX; ++i) asm volatile("" : "+v"(rx[i]));
 #pragma unroll
-        for (int i = 0; i < RG; ++i) asm volatile("" : "+v"(rg[i]));
+        for (int i = 0; i < NRG; ++i) asm volatile("" : "+v"(rg[i]));
+        if constexpr (POOLG) {
+#pragma unroll
+            for (int i = 0; i < NRG; ++i) asm volatile("" : "+v"(rc[i]));
+        }
         // (the additions of zero below are the ring kernel's bias and accumulate-target additions: they turn -0 into +0)
         if constexpr (CX == 8) {
             float v8[8];
@@ -2145,6 +2377,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv_bwd_fused_kernel(const BwdF
 // MFMAs).  Fragment reads of row rho+1 are in flight while row rho is on the matrix cores.
 constexpr int WGD_THREADS = 512;
 
+template <bool POOLG = false>
 __global__ __launch_bounds__(WGD_THREADS) void conv3x3_wgrad_deep_kernel(const WgradArgs a)
 {
     constexpr int CK = 64, CM = 64, PK = wg_pitch(64), PG = wg_pitch(64);
@@ -2185,7 +2418,12 @@ __global__ __launch_bounds__(WGD_THREADS) void conv3x3_wgrad_deep_kernel(const W
     constexpr int GPG = CM / 8;
     constexpr int NG = TH * TW * GPG;
     constexpr int RG = (NG + WGD_THREADS - 1) / WGD_THREADS;
-    u32x4 rin[RIN], rg[RG];
+    // POOLG: the thread's granules of g are pooled ones (poolg_write), with their code words
+    constexpr int PWG = TW / 2, NPG = (TH / 2) * PWG * GPG;
+    constexpr int NRG = POOLG ? (NPG + WGD_THREADS - 1) / WGD_THREADS : RG;
+    u32x4 rin[RIN], rg[NRG];
+    unsigned rc[POOLG ? NRG : 1];
+    const int Hp = a.H >> 1, Wp = a.W >> 1;
     // `tv` is the thread index behind an opaque asm: everything derived from it is recomputed per tile
     // (a few VALU instructions) instead of being hoisted out of the tile loop into ~50 live registers
     auto load_tile = [&](int b, int tyi, int txi) {
@@ -2207,6 +2445,19 @@ __global__ __launch_bounds__(WGD_THREADS) void conv3x3_wgrad_deep_kernel(const W
             const u32x4 *sp = ok ? reinterpret_cast<const u32x4 *>(xb + p * xc + cb + gc * 8) : &g_zero16;
             rin[i] = *sp;
         }
+        if constexpr (POOLG) {
+#pragma unroll
+            for (int i = 0; i < NRG; ++i) {
+                int gi = tv + i * WGD_THREADS;
+                gi = gi < NPG ? gi : NPG - 1;
+                const int pp = gi / GPG, gc = gi % GPG;
+                const int py = (ty0 >> 1) + pp / PWG, px = (tx0 >> 1) + pp % PWG;
+                const bool ok = py < Hp && px < Wp;
+                const size_t e = (((size_t)b * Hp + py) * Wp + px) * (a.COUT >> 3) + ((group * CM) >> 3) + gc;
+                rg[i] = *(ok ? reinterpret_cast<const u32x4 *>(a.g + e * 8) : &g_zero16);
+                rc[i] = *(ok ? a.g_arg + e : reinterpret_cast<const unsigned *>(&g_zero16));
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < RG; ++i) {
             int gi = tv + i * WGD_THREADS;
@@ -2218,6 +2469,7 @@ __global__ __launch_bounds__(WGD_THREADS) void conv3x3_wgrad_deep_kernel(const W
             const u32x4 *sp = ok ? reinterpret_cast<const u32x4 *>(a.g + p * a.COUT + group * CM + gc * 8) : &g_zero16;
             rg[i] = *sp;
         }
+        }
     };
     auto store_tile = [&]() {
         int tv = tid;
@@ -2227,10 +2479,20 @@ __global__ __launch_bounds__(WGD_THREADS) void conv3x3_wgrad_deep_kernel(const W
             const int gi = tv + i * WGD_THREADS;
             if (gi < NIN) *reinterpret_cast<u32x4 *>(x_tile + (size_t)(gi / GPP) * PK + (gi % GPP) * 8) = rin[i];
         }
+        if constexpr (POOLG) {
+#pragma unroll
+            for (int i = 0; i < NRG; ++i) {
+                const int gi = tv + i * WGD_THREADS;
+                const int pp = gi / GPG, gc = gi % GPG;
+                const int r0 = 2 * (pp / PWG), c0 = 2 * (pp % PWG);
+                poolg_write(g_tile + (r0 * TW + c0) * PG + gc * 8, PG, TW * PG, r0, c0, TH, TW, gi < NPG, rg[i], rc[i], a.g_scale);
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < RG; ++i) {
             const int gi = tv + i * WGD_THREADS;
             if (gi < NG) *reinterpret_cast<u32x4 *>(g_tile + (size_t)(gi / GPG) * PG + (gi % GPG) * 8) = rg[i];
+        }
         }
     };
 
@@ -2355,6 +2617,7 @@ int wgrad_deep_slices(int cout, int cin, int B, int H, int W)
 
 bool wgrad_is_deep(int cout, int cin, int c1) { return cin % 64 == 0 && cout % 64 == 0 && c1 % 64 == 0; }
 
+template <bool POOLG = false>
 int launch_wgrad_deep(const WgradArgs &a, hipStream_t st)
 {
     const size_t smem = ((size_t)(HT * WT + 8) * wg_pitch(64) + (size_t)(TH * TW + 8) * wg_pitch(64)) * sizeof(bf16);
@@ -2362,18 +2625,24 @@ int launch_wgrad_deep(const WgradArgs &a, hipStream_t st)
     int dev = 0;
     MMK_CHECK_HIP(hipGetDevice(&dev));
     if (!attr_set[dev & 63]) {
-        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_wgrad_deep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_wgrad_deep_kernel<POOLG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         attr_set[dev & 63] = true;
     }
     const int spatial = wgrad_deep_slices(a.COUT, a.CIN, a.B, a.H, a.W);
     const int chunks = a.CIN / 64, groups = a.COUT / 64;
-    hipLaunchKernelGGL(conv3x3_wgrad_deep_kernel, dim3(spatial, chunks, groups), dim3(WGD_THREADS), smem, st, a);
+    hipLaunchKernelGGL(conv3x3_wgrad_deep_kernel<POOLG>, dim3(spatial, chunks, groups), dim3(WGD_THREADS), smem, st, a);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
 
 int dispatch_wgrad(const WgradArgs &a, hipStream_t st)
 {
+    if (a.g_arg != nullptr) {       // pooled gradient: the second convolutions of the encoder blocks with >= 32 channels
+        if (wgrad_is_deep(a.COUT, a.CIN, a.C1)) return launch_wgrad_deep<true>(a, st);
+        if (a.CIN == 32 && a.COUT == 32) return launch_wgrad<32, 32, false, true>(a, st);
+        mmk::set_error("mmk_conv3x3_wgrad_partial_pooled: unsupported channel counts CIN=%d COUT=%d", a.CIN, a.COUT);
+        return MMK_ERR_ARG;
+    }
     if (wgrad_is_deep(a.COUT, a.CIN, a.C1)) return launch_wgrad_deep(a, st);
     const int CK = cin_chunk(a.CIN), CM = cout_group(a.COUT);
 #define MMK_WG_CASE(K, M) if (CK == K && CM == M) return (M == 16 && a.COUT == 8) ? launch_wgrad<K, M, (M == 16)>(a, st) : launch_wgrad<K, M, false>(a, st)
@@ -4009,8 +4278,12 @@ extern "C" int mmk_conv3x3(const mmk_conv_desc *d, void *stream)
     a.relu = d->relu; a.slope = d->leaky_slope; a.drop_p = d->drop_p; a.seed = d->seed;
     a.pool_y = (bf16 *)d->pool_y;
     a.pool_arg = (unsigned char *)d->pool_arg;
+    a.x1_pool_arg = (const unsigned *)d->x1_pool_arg;
+    a.x1_pool_scale = d->x1_pool_scale;
     return dispatch_conv(a, (hipStream_t)stream);
 }
+
+extern "C" size_t mmk_conv_desc_bytes(void) { return sizeof(mmk_conv_desc); }
 
 extern "C" int32_t mmk_conv3x3_pool_fusable(int32_t cin, int32_t cout, int32_t B, int32_t H, int32_t W)
 {
@@ -4042,7 +4315,7 @@ extern "C" int mmk_conv3x3_wgrad_unpack_batch(int32_t n, const float *const *src
     return MMK_OK;
 }
 
-template <int CX, int CG>
+template <int CX, int CG, bool POOLG = false>
 int launch_bwd_fused(const BwdFusedArgs &a, int c1, hipStream_t st)
 {
     const int spatial = wgrad_slices(CG, CX, c1, a.B, a.H, a.W);     // the partial slices of the two-kernel path: same layout, same sums
@@ -4050,7 +4323,7 @@ int launch_bwd_fused(const BwdFusedArgs &a, int c1, hipStream_t st)
         mmk::set_error("fused backward: occupancy query failed");
         return MMK_ERR_HIP;
     }
-    hipLaunchKernelGGL((conv_bwd_fused_kernel<CX, CG>), dim3(spatial), dim3(CONV_THREADS), 0, st, a);
+    hipLaunchKernelGGL((conv_bwd_fused_kernel<CX, CG, POOLG>), dim3(spatial), dim3(CONV_THREADS), 0, st, a);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -4065,6 +4338,20 @@ extern "C" int mmk_conv_bwd_fused(const void *x, const void *g, const void *wpac
     a.x = (const bf16 *)x; a.g = (const bf16 *)g; a.wpack_t = (const bf16 *)wpack_t; a.dx = (bf16 *)dx; a.scale = scale; a.masked = 1;
     a.B = B; a.H = H; a.W = W; a.partials = partials; a.acc_partials = accumulate;
     return C == 8 ? launch_bwd_fused<8, 8>(a, 8, (hipStream_t)stream) : launch_bwd_fused<16, 16>(a, 16, (hipStream_t)stream);
+}
+
+extern "C" int mmk_conv_bwd_fused_pooled(const void *x, const void *gy, const void *arg, float pool_scale, const void *wpack_t, float scale,
+                                         int32_t B, int32_t H, int32_t W, int32_t C, void *dx, float *partials, int32_t accumulate,
+                                         void *stream)
+{
+    MMK_REQUIRE(x && gy && arg && wpack_t && dx && partials, "mmk_conv_bwd_fused_pooled: NULL pointer");
+    MMK_REQUIRE(B >= 1 && H >= 2 && W >= 2 && C == 16, "mmk_conv_bwd_fused_pooled: bad shape (16 channels)");
+    MMK_REQUIRE((size_t)B * H * W * C < ((size_t)1 << 31), "mmk_conv_bwd_fused_pooled: tensor too large for 32-bit offsets");
+    BwdFusedArgs a = {};
+    a.x = (const bf16 *)x; a.g = (const bf16 *)gy; a.wpack_t = (const bf16 *)wpack_t; a.dx = (bf16 *)dx; a.scale = scale; a.masked = 1;
+    a.B = B; a.H = H; a.W = W; a.partials = partials; a.acc_partials = accumulate;
+    a.g_arg = (const unsigned *)arg; a.g_scale = pool_scale;
+    return launch_bwd_fused<16, 16, true>(a, 16, (hipStream_t)stream);
 }
 
 extern "C" int mmk_conv8x16_bwd_fused(const void *x, const void *g, const void *wpack_t, float scale, int32_t B, int32_t H, int32_t W,
@@ -4113,6 +4400,23 @@ extern "C" int mmk_conv3x3_wgrad_partial(const void *x1, const void *x2, int32_t
     a.x1 = (const bf16 *)x1; a.x2 = (const bf16 *)x2; a.C1 = C1; a.C2 = C2; a.g = (const bf16 *)g;
     a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
     a.partials = partials; a.acc_partials = accumulate;
+    return dispatch_wgrad(a, (hipStream_t)stream);
+}
+
+extern "C" int mmk_conv3x3_wgrad_partial_pooled(const void *x1, const void *x2, int32_t C1, int32_t C2, const void *gy, const void *arg,
+                                                float pool_scale, int32_t cout, int32_t B, int32_t H, int32_t W, float *partials,
+                                                int32_t accumulate, void *stream)
+{
+    MMK_REQUIRE(x1 && gy && arg && partials, "mmk_conv3x3_wgrad_partial_pooled: NULL pointer");
+    MMK_REQUIRE(B >= 1 && H >= 2 && W >= 2, "mmk_conv3x3_wgrad_partial_pooled: bad shape");
+    const int cin = C1 + C2;
+    MMK_REQUIRE(C1 % 8 == 0 && C2 % 8 == 0 && (C2 == 0 || x2), "mmk_conv3x3_wgrad_partial_pooled: bad input split %d+%d", C1, C2);
+    MMK_REQUIRE(chan_ok(cin) && chan_ok(cout), "mmk_conv3x3_wgrad_partial_pooled: unsupported channel counts %d -> %d", cin, cout);
+    WgradArgs a;
+    a.x1 = (const bf16 *)x1; a.x2 = (const bf16 *)x2; a.C1 = C1; a.C2 = C2; a.g = (const bf16 *)gy;
+    a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
+    a.partials = partials; a.acc_partials = accumulate;
+    a.g_arg = (const unsigned *)arg; a.g_scale = pool_scale;
     return dispatch_wgrad(a, (hipStream_t)stream);
 }
 

@@ -125,7 +125,14 @@ bool make_plan(Plan &p, int B, int H, int W, int cin, bool with_scratch)
         p.gz_up[j] = s.tens(B, p.rh[5 - j], p.rw[5 - j], 2 * cs);     // up-sampling adjoint: the lower level's size
     }
     for (int i = 1; i < 6; ++i) {
-        p.gz_d[i] = s.tens(B, p.rh[i - 1], p.rw[i - 1], ENC_CH[i]);
+        // gz_d[i], the full-resolution adjoint of the pooling: the ReLU network does not materialise it (the consumers route
+        // the pooled gradient by the codes themselves); the paths that do (LeakyReLU network, MMK_UNET_POOL_ADJOINT=0) write
+        // it where decoder block 5 - i kept g_u, a tensor of the same shape that its up-sampling adjoint was the last to read
+        // (same stream, earlier in the pass).  813 MB of scratch less at B = 32, 640 x 640.
+        // The alias holds only while g_u's last reader (mmk_upsample_bwd, caller's stream) precedes the encoder loop on that
+        // stream and nothing on the weight-gradient stream reads g_u: a new reader of g_u needs a buffer of its own here.
+        p.gz_d[i] = p.g_u[5 - i];
+        if (p.gz_d[i].h != p.rh[i - 1] || p.gz_d[i].w != p.rw[i - 1] || p.gz_d[i].c != ENC_CH[i]) return false;   // (same shape, or no alias)
         p.gz_a[i] = s.tens(B, p.rh[i - 1], p.rw[i - 1], ENC_CH[i]);
     }
     p.gz_a[0] = s.tens(B, H, W, 8);
@@ -178,6 +185,8 @@ struct ConvCall {
     float drop_p = 0.f;
     unsigned seed = 0;
     void *pool_y = nullptr, *pool_arg = nullptr;
+    const void *x1_arg = nullptr;           // x1 is a pooled gradient, routed by these codes times x1_scale (mmk_conv_desc.x1_pool_arg)
+    float x1_scale = 1.f;
 };
 
 int conv(const Plan &p, int h, int w, float slope, const ConvCall &c, void *stream)
@@ -189,6 +198,7 @@ int conv(const Plan &p, int h, int w, float slope, const ConvCall &c, void *stre
     d.y2 = c.y2; d.relu_src2 = c.src2; d.O2 = c.O2; d.accumulate2 = c.acc2; d.scale2 = c.scale2;
     d.B = p.B; d.H = h; d.W = w; d.relu = c.relu; d.leaky_slope = slope; d.drop_p = c.drop_p; d.seed = c.seed;
     d.pool_y = c.pool_y; d.pool_arg = c.pool_arg;
+    d.x1_pool_arg = c.x1_arg; d.x1_pool_scale = c.x1_scale;
     return mmk_conv3x3(&d, stream);
 }
 
@@ -213,6 +223,25 @@ bool use_side_stream()
         v = (e && e[0] == '0') ? 0 : 1;
     }
     return v == 1;
+}
+
+// The max-pool adjoint of the ReLU network's encoder runs inside the kernels that consume it (the block's second convolution
+// backward: mmk_conv_bwd_fused_pooled / mmk_conv3x3_wgrad_partial_pooled / mmk_conv_desc.x1_pool_arg), which read the pooled
+// gradient and the arg-max codes instead of a full-resolution tensor that is three quarters zeros.  MMK_UNET_POOL_ADJOINT=0
+// keeps the standalone mmk_maxpool2_bwd_arg launch on every level (bit-identical gradients either way).  Read once per
+// backward pass, like MMK_CONV_SPLIT per call: the bit-identity test and an A/B run compare both paths in one process.
+// A string of level digits ("123") pools exactly those levels: how the per-level choice is measured in one build.
+// Default: the levels whose pooled form measured faster beyond the scatter (profiles/r06_pool_adjoint_levels.txt).
+constexpr unsigned POOL_ADJOINT_LEVELS = (1u << 1) | (1u << 2) | (1u << 3) | (1u << 4);
+unsigned pool_adjoint_levels()        // bit i: level i takes the pooled form
+{
+    const unsigned dflt = POOL_ADJOINT_LEVELS;
+    const char *e = getenv("MMK_UNET_POOL_ADJOINT");
+    if (e == nullptr || e[0] == '\0') return dflt;
+    unsigned m = 0;
+    for (; *e; ++e)
+        if (*e >= '1' && *e <= '5') m |= 1u << (*e - '0');
+    return m;
 }
 
 int side_stream(SideStream **out)
@@ -512,10 +541,11 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
     auto can_fuse = [&](int k, int ch, int h, int w) {
         return (ch == 8 || ch == 16) && sl == 0.f && p.slices[k] > 0 && mmk_conv3x3_wgrad_slices(ch, ch, ch, B, h, w) == p.slices[k];
     };
-    auto bwd_fused = [&](int k, int ch, const void *x, const void *g, void *dx, int h, int w) -> int {
+    auto bwd_fused = [&](int k, int ch, const void *x, const void *g, void *dx, int h, int w, const void *g_arg = nullptr) -> int {
+        if (g_arg) return mmk_conv_bwd_fused_pooled(x, g, g_arg, s, at(sc, p.packs_t[k]), 1.f, B, h, w, ch, dx, part_ptr(k), 0, stream);
         return mmk_conv_bwd_fused(x, g, at(sc, p.packs_t[k]), 1.f, B, h, w, ch, dx, part_ptr(k), 0, stream);
     };
-    auto wgrad = [&](int k, const void *x1, int C1, const void *x2, int C2, const void *g, int h, int w) -> int {
+    auto wgrad = [&](int k, const void *x1, int C1, const void *x2, int C2, const void *g, int h, int w, const void *g_arg = nullptr) -> int {
         if (ss) {   // g was produced by the launch just enqueued on the caller's stream
             MMK_CHECK_HIP(hipEventRecord(ss->fork, st));
             MMK_CHECK_HIP(hipStreamWaitEvent(ss->st, ss->fork, 0));
@@ -525,6 +555,7 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
             mmk::set_error("mmk_unet_backward: partial-slice count of layer %d depends on the input split", k);
             return MMK_ERR_ARG;
         }
+        if (g_arg) return mmk_conv3x3_wgrad_partial_pooled(x1, x2, C1, C2, g, g_arg, s, p.cout[k], B, h, w, part_ptr(k), 0, wstream);
         return mmk_conv3x3_wgrad_partial(x1, x2, C1, C2, g, p.cout[k], B, h, w, part_ptr(k), 0, wstream);
     };
 
@@ -604,20 +635,37 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
     // (the final layer's gradients were written on the caller's stream before the fork the reduction waited for)
     if (bucket_events) MMK_CHECK_HIP(hipEventRecord((hipEvent_t)bucket_events[0], (hipStream_t)wstream));
     // ---- encoder, i = 5..1 (g_t = gradient w.r.t. t[i])
+    // levels whose pooling adjoint runs inside its consumers (pool_adjoint_levels).  Per-level choice by measurement (DESIGN.md
+    // 5.3, profiles/r06_pool_adjoint_levels.txt): levels 1-3 win 32-85 us each, level 4 about 4 us; the 256-channel level's 5 us
+    // are inside its run-to-run scatter (it lost by as much in a per-launch table) and it keeps the standalone kernel.  The
+    // 16-channel level needs the one-launch backward of its second convolution, the only thin kernel with pooled staging.
+    const unsigned pool_levels = pool_adjoint_levels();
+    auto pool_adjoint_fused = [&](int i, int ch) {
+        if (!((pool_levels >> i) & 1u)) return false;
+        return ch >= 32 || (ch == 16 && can_fuse(2 * i + 1, ch, p.rh[i - 1], p.rw[i - 1]));
+    };
     const void *g_t = gz;
     for (int i = 5; i >= 1; --i) {
         const int ch = ENC_CH[i], h = p.rh[i - 1], w = p.rw[i - 1];
-        if (sl == 0.f)
-            MMK_TRY(mmk_maxpool2_bwd_arg(at(ws, p.t_arg[i]), g_t, B, h, w, ch, s, at(sc, p.gz_d[i].off), stream));
-        else
-            MMK_TRY(mmk_maxpool2_bwd(at(ws, p.d_enc[i].off), g_t, B, h, w, ch, s, sl, at(sc, p.gz_d[i].off), stream));
+        // ReLU network: the consumers of the pooling's adjoint take it from the pooled gradient and the codes themselves
+        // (gz_d[i] is not written); the weight gradient's fork then waits for the producer of g_t
+        const bool pooled = sl == 0.f && pool_adjoint_fused(i, ch);
+        const void *g_d = pooled ? g_t : at(sc, p.gz_d[i].off);
+        const void *g_arg = pooled ? at(ws, p.t_arg[i]) : nullptr;
+        if (!pooled) {
+            if (sl == 0.f)
+                MMK_TRY(mmk_maxpool2_bwd_arg(at(ws, p.t_arg[i]), g_t, B, h, w, ch, s, at(sc, p.gz_d[i].off), stream));
+            else
+                MMK_TRY(mmk_maxpool2_bwd(at(ws, p.d_enc[i].off), g_t, B, h, w, ch, s, sl, at(sc, p.gz_d[i].off), stream));
+        }
         if (can_fuse(2 * i + 1, ch, h, w)) {
-            MMK_TRY(bwd_fused(2 * i + 1, ch, at(ws, p.a_enc[i].off), at(sc, p.gz_d[i].off), at(sc, p.gz_a[i].off), h, w));
+            MMK_TRY(bwd_fused(2 * i + 1, ch, at(ws, p.a_enc[i].off), g_d, at(sc, p.gz_a[i].off), h, w, g_arg));
         } else {
-            MMK_TRY(wgrad(2 * i + 1, at(ws, p.a_enc[i].off), ch, nullptr, 0, at(sc, p.gz_d[i].off), h, w));
+            MMK_TRY(wgrad(2 * i + 1, at(ws, p.a_enc[i].off), ch, nullptr, 0, g_d, h, w, g_arg));
             ConvCall c;
-            c.x1 = at(sc, p.gz_d[i].off); c.C1 = ch; c.wpack = at(sc, p.packs_t[2 * i + 1]); c.y1 = at(sc, p.gz_a[i].off); c.O1 = ch;
+            c.x1 = g_d; c.C1 = ch; c.wpack = at(sc, p.packs_t[2 * i + 1]); c.y1 = at(sc, p.gz_a[i].off); c.O1 = ch;
             c.src1 = at(ws, p.a_enc[i].off); c.scale1 = 1.f;
+            c.x1_arg = g_arg; c.x1_scale = s;
             MMK_TRY(conv(p, h, w, sl, c, stream));
         }
         // data gradient accumulates into the skip gradient the decoder wrote for t[i-1]

@@ -40,6 +40,10 @@ struct ConvArgs {
     // 16-channel tiles per group of the packing, 0 = the kernel's own width)
     unsigned hash_base = 0;
     int wpack_mtb = 0;
+    // x1 is a POOLED gradient (B,H/2,W/2,C1): the input of the convolution is its max-pool adjoint, routed by these arg-max
+    // codes (layout: pool_arg) and multiplied by x1_pool_scale -- what mmk_maxpool2_bwd_arg would have written (ReLU network)
+    const unsigned *x1_pool_arg = nullptr;
+    float x1_pool_scale = 1.f;
 };
 
 // Inverted-dropout scales (0 or 1/keep) of the 4 consecutive channels starting at element index e4 (a multiple of 4): four

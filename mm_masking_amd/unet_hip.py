@@ -57,14 +57,20 @@ def pack_weights_batch(ws, transposed=False):
 
 def conv3x3(x1, wpack, cout, bias=None, x2=None, relu=False, drop_p=0.0, seed=0, out=None, out2=None, split=None,
             relu_src=None, scale=1.0, relu_src2=None, scale2=1.0, accumulate=False, accumulate2=False, pool_out=None,
-            slope=0.0, pool_arg=None):
+            slope=0.0, pool_arg=None, x1_pool_arg=None, x1_pool_scale=1.0, hw=None):
     """3x3 / pad 1 convolution on NHWC bf16.  input = concat(x1, x2); output channels
     [0,split) -> out, [split,cout) -> out2 (split=None: single output).  ``pool_out`` (B,H//2,W//2,cout):
     the 2x2 max-pool of the output, written by the same pass (layers for which pool_fusable() holds).
     ``slope`` > 0: the LeakyReLU variant (forward activation and the relu_src factors, see include/mmk.h).
     ``pool_arg`` (B,H//2,W//2,cout//2) uint8, with ``pool_out``: the arg-max codes of the pooling windows; the
-    full-resolution output is then NOT written and None is returned (include/mmk.h: mmk_conv_desc.pool_arg)."""
+    full-resolution output is then NOT written and None is returned (include/mmk.h: mmk_conv_desc.pool_arg).
+    ``x1_pool_arg`` (with ``hw`` = (H, W) of the convolution): x1 is a pooled gradient (B,H//2,W//2,C1) and the input is its
+    max-pool adjoint maxpool2_bwd_arg(x1_pool_arg, x1, H, W, x1_pool_scale), taken through the codes inside the kernel
+    (include/mmk.h: mmk_conv_desc.x1_pool_arg)."""
     B, H, W, C1 = x1.shape
+    if x1_pool_arg is not None:
+        H, W = hw
+        assert x1.shape[1:3] == (H // 2, W // 2) and x1_pool_arg.shape == (B, H // 2, W // 2, C1 // 2)
     C2 = 0 if x2 is None else x2.shape[3]
     O1 = cout if split is None else split
     O2 = cout - O1
@@ -77,7 +83,8 @@ def conv3x3(x1, wpack, cout, bias=None, x2=None, relu=False, drop_p=0.0, seed=0,
                       y2=_p(out2), relu_src2=_p(relu_src2), O2=O2, accumulate2=1 if accumulate2 else 0,
                       scale2=float(scale2), B=B, H=H, W=W, relu=1 if relu else 0, leaky_slope=float(slope),
                       drop_p=float(drop_p),
-                      seed=int(seed) & 0xFFFFFFFF, pool_y=_p(pool_out), pool_arg=_p(pool_arg))
+                      seed=int(seed) & 0xFFFFFFFF, pool_y=_p(pool_out), pool_arg=_p(pool_arg), x1_pool_arg=_p(x1_pool_arg),
+                      x1_pool_scale=float(x1_pool_scale))
     _lib.check(_lib.lib().mmk_conv3x3(ctypes.byref(d), _lib.stream_ptr(x1.device)))
     if pool_arg is not None:
         return None
@@ -138,19 +145,35 @@ def partial_buffer(ns, cout, cin, device):
     return torch.empty(ns, 9 * cout * cin + cout, dtype=torch.float32, device=device)
 
 
-def conv3x3_wgrad_partial(x1, g, cout, partials, x2=None, accumulate=False):
-    """Weight + bias gradient as per-workgroup partial sums into `partials` (see partial_buffer)."""
+def conv3x3_wgrad_partial(x1, g, cout, partials, x2=None, accumulate=False, g_pool_arg=None, g_pool_scale=1.0):
+    """Weight + bias gradient as per-workgroup partial sums into `partials` (see partial_buffer).  ``g_pool_arg``: g is a
+    pooled gradient (B,H//2,W//2,cout), routed by these arg-max codes times g_pool_scale inside the kernel
+    (mmk_conv3x3_wgrad_partial_pooled)."""
     B, H, W, C1 = x1.shape
     C2 = 0 if x2 is None else x2.shape[3]
+    if g_pool_arg is not None:
+        assert g.shape == (B, H // 2, W // 2, cout) and g_pool_arg.shape == (B, H // 2, W // 2, cout // 2)
+        _lib.check(_lib.lib().mmk_conv3x3_wgrad_partial_pooled(_p(x1), _p(x2), C1, C2, _p(g), _p(g_pool_arg), float(g_pool_scale),
+                                                               cout, B, H, W, _p(partials), 1 if accumulate else 0,
+                                                               _lib.stream_ptr(x1.device)))
+        return partials
     _lib.check(_lib.lib().mmk_conv3x3_wgrad_partial(_p(x1), _p(x2), C1, C2, _p(g), cout, B, H, W, _p(partials),
                                                     1 if accumulate else 0, _lib.stream_ptr(x1.device)))
     return partials
 
 
-def conv_bwd_fused(x, g, wpack_t, scale, dx, partials, accumulate=False):
+def conv_bwd_fused(x, g, wpack_t, scale, dx, partials, accumulate=False, g_pool_arg=None, g_pool_scale=1.0):
     """Data gradient (ReLU source = x) and partial weight-gradient slices of a C -> C convolution (C = 8, 16) in one launch:
-    bit-identical to conv3x3(g, wpack_t, C, out=dx, relu_src=x, scale=scale) + conv3x3_wgrad_partial(x, g, C, partials)."""
+    bit-identical to conv3x3(g, wpack_t, C, out=dx, relu_src=x, scale=scale) + conv3x3_wgrad_partial(x, g, C, partials).
+    ``g_pool_arg`` (C = 16): g is a pooled gradient (B,H//2,W//2,C), routed by these arg-max codes times g_pool_scale inside
+    the kernel (mmk_conv_bwd_fused_pooled)."""
     B, H, W, C = x.shape
+    if g_pool_arg is not None:
+        assert C == 16 and g.shape == (B, H // 2, W // 2, C) and g_pool_arg.shape == (B, H // 2, W // 2, C // 2) and dx.shape == x.shape
+        _lib.check(_lib.lib().mmk_conv_bwd_fused_pooled(_p(x), _p(g), _p(g_pool_arg), float(g_pool_scale), _p(wpack_t), float(scale),
+                                                        B, H, W, C, _p(dx), _p(partials), 1 if accumulate else 0,
+                                                        _lib.stream_ptr(x.device)))
+        return dx, partials
     assert C in (8, 16) and g.shape == x.shape and dx.shape == x.shape
     _lib.check(_lib.lib().mmk_conv_bwd_fused(_p(x), _p(g), _p(wpack_t), float(scale), B, H, W, C, _p(dx), _p(partials),
                                              1 if accumulate else 0, _lib.stream_ptr(x.device)))

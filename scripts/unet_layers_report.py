@@ -34,7 +34,9 @@ def last_pass(rows, n):
 
 def main():
     prefix, trace = sys.argv[1], sys.argv[2]
-    sch, nf = unet_schedule.schedule()
+    # the trace's process and this one run under the same MMK_UNET_POOL_ADJOINT (scripts/pmc_unet.sh): the levels are recorded
+    levels = unet_schedule.pooled_levels_from(os.environ.get("MMK_UNET_POOL_ADJOINT"))
+    sch, nf = unet_schedule.schedule(pooled_levels=levels)
     db = sqlite3.connect(trace)
     rows = [(r[0], r[2] - r[1]) for r in db.execute("select name, start, end from kernels order by start").fetchall()]
     got = last_pass(rows, len(sch))
@@ -72,6 +74,7 @@ def main():
         if "SQ_VALU_MFMA_BUSY_CYCLES" in c and "GRBM_GUI_ACTIVE" in c and c["GRBM_GUI_ACTIVE"] > 0:
             e["mfma_busy_frac"] = c["SQ_VALU_MFMA_BUSY_CYCLES"] / (1024.0 * c["GRBM_GUI_ACTIVE"] / 8.0)
     json.dump({"shape": "B=32, 640x640, one forward + backward pass on one stream (scripts/prof_unet_pass.py)", "forward_launches": nf,
+               "pool_adjoint_levels_pooled": list(levels),
                "sum_us": {"forward": sum(e["us"] for e in sch[:nf]), "backward": sum(e["us"] for e in sch[nf:])},
                "launches": sch}, open(prefix + "_unet_layers.json", "w"), indent=1)
     # per kernel class

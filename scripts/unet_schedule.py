@@ -19,7 +19,18 @@ def wgrad_kernel(cin, cout, c1):
     return "conv3x3_wgrad_deep_kernel" if (cin % 64 == 0 and cout % 64 == 0 and c1 % 64 == 0) else "conv3x3_wgrad_kernel"
 
 
-def schedule(B=32, H=640, W=640, cin0=1):
+POOLED_LEVELS = (1, 2, 3, 4)      # mmk_unet_driver.hip: POOL_ADJOINT_LEVELS
+
+
+def pooled_levels_from(value):
+    """The levels a value of MMK_UNET_POOL_ADJOINT selects (None / "": the default; "0": none; "123": those), as the driver
+    reads it.  For callers that zip the schedule with a trace: pass what the traced process ran with."""
+    if not value:
+        return POOLED_LEVELS
+    return tuple(int(c) for c in value if c in "12345")
+
+
+def schedule(B=32, H=640, W=640, cin0=1, pooled_levels=POOLED_LEVELS):
     rh = [H >> i for i in range(6)]
     rw = [W >> i for i in range(6)]
     out = []
@@ -136,20 +147,25 @@ def schedule(B=32, H=640, W=640, cin0=1):
             dgrad("dec%d.0 (1st application)" % j, lvl, 2 * cs, cs, 0)
         add("upsample_bwd_kernel", "dec%d.up" % j, "bwd", px(lvl) * 2 * cs * 2 + (px(lvl + 1) * 2 * cs * 2 if j > 0 else 0), px(lvl + 1) * 2 * cs * 2)
     add("unpack_wgrad_batch_kernel", "dec", "reduce weight-gradient slices", 0, 0)
+    # the pooling adjoint runs inside its consumers on `pooled_levels` (mmk_unet_driver.hip: pool_adjoint_levels; the other
+    # levels launch the standalone mmk_maxpool2_bwd_arg): they read the pooled gradient + the codes instead of a
+    # full-resolution gradient.  (Round 4 tried a different form inside the fused launch -- re-deriving the routing from the
+    # block's output -- which was slower: scripts/experiments/r04_pool_fused_backward.patch.)
     for i in range(5, 0, -1):
         ch, lvl = ENC[i], i - 1
-        pool_fused = False      # (round 4 tried the pooling adjoint inside the fused launch: slower, scripts/experiments/r04_pool_fused_backward.patch)
-        if not pool_fused:
-            add("maxpool2_bwd_arg_kernel", "enc%d.pool" % i, "bwd (by the codes)", px(i) * ch // 2 + px(i) * ch * 2, px(lvl) * ch * 2)
-        if pool_fused:
-            # reads x, the block's output d (for the routing) and the pooled gradient; writes dx
-            add("conv_bwd_fused_kernel<16, 16, true>", "enc%d.pool + enc%d.2" % (i, i), "pool bwd + dgrad+wgrad",
-                px(lvl) * (ch + ch) * 2 + px(i) * ch * 2, px(lvl) * ch * 2, 2.0 * 2 * 9 * ch * ch * px(lvl))
-        elif ch in (8, 16):
-            fused("conv_bwd_fused_kernel<%d, %d," % (ch, ch), "enc%d.2" % i, lvl, ch, ch, ch)
+        pooled_g = px(i) * ch // 2 + px(i) * ch * 2          # codes + pooled gradient
+        full_g = px(lvl) * ch * 2
+        fused_here = i in pooled_levels
+        if not fused_here:
+            add("maxpool2_bwd_arg_kernel", "enc%d.pool" % i, "bwd (by the codes)", pooled_g, full_g)
+        g_rd = pooled_g - full_g if fused_here else 0       # what the consumers read instead of the full-resolution gradient
+        tag = " (pooled g)" if fused_here else ""
+        if ch in (8, 16):
+            fused("conv_bwd_fused_kernel<%d, %d," % (ch, ch), "enc%d.2" % i + tag, lvl, ch, ch, ch, extra_rd=g_rd)
         else:
-            wgrad("enc%d.2" % i, lvl, ch, ch, ch)
-            dgrad("enc%d.2" % i, lvl, ch, ch, ch)
+            n = px(lvl)
+            add(wgrad_kernel(ch, ch, ch), "enc%d.2" % i + tag, "wgrad", n * (ch + ch) * 2 + g_rd, 0, 2.0 * 9 * ch * ch * n)
+            add(conv_kernel(ch, ch), "enc%d.2" % i + tag, "dgrad", n * (ch + ch) * 2 + g_rd, n * ch * 2, 2.0 * 9 * ch * ch * n)
         if i == 1:
             fused("conv_bwd_fused_kernel<8, 16,", "enc1.0", lvl, 8, 16, 8, extra_rd=px(lvl) * 8 * 2)       # (+ the skip gradient it adds to)
         else:
