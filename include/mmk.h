@@ -215,6 +215,8 @@ int mmk_bce_fft_threshold_bwd(const float *x, const float *fft, int32_t B, int64
  * mmk_mask_polar_scan (+ _bwd) <- radar_cartesian_to_polar(mask.double(), ...).float() * fft_data, the masked scan of
  *                        icp_weight_policy.py:266, and what autograd does for it
  * mmk_sample_weights_* <- extract_weights (fwd + autograd bwd) radar_utils.py:108-128
+ * mmk_sample_weights_polar_* <- extract_weights for a POLAR mask (absent upstream: SURVEY 8f.3's "polar-aware
+ *                        extract_weights"), sampled with radar_polar_to_cartesian_diff's arithmetic   radar_utils.py:276-323
  * mmk_bev_raster       <- extract_bev_from_pts           radar_utils.py:142-165      */
 
 /* GO-CFAR on (B,A,R) polar power.  w2/guard/mincol/maxcol as derived at
@@ -380,6 +382,35 @@ int mmk_sample_weights_bwd(const float *grad_weights /*B,N*/, const float *pc, i
 int mmk_sample_weights_bwd_pc(const float *grad_weights /*B,N*/, const float *mask /*B,H,W*/, const float *pc,
                               int32_t B, int32_t N, int32_t pc_cols, int32_t H, int32_t W,
                               int32_t cart_pixel_width, float cart_resolution, float *grad_pc, void *stream);
+
+/* The polar-aware sampler (radar_utils.extract_weights_polar <- the extract_weights call of icp_weight_policy.py:205 when
+ * the mask is the polar network's (A,R) image; params["polar_sampling"]).  weights[b,n] = bilinear(mask[b], point n) at the
+ * point's own place in the polar image: rng = sqrt(y^2 + x^2), ang = atan2(y, x) brought into [0, 2 pi) -- the geometry of
+ * form_cart_range_angle_grid (radar_utils.py:230-256) -- then the sampling position of mmk_polar_to_cart
+ * (radar_utils.py:276-323: u = (rng - res / 2) / res clamped at 0, v from the azimuth table with the wobble fix or the
+ * uniform step, the crossover rows, grid_sample's align_corners=True round trip), so a point at the centre of a Cartesian
+ * pixel reads what mmk_polar_to_cart writes to that pixel.  Taps outside the (padded) image read 0; fake points
+ * (x==0 && y==0) get 0.  azimuths (B,A) ascending, A floats of LDS per block. */
+int mmk_sample_weights_polar_fwd(const float *mask /*B,A,R*/, const float *pc /*B,N,pc_cols*/, const float *azimuths /*B,A*/,
+                                 int32_t B, int32_t N, int32_t pc_cols, int32_t A, int32_t R, float radar_resolution,
+                                 int32_t interpolate_crossover, int32_t fix_wobble, float *weights /*B,N*/, void *stream);
+/* Its backward in the mask (_SampleWeightsPolar.backward <- autograd through that gather): grad_mask (B,A,R) is zero-filled
+ * here, then receives the scatter-add of grad_weights * tap weight with the crossover rows folded onto their data rows
+ * (padded row 0 -> row A-1, padded row A+1 -> row 0), by the ordered chain passes of mmk_sample_weights_bwd: ascending
+ * (point, tap) order, no float atomics, bit-reproducible; untouched cells are exactly +0.
+ * ws: mmk_sample_weights_polar_bwd_ws_bytes(B, N) bytes. */
+size_t mmk_sample_weights_polar_bwd_ws_bytes(int32_t B, int32_t N);
+int mmk_sample_weights_polar_bwd(const float *grad_weights /*B,N*/, const float *pc, const float *azimuths, int32_t B, int32_t N,
+                                 int32_t pc_cols, int32_t A, int32_t R, float radar_resolution, int32_t interpolate_crossover,
+                                 int32_t fix_wobble, float *grad_mask /*B,A,R*/, void *ws, size_t ws_bytes, void *stream);
+/* Its backward in the points (_SampleWeightsPolar.backward when scan_pc requires grad): grad_pc (B,N,pc_cols) = the bilinear
+ * slopes along u and v times du/drng (1 / res, 0 where u is clamped) and dv/dang (the table segment's slope where the wobble
+ * fix interpolates, else 0; 1 / step without it), chained through rng and ang.  Written whole: columns 0 and 1 carry it; the
+ * other columns and fake points get 0.  One thread per point, no scatter.  The azimuths get no gradient. */
+int mmk_sample_weights_polar_bwd_pc(const float *grad_weights /*B,N*/, const float *mask /*B,A,R*/, const float *pc,
+                                    const float *azimuths, int32_t B, int32_t N, int32_t pc_cols, int32_t A, int32_t R,
+                                    float radar_resolution, int32_t interpolate_crossover, int32_t fix_wobble,
+                                    float *grad_pc /*B,N,pc_cols*/, void *stream);
 
 /* ---- loader primitives (icp_weight_dataset.py:323-362: PNG rows -> load_radar -> augmentation roll -> polar -> Cartesian)
  * mmk_host_read_rows: HOST function, no GPU call, thread-safe: rows [0,rows) of a raw row-major byte file (header_bytes

@@ -234,6 +234,12 @@ def _declare(lib):
         "mmk_sample_weights_bwd_ws_bytes": (sz, [i32, i32]),
         "mmk_sample_weights_bwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, f32, c_vp, c_vp, sz, c_vp]),
         "mmk_sample_weights_bwd_pc": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, i32, f32, c_vp, c_vp]),
+        "mmk_sample_weights_polar_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, f32, i32, i32, c_vp, c_vp]),
+        "mmk_sample_weights_polar_bwd_ws_bytes": (sz, [i32, i32]),
+        "mmk_sample_weights_polar_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, f32, i32, i32, c_vp, c_vp, sz,
+                                                        c_vp]),
+        "mmk_sample_weights_polar_bwd_pc": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, f32, i32, i32, c_vp,
+                                                           c_vp]),
         "mmk_weight_stats": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, c_vp, c_vp, c_vp]),
         "mmk_bev_raster": (ctypes.c_int, [c_vp, i32, i32, i32, i32, f32, c_vp, c_vp]),
     }

@@ -435,11 +435,15 @@ struct PolarTaps {
     float wx, wy;        // ix - x0, iy - y0
 };
 
-__device__ __forceinline__ PolarTaps polar_taps(const float *laz, float rng, float ang, int A, int R, float res, float half_res,
-                                                int wrap, int fix_wobble)
+// (the form with the two slopes: du = du/drng -- 1 / res, 0 where u is clamped at 0 -- and dv = dv/dang -- with the wobble fix
+// the slope of the table's segment below c3, 0 where delta is gated off; without it 1 / step.  The normalise / denormalise
+// round trip has slope 1.  polar_taps() below discards them and compiles to what it was before they existed.)
+__device__ __forceinline__ PolarTaps polar_taps_slopes(const float *laz, float rng, float ang, int A, int R, float res, float half_res,
+                                                       int wrap, int fix_wobble, float &du, float &dv)
 {
     float u = (rng - half_res) / res;
     float v;
+    du = (u < 0.f) ? 0.f : 1.0f / res;
     if (fix_wobble) {
         // lower_bound: first i with laz[i] >= ang.  The table is ascending and nearly uniform (the wobble is a fraction of a
         // step), so the search starts from the uniform table's answer and walks: two or three dependent LDS reads instead
@@ -458,9 +462,11 @@ __device__ __forceinline__ PolarTaps polar_taps(const float *laz, float rng, flo
         const float df = ang - a3;
         const float delta = ((df * ((df < 0.f) ? 1.f : 0.f)) * ((c3 > 0) ? 1.f : 0.f)) / ((a3 - a2) + 1e-14f);
         v = (float)c3 + delta;
+        dv = (df < 0.f && c3 > 0) ? 1.0f / ((a3 - a2) + 1e-14f) : 0.f;
     } else {
         const float step = (laz[A - 1] - laz[0]) / (float)(A - 1);
         v = (ang - laz[0]) / step;
+        dv = 1.0f / step;
     }
     if (u < 0.f) u = 0.f;
     const int rows = wrap ? A + 2 : A;
@@ -477,6 +483,13 @@ __device__ __forceinline__ PolarTaps polar_taps(const float *laz, float rng, flo
     t.xi = (int)x0;
     t.yi = (int)y0;
     return t;
+}
+
+__device__ __forceinline__ PolarTaps polar_taps(const float *laz, float rng, float ang, int A, int R, float res, float half_res,
+                                                int wrap, int fix_wobble)
+{
+    float du, dv;
+    return polar_taps_slopes(laz, rng, ang, A, R, res, half_res, wrap, fix_wobble, du, dv);
 }
 
 // R5 radar_polar_to_cartesian_diff (radar_utils.py:258-336).  One thread per Cartesian
@@ -582,6 +595,82 @@ __device__ __forceinline__ Taps weight_taps(const float *__restrict__ p, int H, 
     return t;
 }
 
+// The polar counterpart (extract_weights_polar): where the point lies in a POLAR mask (A, R).  rng and ang are the point's
+// own (the geometry of form_cart_range_angle_grid: pixel (i, j) is the point x = -coords[i], y = coords[j], so that
+// ang = atan2(y, x) brought into [0, 2 pi)), the position in the image is polar_taps' -- the arithmetic of
+// radar_polar_to_cartesian_diff, so a point at a Cartesian pixel's centre reads what that pixel gets -- and the four weights
+// are formed as weight_taps forms them.  A fake point (0, 0) has no taps (`fake`; its Taps are not to be used).
+__device__ __forceinline__ Taps polar_weight_taps(const float *__restrict__ p, const float *laz, int A, int R, float res,
+                                                  float half_res, int wrap, int fix_wobble, bool &fake, float &rng, float &du,
+                                                  float &dv)
+{
+    const float x = p[0], y = p[1];
+    fake = (x == 0.0f) && (y == 0.0f);
+    rng = sqrtf(y * y + x * x);
+    float ang = atan2f(y, x);
+    if (ang < 0.0f) ang = ang + 6.2831855f;        // 2 pi in fp32
+    const PolarTaps pt = polar_taps_slopes(laz, rng, ang, A, R, res, half_res, wrap, fix_wobble, du, dv);
+    Taps t;
+    t.xi = pt.xi;
+    t.yi = pt.yi;
+    t.w00 = (1.0f - pt.wy) * (1.0f - pt.wx);
+    t.w01 = (1.0f - pt.wy) * pt.wx;
+    t.w10 = pt.wy * (1.0f - pt.wx);
+    t.w11 = pt.wy * pt.wx;
+    t.wx = pt.wx;
+    t.wy = pt.wy;
+    return t;
+}
+
+// Cell of the polar image behind tap (yk, xk) of the (wrap-padded) one, -1 outside it: with the crossover rows, padded row 0
+// is row A - 1 and padded row A + 1 is row 0 (the concatenation at radar_utils.py:318), every other row yk - 1.
+__device__ __forceinline__ int polar_cell(int yk, int xk, int A, int R, int wrap)
+{
+    const int rows = wrap ? A + 2 : A;
+    if (xk < 0 || xk >= R || yk < 0 || yk >= rows) return -1;
+    int r = yk;
+    if (wrap) r = (yk == 0) ? (A - 1) : ((yk == A + 1) ? 0 : yk - 1);
+    return r * R + xk;
+}
+
+// The two tap-to-cell mappings of the ordered scatter below: how a point becomes four taps (`taps`; `live` false: none) and
+// which cell of the gradient image a tap falls on (`cell`, -1: none).  `stage` brings what `taps` reads from LDS there
+// (every thread of the block calls it before any returns).
+struct CartWeightGeom {
+    int H, W, cw;
+    float cres;
+    __device__ __forceinline__ void stage(float *, int) const {}
+    __device__ __forceinline__ Taps taps(const float *__restrict__ p, const float *, bool &live) const
+    {
+        live = true;                               // a fake point's taps lie outside every image (weight_taps)
+        return weight_taps(p, H, W, cw, cres);
+    }
+    __device__ __forceinline__ int cell(int yy, int xx) const { return (xx >= 0 && xx < W && yy >= 0 && yy < H) ? yy * W + xx : -1; }
+    __host__ __device__ size_t cells() const { return (size_t)H * W; }
+};
+
+struct PolarWeightGeom {
+    const float *az;                               // (B, A)
+    int A, R;
+    float res, half_res;
+    int wrap, fix_wobble;
+    __device__ __forceinline__ void stage(float *laz, int b) const
+    {
+        for (int i = threadIdx.x; i < A; i += blockDim.x) laz[i] = az[(size_t)b * A + i];
+        __syncthreads();
+    }
+    __device__ __forceinline__ Taps taps(const float *__restrict__ p, const float *laz, bool &live) const
+    {
+        bool fake;
+        float rng, du, dv;
+        const Taps t = polar_weight_taps(p, laz, A, R, res, half_res, wrap, fix_wobble, fake, rng, du, dv);
+        live = !fake;
+        return t;
+    }
+    __device__ __forceinline__ int cell(int yk, int xk) const { return polar_cell(yk, xk, A, R, wrap); }
+    __host__ __device__ size_t cells() const { return (size_t)A * R; }
+};
+
 __global__ void sample_weights_fwd_kernel(const float *__restrict__ mask, const float *__restrict__ pc, int N,
                                           int cols, int H, int W, int cw, float cres, float *__restrict__ out)
 {
@@ -597,6 +686,28 @@ __global__ void sample_weights_fwd_kernel(const float *__restrict__ mask, const 
                              tap(t.yi + 1, t.xi + 1) * t.w11;
 }
 
+// extract_weights_polar: the same gather from a polar mask, the item's azimuth table in LDS.  The sum is formed in
+// sample_weights_fwd_kernel's order; taps outside the padded image read 0, a fake point gets 0.
+__global__ __launch_bounds__(256) void sample_weights_polar_fwd_kernel(const float *__restrict__ mask, const float *__restrict__ pc,
+                                                                       int N, int cols, PolarWeightGeom g, float *__restrict__ out)
+{
+    extern __shared__ float laz[];
+    const int b = blockIdx.y;
+    g.stage(laz, b);
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    bool live;
+    const Taps t = g.taps(pc + ((size_t)b * N + n) * cols, laz, live);
+    const float *m = mask + (size_t)b * g.cells();
+    auto tap = [&](int yy, int xx) -> float {
+        const int c = g.cell(yy, xx);
+        return c >= 0 ? m[c] : 0.0f;
+    };
+    out[(size_t)b * N + n] = live ? tap(t.yi, t.xi) * t.w00 + tap(t.yi, t.xi + 1) * t.w01 + tap(t.yi + 1, t.xi) * t.w10 +
+                                        tap(t.yi + 1, t.xi + 1) * t.w11
+                                  : 0.0f;
+}
+
 // Backward of the gather = scatter-add of g * w into the four taps of every point, WITHOUT float atomics (their order of
 // arrival would make the mask gradient differ from run to run where several taps fall on one pixel: neighbouring
 // azimuths near the sensor, neighbouring peaks of one azimuth).  Three passes over the 4 N entries e = 4 n + q of an image:
@@ -607,29 +718,36 @@ __global__ void sample_weights_fwd_kernel(const float *__restrict__ mask, const 
 //          values in ascending entry order (repeated selection of the next-larger index: chains are short) -- the order
 //          of a sequential loop over points and taps, as PyTorch's CPU grid_sample backward runs it.
 //   store  the owners write the sums over the chain heads.
-__device__ __forceinline__ int tap_pixel(const Taps &t, int q, int H, int W, float &w)
+// The passes are shared by the Cartesian and the polar sampler: only `link` knows the geometry (Geom: CartWeightGeom or
+// PolarWeightGeom above); `sum` and `store` see cells of an image of H * W words.  Two taps of one point may fall on the same
+// cell (a polar point between the last and the first azimuth, A = 2): they are two entries of that cell's chain.
+template <class Geom>
+__device__ __forceinline__ int tap_pixel(const Geom &g, const Taps &t, int q, float &w)
 {
-    const int yy = t.yi + (q >> 1), xx = t.xi + (q & 1);
     w = q == 0 ? t.w00 : (q == 1 ? t.w01 : (q == 2 ? t.w10 : t.w11));
-    return (xx >= 0 && xx < W && yy >= 0 && yy < H) ? yy * W + xx : -1;
+    return g.cell(t.yi + (q >> 1), t.xi + (q & 1));
 }
 
+template <class Geom>
 __global__ void sample_weights_bwd_link_kernel(const float *__restrict__ gw, const float *__restrict__ pc, int N, int cols,
-                                               int H, int W, int cw, float cres, float *__restrict__ gmask,
-                                               int *__restrict__ next, float *__restrict__ val, int *__restrict__ pix)
+                                               Geom g, float *__restrict__ gmask, int *__restrict__ next,
+                                               float *__restrict__ val, int *__restrict__ pix)
 {
+    extern __shared__ float lds[];
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
+    g.stage(lds, b);
     if (e >= 4 * N) return;
     const int n = e >> 2, q = e & 3;
-    const Taps t = weight_taps(pc + ((size_t)b * N + n) * cols, H, W, cw, cres);
+    bool live;
+    const Taps t = g.taps(pc + ((size_t)b * N + n) * cols, lds, live);
     float w;
-    const int p = tap_pixel(t, q, H, W, w);
+    const int p = live ? tap_pixel(g, t, q, w) : -1;
     const size_t o = (size_t)b * 4 * N + e;
     pix[o] = p;
     if (p < 0) return;
     val[o] = gw[(size_t)b * N + n] * w;
-    int *head = reinterpret_cast<int *>(gmask + (size_t)b * H * W + p);
+    int *head = reinterpret_cast<int *>(gmask + g.cells() * b + p);
     next[o] = atomicExch(head, e + 1) - 1;
 }
 
@@ -704,6 +822,45 @@ __global__ void sample_weights_bwd_pc_kernel(const float *__restrict__ gw, const
     // gx = ((y / cres) / (cw − 1)) · 2,  gy = ((−x / cres) / (cw − 1)) · 2
     g[0] = -(((ggy * 2.0f) / (float)(cw - 1)) / cres);
     g[1] = ((ggx * 2.0f) / (float)(cw - 1)) / cres;
+}
+
+// dL/dpc of the polar gather.  With (u, v) the position in the image, gu and gv are the bilinear slopes of
+// sample_weights_bwd_pc_kernel (times g); du/drng and dv/dang come from polar_taps_slopes, and rng = sqrt(x^2 + y^2),
+// ang = atan2(y, x) give drng/d(x, y) = (x, y) / rng, dang/d(x, y) = (-y, x) / rng^2.  One thread per point, no scatter; fake
+// rows and every column but x, y get 0.  (A real point whose squares underflow to rng = 0 has no direction: 0 as well.)
+__global__ __launch_bounds__(256) void sample_weights_polar_bwd_pc_kernel(const float *__restrict__ gw, const float *__restrict__ mask,
+                                                                          const float *__restrict__ pc, int N, int cols,
+                                                                          PolarWeightGeom g, float *__restrict__ gpc)
+{
+    extern __shared__ float laz[];
+    const int b = blockIdx.y;
+    g.stage(laz, b);
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const float *p = pc + ((size_t)b * N + n) * cols;
+    float *o = gpc + ((size_t)b * N + n) * cols;
+    for (int c = 2; c < cols; ++c) o[c] = 0.0f;
+    bool fake;
+    float rng, du, dv;
+    const Taps t = polar_weight_taps(p, laz, g.A, g.R, g.res, g.half_res, g.wrap, g.fix_wobble, fake, rng, du, dv);
+    if (fake || !(rng > 0.0f)) {
+        o[0] = 0.0f;
+        o[1] = 0.0f;
+        return;
+    }
+    const float *m = mask + (size_t)b * g.cells();
+    auto tap = [&](int yy, int xx) -> float {
+        const int c = g.cell(yy, xx);
+        return c >= 0 ? m[c] : 0.0f;
+    };
+    const float m00 = tap(t.yi, t.xi), m01 = tap(t.yi, t.xi + 1), m10 = tap(t.yi + 1, t.xi), m11 = tap(t.yi + 1, t.xi + 1);
+    const float go = gw[(size_t)b * N + n];
+    const float gu = ((m01 - m00) * (1.0f - t.wy) + (m11 - m10) * t.wy) * go;
+    const float gv = ((m10 - m00) * (1.0f - t.wx) + (m11 - m01) * t.wx) * go;
+    const float x = p[0], y = p[1];
+    const float gr = gu * du, ga = gv * dv, r2 = rng * rng;
+    o[0] = gr * (x / rng) - ga * (y / r2);
+    o[1] = gr * (y / rng) + ga * (x / r2);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1767,8 +1924,9 @@ extern "C" int mmk_sample_weights_bwd(const float *grad_weights, const float *pc
     float *res = reinterpret_cast<float *>(pix + ne);
     MMK_CHECK_HIP(hipMemsetAsync(grad_mask, 0, sizeof(float) * (size_t)B * H * W, st));
     const dim3 grid((4 * N + 255) / 256, B);
-    hipLaunchKernelGGL(sample_weights_bwd_link_kernel, grid, dim3(256), 0, st, grad_weights, pc, N, pc_cols, H, W, cart_pixel_width,
-                       cart_resolution, grad_mask, next, val, pix);
+    const CartWeightGeom geom{H, W, cart_pixel_width, cart_resolution};
+    hipLaunchKernelGGL(sample_weights_bwd_link_kernel<CartWeightGeom>, grid, dim3(256), 0, st, grad_weights, pc, N, pc_cols, geom,
+                       grad_mask, next, val, pix);
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(sample_weights_bwd_sum_kernel, grid, dim3(256), 0, st, N, H, W, grad_mask, next, val, pix, res);
     MMK_LAUNCH_CHECK();
@@ -1786,6 +1944,86 @@ extern "C" int mmk_sample_weights_bwd_pc(const float *grad_weights, const float 
                 "mmk_sample_weights_bwd_pc: bad shape");
     hipLaunchKernelGGL(sample_weights_bwd_pc_kernel, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, grad_weights, mask,
                        pc, N, pc_cols, H, W, cart_pixel_width, cart_resolution, grad_pc);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+// Argument checks shared by the three polar sampler entries; on success `g` holds the launch's geometry.
+static int polar_weight_geom(const char *who, const float *azimuths, int32_t B, int32_t N, int32_t pc_cols, int32_t A, int32_t R,
+                             float radar_resolution, int32_t interpolate_crossover, int32_t fix_wobble, PolarWeightGeom &g)
+{
+    MMK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && pc_cols >= 2 && A >= 2 && R >= 2, "%s: bad shape", who);
+    MMK_REQUIRE(radar_resolution > 0.0f, "%s: radar_resolution must be positive", who);
+    MMK_REQUIRE((size_t)A * 4 <= 64 * 1024, "%s: too many azimuths (%d)", who, A);
+    MMK_REQUIRE((size_t)(A + 2) * R < ((size_t)1 << 31), "%s: shape too large", who);
+    g = PolarWeightGeom{azimuths, A, R, radar_resolution, (float)((double)radar_resolution / 2.0), interpolate_crossover ? 1 : 0,
+                        fix_wobble ? 1 : 0};
+    return MMK_OK;
+}
+
+extern "C" int mmk_sample_weights_polar_fwd(const float *mask, const float *pc, const float *azimuths, int32_t B, int32_t N,
+                                            int32_t pc_cols, int32_t A, int32_t R, float radar_resolution,
+                                            int32_t interpolate_crossover, int32_t fix_wobble, float *weights, void *stream)
+{
+    MMK_REQUIRE(mask && pc && azimuths && weights, "mmk_sample_weights_polar_fwd: NULL pointer");
+    PolarWeightGeom g;
+    if (int rc = polar_weight_geom("mmk_sample_weights_polar_fwd", azimuths, B, N, pc_cols, A, R, radar_resolution,
+                                   interpolate_crossover, fix_wobble, g))
+        return rc;
+    hipLaunchKernelGGL(sample_weights_polar_fwd_kernel, dim3((N + 255) / 256, B), dim3(256), (size_t)A * 4, (hipStream_t)stream, mask,
+                       pc, N, pc_cols, g, weights);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" size_t mmk_sample_weights_polar_bwd_ws_bytes(int32_t B, int32_t N)
+{
+    return mmk_sample_weights_bwd_ws_bytes(B, N);       // the same chain words: one of each per (point, tap)
+}
+
+extern "C" int mmk_sample_weights_polar_bwd(const float *grad_weights, const float *pc, const float *azimuths, int32_t B, int32_t N,
+                                            int32_t pc_cols, int32_t A, int32_t R, float radar_resolution,
+                                            int32_t interpolate_crossover, int32_t fix_wobble, float *grad_mask, void *ws,
+                                            size_t ws_bytes, void *stream)
+{
+    MMK_REQUIRE(grad_weights && pc && azimuths && grad_mask && ws, "mmk_sample_weights_polar_bwd: NULL pointer");
+    PolarWeightGeom g;
+    if (int rc = polar_weight_geom("mmk_sample_weights_polar_bwd", azimuths, B, N, pc_cols, A, R, radar_resolution,
+                                   interpolate_crossover, fix_wobble, g))
+        return rc;
+    MMK_REQUIRE((size_t)N * 4 < ((size_t)1 << 30), "mmk_sample_weights_polar_bwd: shape too large");
+    MMK_REQUIRE(ws_bytes >= mmk_sample_weights_polar_bwd_ws_bytes(B, N),
+                "mmk_sample_weights_polar_bwd: workspace too small (%zu < %zu bytes)", ws_bytes,
+                mmk_sample_weights_polar_bwd_ws_bytes(B, N));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ne = (size_t)B * N * 4;
+    int *next = static_cast<int *>(ws);
+    float *val = reinterpret_cast<float *>(next + ne);
+    int *pix = reinterpret_cast<int *>(val + ne);
+    float *res = reinterpret_cast<float *>(pix + ne);
+    MMK_CHECK_HIP(hipMemsetAsync(grad_mask, 0, sizeof(float) * (size_t)B * A * R, st));
+    const dim3 grid((4 * N + 255) / 256, B);
+    hipLaunchKernelGGL(sample_weights_bwd_link_kernel<PolarWeightGeom>, grid, dim3(256), (size_t)A * 4, st, grad_weights, pc, N,
+                       pc_cols, g, grad_mask, next, val, pix);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sample_weights_bwd_sum_kernel, grid, dim3(256), 0, st, N, A, R, grad_mask, next, val, pix, res);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sample_weights_bwd_store_kernel, grid, dim3(256), 0, st, N, A, R, pix, res, grad_mask);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_sample_weights_polar_bwd_pc(const float *grad_weights, const float *mask, const float *pc, const float *azimuths,
+                                               int32_t B, int32_t N, int32_t pc_cols, int32_t A, int32_t R, float radar_resolution,
+                                               int32_t interpolate_crossover, int32_t fix_wobble, float *grad_pc, void *stream)
+{
+    MMK_REQUIRE(grad_weights && mask && pc && azimuths && grad_pc, "mmk_sample_weights_polar_bwd_pc: NULL pointer");
+    PolarWeightGeom g;
+    if (int rc = polar_weight_geom("mmk_sample_weights_polar_bwd_pc", azimuths, B, N, pc_cols, A, R, radar_resolution,
+                                   interpolate_crossover, fix_wobble, g))
+        return rc;
+    hipLaunchKernelGGL(sample_weights_polar_bwd_pc_kernel, dim3((N + 255) / 256, B), dim3(256), (size_t)A * 4, (hipStream_t)stream,
+                       grad_weights, mask, pc, N, pc_cols, g, grad_pc);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

@@ -504,7 +504,8 @@ def finish_batch(batch, device, network_input_type="cartesian", float_type=torch
     batched launch instead of one per item; ``aug_cs`` (native item path) is the augmentation's rotation of the clouds
     (icp_weight_dataset.py:435-443), applied here as [x y] @ [[c, -s], [s, c]].  ``keep_polar``: ``loc_data`` also carries
     ``fft_polar`` (the fp32 polar image formed here anyway) and ``azimuths`` (B,A), both on ``device`` -- what the policy's
-    ``mask_target="scan"`` mode reads; the default leaves the dictionary as it was."""
+    ``mask_target="scan"`` mode reads, and the azimuths what ``params["polar_sampling"]`` reads; the default leaves the
+    dictionary as it was."""
     from . import radar_utils as ru
     device = torch.device(device)
     loc = batch["loc_data"]
@@ -563,7 +564,7 @@ class DeviceLoader:
             raise ValueError("passes > 1 (several passes over the data in ONE iteration, the pipeline kept full across them) "
                              "is a feature of the thread mode")
         self.passes = int(passes)
-        self.keep_polar = bool(keep_polar)       # finish_batch(keep_polar=...): fft_polar and azimuths for mask_target="scan"
+        self.keep_polar = bool(keep_polar)       # finish_batch(keep_polar=...): fft_polar and azimuths for mask_target="scan" / polar_sampling
         self.dataset, self.device, self.mode = dataset, torch.device(device), mode
         self.batch_size, self.shuffle, self.drop_last, self.num_workers = int(batch_size), shuffle, drop_last, int(num_workers)
         self.loader = None

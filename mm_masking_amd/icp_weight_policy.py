@@ -24,7 +24,7 @@ import torch.nn as nn
 from torch.nn import ModuleList
 
 from .dICP.ICP import ICP
-from .radar_utils import (_extract_weights_stats, cfar_mask, extract_pc_padded, extract_weights, form_cart_range_angle_grid,
+from .radar_utils import (_extract_weights_polar_stats, _extract_weights_stats, cfar_mask, extract_pc_padded, extract_weights, form_cart_range_angle_grid,
                           form_polar_range_grid, mask_polar_scan)
 
 
@@ -104,6 +104,14 @@ class LearnICPWeightPolicy(nn.Module):
         self.mask_target = params.get("mask_target", "weights")
         if self.mask_target not in ("weights", "scan"):
             raise ValueError("mask_target must be 'weights' or 'scan' (got %r)" % (self.mask_target,))
+        # params["polar_sampling"] (absent upstream): a polar network's mask is sampled where the points lie in the polar image
+        # (radar_utils.extract_weights_polar) instead of with point_to_cart_idx's Cartesian normalisation, the reference's
+        # latent bug that the default keeps.  forward then reads batch_scan["azimuths"].
+        self.polar_sampling = bool(params.get("polar_sampling", False))
+        if self.polar_sampling and network_input_type != "polar":
+            raise ValueError("polar_sampling needs network_input_type='polar': a Cartesian mask is sampled on its own grid already")
+        if self.polar_sampling and self.mask_target != "weights":
+            raise ValueError("polar_sampling needs mask_target='weights': the scan mode does not weigh points with the mask")
         # data-parallel jobs: reduce the min-max normalisation's extrema over the ranks (one MAX all-reduce of 2C floats), so
         # that it stays global over the whole batch as in the single-process reference (icp_weight_policy.py:151-155).
         # Default: ON whenever the process is a rank of a multi-rank job, so that N ranks x B pairs normalise like one
@@ -237,6 +245,20 @@ class LearnICPWeightPolicy(nn.Module):
                 raise _lib.MmkError("mask_target='scan' runs the radar front end in HIP kernels with no CPU path: "
                                     "params['device'] must be a HIP device")
 
+        if self.polar_sampling and not mask_only:
+            from . import _lib
+            if "azimuths" not in batch_scan:
+                raise KeyError("polar_sampling needs batch_scan['azimuths'] (prepare_batch with params['polar_sampling'] = True, "
+                               "or finish_batch(keep_polar=True))")
+            if torch.device(self.device).type != "cuda":
+                raise _lib.MmkError("polar_sampling samples the mask in a HIP kernel with no CPU path: "
+                                    "params['device'] must be a HIP device")
+            n_az = batch_scan["azimuths"].shape[1]
+            if override_mask is not None and (override_mask.ndim != 3 or override_mask.shape[0] != scan_pc_raw.shape[0] or
+                                              override_mask.shape[1] != n_az):
+                raise ValueError("polar_sampling: override_mask must be a polar (B, %d, R) mask (got %s)"
+                                 % (n_az, tuple(override_mask.shape)))
+
         if override_mask is None:
             raw_in = self._network_input(fft_data, fft_cfar, normalize=False)
             if self.unet_backend == "hip":
@@ -302,8 +324,12 @@ class LearnICPWeightPolicy(nn.Module):
         if mask_only:
             return weight_mask
 
-        (weights, diff_mean_num_non0, mean_num_non0, mean_w, max_w, min_w), stats = \
-            _extract_weights_stats(weight_mask, scan_pc_raw)
+        if self.polar_sampling:
+            (weights, diff_mean_num_non0, mean_num_non0, mean_w, max_w, min_w), stats = \
+                _extract_weights_polar_stats(weight_mask, scan_pc_raw, batch_scan["azimuths"], self.res)
+        else:
+            (weights, diff_mean_num_non0, mean_num_non0, mean_w, max_w, min_w), stats = \
+                _extract_weights_stats(weight_mask, scan_pc_raw)
         self.mean_num_pts = mean_num_non0
         self.max_w = max_w
         self.min_w = min_w

@@ -19,7 +19,7 @@ import torch
 from . import _lib
 
 __all__ = ["load_pc_from_file", "load_radar", "cfar_mask", "extract_pc", "extract_pc_padded", "extract_weights",
-           "extract_bev_from_pts", "mean_peaks_parallel_fast", "pol_2_cart", "radar_polar_to_cartesian",
+           "extract_weights_polar", "polar_target_from_pts", "extract_bev_from_pts", "mean_peaks_parallel_fast", "pol_2_cart", "radar_polar_to_cartesian",
            "radar_polar_to_cartesian_diff", "radar_cartesian_to_polar", "mask_polar_scan", "point_to_cart_idx",
            "form_cart_range_angle_grid", "form_polar_range_grid"]
 
@@ -656,6 +656,88 @@ def extract_weights(mask, scan_pc):
     F.grid_sample is in its grid, in the x and y columns of ``scan_pc`` (its other columns and the fake
     (0, 0) rows get 0); diff_mean_num_non0 is differentiable through the weights."""
     return _extract_weights_stats(mask, scan_pc)[0]
+
+
+class _SampleWeightsPolar(torch.autograd.Function):
+    """Bilinear gather of a polar mask at the scan points' own ranges and angles (mmk_sample_weights_polar_fwd); backward is
+    the ordered scatter-add into the taps with the crossover rows folded onto their data rows (mmk_sample_weights_polar_bwd)
+    and, when the points require grad, the slope at each point chained through its range and angle
+    (mmk_sample_weights_polar_bwd_pc).  The azimuths, the resolution and the two flags are constants."""
+
+    @staticmethod
+    def forward(ctx, mask, pc, az, radar_resolution, interpolate_crossover, fix_wobble):
+        B, A, R = mask.shape
+        N, cols = pc.shape[1], pc.shape[2]
+        out = torch.empty(B, N, dtype=torch.float32, device=mask.device)
+        args = (float(radar_resolution), 1 if interpolate_crossover else 0, 1 if fix_wobble else 0)
+        _lib.check(_lib.lib().mmk_sample_weights_polar_fwd(_lib.ptr(mask, torch.float32, "mask"), _lib.ptr(pc), _lib.ptr(az), B, N,
+                                                           cols, A, R, *args, _lib.ptr(out), _lib.stream_ptr(mask.device)))
+        ctx.save_for_backward(pc, az, mask if ctx.needs_input_grad[1] else None)
+        ctx.shape = (B, A, R)
+        ctx.args = args
+        return out
+
+    @staticmethod
+    def backward(ctx, gw):
+        pc, az, mask = ctx.saved_tensors
+        B, A, R = ctx.shape
+        N, cols = pc.shape[1], pc.shape[2]
+        gw = gw.contiguous().float()
+        L = _lib.lib()
+        gmask = None
+        if ctx.needs_input_grad[0]:
+            gmask = torch.empty(B, A, R, dtype=torch.float32, device=gw.device)
+            nb = int(L.mmk_sample_weights_polar_bwd_ws_bytes(B, N))
+            ws = _workspace(nb, gw.device)
+            _lib.check(L.mmk_sample_weights_polar_bwd(_lib.ptr(gw), _lib.ptr(pc), _lib.ptr(az), B, N, cols, A, R, *ctx.args,
+                                                      _lib.ptr(gmask), _lib.ptr(ws), nb, _lib.stream_ptr(gw.device)))
+        gpc = None
+        if ctx.needs_input_grad[1]:
+            gpc = torch.empty_like(pc)
+            _lib.check(L.mmk_sample_weights_polar_bwd_pc(_lib.ptr(gw), _lib.ptr(mask), _lib.ptr(pc), _lib.ptr(az), B, N, cols, A, R,
+                                                         *ctx.args, _lib.ptr(gpc), _lib.stream_ptr(gw.device)))
+        return gmask, gpc, None, None, None, None
+
+
+def _extract_weights_polar_stats(mask, scan_pc, azimuths, radar_resolution, interpolate_crossover=True, fix_wobble=True):
+    """extract_weights_polar plus the raw statistics vector of mmk_weight_stats, as _extract_weights_stats."""
+    if mask.ndim != 3 or scan_pc.ndim != 3 or scan_pc.shape[0] != mask.shape[0]:
+        raise ValueError("mask must be (B,A,R) and scan_pc (B,N,>=2) (got %s and %s)" % (tuple(mask.shape), tuple(scan_pc.shape)))
+    if tuple(azimuths.shape) != (mask.shape[0], mask.shape[1]):
+        raise ValueError("azimuths must be (B, %d) (got %s)" % (mask.shape[1], tuple(azimuths.shape)))
+    dev = _hip_device(mask)
+    m = mask if (mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous()) else \
+        mask.to(device=dev, dtype=torch.float32).contiguous()
+    pc = scan_pc.to(device=dev, dtype=torch.float32).contiguous()      # not detached: differentiable in x, y
+    az = _lib.dev_f32(azimuths, dev)
+    weights = _SampleWeightsPolar.apply(m, pc, az, radar_resolution, interpolate_crossover, fix_wobble)
+    diff_mean_num_non0, st = _WeightStats.apply(weights, pc)
+    if not mask.is_cuda:
+        weights = weights.to(mask.device)
+    return (weights, diff_mean_num_non0, st[1], st[2], st[3], st[4]), st
+
+
+def extract_weights_polar(mask, scan_pc, azimuths, radar_resolution, interpolate_crossover=True, fix_wobble=True):
+    """extract_weights for a POLAR mask (B,A,R): every point reads the mask where it lies in the polar image -- its range
+    and its angle against the item's azimuth table ``azimuths`` (B,A), ascending, on the host or the device -- with the
+    sampling arithmetic of ``radar_polar_to_cartesian_diff`` (radar_utils.py:276-323; the two flags are its flags), so a
+    point at the centre of a pixel of the 0.2384 m Cartesian grid gets what that function writes to the pixel.  Absent
+    upstream, whose extract_weights samples any mask with the Cartesian grid's normalisation (kept as is in
+    ``extract_weights``).  Returns extract_weights' 6-tuple, the statistics from the same fused pass.  The weights are
+    differentiable in ``mask`` and in the x and y columns of ``scan_pc`` (its other columns and the fake (0, 0) rows get 0);
+    the azimuths are constants."""
+    return _extract_weights_polar_stats(mask, scan_pc, azimuths, radar_resolution, interpolate_crossover, fix_wobble)[0]
+
+
+def polar_target_from_pts(pc, azimuths, radar_resolution, polar_pixel_shape=(400, 3360)):
+    """The map-point BCE target in a polar mask's own geometry:
+    ``radar_cartesian_to_polar(extract_bev_from_pts(pc).double(), azimuths, radar_resolution, polar_pixel_shape=...)`` as
+    fp32 -- the reference's 640 x 640 raster of the points resampled onto the (A,R) grid, a soft target in [0, 1].  The
+    reference has no such target (its polar network cannot form the map-point loss); composing the two pinned operators is
+    this build's choice.  (B,M,>=2) + (B,A) -> (B,A,R) fp32, no gradient."""
+    with torch.no_grad():
+        bev = extract_bev_from_pts(pc)
+        return radar_cartesian_to_polar(bev.double(), azimuths, radar_resolution, polar_pixel_shape=polar_pixel_shape).float()
 
 
 # ----------------------------------------------------------------------------- R10

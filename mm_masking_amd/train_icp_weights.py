@@ -55,7 +55,8 @@ def prepare_batch(raw, params, max_loc_pts=5120, polar_res=0.0596):
     polar -> Cartesian for the FFT and CFAR images (kept polar for a polar network).  ``raw`` holds device tensors
     fft_polar (B,400,3360), azimuths (B,400), az_times (B,400), map_pc (B,M,6),
     T_init, T_gt.  Returns the reference's dict-of-dicts batch; with params["mask_target"] == "scan" its ``loc_data`` also
-    carries fft_polar, azimuths and az_times (what the policy's scan mode reads)."""
+    carries fft_polar, azimuths and az_times (what the policy's scan mode reads), with params["polar_sampling"] the azimuths
+    (what the polar sampler and the polar map-point target read)."""
     fft = raw["fft_polar"]
     az = raw["azimuths"]
     cfar = ru.cfar_mask(fft, polar_res, a_thresh=params["a_thresh"], b_thresh=params["b_thresh"], diff=False)
@@ -67,6 +68,8 @@ def prepare_batch(raw, params, max_loc_pts=5120, polar_res=0.0596):
     loc_data = {"raw_pc": pc, "filtered_pc": pc, "fft_data": fft_img, "fft_cfar": cfar_img, "timestamp": 0}
     if params.get("mask_target") == "scan":
         loc_data.update({"fft_polar": fft, "azimuths": az, "az_times": raw["az_times"]})
+    if params.get("polar_sampling"):
+        loc_data["azimuths"] = az
     map_data = {"pc": raw["map_pc"], "timestamp": 0}
     T_data = {"T_ml_init": raw["T_init"], "T_ml_gt": raw["T_gt"]}
     return {"loc_data": loc_data, "map_data": map_data, "transforms": T_data}
@@ -231,6 +234,19 @@ def _bce_mean(mask, target):
     return torch.nn.BCELoss()(mask, target)
 
 
+def _map_pts_target(model, batch_scan, batch_map, device):
+    """The map-point target of the BCE term and of generate_baseline's override mask: the reference's 640 x 640 raster
+    (train_icp_weights.py:209,318), or, for a policy with params["polar_sampling"], that raster in the polar mask's own
+    geometry (ru.polar_target_from_pts with the scan's azimuths)."""
+    pc = batch_map["pc"].to(device)
+    if not getattr(model, "polar_sampling", False):
+        return ru.extract_bev_from_pts(pc)
+    if "azimuths" not in batch_scan:
+        raise KeyError("polar_sampling needs batch_scan['azimuths'] (prepare_batch with params['polar_sampling'] = True, "
+                       "or finish_batch(keep_polar=True))")
+    return ru.polar_target_from_pts(pc, batch_scan["azimuths"], model.res, tuple(batch_scan["fft_data"].shape[1:]))
+
+
 def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map, model, loss_weights=[],
                        icp_loss_only_iter=0, gt_eye=True, epoch=0):
     """train_icp_weights.py:179-253.  Same values and shapes as the reference's expression
@@ -270,7 +286,7 @@ def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map
         if loss_weights["cfar"] > 0.0:
             terms["cfar"] = mask_criterion(mask, batch_scan["fft_cfar"].to(mask.device))
         if loss_weights["mask_pts"] > 0.0:
-            map_pts_mask = ru.extract_bev_from_pts(batch_map["pc"].to(mask.device))
+            map_pts_mask = _map_pts_target(model, batch_scan, batch_map, mask.device)
             terms["mask_pts"] = mask_criterion(mask, map_pts_mask)
         if loss_weights["num_pts"] > 0.0:
             terms["num_pts"] = model.mean_all_pts - num_non0
@@ -414,7 +430,7 @@ def generate_baseline(model, iterator, baseline_type="train", device="cpu",
                 ones_mask = torch.where(fft_data > 3.0 * mean_azimuth, torch.ones_like(fft_data),
                                         torch.zeros_like(fft_data))
             elif loss_weights.get("mask_pts", 0.0) > 0.0:
-                ones_mask = ru.extract_bev_from_pts(batch_map["pc"].to(device))
+                ones_mask = _map_pts_target(model, batch_scan, batch_map, device)
             else:
                 ones_mask = torch.ones_like(fft_data)
             T_pred_ones, mask_ones, num_non0 = model(batch_scan, batch_map, batch_T_init, binary=binary,
