@@ -152,6 +152,23 @@ int mmk_nn_search(const float *source /*B,N,3*/, const float *target_planar,
                   int32_t *idx, float *d2, void *workspace, size_t workspace_bytes,
                   void *stream);
 
+/* Target normals: exact k-nearest-neighbour PCA of a cloud against itself.  Produces the normals
+ * columns of the map tensor (mm_masking/icp_weight_dataset.py:395-398: xyz | normal), which upstream come out of vtr3
+ * pose graphs.  points (B,M,cols), cols >= dim; the search uses the first dim coordinates with the ICP's own distance and
+ * key (ascending d2, ties to the lowest index; a row is its own first neighbour).  k in 3..32.  max_radius > 0 drops
+ * rows with d2 > max_radius^2; pad_val > 0 makes every row with a |coordinate| >= pad_val a padding row: never a
+ * neighbour, all its outputs 0 (nbr_idx -1).  viewpoint (B,3) or NULL = the origin: the normal is flipped to face it.
+ * normals (B,M,3) unit length (nz = 0 for dim 2), or 0 with fewer than 3 neighbours kept; curvature (B,M) = lambda_min /
+ * sum(lambda); count (B,M) = neighbours kept; nbr_idx (B,M,k) in key order, unused slots -1.  The last three are
+ * optional.  Every value depends on the pair's own rows alone: bit-reproducible, no float atomics.  Asynchronous on
+ * `stream`, no allocation; workspace: mmk_knn_normals_workspace_bytes(B, M) bytes.                                    */
+size_t mmk_knn_normals_workspace_bytes(int32_t B, int32_t M);
+int mmk_knn_normals(const float *points /*B,M,cols*/, int32_t B, int32_t M, int32_t cols, int32_t dim /*2|3*/,
+                    int32_t k /*3..32*/, float max_radius /*<= 0: none*/, float pad_val /*<= 0: no padding rows*/,
+                    const float *viewpoint /*B,3 or NULL = origin*/,
+                    float *normals /*B,M,3*/, float *curvature /*B,M or NULL*/, int32_t *count /*B,M or NULL*/,
+                    int32_t *nbr_idx /*B,M,k or NULL*/, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Measurement hook (bench.py): while enabled, every nn_search launch made by this
  * process (inside mmk_icp_forward or mmk_nn_search) is bracketed by HIP events on its
  * launch stream.  _end() waits for the recorded events and returns the per-launch

@@ -791,6 +791,238 @@ __global__ __launch_bounds__(256) void grid_nn_kernel(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------
+// Target normals (DESIGN.md §3 "N1"): the k nearest valid rows of a cloud to each of its own rows, EXACT, through the
+// same grid, then the smallest eigenpair of their covariance.  Serves the normals columns of the reference's map tensor
+// (mm_masking/icp_weight_dataset.py:395-398), which upstream come out of vtr3 and nothing here could produce.
+//
+// One point per thread, taken in the grid's cell order (neighbouring lanes walk the same cells; results go to the row's
+// own index, so the order is invisible).  The top-k is an array of packed keys (bits(d2) << 32 | index: integer order =
+// nearer first, ties to the lowest index) held in registers in DESCENDING order, so that the worst kept key is the static
+// slot 0: a candidate below it replaces it and sinks through k - 1 unrolled compare-exchanges.  Every index into the
+// array is a compile-time constant; slots >= k are switched off by predicates on that constant (a run-time index would
+// put the array into scratch memory).
+//
+// Unlike grid_nn_kernel's minimum, a top-k must not see a candidate twice, so each radius scans only the annulus that
+// the previous square left out (full rows above and below it, two side segments beside it).  The stopping rule is that
+// kernel's: after the square of radius r every unvisited row is at least r cells away in x or in y -- rows and queries
+// outside the +-128 m grid are clamped into the border cells, which only puts them farther away than the bound, so a
+// cloud far from the origin costs time, never exactness -- and the search ends when the k-th distance is below that
+// bound (1 mm of slack for the float cell assignment) or the bound has passed max_radius.  A query that GRID_RMAX rings
+// do not settle starts over and scans every row.
+constexpr int KNN_THREADS = 256;
+constexpr int KNN_JACOBI_SWEEPS = 8;
+constexpr unsigned long long KNN_EMPTY = ~0ull;
+
+template <int DIM>
+__device__ __forceinline__ bool knn_is_pad(float x, float y, float z, float pad_val)
+{
+    bool pad = fabsf(x) >= pad_val || fabsf(y) >= pad_val;
+    if constexpr (DIM == 3) pad = pad || fabsf(z) >= pad_val;
+    return pad_val > 0.f && pad;
+}
+
+// One Jacobi rotation of a symmetric 3x3 in the (p,q) plane; r is the third index.  (Golub & Van Loan, Alg. 8.4.1.)
+__device__ __forceinline__ void jacobi_rot(double &app, double &aqq, double &apq, double &arp, double &arq, double &v0p,
+                                           double &v0q, double &v1p, double &v1q, double &v2p, double &v2q)
+{
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    app -= t * apq;
+    aqq += t * apq;
+    apq = 0.0;
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    arp = rp;
+    arq = rq;
+    const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q;
+    const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
+    const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
+    v0p = a0, v0q = b0, v1p = a1, v1q = b1, v2p = a2, v2q = b2;
+}
+
+template <int DIM, int KC>
+__global__ __launch_bounds__(KNN_THREADS) void knn_normals_kernel(
+    const float *__restrict__ pts_in, int M, int cols, int k, float max_radius, float pad_val,
+    const float *__restrict__ viewpoint, const int32_t *__restrict__ starts, const float4 *__restrict__ sorted,
+    float *__restrict__ normals, float *__restrict__ curvature, int32_t *__restrict__ count_out, int32_t *__restrict__ nbr_idx)
+{
+    const int b = blockIdx.y;
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= M) return;
+    const float4 *pts = sorted + (size_t)b * M;
+    const float4 q = pts[s];
+    const int row = __float_as_int(q.w);
+    const size_t orow = (size_t)b * M + row;
+    if (knn_is_pad<DIM>(q.x, q.y, q.z, pad_val)) {
+        normals[orow * 3 + 0] = 0.f;
+        normals[orow * 3 + 1] = 0.f;
+        normals[orow * 3 + 2] = 0.f;
+        if (curvature != nullptr) curvature[orow] = 0.f;
+        if (count_out != nullptr) count_out[orow] = 0;
+        if (nbr_idx != nullptr)
+            for (int j = 0; j < k; ++j) nbr_idx[orow * k + j] = -1;
+        return;
+    }
+    float p[DIM];
+    p[0] = q.x;
+    p[1] = q.y;
+    if constexpr (DIM == 3) p[2] = q.z;
+    const int cx = grid_coord(p[0]), cy = grid_coord(p[1]);
+    const int32_t *st = starts + (size_t)b * (GRID_NC + 1);
+    const bool use_r = max_radius > 0.f;
+    const float r2 = max_radius * max_radius;
+
+    unsigned long long a[KC];   // descending: a[0] is the worst kept key, KNN_EMPTY while fewer than k are kept
+#pragma unroll
+    for (int j = 0; j < KC; ++j) a[j] = KNN_EMPTY;
+
+    // ONE scan site (the unrolled top-k update is long, and a second copy of it would double the kernel): step 0..7 scan the
+    // annulus of radii[step], step 8 is the exhaustive scan, written as a single "row" that spans every sorted row.
+    // Candidates are fetched eight at a time (independent 16-byte loads), as in grid_nn_kernel; the tail's repeats of the
+    // last row are switched off, not offered twice.
+    bool done = false;
+    int rp = -1;   // the square of radius rp has been scanned
+    for (int step = 0; step <= 8 && !done; ++step) {
+        const bool all = step == 8;   // fewer than k rows within GRID_RMAX rings: start over, scan every row (still exact)
+        const int r = step == 0 ? 1 : step == 1 ? 2 : step == 2 ? 3 : step == 3 ? 5 : step == 4 ? 8 : step == 5 ? 12 : step == 6 ? 17 : GRID_RMAX;
+        if (all) {
+#pragma unroll
+            for (int j = 0; j < KC; ++j) a[j] = KNN_EMPTY;
+        }
+        for (int rc = 0; rc < (all ? 1 : 4); ++rc) {
+            // rows above the old square (at first, rp = -1: down to the query's own row), rows below it, the two segments
+            // beside it; clipped to the grid
+            int x0 = rc == 3 ? cx + rp + 1 : cx - r, x1 = rc == 2 ? cx - rp - 1 : cx + r;
+            int y0 = rc == 0 ? cy - r : rc == 1 ? cy + max(rp, 0) + 1 : cy - rp, y1 = rc == 0 ? cy - rp - 1 : rc == 1 ? cy + r : cy + rp;
+            x0 = max(x0, 0), y0 = max(y0, 0), x1 = min(x1, GRID_N - 1), y1 = min(y1, GRID_N - 1);
+            if (all) x0 = x1 = y0 = y1 = 0;
+            if (x0 > x1) continue;
+            for (int y = y0; y <= y1; ++y) {
+                const int k0 = all ? 0 : st[y * GRID_N + x0], k1 = all ? M : st[y * GRID_N + x1 + 1];
+                for (int kk = k0; kk < k1; kk += 8) {
+                    float4 t[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) t[u] = pts[min(kk + u, k1 - 1)];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const float d = nn_dist<DIM>(t[u].x, t[u].y, t[u].z, p);
+                        const unsigned long long key =
+                            ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)__float_as_uint(t[u].w);
+                        if (kk + u < k1 && !knn_is_pad<DIM>(t[u].x, t[u].y, t[u].z, pad_val) && !(use_r && d > r2) && key < a[0]) {
+                            a[0] = key;
+#pragma unroll
+                            for (int j = 0; j + 1 < KC; ++j) {
+                                const bool sw = (j + 1 < k) && a[j] < a[j + 1];
+                                const unsigned long long hi = sw ? a[j + 1] : a[j], lo = sw ? a[j] : a[j + 1];
+                                a[j] = hi;
+                                a[j + 1] = lo;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        rp = r;
+        const float lim = (float)r * GRID_CELL - 1e-3f;   // 1 mm of slack for the float cell assignment
+        done = all || (a[0] != KNN_EMPTY && __uint_as_float((unsigned)(a[0] >> 32)) < lim * lim) || (use_r && lim > max_radius);
+    }
+
+    // ---- neighbours in key order = slots k-1 .. 0; the empty slots are the leading ones
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < KC; ++j) cnt += (j < k && a[j] != KNN_EMPTY) ? 1 : 0;
+    if (count_out != nullptr) count_out[orow] = cnt;
+    if (nbr_idx != nullptr) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            if (j < k) nbr_idx[orow * k + (k - 1 - j)] = a[j] != KNN_EMPTY ? (int32_t)(unsigned)a[j] : -1;
+    }
+    float n0 = 0.f, n1 = 0.f, n2 = 0.f, curv = 0.f;
+    if (cnt >= 3) {
+        const float *base = pts_in + (size_t)b * M * cols;
+        // two passes in fp64 over the fp32 coordinates, in key order
+        double mx = 0.0, my = 0.0, mz = 0.0;
+#pragma unroll
+        for (int j = KC - 1; j >= 0; --j) {
+            if (j < k && a[j] != KNN_EMPTY) {
+                const float *t = base + (size_t)(unsigned)a[j] * cols;
+                mx += (double)t[0];
+                my += (double)t[1];
+                if constexpr (DIM == 3) mz += (double)t[2];
+            }
+        }
+        // divided, not scaled by 1 / cnt: the centroid of rows that share a coordinate is then that coordinate exactly
+        const double inv = 1.0 / (double)cnt;
+        mx /= (double)cnt, my /= (double)cnt, mz /= (double)cnt;
+        double cxx = 0.0, cxy = 0.0, cxz = 0.0, cyy = 0.0, cyz = 0.0, czz = 0.0;
+#pragma unroll
+        for (int j = KC - 1; j >= 0; --j) {
+            if (j < k && a[j] != KNN_EMPTY) {
+                const float *t = base + (size_t)(unsigned)a[j] * cols;
+                const double dx = (double)t[0] - mx, dy = (double)t[1] - my;
+                cxx += dx * dx;
+                cxy += dx * dy;
+                cyy += dy * dy;
+                if constexpr (DIM == 3) {
+                    const double dz = (double)t[2] - mz;
+                    cxz += dx * dz;
+                    cyz += dy * dz;
+                    czz += dz * dz;
+                }
+            }
+        }
+        cxx *= inv, cxy *= inv, cyy *= inv, cxz *= inv, cyz *= inv, czz *= inv;
+        double ex, ey, ez = 0.0, lmin, lsum;
+        if constexpr (DIM == 2) {
+            // closed form: lambda_min = (a + c) / 2 - sqrt(((a - c) / 2)^2 + b^2); its eigenvector is (b, l - a) and also
+            // (l - c, b) -- the longer of the two is the well-conditioned one
+            const double h = 0.5 * (cxx - cyy), root = cxy == 0.0 ? fabs(h) : sqrt(h * h + cxy * cxy);
+            lmin = 0.5 * (cxx + cyy) - root;
+            lsum = cxx + cyy;
+            const double u0 = cxy, u1 = lmin - cxx, w0 = lmin - cyy, w1 = cxy;
+            const bool first = u0 * u0 + u1 * u1 >= w0 * w0 + w1 * w1;
+            ex = first ? u0 : w0;
+            ey = first ? u1 : w1;
+            if (ex == 0.0 && ey == 0.0) ex = 1.0;   // isotropic: every direction is an eigenvector
+        } else {
+            // cyclic Jacobi, KNN_JACOBI_SWEEPS sweeps of the rotations (0,1), (0,2), (1,2): convergence is quadratic once the
+            // off-diagonal norm is small against the gaps, which a 3x3 reaches within three or four sweeps (off/||A|| goes
+            // ~1e-1, 1e-2, 1e-4, 1e-8, < 1e-16), so 8 leaves several sweeps that rotate by nothing
+            double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+            for (int sweep = 0; sweep < KNN_JACOBI_SWEEPS; ++sweep) {
+                jacobi_rot(cxx, cyy, cxy, cxz, cyz, v00, v01, v10, v11, v20, v21);
+                jacobi_rot(cxx, czz, cxz, cxy, cyz, v00, v02, v10, v12, v20, v22);
+                jacobi_rot(cyy, czz, cyz, cxy, cxz, v01, v02, v11, v12, v21, v22);
+            }
+            lsum = cxx + cyy + czz;
+            // the smallest eigenvalue's column (ties to the lower index), by selects: an indexed pick would go through scratch
+            const bool s1 = cyy < cxx;
+            const double l01 = s1 ? cyy : cxx;
+            const bool s2 = czz < l01;
+            lmin = s2 ? czz : l01;
+            ex = s2 ? v02 : (s1 ? v01 : v00);
+            ey = s2 ? v12 : (s1 ? v11 : v10);
+            ez = s2 ? v22 : (s1 ? v21 : v20);
+        }
+        const double nrm = sqrt(ex * ex + ey * ey + ez * ez);
+        ex /= nrm, ey /= nrm, ez /= nrm;
+        double vx = 0.0, vy = 0.0, vz = 0.0;
+        if (viewpoint != nullptr) vx = (double)viewpoint[b * 3 + 0], vy = (double)viewpoint[b * 3 + 1], vz = (double)viewpoint[b * 3 + 2];
+        double dot = ex * (vx - (double)p[0]) + ey * (vy - (double)p[1]);
+        if constexpr (DIM == 3) dot += ez * (vz - (double)p[2]);
+        if (dot < 0.0) ex = -ex, ey = -ey, ez = -ez;
+        n0 = (float)ex, n1 = (float)ey, n2 = (float)ez;
+        lmin = fmax(lmin, 0.0);
+        curv = lsum > 0.0 ? (float)(lmin / lsum) : 0.f;
+    }
+    normals[orow * 3 + 0] = n0;
+    normals[orow * 3 + 1] = n1;
+    normals[orow * 3 + 2] = n2;
+    if (curvature != nullptr) curvature[orow] = curv;
+}
+
+// ------------------------------------------------------------------------------------------
 // I3 + I4 per-point terms (oracle: per_point_terms).
 template <int DIM, int TYPE>
 struct PointTerms {
@@ -1912,6 +2144,79 @@ extern "C" int mmk_nn_search(const float *source, const float *target_planar, co
     int rc = launch_nn(dim, source, target_planar, T, nullptr, nullptr, nullptr, nullptr, B, N, pl, packed, seed0, nullptr, nullptr, nullptr, st);
     if (rc != MMK_OK) return rc;
     hipLaunchKernelGGL(nn_unpack_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, packed, B * N, idx, d2);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+namespace {
+
+struct KnnWs {
+    int32_t *counts, *cursor, *starts;
+    float4 *sorted;
+    size_t bytes;
+};
+
+KnnWs knn_carve(int32_t B, int32_t M, void *workspace, size_t workspace_bytes)
+{
+    mmk::Arena ar(workspace, workspace_bytes);
+    KnnWs w;
+    w.counts = ar.take<int32_t>((size_t)B * GRID_NC * 2);
+    w.cursor = w.counts + (size_t)B * GRID_NC;
+    w.starts = ar.take<int32_t>((size_t)B * (GRID_NC + 1));
+    w.sorted = ar.take<float4>((size_t)B * M);
+    w.bytes = mmk::align_up(ar.off, 256);
+    return w;
+}
+
+template <int DIM, int KC>
+void knn_launch(const float *points, int B, int M, int cols, int k, float max_radius, float pad_val, const float *viewpoint,
+                const KnnWs &w, float *normals, float *curvature, int32_t *count, int32_t *nbr_idx, hipStream_t st)
+{
+    hipLaunchKernelGGL((knn_normals_kernel<DIM, KC>), dim3((M + KNN_THREADS - 1) / KNN_THREADS, B), dim3(KNN_THREADS), 0, st, points,
+                       M, cols, k, max_radius, pad_val, viewpoint, w.starts, w.sorted, normals, curvature, count, nbr_idx);
+}
+
+}  // namespace
+
+extern "C" size_t mmk_knn_normals_workspace_bytes(int32_t B, int32_t M)
+{
+    if (B < 1 || M < 1) return 0;
+    return knn_carve(B, M, nullptr, 0).bytes;
+}
+
+extern "C" int mmk_knn_normals(const float *points, int32_t B, int32_t M, int32_t cols, int32_t dim, int32_t k, float max_radius,
+                               float pad_val, const float *viewpoint, float *normals, float *curvature, int32_t *count,
+                               int32_t *nbr_idx, void *workspace, size_t workspace_bytes, void *stream)
+{
+    MMK_REQUIRE(points && normals, "mmk_knn_normals: NULL pointer");
+    MMK_REQUIRE(B >= 1 && M >= 1 && B <= 65535, "mmk_knn_normals: B must be in 1..65535 and M >= 1 (got %d, %d)", B, M);
+    MMK_REQUIRE((dim == 2 || dim == 3) && cols >= dim, "mmk_knn_normals: dim must be 2|3 and <= cols");
+    MMK_REQUIRE(k >= 3 && k <= 32, "mmk_knn_normals: k must be in 3..32 (got %d)", k);
+    const KnnWs w = knn_carve(B, M, workspace, workspace_bytes);
+    if (workspace == nullptr || w.bytes > workspace_bytes) {
+        mmk::set_error("mmk_knn_normals: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
+        return MMK_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // the grid of the ICP's exact search, built by the same kernels
+    MMK_CHECK_HIP(hipMemsetAsync(w.counts, 0, sizeof(int32_t) * (size_t)B * GRID_NC * 2, st));
+    hipLaunchKernelGGL(grid_count_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, points, M, cols, w.counts);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(grid_scan_kernel, dim3(B), dim3(256), 0, st, w.counts, w.starts);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(grid_fill_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, points, M, cols, dim, w.starts, w.cursor, w.sorted);
+    MMK_LAUNCH_CHECK();
+#define KNN_GO(D, KC) knn_launch<D, KC>(points, B, M, cols, k, max_radius, pad_val, viewpoint, w, normals, curvature, count, nbr_idx, st)
+    if (dim == 2) {
+        if (k <= 8) KNN_GO(2, 8);
+        else if (k <= 16) KNN_GO(2, 16);
+        else KNN_GO(2, 32);
+    } else {
+        if (k <= 8) KNN_GO(3, 8);
+        else if (k <= 16) KNN_GO(3, 16);
+        else KNN_GO(3, 32);
+    }
+#undef KNN_GO
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

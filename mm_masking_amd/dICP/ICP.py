@@ -10,6 +10,9 @@ Keeps the call contract the reference relies on
          trim_dist=5.0, loss_fn={"name": "cauchy"|"huber", "metric": k}, dim=2|3)
         -> {"T": (B,4,4)}
 
+pt2pl takes its normals from the target's columns 3..5; with ``parameters.target_normals:
+estimate`` in the YAML an xyz-only target gets them from ``normals.estimate_normals`` per call.
+
 The arithmetic (nearest neighbour, trim + robust weights, Jacobian accumulation,
 Gauss-Newton solve, SE(2)/SE(3) update, and the reverse sweep that yields
 dL/dweight) runs in the HIP kernels of csrc/mmk_icp.hip through the C ABI
@@ -35,6 +38,7 @@ import torch
 import yaml
 
 from .. import _lib
+from .normals import with_normals
 
 _DEFAULT_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "config", "dICP_config.yaml")
 
@@ -194,6 +198,14 @@ class ICP:
         self.nn_search = ICP.NN_SEARCH_OVERRIDE or str((cfg.get("parameters") or {}).get("nn_search", "brute"))
         if self.nn_search not in _lib.NN_METHODS:
             raise ValueError("dICP config: nn_search must be 'brute' or 'grid' (got %r)" % (self.nn_search,))
+        # pt2pl with an xyz-only target: "given" refuses it (the normals are the caller's), "estimate" computes them per
+        # call with normals.estimate_normals (k = normals_k, the call's dim, viewpoint = origin, pad_val = target_pad_val)
+        self.target_normals = str((cfg.get("parameters") or {}).get("target_normals", "given"))
+        if self.target_normals not in ("given", "estimate"):
+            raise ValueError("dICP config: target_normals must be 'given' or 'estimate' (got %r)" % (self.target_normals,))
+        self.normals_k = int((cfg.get("parameters") or {}).get("normals_k", 16))
+        if not 3 <= self.normals_k <= 32:
+            raise ValueError("dICP config: normals_k must be in 3..32 (got %r)" % (self.normals_k,))
         self.last_state = None
         self.last_iterations = None
 
@@ -213,7 +225,8 @@ class ICP:
             raise ValueError("source must be (B,N,3)")
         if target.ndim != 3 or target.shape[-1] not in (3, 6):
             raise ValueError("target must be (B,M,3) or (B,M,6)")
-        if self.icp_type == "pt2pl" and target.shape[-1] != 6:
+        estimate = self.icp_type == "pt2pl" and target.shape[-1] != 6 and self.target_normals == "estimate"
+        if self.icp_type == "pt2pl" and target.shape[-1] != 6 and not estimate:
             raise ValueError("pt2pl needs target normals: target must be (B,M,6)")
         if dim not in (2, 3):
             raise ValueError("dim must be 2 or 3")
@@ -227,6 +240,9 @@ class ICP:
         # not detached: autograd undoes the move / cast for the clouds' gradients
         src = source.to(device=dev, dtype=torch.float32).contiguous()
         tgt = target.to(device=dev, dtype=torch.float32).contiguous()
+        if estimate:
+            # constants, like the map itself: the target's gradient flows through xyz only
+            tgt = with_normals(tgt, k=self.normals_k, dim=dim, pad_val=self.target_pad_val).contiguous()
         B, N, _ = src.shape
         M = tgt.shape[1]
         if T_init is None:

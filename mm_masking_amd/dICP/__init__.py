@@ -1,2 +1,3 @@
 """Drop-in for the ``dICP`` package (lisusdaniil/dICP, absent upstream): ``from dICP.ICP import ICP``."""
 from .ICP import ICP  # noqa: F401
+from .normals import estimate_normals, with_normals  # noqa: F401

@@ -129,6 +129,8 @@ class ICPWeightDataset(torch.utils.data.Dataset):
               T_map_sensor_robot (4,4) (:118-124)
         .../scan/<loc_stamp>_raw.bin, _filt.bin    float32 x 3 per point (extract_points_and_map's clouds)
         .../map/<map_stamp>.bin                    float32 x 6 per point, xyz | normal in the robot frame
+        .../map/<map_stamp>_xyz.bin                optional, float32 x 3: a map without normals; when <map_stamp>.bin is
+                                                   missing it is written once from this file with estimated normals
 
     The per-item work is the reference's: PNG rows -> load_radar, zero / target_pad_val padding to the largest
     cloud of the set, map filtering by elevation and normal, rotation augmentation, polar -> Cartesian (HIP
@@ -188,6 +190,7 @@ class ICPWeightDataset(torch.utils.data.Dataset):
         self.max_map_pts = int(params.get("max_map_pts", 0))
         scan_max = self.max_loc_pts == 0 or self.max_map_pts == 0
         radar_in = not (map_sensor == "lidar" and loc_sensor == "lidar")
+        self._write_map_normals(loc_pairs, sensor_dir_name, radar_in, num_samples, params)
         for pair_idx, (map_seq, loc_seq) in enumerate(loc_pairs):
             pdir = os.path.join(data_dir, "vtr_export", sensor_dir_name, map_seq, loc_seq)
             idx = np.load(os.path.join(pdir, "index.npz"), allow_pickle=False)
@@ -238,6 +241,56 @@ class ICPWeightDataset(torch.utils.data.Dataset):
         fft = torch.tensor(fft, dtype=self.float_type).unsqueeze(0)
         cfar = ru.cfar_mask(fft, self.polar_res, a_thresh=self.a_thresh, b_thresh=self.b_thresh, diff=False)
         write_png_gray(cfar_path, np.rint(255.0 * cfar.squeeze(0).cpu().numpy()).astype(np.uint8))
+
+    def _write_map_normals(self, loc_pairs, sensor_dir_name, radar_in, num_samples, params, max_rows=1 << 21):
+        """The normals cache, as the CFAR cache: a map that the export holds only as ``map/<map_stamp>_xyz.bin`` (float32 x 3,
+        robot frame) gets its ``map/<map_stamp>.bin`` (xyz | normal) written once, with normals.estimate_normals (dim 3,
+        k = params["map_normal_k"], max_radius = params["map_normal_radius"], seen from the robot-frame origin).  Only the
+        maps of the samples this Dataset will use; distinct maps are grouped into padded batches of at most ``max_rows``
+        rows, one launch each (the result does not depend on the batch).  Everything downstream reads the cache as an
+        ordinary export.  A map with neither file is left to _read_clouds' error."""
+        todo, seen, n = [], set(), 0
+        for map_seq, loc_seq in loc_pairs:
+            pdir = os.path.join(self.data_dir, "vtr_export", sensor_dir_name, map_seq, loc_seq)
+            idx = np.load(os.path.join(pdir, "index.npz"), allow_pickle=False)
+            for ii in range(len(idx["loc_stamp"])):
+                if radar_in and not os.path.exists(os.path.join(self.data_dir, "vtr_data", loc_seq, "radar",
+                                                                "%d.png" % int(idx["loc_stamp"][ii]))):
+                    continue
+                n += 1
+                path = os.path.join(pdir, "map", "%d.bin" % int(idx["map_stamp"][ii]))
+                xyz = path[:-4] + "_xyz.bin"
+                if path not in seen and not os.path.exists(path) and os.path.exists(xyz):
+                    seen.add(path)
+                    todo.append((path, load_xyz_bin(xyz, 3)))
+                if num_samples > 0 and n >= num_samples:
+                    break
+        if not todo:
+            return
+        from .dICP.normals import estimate_normals
+        k, radius = int(params.get("map_normal_k", 16)), params.get("map_normal_radius")
+        todo.sort(key=lambda t: t[1].shape[0])
+        while todo:
+            rows = max(todo[0][1].shape[0], 1)
+            group = [todo.pop(0)]
+            while todo and (len(group) + 1) * max(todo[0][1].shape[0], 1) <= max(max_rows, rows):
+                group.append(todo.pop(0))
+            rows = max(max(c.shape[0] for _, c in group), 1)
+            # padding rows sit beyond every real coordinate (target_pad_val unless a map reaches that far)
+            pad = max(float(self.target_pad_val), 2.0 * max([float(np.abs(c).max()) for _, c in group if c.size] + [0.0]))
+            batch = np.full((len(group), rows, 3), pad, dtype=np.float32)
+            for j, (_, c) in enumerate(group):
+                batch[j, :c.shape[0]] = c
+            if not torch.cuda.is_available():
+                from . import _lib
+                raise _lib.MmkError("ICPWeightDataset: %s holds xyz only and estimating its normals needs an MI355X/HIP "
+                                    "device" % (group[0][0][:-4] + "_xyz.bin"))
+            normals = estimate_normals(torch.from_numpy(batch).cuda(), k=k, dim=3, max_radius=radius, pad_val=pad).cpu().numpy()
+            for j, (path, c) in enumerate(group):
+                tmp = "%s.%d.%d.tmp" % (path, os.getpid(), threading.get_ident())
+                with open(tmp, "wb") as f:           # atomically: ranks of a multi-rank job may race for the same file
+                    f.write(np.ascontiguousarray(np.concatenate((c, normals[j, :c.shape[0]]), axis=1), dtype=np.float32).tobytes())
+                os.replace(tmp, path)
 
     @staticmethod
     def _read_clouds(pdir, loc_stamp, map_stamp):

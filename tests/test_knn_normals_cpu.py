@@ -1,0 +1,149 @@
+"""CPU: the C ABI of the normal estimator (mmk_knn_normals) -- declared, exported, bound, host-side argument checks (no
+launch) -- the Python wrapper's checks, the dICP config key, and the known answers of the test-side restatement
+(knn_normals_ref.py) that the GPU tests compare the kernel with."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import yaml
+
+from mm_masking_amd import _lib
+from mm_masking_amd import dICP
+from mm_masking_amd.dICP.ICP import ICP
+from knn_normals_ref import knn_normals_ref, lattice_line, lattice_plane, nn_dist_f32
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("mmk_knn_normals_workspace_bytes", "mmk_knn_normals")
+
+
+@pytest.fixture(scope="module")
+def L():
+    _lib.build()
+    return _lib.lib()
+
+
+def test_new_entries_declared_exported_and_bound(L):
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mmk.h")).read(), flags=re.S)
+    for name in NEW:
+        assert re.search(r"\b%s\s*\(" % name, hdr), name
+        assert hasattr(L, name) and name in _lib.EXPORTED, name
+    assert L.mmk_version() == 502
+    assert callable(dICP.estimate_normals) and callable(dICP.with_normals)
+
+
+def test_workspace_bytes_grow_with_b_and_m(L):
+    f = L.mmk_knn_normals_workspace_bytes
+    by_m = [f(2, m) for m in (1, 700, 20480, 100000)]
+    by_b = [f(b, 700) for b in (1, 2, 32)]
+    assert by_m[0] > 0 and all(a < b for a, b in zip(by_m, by_m[1:]))
+    assert all(a < b for a, b in zip(by_b, by_b[1:]))
+    assert f(0, 700) == 0 and f(2, 0) == 0
+    # the grid (two counters and a start per cell) plus one float4 per row
+    assert f(1, 100000) >= 3 * 128 * 128 * 4 + 100000 * 16
+
+
+NULL = ctypes.c_void_p(0)
+FAKE = ctypes.c_void_p(4096)          # never dereferenced: every call below fails on the host before any launch
+
+
+def _call(L, points=FAKE, normals=FAKE, ws=FAKE, nbytes=None, B=2, M=100, cols=3, dim=3, k=16):
+    nbytes = L.mmk_knn_normals_workspace_bytes(max(B, 1), max(M, 1)) if nbytes is None else nbytes
+    return L.mmk_knn_normals(points, B, M, cols, dim, k, 0.0, 0.0, NULL, normals, NULL, NULL, NULL, ws, nbytes, NULL)
+
+
+def test_abi_argument_checks(L):
+    for name in ("points", "normals"):
+        assert _call(L, **{name: NULL}) == -1 and b"NULL" in L.mmk_last_error(), name
+    for bad in ({"B": 0}, {"M": 0}, {"B": -1}, {"dim": 1}, {"dim": 4}, {"cols": 2, "dim": 3}, {"cols": 1, "dim": 2},
+                {"k": 2}, {"k": 33}, {"k": 0}):
+        assert _call(L, **bad) == -1, bad
+    assert _call(L, k=33) == -1 and b"3..32" in L.mmk_last_error()
+    need = L.mmk_knn_normals_workspace_bytes(2, 100)
+    assert _call(L, nbytes=need - 1) != 0 and b"workspace" in L.mmk_last_error()
+    assert _call(L, ws=NULL) != 0 and b"workspace" in L.mmk_last_error()
+
+
+def test_wrapper_argument_checks_raise_value_error():
+    pts = torch.zeros(1, 10, 3)
+    for bad in ({"k": 2}, {"k": 33}, {"k": 0}, {"dim": 1}, {"dim": 4}):
+        with pytest.raises(ValueError):
+            dICP.estimate_normals(pts, **bad)
+    with pytest.raises(ValueError, match="columns"):
+        dICP.estimate_normals(torch.zeros(1, 10, 2), dim=3)
+    with pytest.raises(ValueError):
+        dICP.estimate_normals(torch.zeros(10, 3))
+    with pytest.raises(ValueError):
+        dICP.with_normals(pts, k=40)
+
+
+def test_no_device_is_an_error_not_a_fallback():
+    with pytest.raises(_lib.MmkError, match="HIP device"):
+        dICP.estimate_normals(torch.zeros(1, 10, 3))
+    with pytest.raises(_lib.MmkError, match="HIP device"):
+        dICP.with_normals(torch.zeros(1, 10, 3), k=5, dim=2)
+
+
+def _yaml(tmp_path, **params):
+    path = os.path.join(str(tmp_path), "cfg.yaml")
+    with open(path, "w") as f:
+        yaml.safe_dump({"dICP": {"target_pad_val": 1000.0, "parameters": params}}, f)
+    return path
+
+
+def test_config_key(tmp_path):
+    d = ICP("pt2pl")
+    assert d.target_normals == "given" and d.normals_k == 16               # the built-in YAML keeps `given`
+    e = ICP("pt2pl", config_path=_yaml(tmp_path, target_normals="estimate", normals_k=9))
+    assert e.target_normals == "estimate" and e.normals_k == 9
+    assert ICP("pt2pl", config_path=_yaml(tmp_path, target_normals="estimate")).normals_k == 16
+    with pytest.raises(ValueError, match="target_normals"):
+        ICP("pt2pl", config_path=_yaml(tmp_path, target_normals="pca"))
+    with pytest.raises(ValueError, match="normals_k"):
+        ICP("pt2pl", config_path=_yaml(tmp_path, target_normals="estimate", normals_k=40))
+    src, tgt = torch.zeros(1, 8, 3), torch.zeros(1, 12, 3)
+    with pytest.raises(ValueError, match=re.escape("pt2pl needs target normals: target must be (B,M,6)")):
+        d.icp(src, tgt, dim=2)
+    # with `estimate` the xyz-only target passes the shape check and fails where the device is needed
+    if not torch.cuda.is_available():
+        with pytest.raises(_lib.MmkError):
+            e.icp(src, tgt, dim=2)
+
+
+def test_restatement_distance_is_the_fp32_fmaf_form():
+    rng = np.random.default_rng(0)
+    pts = rng.uniform(-50, 50, (200, 3)).astype(np.float32)
+    d = nn_dist_f32(pts, pts[3], 3)
+    exact = ((pts.astype(np.float64) - pts[3].astype(np.float64)) ** 2).sum(axis=1)
+    assert d.dtype == np.float32 and d[3] == 0
+    assert np.abs(d - exact).max() <= 3 * 2.0 ** -24 * exact.max() + 1e-4          # fp32 differences of values up to 100
+    ints = np.round(pts)                                                             # integers: every step is exact
+    assert np.array_equal(nn_dist_f32(ints, ints[0], 2), ((ints[:, :2] - ints[0, :2]) ** 2).sum(axis=1).astype(np.float32))
+
+
+def test_restatement_known_answers():
+    line = lattice_line(12, 3.0)
+    r = knn_normals_ref(line, 5, 2)
+    assert np.array_equal(r["normals"], np.tile([-1.0, 0.0, 0.0], (12, 1)))        # faces the origin
+    assert np.array_equal(r["curvature"], np.zeros(12)) and (r["count"] == 5).all()
+    assert np.array_equal(r["nbr_idx"][0], [0, 1, 2, 3, 4]) and np.array_equal(r["nbr_idx"][5], [5, 4, 6, 3, 7])
+    r = knn_normals_ref(line, 5, 2, viewpoint=[10.0, 0.0, 0.0])
+    assert np.array_equal(r["normals"], np.tile([1.0, 0.0, 0.0], (12, 1)))
+    plane = lattice_plane(8, 5.0)
+    r = knn_normals_ref(plane, 9, 3)
+    assert np.abs(r["normals"] - np.array([0.0, 0.0, -1.0])).max() < 1e-12 and np.abs(r["curvature"]).max() < 1e-15
+    r = knn_normals_ref(plane, 9, 3, viewpoint=[0.0, 0.0, 9.0])
+    assert np.abs(r["normals"] - np.array([0.0, 0.0, 1.0])).max() < 1e-12
+
+
+def test_restatement_padding_radius_and_ties():
+    pts = np.array([[0, 0, 0], [1000, 1000, 1000], [1, 0, 0], [0, 1, 0], [0, 0, 0], [50, 50, 0]], np.float32)
+    r = knn_normals_ref(pts, 3, 2, pad_val=1000.0)
+    assert np.array_equal(r["nbr_idx"][0], [0, 4, 2]) and np.array_equal(r["nbr_idx"][4], [0, 4, 2])   # ties: lowest index
+    assert r["count"][1] == 0 and (r["nbr_idx"][1] == -1).all() and not (r["nbr_idx"] == 1).any()
+    assert not r["normals"][1].any()
+    r = knn_normals_ref(pts, 3, 2, max_radius=0.5, pad_val=1000.0)
+    assert np.array_equal(r["count"], [2, 0, 1, 1, 2, 1]) and not r["normals"].any() and not r["curvature"].any()
+    assert np.array_equal(r["nbr_idx"][5], [5, -1, -1])
