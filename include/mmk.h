@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 502 /* 0.5.2: mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 502 /* 0.5.2: mmk_icp_params.trim_steep appended and mmk_icp_params_bytes (the soft tanh trim gate of the dICP; the struct grows at its end and 0 keeps the hard gate: additions only, the number stays), mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -70,7 +70,15 @@ typedef struct {
                            back (synchronises `stream`) and stop when all pairs
                            froze; 0: run max_iter iterations, never synchronise   */
     int32_t nn_method;  /* MMK_NN_BRUTE | MMK_NN_GRID: both return identical indices     */
+    float trim_steep;   /* 0: hard trim gate keep = d2 < trim_dist^2;
+                           > 0: soft gate keep = 0.5 - 0.5 tanh(trim_steep (d - trim_dist)),
+                           differentiated in both backward entries (I3', I7'); negative
+                           or non-finite: MMK_ERR_ARG ("trim_steep"), workspace size 0  */
 } mmk_icp_params;
+
+/* sizeof(mmk_icp_params) of the library, for a binding to check its mirror of the struct against (the struct grows at its
+ * end: trim_steep was appended; a caller built against the shorter struct must not be mixed with this library).          */
+size_t mmk_icp_params_bytes(void);
 
 size_t mmk_icp_workspace_bytes(const mmk_icp_params *p);
 
@@ -99,8 +107,9 @@ int mmk_icp_backward(const mmk_icp_params *p, const float *source, const float *
 
 /* The same sweep, also differentiated in the clouds: grad_source (B,N,3) = dL/dsource, grad_target (B,M,tgt_cols) =
  * dL/dtarget, each optional (both NULL: bit-identical to mmk_icp_backward).  As in autograd through the unrolled
- * iterations, the correspondences, the trim gate, the freeze decisions and the non-positive-definite fallback are
- * constants.  Entries outside the arithmetic are exactly 0: source z for dim 2; target columns dim..2 and the normals for
+ * iterations, the correspondences, the hard trim gate, the freeze decisions and the non-positive-definite fallback are
+ * constants; the soft gate (trim_steep > 0) is differentiated in the points (both entries: it moves dL/dT_init through the
+ * poses, and dL/dsource, dL/dtarget xyz directly), while trim_dist and trim_steep themselves get no gradient.  Entries outside the arithmetic are exactly 0: source z for dim 2; target columns dim..2 and the normals for
  * pt2pt (normal columns >= 3 + dim for pt2pl); targets that were never a correspondent.  The target gradient is a scatter
  * of up to K*N rows per target, summed as 64-bit fixed point (no float atomics, bit-reproducible; resolution max|row
  * entry| * 2^(ceil(log2(K*N)) - 62)); a non-finite entry makes that pair's target gradient NaN.  workspace:

@@ -44,7 +44,8 @@ class IcpParams(ctypes.Structure):
                 ("tgt_cols", ctypes.c_int32), ("dim", ctypes.c_int32), ("icp_type", ctypes.c_int32),
                 ("loss", ctypes.c_int32), ("loss_k", ctypes.c_float), ("trim_dist", ctypes.c_float),
                 ("tolerance", ctypes.c_float), ("max_iter", ctypes.c_int32), ("save_state", ctypes.c_int32),
-                ("check_every", ctypes.c_int32), ("nn_method", ctypes.c_int32)]
+                ("check_every", ctypes.c_int32), ("nn_method", ctypes.c_int32),
+                ("trim_steep", ctypes.c_float)]        # 0 (the default of a keyword construction): the hard trim gate
 
 
 class ConvDesc(ctypes.Structure):
@@ -128,6 +129,7 @@ def _declare(lib):
     sig = {
         "mmk_version": (ctypes.c_int, []),
         "mmk_last_error": (ctypes.c_char_p, []),
+        "mmk_icp_params_bytes": (sz, []),
         "mmk_icp_workspace_bytes": (sz, [P]),
         "mmk_icp_forward": (ctypes.c_int, [P] + [c_vp] * 10 + [c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
         "mmk_icp_backward": (ctypes.c_int, [P] + [c_vp] * 11 + [c_vp, sz, c_vp]),
@@ -269,6 +271,8 @@ def lib():
         EXPORTED = _declare(loaded)
         if loaded.mmk_conv_desc_bytes() != ctypes.sizeof(ConvDesc):
             raise MmkError("%s: mmk_conv_desc is %d bytes, the ctypes mirror %d" % (SO_PATH, loaded.mmk_conv_desc_bytes(), ctypes.sizeof(ConvDesc)))
+        if loaded.mmk_icp_params_bytes() != ctypes.sizeof(IcpParams):
+            raise MmkError("%s: mmk_icp_params is %d bytes, the ctypes mirror %d" % (SO_PATH, loaded.mmk_icp_params_bytes(), ctypes.sizeof(IcpParams)))
         _lib = loaded
     return _lib
 

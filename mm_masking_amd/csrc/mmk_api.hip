@@ -20,3 +20,4 @@ void set_error(const char *fmt, ...)
 
 extern "C" int mmk_version(void) { return MMK_VERSION; }
 extern "C" const char *mmk_last_error(void) { return g_err; }
+extern "C" size_t mmk_icp_params_bytes(void) { return sizeof(mmk_icp_params); }

@@ -1035,12 +1035,15 @@ struct PointTerms {
     float J[NR][P];
     float er[NR];
     float d2, r2, keep, rho, w, omega;
+    float d, th;        // soft gate only (I3'): distance and tanh of the gate's argument, for the backward
 };
 
+// The trim gate: trim_steep == 0 is the hard gate of I3 (keep = d2 < trim2), > 0 the soft gate of I3'.  The mode is a
+// launch constant, so the branch is uniform over the grid and the hard path is the arithmetic it always was.
 template <int DIM, int TYPE>
 __device__ __forceinline__ void point_terms(PointTerms<DIM, TYPE> &t, const float *T, const float *srow,
                                             const float *trow, float omega, int loss, float k, float k2,
-                                            float trim2)
+                                            float trim2, float trim_dist, float trim_steep)
 {
     constexpr int P = PointTerms<DIM, TYPE>::P;
     constexpr int NR = PointTerms<DIM, TYPE>::NR;
@@ -1053,7 +1056,17 @@ __device__ __forceinline__ void point_terms(PointTerms<DIM, TYPE> &t, const floa
     float d2 = t.ev[0] * t.ev[0] + t.ev[1] * t.ev[1];
     if constexpr (DIM == 3) d2 = d2 + t.ev[2] * t.ev[2];
     t.d2 = d2;
-    t.keep = (d2 < trim2) ? 1.f : 0.f;
+    if (trim_steep > 0.f) {
+        const float d = sqrtf(d2);
+        const float th = tanhf(trim_steep * (d - trim_dist));
+        t.d = d;
+        t.th = th;
+        t.keep = 0.5f - 0.5f * th;
+    } else {
+        t.d = 0.f;
+        t.th = 0.f;
+        t.keep = (d2 < trim2) ? 1.f : 0.f;
+    }
     if (TYPE == MMK_ICP_PT2PL) {
 #pragma unroll
         for (int c = 0; c < DIM; ++c) t.n[c] = trow[3 + c];
@@ -1115,7 +1128,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
     const unsigned long long *__restrict__ packed, unsigned long long *__restrict__ packed_next,
     const int32_t *__restrict__ allzero, const int32_t *__restrict__ zrep, int nn_pts, int nn_nsb,
     int32_t *__restrict__ idx_out, int N, int M, int loss, float k,
-    float k2, float trim2, double *__restrict__ partials, int32_t *__restrict__ status)
+    float k2, float trim2, float trim_dist, float trim_steep, double *__restrict__ partials, int32_t *__restrict__ status)
 {
     constexpr int P = PointTerms<DIM, TYPE>::P;
     constexpr int NR = PointTerms<DIM, TYPE>::NR;
@@ -1148,7 +1161,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
         const float omega = weight ? weight[(size_t)b * N + i] : 1.f;
         PointTerms<DIM, TYPE> t;
         point_terms<DIM, TYPE>(t, T, src + ((size_t)b * N + i) * 3, tgt + ((size_t)b * M + j) * tgt_cols, omega,
-                               loss, k, k2, trim2);
+                               loss, k, k2, trim2, trim_dist, trim_steep);
         int a = 0;
 #pragma unroll
         for (int m = 0; m < P; ++m) {
@@ -1513,7 +1526,8 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     const float *__restrict__ src, const float *__restrict__ tgt, int tgt_cols,
     const float *__restrict__ weight, const float *__restrict__ Tk, const int32_t *__restrict__ active,
     const int32_t *__restrict__ idx, const double *__restrict__ lam64, const double *__restrict__ delta64, int N,
-    int M, int loss, float k, float k2, float trim2, float *__restrict__ gw, double *__restrict__ pparts,
+    int M, int loss, float k, float k2, float trim2, float trim_dist, float trim_steep, float *__restrict__ gw,
+    double *__restrict__ pparts,
     float *__restrict__ gsrc, float *__restrict__ rows, unsigned *__restrict__ pmax)
 {
     constexpr int P = PointTerms<DIM, TYPE>::P;
@@ -1542,7 +1556,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
         const float omega = weight ? weight[(size_t)b * N + i] : 1.f;
         PointTerms<DIM, TYPE> t;
         point_terms<DIM, TYPE>(t, T, src + ((size_t)b * N + i) * 3, tgt + ((size_t)b * M + j) * tgt_cols, omega,
-                               loss, k, k2, trim2);
+                               loss, k, k2, trim2, trim_dist, trim_steep);
         float wbar = 0.f;
         float ebar[NR];
         float Jbar[NR][P];
@@ -1604,6 +1618,19 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
                 pbar[DIM - 1] += -ny * j3 + nx * j4;
             }
         }
+        // soft gate (I7'): keep = 0.5 - 0.5 tanh(steep (d - trim)), d = |ev|, ev = q - p; a coincident point (d == 0) gets 0
+        float gev[DIM];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) gev[c] = 0.f;
+        if (trim_steep > 0.f) {
+            const float keepbar = (wbar * t.omega) * t.rho;
+            const float dbar = keepbar * (-0.5f * trim_steep * (1.f - t.th * t.th));
+#pragma unroll
+            for (int c = 0; c < DIM; ++c) {
+                gev[c] = (t.d > 0.f) ? dbar * (t.ev[c] / t.d) : 0.f;
+                pbar[c] -= gev[c];
+            }
+        }
         // p = R s + t
 #pragma unroll
         for (int r = 0; r < DIM; ++r) {
@@ -1644,6 +1671,10 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
                         q[DIM + 1] += j5 * px - j3 * pz;
                         q[DIM + DIM - 1] += j3 * py - j4 * px;
                     }
+                }
+                if (trim_steep > 0.f) {     // the gate's path into the correspondent's xyz (the normals get nothing from it)
+#pragma unroll
+                    for (int c = 0; c < DIM; ++c) q[c] += gev[c];
                 }
                 float *row = rows + ((size_t)b * N + i) * C;
 #pragma unroll
@@ -1864,6 +1895,8 @@ int check_params(const mmk_icp_params *p)
     MMK_REQUIRE(p->max_iter >= 1, "mmk_icp: max_iter must be >= 1");
     MMK_REQUIRE(p->loss == MMK_LOSS_NONE || p->loss_k > 0.f, "mmk_icp: loss metric must be > 0");
     MMK_REQUIRE(p->nn_method == MMK_NN_BRUTE || p->nn_method == MMK_NN_GRID, "mmk_icp: bad nn_method %d", p->nn_method);
+    MMK_REQUIRE(std::isfinite(p->trim_steep) && p->trim_steep >= 0.f, "mmk_icp: trim_steep must be finite and >= 0 (got %g)",
+                (double)p->trim_steep);
     return MMK_OK;
 }
 
@@ -1946,6 +1979,7 @@ int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, con
     const NNPlan pl = nn_plan(B, N, M, DIM);
     const int nblk = (N + ACC_THREADS - 1) / ACC_THREADS;
     const float k = p->loss_k, k2 = p->loss_k * p->loss_k, trim2 = p->trim_dist * p->trim_dist;
+    const float trim_dist = p->trim_dist, trim_steep = p->trim_steep;
     int k_done = 0;
     // (keys, status word, zero-row representatives: icp_init_kernel in mmk_icp_forward)
     const bool use_grid = p->nn_method == MMK_NN_GRID;
@@ -1992,7 +2026,7 @@ int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, con
             if (rc != MMK_OK) return rc;
         }
         hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
-                           p->tgt_cols, weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, p->loss, k, k2, trim2,
+                           p->tgt_cols, weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, p->loss, k, k2, trim2, trim_dist, trim_steep,
                            w.partials, w.status);
         MMK_LAUNCH_CHECK();
         hipLaunchKernelGGL(icp_solve_kernel<DIM>, dim3(B), dim3(64), 0, st, w.partials, nblk, Tk,
@@ -2031,6 +2065,7 @@ int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, co
     const int B = p->B, N = p->N, M = p->M;
     const int nblk = (N + ACC_THREADS - 1) / ACC_THREADS;
     const float k = p->loss_k, k2 = p->loss_k * p->loss_k, trim2 = p->trim_dist * p->trim_dist;
+    const float trim_dist = p->trim_dist, trim_steep = p->trim_steep;
     constexpr int C = tgt_row_cols(DIM, TYPE), L = tgt_acc_cols(C);
     MMK_CHECK_HIP(hipMemsetAsync(gw, 0, sizeof(float) * (size_t)B * N, st));
     if (gsrc) MMK_CHECK_HIP(hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * N * 3, st));
@@ -2051,12 +2086,12 @@ int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, co
         if (gsrc || gtgt)
             hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, true>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
                                p->tgt_cols, weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam,
-                               delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, gw, w.partials, gsrc,
+                               delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, trim_dist, trim_steep, gw, w.partials, gsrc,
                                gtgt ? pw.rows + (size_t)it * B * N * C : static_cast<float *>(nullptr), pw.pmax);
         else
             hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, false>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
                                p->tgt_cols, weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam,
-                               delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, gw, w.partials,
+                               delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, trim_dist, trim_steep, gw, w.partials,
                                static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<unsigned *>(nullptr));
         MMK_LAUNCH_CHECK();
         nparts = nblk;
@@ -2331,7 +2366,7 @@ int run_accumulate(const mmk_icp_params *p, const float *src, const float *tgt, 
     hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE>), dim3(nblk, p->B), dim3(ACC_THREADS), 0, st, src, tgt, p->tgt_cols, weight,
                        T, static_cast<const int32_t *>(nullptr), keys, static_cast<unsigned long long *>(nullptr),
                        static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr), 1, 1, idx, p->N, p->M, p->loss,
-                       p->loss_k, p->loss_k * p->loss_k, p->trim_dist * p->trim_dist, partials, status);
+                       p->loss_k, p->loss_k * p->loss_k, p->trim_dist * p->trim_dist, p->trim_dist, p->trim_steep, partials, status);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

@@ -25,8 +25,11 @@ Differentiable (``differentiable=True``, grad enabled) in ``weight``, ``T_init``
 ``source`` and ``target`` (xyz and, for pt2pl, the normals): ``T`` requires grad
 when any of them does, and each one that does gets its gradient in its own dtype
 and on its own device.  As in autograd through the unrolled iterations, the
-correspondences, the trim gate, the freeze decisions and the non-positive-definite
-fallback are constants.  Entries outside the arithmetic get exactly 0: source z for
+correspondences, the hard trim gate, the freeze decisions and the non-positive-definite
+fallback are constants.  With ``parameters.trim: tanh`` in the YAML (or ``icp.trim = "tanh"``)
+the gate is ``0.5 - 0.5 tanh(tanh_steepness (d - trim_dist))`` and is differentiated in
+the points like every other factor of a point's weight; ``trim_dist`` and the steepness
+get no gradient.  Entries outside the arithmetic get exactly 0: source z for
 dim 2, target columns dim..2, the normals for pt2pt (columns >= 3 + dim for pt2pl)
 and targets that never were a correspondent.  The clouds' adjoints come from
 ``mmk_icp_backward_points``; without them the backward is ``mmk_icp_backward``.
@@ -206,8 +209,22 @@ class ICP:
         self.normals_k = int((cfg.get("parameters") or {}).get("normals_k", 16))
         if not 3 <= self.normals_k <= 32:
             raise ValueError("dICP config: normals_k must be in 3..32 (got %r)" % (self.normals_k,))
+        # the trim gate: "hard" keep = d2 < trim_dist^2 (a constant of the backward), "tanh" the soft gate
+        # keep = 0.5 - 0.5 tanh(tanh_steepness (d - trim_dist)), differentiated in the points (DESIGN.md §3 I3', I7')
+        self.trim = str((cfg.get("parameters") or {}).get("trim", "hard"))
+        self.tanh_steepness = float((cfg.get("parameters") or {}).get("tanh_steepness", 10.0))
+        self._trim_steep()
         self.last_state = None
         self.last_iterations = None
+
+    def _trim_steep(self):
+        """mmk_icp_params.trim_steep of the instance's gate (attributes are assignable: validated at every use)."""
+        if self.trim not in ("hard", "tanh"):
+            raise ValueError("dICP config: trim must be 'hard' or 'tanh' (got %r)" % (self.trim,))
+        steep = float(self.tanh_steepness)
+        if not (steep > 0.0 and steep != float("inf")):
+            raise ValueError("dICP config: tanh_steepness must be a finite number > 0 (got %r)" % (self.tanh_steepness,))
+        return steep if self.trim == "tanh" else 0.0
 
     def _params(self, B, N, M, tgt_cols, dim, loss_fn, trim_dist, save_state):
         name = None if loss_fn is None else loss_fn.get("name")
@@ -218,7 +235,7 @@ class ICP:
                               trim_dist=float(trim_dist), tolerance=self.tolerance, max_iter=self.max_iterations,
                               save_state=1 if save_state else 0,
                               check_every=0 if save_state else self.check_every,
-                              nn_method=_lib.NN_METHODS[self.nn_search])
+                              nn_method=_lib.NN_METHODS[self.nn_search], trim_steep=self._trim_steep())
 
     def icp(self, source, target, T_init=None, weight=None, trim_dist=5.0, loss_fn=None, dim=3):
         if source.ndim != 3 or source.shape[-1] != 3:

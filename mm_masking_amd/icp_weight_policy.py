@@ -92,6 +92,20 @@ class LearnICPWeightPolicy(nn.Module):
         self.icp_loss_fn = params.get("icp_loss_fn", {"name": "cauchy", "metric": 1.0})
         self.icp_trim_dist = params.get("icp_trim_dist", 5.0)
         self.icp_dim = params.get("icp_dim", 2)
+        # params["icp_trim"] / ["icp_tanh_steepness"] (absent upstream): the trim gate of the TRAINING instance, "hard" or the
+        # soft "tanh" gate that the backward differentiates (dICP/ICP.py); the inference instance keeps the hard gate
+        self.icp_trim = params.get("icp_trim", "hard")
+        if self.icp_trim not in ("hard", "tanh"):
+            raise ValueError("icp_trim must be 'hard' or 'tanh' (got %r)" % (self.icp_trim,))
+        steep = params.get("icp_tanh_steepness", 10.0)
+        if isinstance(steep, bool) or not isinstance(steep, (int, float)) or not (0.0 < float(steep) < float("inf")):
+            raise ValueError("icp_tanh_steepness must be a finite number > 0 (got %r)" % (steep,))
+        self.icp_tanh_steepness = float(steep)
+        if "icp_trim" in params:                    # (absent: whatever the dICP configuration says, "hard" by default)
+            self.ICP_alg.trim = self.icp_trim
+        if "icp_tanh_steepness" in params:
+            self.ICP_alg.tanh_steepness = self.icp_tanh_steepness
+        self.ICP_alg_inference.trim = "hard"
         # "hip" (the product path): hand-written NHWC bf16 kernels (csrc/mmk_unet.hip), fp32 masters;
         # "torch": the nn.Module tree evaluated by PyTorch on the CPU -- host-logic mirror for tests only
         self.unet_backend = params.get("unet_backend", "hip")
