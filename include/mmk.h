@@ -109,7 +109,7 @@ int mmk_icp_backward(const mmk_icp_params *p, const float *source, const float *
  * dL/dtarget, each optional (both NULL: bit-identical to mmk_icp_backward).  As in autograd through the unrolled
  * iterations, the correspondences, the hard trim gate, the freeze decisions and the non-positive-definite fallback are
  * constants; the soft gate (trim_steep > 0) is differentiated in the points (both entries: it moves dL/dT_init through the
- * poses, and dL/dsource, dL/dtarget xyz directly), while trim_dist and trim_steep themselves get no gradient.  Entries outside the arithmetic are exactly 0: source z for dim 2; target columns dim..2 and the normals for
+ * poses, and dL/dsource, dL/dtarget xyz directly), while trim_dist and trim_steep themselves get no gradient here (mmk_icp_backward_hp gives it).  Entries outside the arithmetic are exactly 0: source z for dim 2; target columns dim..2 and the normals for
  * pt2pt (normal columns >= 3 + dim for pt2pl); targets that were never a correspondent.  The target gradient is a scatter
  * of up to K*N rows per target, summed as 64-bit fixed point (no float atomics, bit-reproducible; resolution max|row
  * entry| * 2^(ceil(log2(K*N)) - 62)); a non-finite entry makes that pair's target gradient NaN.  workspace:
@@ -130,8 +130,45 @@ int mmk_icp_backward_points(const mmk_icp_params *p, const float *source, const 
  * error, never the result of the caller's data; the row was clamped to stay in bounds and the poses of that call are
  * not to be trusted.                                                                                                     */
 #define MMK_ICP_STATUS_UNARMED_KEY 1
+/* MMK_ICP_STATUS_BAD_HYPER (mmk_icp_forward_hp): a value of `hyper` the call used was non-finite or out of range -- k > 0
+ * under Cauchy / Huber, trim_dist >= 0, the steepness > 0 in soft mode; values the call does not use are not looked at.
+ * The caller's data, not an internal error: the arithmetic ran on (floats only, nothing leaves its bounds) and the poses
+ * are whatever it gave.                                                                                                   */
+#define MMK_ICP_STATUS_BAD_HYPER 2
 int mmk_icp_status(const mmk_icp_params *p, const void *workspace, size_t workspace_bytes,
                    int32_t *status_out, void *stream);
+
+/* mmk_icp_forward with the robust scale k, the trim distance and the gate's steepness read ON THE DEVICE (DESIGN.md §3
+ * I3''): hyper fp32 (1,3) (per_pair = 0, shared by the batch) or (B,3) (per_pair = 1), columns (k, trim_dist, trim_steep);
+ * loss_k and trim_dist of `p` are then ignored, and p->trim_steep only selects the gate (0 hard: column 2 is never read;
+ * > 0 soft: the steepness is column 2).  k*k and trim_dist*trim_dist are single fp32 products, so a call whose array holds
+ * the values of a scalar call is bit-identical to it.  Nothing is read back: values out of range raise
+ * MMK_ICP_STATUS_BAD_HYPER in the status word (mmk_icp_status).  hyper == NULL: mmk_icp_forward exactly.  Workspace:
+ * mmk_icp_workspace_bytes(p).  per_pair other than 0 / 1: MMK_ERR_ARG.                                                    */
+int mmk_icp_forward_hp(const mmk_icp_params *p, const float *source /*B,N,3*/,
+                       const float *target /*B,M,tgt_cols*/, const float *weight /*B,N*/,
+                       const float *T_init /*B,16*/, float *T_out /*B,16*/,
+                       int32_t *idx_hist, float *T_hist, double *delta_hist, double *A_hist,
+                       int32_t *active_hist, const float *hyper /*1|B,3*/, int32_t per_pair,
+                       void *workspace, size_t workspace_bytes, int *iters_run, void *stream);
+
+/* The reverse sweep of a mmk_icp_forward_hp call: mmk_icp_backward_points' arguments (grad_source and grad_target each
+ * optional, so the entry serves both backward shapes) plus the forward's `hyper` / per_pair and grad_hyper (B,3 -- one
+ * row per pair also when hyper is shared: the caller adds the rows -- or NULL) = dL/d(k, trim_dist, trim_steep), DESIGN.md
+ * §3 I7'': per point and active iteration in fp32, summed per pair in fp64 by block partials in a fixed order (no float
+ * atomics: bit-reproducible).  Exactly 0: trim_dist and trim_steep under the hard gate, k without a robust loss, and
+ * whatever a pair's frozen iterations would add.  hyper == NULL (grad_hyper must be NULL too): mmk_icp_backward_points
+ * exactly.  workspace: mmk_icp_backward_hp_workspace_bytes(p, grad_target != NULL, hyper != NULL) bytes -- the older
+ * entries' sizes are unchanged.  Argument errors return MMK_ERR_ARG.                                                      */
+size_t mmk_icp_backward_hp_workspace_bytes(const mmk_icp_params *p, int32_t with_target, int32_t with_hyper);
+int mmk_icp_backward_hp(const mmk_icp_params *p, const float *source, const float *target,
+                        const float *weight, const int32_t *idx_hist, const float *T_hist,
+                        const double *delta_hist, const double *A_hist,
+                        const int32_t *active_hist, const float *grad_T /*B,16*/,
+                        float *grad_weight /*B,N*/, float *grad_T_init /*B,16 or NULL*/,
+                        float *grad_source /*B,N,3 or NULL*/, float *grad_target /*B,M,tgt_cols or NULL*/,
+                        const float *hyper /*1|B,3*/, int32_t per_pair, float *grad_hyper /*B,3 or NULL*/,
+                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* The stages of one iteration on their own (SURVEY.md 8b names them; mmk_icp_forward is these in a loop behind the NN search).
  * mmk_icp_accumulate (stages I3 + I4): consumes nearest-neighbour keys ((bits of d2) << 32 | index, (B,N) uint64 -- the

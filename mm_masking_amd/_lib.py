@@ -136,6 +136,9 @@ def _declare(lib):
         "mmk_icp_backward_points_workspace_bytes": (sz, [P, i32]),
         "mmk_icp_backward_points": (ctypes.c_int, [P] + [c_vp] * 13 + [c_vp, sz, c_vp]),
         "mmk_icp_status": (ctypes.c_int, [P, c_vp, sz, c_vp, c_vp]),
+        "mmk_icp_forward_hp": (ctypes.c_int, [P] + [c_vp] * 10 + [c_vp, i32, c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
+        "mmk_icp_backward_hp_workspace_bytes": (sz, [P, i32, i32]),
+        "mmk_icp_backward_hp": (ctypes.c_int, [P] + [c_vp] * 13 + [c_vp, i32, c_vp, c_vp, sz, c_vp]),
         "mmk_pose_loss_fwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp]),
         "mmk_pose_loss_bwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, c_vp]),
         "mmk_bce_ws_bytes": (sz, []),

@@ -1120,21 +1120,61 @@ __device__ __forceinline__ void point_terms(PointTerms<DIM, TYPE> &t, const floa
     t.w = (omega * t.keep) * rho;
 }
 
+// I3'': the pair's robust scale, trim distance and steepness from the device array `hyper` (rows of (k, trim_dist,
+// trim_steep), row stride `hstride` = 0 shared | 3 per pair).  b is blockIdx.y, so the loads are uniform over the block.
+// k2 and trim2 are the single fp32 products the host forms for the scalar launches.  The gate's MODE stays the launch
+// constant (trim_steep 0 | > 0); in hard mode column 2 is never read.
+struct HyperVals {
+    float k, k2, trim2, trim_dist, trim_steep;
+};
+
+__device__ __forceinline__ HyperVals load_hyper(const float *__restrict__ hyper, int hstride, int b, float trim_steep_mode)
+{
+    const float *h = hyper + (size_t)b * hstride;
+    HyperVals v;
+    v.k = h[0];
+    v.k2 = v.k * v.k;
+    v.trim_dist = h[1];
+    v.trim2 = v.trim_dist * v.trim_dist;
+    v.trim_steep = trim_steep_mode > 0.f ? h[2] : 0.f;
+    return v;
+}
+
+// A value of `hyper` the launch will use that is non-finite or out of range (k > 0 under a robust loss, trim_dist >= 0,
+// steepness > 0 in soft mode): MMK_ICP_STATUS_BAD_HYPER.  (NaN fails every comparison.)
+__device__ __forceinline__ bool hyper_is_bad(const HyperVals &v, int loss, bool soft)
+{
+    const float big = 3.4028234663852886e38f;
+    bool ok = v.trim_dist >= 0.f && v.trim_dist <= big;
+    if (loss != MMK_LOSS_NONE) ok = ok && v.k > 0.f && v.k <= big;
+    if (soft) ok = ok && v.trim_steep > 0.f && v.trim_steep <= big;
+    return !ok;
+}
+
 // Accumulate A (upper triangle, row-major) and b for one pair; one point per thread.
-template <int DIM, int TYPE>
+// HP: k, trim_dist and the steepness come from `hyper` (I3'') instead of the launch's scalars; `hcheck` != 0 (the first
+// iteration of a call) has one thread per pair validate them.
+template <int DIM, int TYPE, bool HP = false>
 __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
     const float *__restrict__ src, const float *__restrict__ tgt, int tgt_cols,
     const float *__restrict__ weight, const float *__restrict__ Tk, const int32_t *__restrict__ active,
     const unsigned long long *__restrict__ packed, unsigned long long *__restrict__ packed_next,
     const int32_t *__restrict__ allzero, const int32_t *__restrict__ zrep, int nn_pts, int nn_nsb,
     int32_t *__restrict__ idx_out, int N, int M, int loss, float k,
-    float k2, float trim2, float trim_dist, float trim_steep, double *__restrict__ partials, int32_t *__restrict__ status)
+    float k2, float trim2, float trim_dist, float trim_steep, double *__restrict__ partials, int32_t *__restrict__ status,
+    const float *__restrict__ hyper, int hstride, int hcheck)
 {
     constexpr int P = PointTerms<DIM, TYPE>::P;
     constexpr int NR = PointTerms<DIM, TYPE>::NR;
     constexpr int NACC = nacc(DIM);
     const int b = blockIdx.y;
     if (active != nullptr && active[b] == 0) return;
+    if constexpr (HP) {
+        const HyperVals hv = load_hyper(hyper, hstride, b, trim_steep);
+        if (hcheck != 0 && blockIdx.x == 0 && threadIdx.x == 0 && status != nullptr && hyper_is_bad(hv, loss, trim_steep > 0.f))
+            atomicOr(status, (int32_t)MMK_ICP_STATUS_BAD_HYPER);
+        k = hv.k, k2 = hv.k2, trim2 = hv.trim2, trim_dist = hv.trim_dist, trim_steep = hv.trim_steep;
+    }
     const int i = blockIdx.x * ACC_THREADS + threadIdx.x;
     double acc[NACC];
 #pragma unroll
@@ -1521,24 +1561,33 @@ __host__ __device__ constexpr int tgt_acc_cols(int c) { return c <= 2 ? 2 : (c <
 // thread owns its point, iterations are ordered launches), and the point's contribution to its correspondent's target
 // gradient as a row of `rows` ((B,N,tgt_row_cols), may be NULL), with the pair's largest |entry| as float bits in pmax (B)
 // by an INTEGER max (order independent): icp_bwd_target_scatter_kernel adds the rows up after the sweep.
-template <int DIM, int TYPE, bool PTS>
+// HP (mmk_icp_backward_hp, I7''): k, trim_dist and the steepness come from `hyper` as in the forward, and the block's fp64
+// sums of the per-point adjoints (k̄, c̄, s̄) go to `hparts` (nblk,B rows of 3 for this iteration) by the reduction of the pose
+// parts: wave shuffle -> LDS -> one partial per block, no atomics.  A frozen pair's blocks write exact zeros.
+template <int DIM, int TYPE, bool PTS, bool HP = false>
 __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     const float *__restrict__ src, const float *__restrict__ tgt, int tgt_cols,
     const float *__restrict__ weight, const float *__restrict__ Tk, const int32_t *__restrict__ active,
     const int32_t *__restrict__ idx, const double *__restrict__ lam64, const double *__restrict__ delta64, int N,
     int M, int loss, float k, float k2, float trim2, float trim_dist, float trim_steep, float *__restrict__ gw,
     double *__restrict__ pparts,
-    float *__restrict__ gsrc, float *__restrict__ rows, unsigned *__restrict__ pmax)
+    float *__restrict__ gsrc, float *__restrict__ rows, unsigned *__restrict__ pmax,
+    const float *__restrict__ hyper, int hstride, double *__restrict__ hparts)
 {
     constexpr int P = PointTerms<DIM, TYPE>::P;
     constexpr int NR = PointTerms<DIM, TYPE>::NR;
     constexpr int NP = npose(DIM);
+    constexpr int NH = HP ? 3 : 0;
     constexpr int C = tgt_row_cols(DIM, TYPE);
     const int b = blockIdx.y;
     const int i = blockIdx.x * ACC_THREADS + threadIdx.x;
-    double acc[NP];
+    double acc[NP + NH];
 #pragma unroll
-    for (int a = 0; a < NP; ++a) acc[a] = 0.0;
+    for (int a = 0; a < NP + NH; ++a) acc[a] = 0.0;
+    if constexpr (HP) {
+        const HyperVals hv = load_hyper(hyper, hstride, b, trim_steep);
+        k = hv.k, k2 = hv.k2, trim2 = hv.trim2, trim_dist = hv.trim_dist, trim_steep = hv.trim_steep;
+    }
     const bool act = active[b] != 0;
     unsigned mbits = 0u;
 
@@ -1586,6 +1635,16 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
 #pragma unroll
         for (int r = 0; r < NR; ++r) ebar[r] += 2.f * t.er[r] * r2bar;
         gw[(size_t)b * N + i] += gomega;
+        if constexpr (HP) {             // k̄ (I7''): rho = 1 / (1 + r2 / k2) | k / r past the knee
+            float kbar = 0.f;
+            if (loss == MMK_LOSS_CAUCHY) {
+                kbar = rhobar * ((2.f * t.r2 * (t.rho * t.rho)) / (k * k2));
+            } else if (loss == MMK_LOSS_HUBER) {
+                const float r = sqrtf(t.r2);
+                if (r > k) kbar = rhobar / r;
+            }
+            acc[NP + 0] = (double)kbar;
+        }
 
         float pbar[DIM];
 #pragma unroll
@@ -1629,6 +1688,11 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
             for (int c = 0; c < DIM; ++c) {
                 gev[c] = (t.d > 0.f) ? dbar * (t.ev[c] / t.d) : 0.f;
                 pbar[c] -= gev[c];
+            }
+            if constexpr (HP) {         // c̄, s̄ (I7''): the hard gate is a constant and leaves both at exactly 0
+                const float g = 0.5f * (1.f - t.th * t.th);
+                acc[NP + 1] = (double)(keepbar * (trim_steep * g));
+                acc[NP + 2] = (double)(keepbar * (-g * (t.d - trim_dist)));
             }
         }
         // p = R s + t
@@ -1686,7 +1750,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
         }
     }
 
-    __shared__ double red[ACC_THREADS / 64][NP];
+    __shared__ double red[ACC_THREADS / 64][NP + NH];
     __shared__ unsigned wmax[ACC_THREADS / 64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if constexpr (PTS) {
@@ -1695,7 +1759,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
         if (lane == 0) wmax[wv] = mbits;
     }
 #pragma unroll
-    for (int a = 0; a < NP; ++a) {
+    for (int a = 0; a < NP + NH; ++a) {
         double v = wave_sum(acc[a]);
         if (lane == 0) red[wv][a] = v;
     }
@@ -1713,6 +1777,36 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
 #pragma unroll
         for (int w = 0; w < ACC_THREADS / 64; ++w) v += red[w][threadIdx.x];
         pparts[((size_t)b * gridDim.x + blockIdx.x) * NP + threadIdx.x] = v;
+    }
+    if constexpr (HP) {
+        if (threadIdx.x >= 64 && threadIdx.x < 64 + NH) {       // (a wave of its own: wave 0 writes the pose parts)
+            const int c = threadIdx.x - 64;
+            double v = 0.0;
+#pragma unroll
+            for (int w = 0; w < ACC_THREADS / 64; ++w) v += red[w][NP + c];
+            hparts[((size_t)b * gridDim.x + blockIdx.x) * 3 + c] = v;
+        }
+    }
+}
+
+// grad_hyper (B,3) = the ordered sum of a pair's block partials over the iterations and blocks: `hparts` is (K,B,nblk,3).
+// One wave per pair: lane l adds the rows l, l + 64, ... in index order, then the lanes are added by the fixed shuffle tree
+// -- the same order in every run.
+__global__ __launch_bounds__(64) void icp_bwd_hyper_final_kernel(const double *__restrict__ hparts, int K, int B, int nblk,
+                                                                 float *__restrict__ grad_hyper)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int e = lane; e < K * nblk; e += 64) {
+        const int it = e / nblk, blk = e % nblk;
+        const double *row = hparts + (((size_t)it * B + b) * nblk + blk) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] += row[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double s = wave_sum(v[c]);
+        if (lane == 0) grad_hyper[(size_t)b * 3 + c] = (float)s;
     }
 }
 
@@ -1970,10 +2064,30 @@ IcpPtsWs carve_points(const mmk_icp_params *p, bool with_target, void *ws, size_
     return w;
 }
 
+// The hyper-parameter array of the _hp entries (I3'', I7'') and the scratch of its gradient: a workspace of its own BEHIND
+// mmk_icp_backward_points' (carve_points above), so that the older entries' layouts and sizes stay what they are.
+struct IcpHyper {
+    const float *hyper = nullptr;   // (1 | B, 3): k, trim_dist, trim_steep; NULL: the scalars of mmk_icp_params
+    int hstride = 0;                // 0 shared | 3 per pair
+    double *hparts = nullptr;       // (K,B,nblk,3): block partials of (k̄, c̄, s̄), every entry written by the sweep
+    float *grad_hyper = nullptr;    // (B,3) or NULL
+    size_t bytes = 0;               // whole workspace of mmk_icp_backward_hp
+};
+
+IcpHyper carve_hyper(const mmk_icp_params *p, bool with_target, bool with_hyper, void *ws, size_t cap)
+{
+    mmk::Arena ar(ws, cap);
+    ar.off = carve_points(p, with_target, nullptr, 0).bytes;
+    IcpHyper h;
+    if (with_hyper) h.hparts = ar.take<double>((size_t)p->max_iter * p->B * ((p->N + ACC_THREADS - 1) / ACC_THREADS) * 3);
+    h.bytes = mmk::align_up(ar.off, 256);
+    return h;
+}
+
 template <int DIM, int TYPE>
 int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight, float *T_hist,
                 int32_t *idx_hist, double *delta_hist, double *A_hist, int32_t *active_hist, const IcpWs &w,
-                int *iters_run, hipStream_t st)
+                int *iters_run, hipStream_t st, const float *hyper = nullptr, int hstride = 0)
 {
     const int B = p->B, N = p->N, M = p->M;
     const NNPlan pl = nn_plan(B, N, M, DIM);
@@ -2025,9 +2139,14 @@ int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, con
             int rc = launch_nn(DIM, src, w.tgtp, Tk, act, prev, dedup ? w.ulist : nullptr, w.ucnt, B, N, pl, keys, w.seed0, az, zr, w.tdec, st);
             if (rc != MMK_OK) return rc;
         }
-        hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
-                           p->tgt_cols, weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, p->loss, k, k2, trim2, trim_dist, trim_steep,
-                           w.partials, w.status);
+        if (hyper != nullptr)
+            hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE, true>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
+                               p->tgt_cols, weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, p->loss, k, k2, trim2, trim_dist,
+                               trim_steep, w.partials, w.status, hyper, hstride, it == 0 ? 1 : 0);
+        else
+            hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
+                               p->tgt_cols, weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, p->loss, k, k2, trim2, trim_dist,
+                               trim_steep, w.partials, w.status, static_cast<const float *>(nullptr), 0, 0);
         MMK_LAUNCH_CHECK();
         hipLaunchKernelGGL(icp_solve_kernel<DIM>, dim3(B), dim3(64), 0, st, w.partials, nblk, Tk,
                            T_hist + (size_t)(it + 1) * B * 16, delta_hist + (size_t)it * B * 6,
@@ -2060,7 +2179,7 @@ template <int DIM, int TYPE>
 int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight,
                  const int32_t *idx_hist, const float *T_hist, const double *delta_hist, const double *A_hist,
                  const int32_t *active_hist, const float *grad_T, float *gw, float *grad_T_init, float *gsrc, float *gtgt,
-                 const IcpWs &w, const IcpPtsWs &pw, hipStream_t st)
+                 const IcpWs &w, const IcpPtsWs &pw, hipStream_t st, const IcpHyper &hy)
 {
     const int B = p->B, N = p->N, M = p->M;
     const int nblk = (N + ACC_THREADS - 1) / ACC_THREADS;
@@ -2083,22 +2202,35 @@ int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, co
         hipLaunchKernelGGL(icp_bwd_pair_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, Tk,
                            delta_hist + (size_t)it * B * 6, A_hist + (size_t)it * B * 36, act, Gout, w.lam);
         MMK_LAUNCH_CHECK();
-        if (gsrc || gtgt)
-            hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, true>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
-                               p->tgt_cols, weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam,
-                               delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, trim_dist, trim_steep, gw, w.partials, gsrc,
-                               gtgt ? pw.rows + (size_t)it * B * N * C : static_cast<float *>(nullptr), pw.pmax);
+        const float *const nohyper = nullptr;
+        double *const noparts = nullptr;
+        double *hp = hy.hparts ? hy.hparts + (size_t)it * B * nblk * 3 : noparts;
+#define MMK_BWD_POINT(PTS_, HP_, GSRC, ROWS, PMAX, HYPER, HPARTS)                                                                      \
+    hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, PTS_, HP_>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt, p->tgt_cols,  \
+                       weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam, delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2,   \
+                       trim2, trim_dist, trim_steep, gw, w.partials, GSRC, ROWS, PMAX, HYPER, hy.hstride, HPARTS)
+        float *const rows = gtgt ? pw.rows + (size_t)it * B * N * C : static_cast<float *>(nullptr);
+        if (hy.hparts != nullptr && (gsrc || gtgt))
+            MMK_BWD_POINT(true, true, gsrc, rows, pw.pmax, hy.hyper, hp);
+        else if (hy.hparts != nullptr)
+            MMK_BWD_POINT(false, true, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<unsigned *>(nullptr),
+                          hy.hyper, hp);
+        else if (gsrc || gtgt)
+            MMK_BWD_POINT(true, false, gsrc, rows, pw.pmax, nohyper, noparts);
         else
-            hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, false>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
-                               p->tgt_cols, weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam,
-                               delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2, trim2, trim_dist, trim_steep, gw, w.partials,
-                               static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<unsigned *>(nullptr));
+            MMK_BWD_POINT(false, false, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<unsigned *>(nullptr),
+                          nohyper, noparts);
+#undef MMK_BWD_POINT
         MMK_LAUNCH_CHECK();
         nparts = nblk;
         double *t = Gin; Gin = Gout; Gout = t;
     }
     if (grad_T_init) {
         hipLaunchKernelGGL(bwd_final_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, grad_T_init);
+        MMK_LAUNCH_CHECK();
+    }
+    if (hy.grad_hyper) {
+        hipLaunchKernelGGL(icp_bwd_hyper_final_kernel, dim3(B), dim3(64), 0, st, hy.hparts, p->max_iter, B, nblk, hy.grad_hyper);
         MMK_LAUNCH_CHECK();
     }
     if (gtgt) {
@@ -2119,19 +2251,20 @@ int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, co
 int dispatch_backward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight,
                       const int32_t *idx_hist, const float *T_hist, const double *delta_hist, const double *A_hist,
                       const int32_t *active_hist, const float *grad_T, float *gw, float *grad_T_init, float *gsrc,
-                      float *gtgt, const IcpWs &w, const IcpPtsWs &pw, hipStream_t st)
+                      float *gtgt, const IcpWs &w, const IcpPtsWs &pw, hipStream_t st,
+                      const IcpHyper &hy = IcpHyper())
 {
     if (p->dim == 2 && p->icp_type == MMK_ICP_PT2PT)
         return run_backward<2, MMK_ICP_PT2PT>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
-                                              grad_T_init, gsrc, gtgt, w, pw, st);
+                                              grad_T_init, gsrc, gtgt, w, pw, st, hy);
     if (p->dim == 2)
         return run_backward<2, MMK_ICP_PT2PL>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
-                                              grad_T_init, gsrc, gtgt, w, pw, st);
+                                              grad_T_init, gsrc, gtgt, w, pw, st, hy);
     if (p->icp_type == MMK_ICP_PT2PT)
         return run_backward<3, MMK_ICP_PT2PT>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
-                                              grad_T_init, gsrc, gtgt, w, pw, st);
+                                              grad_T_init, gsrc, gtgt, w, pw, st, hy);
     return run_backward<3, MMK_ICP_PT2PL>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
-                                          grad_T_init, gsrc, gtgt, w, pw, st);
+                                          grad_T_init, gsrc, gtgt, w, pw, st, hy);
 }
 
 }  // namespace
@@ -2293,18 +2426,20 @@ extern "C" size_t mmk_icp_workspace_bytes(const mmk_icp_params *p)
     return carve(p, nullptr, 0).bytes;
 }
 
-extern "C" int mmk_icp_forward(const mmk_icp_params *p, const float *source, const float *target,
-                               const float *weight, const float *T_init, float *T_out, int32_t *idx_hist,
-                               float *T_hist, double *delta_hist, double *A_hist, int32_t *active_hist,
-                               void *workspace, size_t workspace_bytes, int *iters_run, void *stream)
+namespace {
+// mmk_icp_forward (hyper NULL) and mmk_icp_forward_hp
+int forward_impl(const char *who, const mmk_icp_params *p, const float *source, const float *target, const float *weight,
+                 const float *T_init, float *T_out, int32_t *idx_hist, float *T_hist, double *delta_hist, double *A_hist,
+                 int32_t *active_hist, const float *hyper, int hstride, void *workspace, size_t workspace_bytes, int *iters_run,
+                 void *stream)
 {
     int rc = check_params(p);
     if (rc != MMK_OK) return rc;
     MMK_REQUIRE(source && target && T_init && T_out && idx_hist && T_hist && delta_hist && A_hist && active_hist,
-                "mmk_icp_forward: NULL pointer");
+                "%s: NULL pointer", who);
     const IcpWs w = carve(p, workspace, workspace_bytes);
     if (workspace == nullptr || w.bytes > workspace_bytes) {
-        mmk::set_error("mmk_icp_forward: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
+        mmk::set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, w.bytes);
         return MMK_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -2323,17 +2458,42 @@ extern "C" int mmk_icp_forward(const mmk_icp_params *p, const float *source, con
         MMK_LAUNCH_CHECK();
     }
     if (p->dim == 2 && p->icp_type == MMK_ICP_PT2PT)
-        rc = run_forward<2, MMK_ICP_PT2PT>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st);
+        rc = run_forward<2, MMK_ICP_PT2PT>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st, hyper,
+                                           hstride);
     else if (p->dim == 2)
-        rc = run_forward<2, MMK_ICP_PT2PL>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st);
+        rc = run_forward<2, MMK_ICP_PT2PL>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st, hyper,
+                                           hstride);
     else if (p->icp_type == MMK_ICP_PT2PT)
-        rc = run_forward<3, MMK_ICP_PT2PT>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st);
+        rc = run_forward<3, MMK_ICP_PT2PT>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st, hyper,
+                                           hstride);
     else
-        rc = run_forward<3, MMK_ICP_PT2PL>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st);
+        rc = run_forward<3, MMK_ICP_PT2PL>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st, hyper,
+                                           hstride);
     if (rc != MMK_OK) return rc;
     MMK_CHECK_HIP(hipMemcpyAsync(T_out, T_hist + (size_t)p->max_iter * B * 16, sizeof(float) * B * 16,
                                  hipMemcpyDeviceToDevice, st));
     return MMK_OK;
+}
+}  // namespace
+
+extern "C" int mmk_icp_forward(const mmk_icp_params *p, const float *source, const float *target,
+                               const float *weight, const float *T_init, float *T_out, int32_t *idx_hist,
+                               float *T_hist, double *delta_hist, double *A_hist, int32_t *active_hist,
+                               void *workspace, size_t workspace_bytes, int *iters_run, void *stream)
+{
+    return forward_impl("mmk_icp_forward", p, source, target, weight, T_init, T_out, idx_hist, T_hist, delta_hist, A_hist, active_hist,
+                        nullptr, 0, workspace, workspace_bytes, iters_run, stream);
+}
+
+extern "C" int mmk_icp_forward_hp(const mmk_icp_params *p, const float *source, const float *target,
+                                  const float *weight, const float *T_init, float *T_out, int32_t *idx_hist,
+                                  float *T_hist, double *delta_hist, double *A_hist, int32_t *active_hist,
+                                  const float *hyper, int32_t per_pair, void *workspace, size_t workspace_bytes,
+                                  int *iters_run, void *stream)
+{
+    MMK_REQUIRE(per_pair == 0 || per_pair == 1, "mmk_icp_forward_hp: per_pair must be 0 or 1 (got %d)", per_pair);
+    return forward_impl("mmk_icp_forward_hp", p, source, target, weight, T_init, T_out, idx_hist, T_hist, delta_hist, A_hist,
+                        active_hist, hyper, per_pair ? 3 : 0, workspace, workspace_bytes, iters_run, stream);
 }
 
 extern "C" int mmk_icp_status(const mmk_icp_params *p, const void *workspace, size_t workspace_bytes, int32_t *status_out,
@@ -2366,7 +2526,8 @@ int run_accumulate(const mmk_icp_params *p, const float *src, const float *tgt, 
     hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE>), dim3(nblk, p->B), dim3(ACC_THREADS), 0, st, src, tgt, p->tgt_cols, weight,
                        T, static_cast<const int32_t *>(nullptr), keys, static_cast<unsigned long long *>(nullptr),
                        static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr), 1, 1, idx, p->N, p->M, p->loss,
-                       p->loss_k, p->loss_k * p->loss_k, p->trim_dist * p->trim_dist, p->trim_dist, p->trim_steep, partials, status);
+                       p->loss_k, p->loss_k * p->loss_k, p->trim_dist * p->trim_dist, p->trim_dist, p->trim_steep, partials, status,
+                       static_cast<const float *>(nullptr), 0, 0);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -2453,4 +2614,38 @@ extern "C" int mmk_icp_backward_points(const mmk_icp_params *p, const float *sou
     const IcpWs w = carve(p, workspace, workspace_bytes);
     return dispatch_backward(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight,
                              grad_T_init, grad_source, grad_target, w, pw, (hipStream_t)stream);
+}
+
+extern "C" size_t mmk_icp_backward_hp_workspace_bytes(const mmk_icp_params *p, int32_t with_target, int32_t with_hyper)
+{
+    if (check_params(p) != MMK_OK) return 0;
+    return carve_hyper(p, with_target != 0, with_hyper != 0, nullptr, 0).bytes;
+}
+
+extern "C" int mmk_icp_backward_hp(const mmk_icp_params *p, const float *source, const float *target,
+                                   const float *weight, const int32_t *idx_hist, const float *T_hist,
+                                   const double *delta_hist, const double *A_hist, const int32_t *active_hist,
+                                   const float *grad_T, float *grad_weight, float *grad_T_init, float *grad_source,
+                                   float *grad_target, const float *hyper, int32_t per_pair, float *grad_hyper,
+                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_params(p);
+    if (rc != MMK_OK) return rc;
+    MMK_REQUIRE(p->save_state, "mmk_icp_backward_hp: forward must have run with save_state = 1");
+    MMK_REQUIRE(source && target && idx_hist && T_hist && delta_hist && A_hist && active_hist && grad_T && grad_weight,
+                "mmk_icp_backward_hp: NULL pointer");
+    MMK_REQUIRE(per_pair == 0 || per_pair == 1, "mmk_icp_backward_hp: per_pair must be 0 or 1 (got %d)", per_pair);
+    MMK_REQUIRE(grad_hyper == nullptr || hyper != nullptr, "mmk_icp_backward_hp: grad_hyper needs hyper");
+    MMK_REQUIRE(grad_target == nullptr || p->max_iter <= 65535,
+                "mmk_icp_backward_hp: the target gradient needs max_iter <= 65535 (got %d)", p->max_iter);
+    IcpHyper hy = carve_hyper(p, grad_target != nullptr, hyper != nullptr, workspace, workspace_bytes);
+    MMK_REQUIRE(workspace != nullptr && hy.bytes <= workspace_bytes, "mmk_icp_backward_hp: workspace too small (%zu < %zu bytes)",
+                workspace_bytes, hy.bytes);
+    hy.hyper = hyper;
+    hy.hstride = per_pair ? 3 : 0;
+    hy.grad_hyper = grad_hyper;
+    const IcpPtsWs pw = carve_points(p, grad_target != nullptr, workspace, workspace_bytes);
+    const IcpWs w = carve(p, workspace, workspace_bytes);
+    return dispatch_backward(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight,
+                             grad_T_init, grad_source, grad_target, w, pw, (hipStream_t)stream, hy);
 }

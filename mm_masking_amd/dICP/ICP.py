@@ -28,11 +28,23 @@ and on its own device.  As in autograd through the unrolled iterations, the
 correspondences, the hard trim gate, the freeze decisions and the non-positive-definite
 fallback are constants.  With ``parameters.trim: tanh`` in the YAML (or ``icp.trim = "tanh"``)
 the gate is ``0.5 - 0.5 tanh(tanh_steepness (d - trim_dist))`` and is differentiated in
-the points like every other factor of a point's weight; ``trim_dist`` and the steepness
-get no gradient.  Entries outside the arithmetic get exactly 0: source z for
+the points like every other factor of a point's weight.  Entries outside the arithmetic get exactly 0: source z for
 dim 2, target columns dim..2, the normals for pt2pt (columns >= 3 + dim for pt2pl)
 and targets that never were a correspondent.  The clouds' adjoints come from
 ``mmk_icp_backward_points``; without them the backward is ``mmk_icp_backward``.
+
+The robust scale ``loss_fn["metric"]``, ``trim_dist`` and the instance's ``tanh_steepness`` may each be a number or a
+tensor of shape ``()``, ``(1,)`` (one value for the batch) or ``(B,)`` (one per pair); any other shape is a ValueError
+before the device is touched.  With numbers only, the call is the one it always was.  With a tensor among them the call
+goes through ``mmk_icp_forward_hp`` / ``mmk_icp_backward_hp`` (DESIGN.md §3 I3'', I7''): the three values are put into one
+device array (numbers are broadcast there), nothing is read back, and a call whose tensors hold the values of a number call
+is bit-identical to it.  Each tensor that requires grad gets its gradient in its own shape, dtype and device -- a shared
+value the sum over the pairs -- and ``T`` requires grad when one of them does.  The hard gate gives ``trim_dist`` and the
+steepness exactly 0, no robust loss gives the metric exactly 0.  A tensor cannot be validated on the host without a
+synchronisation: the kernels raise ``MMK_ICP_STATUS_BAD_HYPER`` for a value the call uses that is non-finite or out of
+range (metric > 0 under Cauchy / Huber, trim_dist >= 0, steepness > 0 under the tanh gate), and the next ICP call, or
+``check_errors()``, turns it into an MmkError.  Nothing here keeps a learned value in range, and ``tolerance`` and
+``target_pad_val`` get no gradient.
 """
 import ctypes
 import os
@@ -71,6 +83,7 @@ def _state_buffers(p, device):
 
 
 ICP_STATUS_UNARMED_KEY = 1          # include/mmk.h: MMK_ICP_STATUS_UNARMED_KEY
+ICP_STATUS_BAD_HYPER = 2            # include/mmk.h: MMK_ICP_STATUS_BAD_HYPER
 
 
 class _StatusWatch:
@@ -108,6 +121,11 @@ class _StatusWatch:
         if bad & ICP_STATUS_UNARMED_KEY:
             raise _lib.MmkError("dICP: a source row reached the accumulation stage with a nearest-neighbour key that no search "
                                 "kernel wrote (MMK_ICP_STATUS_UNARMED_KEY) -- internal error, the poses of that call are invalid")
+        if bad & ICP_STATUS_BAD_HYPER:
+            raise _lib.MmkError("dICP: a device-resident hyper-parameter of an ICP call (loss_fn['metric'], trim_dist or "
+                                "tanh_steepness given as a tensor) was non-finite or out of range: the metric must be > 0, "
+                                "trim_dist >= 0, the steepness > 0 (MMK_ICP_STATUS_BAD_HYPER); the poses of that call are what "
+                                "the arithmetic gave with it")
         if bad:
             raise _lib.MmkError("dICP: the ICP kernels raised status bits 0x%x" % bad)
 
@@ -120,7 +138,38 @@ def check_errors(wait=True):
     _status.check(wait=wait)
 
 
-def _forward(p, src, tgt, weight, T_init):
+HYPER_NAMES = ("loss_fn['metric']", "trim_dist", "tanh_steepness")      # the columns of the device array `hyper`
+
+
+def _hyper_sizes(values, B):
+    """Validate the three values (number, or tensor of shape (), (1,) or (B,)) without touching the device.  Returns None
+    when all are numbers, else whether the device array takes one row per pair."""
+    per_pair, any_tensor = False, False
+    for name, v in zip(HYPER_NAMES, values):
+        if isinstance(v, torch.Tensor):
+            any_tensor = True
+            if tuple(v.shape) not in ((), (1,), (B,)):
+                raise ValueError("%s must be a number or a tensor of shape (), (1,) or (B,) = (%d,) (got shape %s)"
+                                 % (name, B, tuple(v.shape)))
+            if not (v.is_floating_point()):
+                raise ValueError("%s: a tensor must have a floating-point dtype (got %s)" % (name, v.dtype))
+            per_pair = per_pair or (v.ndim == 1 and v.shape[0] == B and B > 1)
+    return per_pair if any_tensor else None
+
+
+def _hyper_array(values, per_pair, B, dev):
+    """(1 | B, 3) fp32 on the device: tensors moved / cast, numbers broadcast there; nothing is read back."""
+    n = B if per_pair else 1
+    cols = []
+    for v in values:
+        if isinstance(v, torch.Tensor):
+            cols.append(v.detach().to(device=dev, dtype=torch.float32).reshape(-1).expand(n))
+        else:
+            cols.append(torch.full((n,), float(v), dtype=torch.float32, device=dev))
+    return torch.stack(cols, dim=1).contiguous()
+
+
+def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False):
     L = _lib.lib()
     dev = src.device
     _status.check()
@@ -128,6 +177,15 @@ def _forward(p, src, tgt, weight, T_init):
     st = _state_buffers(p, dev)
     T_out = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
     iters = ctypes.c_int(0)
+    if hyper is not None:
+        _lib.check(L.mmk_icp_forward_hp(ctypes.byref(p), _lib.ptr(src, torch.float32, "source"),
+                                        _lib.ptr(tgt, torch.float32, "target"), _lib.ptr(weight, torch.float32, "weight"),
+                                        _lib.ptr(T_init, torch.float32, "T_init"), _lib.ptr(T_out), _lib.ptr(st["idx"]),
+                                        _lib.ptr(st["T"]), _lib.ptr(st["delta"]), _lib.ptr(st["A"]), _lib.ptr(st["active"]),
+                                        _lib.ptr(hyper), 1 if per_pair else 0, _lib.ptr(ws), ws.numel(), ctypes.byref(iters),
+                                        _lib.stream_ptr(dev)))
+        _status.watch(p, ws, dev)
+        return T_out, st, iters.value
     _lib.check(L.mmk_icp_forward(ctypes.byref(p), _lib.ptr(src, torch.float32, "source"),
                                  _lib.ptr(tgt, torch.float32, "target"), _lib.ptr(weight, torch.float32, "weight"),
                                  _lib.ptr(T_init, torch.float32, "T_init"), _lib.ptr(T_out), _lib.ptr(st["idx"]),
@@ -173,6 +231,52 @@ class _IcpFunction(torch.autograd.Function):
         _lib.check(L.mmk_icp_backward_points(ctypes.byref(p), *state, _lib.ptr(gs), _lib.ptr(gt), _lib.ptr(ws), ws.numel(),
                                              _lib.stream_ptr(dev)))
         return gw, gT0, gs, gt, None
+
+
+class _IcpHpFunction(torch.autograd.Function):
+    """_IcpFunction for a call with device-resident hyper-parameters (mmk_icp_forward_hp / mmk_icp_backward_hp): `values` are
+    the metric, trim_dist and the steepness as given (tensor or number); a tensor among them that requires grad gets the
+    pair sums of I7'' -- its own row each for a (B,) tensor, their fp64 sum for a shared one."""
+
+    @staticmethod
+    def forward(ctx, weight, T_init, src, tgt, v_k, v_c, v_s, p, per_pair):
+        values = (v_k, v_c, v_s)
+        hyper = _hyper_array(values, per_pair, p.B, src.device)
+        T_out, st, _ = _forward(p, src, tgt, weight, T_init, hyper, per_pair)
+        _IcpFunction.last_active = st["active"]
+        ctx.p, ctx.per_pair = p, per_pair
+        ctx.meta = [(tuple(v.shape), v.dtype, v.device) if isinstance(v, torch.Tensor) else None for v in values]
+        ctx.save_for_backward(weight, src, tgt, st["idx"], st["T"], st["delta"], st["A"], st["active"], hyper)
+        return T_out
+
+    @staticmethod
+    def backward(ctx, grad_T):
+        weight, src, tgt, idx, T_hist, delta, A, active, hyper = ctx.saved_tensors
+        p = ctx.p
+        L = _lib.lib()
+        dev = src.device
+        gT = grad_T.contiguous().float()
+        gw = torch.empty(p.B, p.N, dtype=torch.float32, device=dev)
+        gT0 = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
+        need_src, need_tgt = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        need_h = ctx.needs_input_grad[4:7]
+        state = [_lib.ptr(t) for t in (src, tgt, weight, idx, T_hist, delta, A, active, gT, gw, gT0)]
+        ws = torch.empty(int(L.mmk_icp_backward_hp_workspace_bytes(ctypes.byref(p), 1 if need_tgt else 0, 1)),
+                         dtype=torch.uint8, device=dev)
+        gs = torch.empty(p.B, p.N, 3, dtype=torch.float32, device=dev) if need_src else None
+        gt = torch.empty(p.B, p.M, p.tgt_cols, dtype=torch.float32, device=dev) if need_tgt else None
+        gh = torch.empty(p.B, 3, dtype=torch.float32, device=dev) if any(need_h) else None
+        _lib.check(L.mmk_icp_backward_hp(ctypes.byref(p), *state, _lib.ptr(gs), _lib.ptr(gt), _lib.ptr(hyper),
+                                         1 if ctx.per_pair else 0, _lib.ptr(gh), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        gv = [None, None, None]
+        for c in range(3):
+            if need_h[c]:
+                shape, dtype, device = ctx.meta[c]
+                g = gh[:, c]
+                if not (len(shape) == 1 and shape[0] == p.B and ctx.per_pair):
+                    g = g.double().sum()             # a shared value: the sum over the pairs, rounded once
+                gv[c] = g.to(device=device, dtype=dtype).reshape(shape)
+        return gw, gT0, gs, gt, gv[0], gv[1], gv[2], None, None
 
 
 class ICP:
@@ -226,16 +330,28 @@ class ICP:
             raise ValueError("dICP config: tanh_steepness must be a finite number > 0 (got %r)" % (self.tanh_steepness,))
         return steep if self.trim == "tanh" else 0.0
 
-    def _params(self, B, N, M, tgt_cols, dim, loss_fn, trim_dist, save_state):
+    def _params(self, B, N, M, tgt_cols, dim, loss_fn, trim_dist, save_state, on_device=False):
+        """``on_device``: the metric, trim_dist and the steepness travel in the device array of the _hp entries; the struct
+        then carries placeholders for the first two and only the gate's MODE in trim_steep."""
         name = None if loss_fn is None else loss_fn.get("name")
         if name not in _lib.LOSSES:
             raise ValueError("unknown loss_fn name %r" % (name,))
+        if on_device:
+            loss_k, trim_dist = 1.0, 0.0
+            if isinstance(self.tanh_steepness, torch.Tensor):       # (no host validation of a tensor: the device flag replaces it)
+                if self.trim not in ("hard", "tanh"):
+                    raise ValueError("dICP config: trim must be 'hard' or 'tanh' (got %r)" % (self.trim,))
+                steep = 1.0 if self.trim == "tanh" else 0.0
+            else:
+                steep = self._trim_steep()
+        else:
+            loss_k, steep = float(1.0 if loss_fn is None else loss_fn.get("metric", 1.0)), self._trim_steep()
         return _lib.IcpParams(B=B, N=N, M=M, tgt_cols=tgt_cols, dim=dim, icp_type=_lib.ICP_TYPES[self.icp_type],
-                              loss=_lib.LOSSES[name], loss_k=float(1.0 if loss_fn is None else loss_fn.get("metric", 1.0)),
+                              loss=_lib.LOSSES[name], loss_k=loss_k,
                               trim_dist=float(trim_dist), tolerance=self.tolerance, max_iter=self.max_iterations,
                               save_state=1 if save_state else 0,
                               check_every=0 if save_state else self.check_every,
-                              nn_method=_lib.NN_METHODS[self.nn_search], trim_steep=self._trim_steep())
+                              nn_method=_lib.NN_METHODS[self.nn_search], trim_steep=steep)
 
     def icp(self, source, target, T_init=None, weight=None, trim_dist=5.0, loss_fn=None, dim=3):
         if source.ndim != 3 or source.shape[-1] != 3:
@@ -247,6 +363,8 @@ class ICP:
             raise ValueError("pt2pl needs target normals: target must be (B,M,6)")
         if dim not in (2, 3):
             raise ValueError("dim must be 2 or 3")
+        values = (1.0 if loss_fn is None else loss_fn.get("metric", 1.0), trim_dist, self.tanh_steepness)
+        per_pair = _hyper_sizes(values, source.shape[0])            # None: numbers only, the call it always was
         if source.is_cuda:
             dev = source.device
         elif torch.cuda.is_available():
@@ -270,16 +388,21 @@ class ICP:
         if weight is not None:
             w = weight.to(device=dev, dtype=torch.float32).contiguous()
         need_grad = self.differentiable and torch.is_grad_enabled() and (
-            (w is not None and w.requires_grad) or T0.requires_grad or src.requires_grad or tgt.requires_grad)
-        p = self._params(B, N, M, tgt.shape[-1], dim, loss_fn, trim_dist, save_state=need_grad)
+            (w is not None and w.requires_grad) or T0.requires_grad or src.requires_grad or tgt.requires_grad or
+            any(isinstance(v, torch.Tensor) and v.requires_grad for v in values))
+        p = self._params(B, N, M, tgt.shape[-1], dim, loss_fn, trim_dist, save_state=need_grad, on_device=per_pair is not None)
         if need_grad:
             if w is None:
                 w = torch.ones(B, N, dtype=torch.float32, device=dev)
-            T = _IcpFunction.apply(w, T0, src, tgt, p)
+            if per_pair is None:
+                T = _IcpFunction.apply(w, T0, src, tgt, p)
+            else:
+                T = _IcpHpFunction.apply(w, T0, src, tgt, values[0], values[1], values[2], p, per_pair)
             self.last_iterations = p.max_iter
         else:
             with torch.no_grad():
-                T, st, iters = _forward(p, src, tgt, None if w is None else w.detach(), T0.detach())
+                hyper = None if per_pair is None else _hyper_array(values, per_pair, B, dev)
+                T, st, iters = _forward(p, src, tgt, None if w is None else w.detach(), T0.detach(), hyper, bool(per_pair))
             self.last_state = st
             self.last_iterations = iters
         return {"T": T if T.device == out_device else T.to(out_device)}

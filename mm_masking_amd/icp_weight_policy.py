@@ -163,6 +163,28 @@ class LearnICPWeightPolicy(nn.Module):
                 raise ValueError("learn_cfar needs mask_target='scan': the default mode never runs the detector in its forward")
             self.cfar_a = nn.Parameter(torch.tensor(float(self.a_thres), dtype=torch.float32))
             self.cfar_b = nn.Parameter(torch.tensor(float(self.b_thres), dtype=torch.float32))
+        # params["learn_icp"] (absent upstream): names out of ("metric", "trim_dist", "tanh_steepness") whose value inside
+        # the ICP becomes a scalar parameter (one value for the batch), read by the training instance on the device and
+        # trained through the ICP's hyper-parameter gradients (dICP/ICP.py).  They start from icp_loss_fn["metric"],
+        # icp_trim_dist and icp_tanh_steepness.  Nothing keeps a learned value in range: the ICP's status flag reports one
+        # that left it.
+        learn_icp = params.get("learn_icp", ())
+        if isinstance(learn_icp, str):
+            learn_icp = (learn_icp,)
+        self.learn_icp = tuple(learn_icp)
+        for name in self.learn_icp:
+            if name not in ("metric", "trim_dist", "tanh_steepness"):
+                raise ValueError("learn_icp: unknown name %r (choose from 'metric', 'trim_dist', 'tanh_steepness')" % (name,))
+            if name in ("trim_dist", "tanh_steepness") and self.icp_trim != "tanh":
+                raise ValueError("learn_icp: %r needs icp_trim='tanh': the hard gate is a constant of the backward" % (name,))
+            if name == "metric" and (self.icp_loss_fn is None or self.icp_loss_fn.get("name") not in ("cauchy", "huber")):
+                raise ValueError("learn_icp: 'metric' needs a robust loss (icp_loss_fn name 'cauchy' or 'huber')")
+        if "metric" in self.learn_icp:
+            self.icp_metric = nn.Parameter(torch.tensor(float(self.icp_loss_fn.get("metric", 1.0)), dtype=torch.float32))
+        if "trim_dist" in self.learn_icp:
+            self.icp_trim_dist_p = nn.Parameter(torch.tensor(float(self.icp_trim_dist), dtype=torch.float32))
+        if "tanh_steepness" in self.learn_icp:
+            self.icp_tanh_steepness_p = nn.Parameter(torch.tensor(self.icp_tanh_steepness, dtype=torch.float32))
 
     @property
     def global_minmax(self):
@@ -388,6 +410,15 @@ class LearnICPWeightPolicy(nn.Module):
         """icp_weight_policy.py:277-288 (loss_fn / trim_dist / dim hard-coded there;
         overridable here through optional params keys)."""
         alg = self.ICP_alg if self.training else self.ICP_alg_inference
-        icp_result = alg.icp(scan_pc, map_pc, T_init=T_init, weight=weights, trim_dist=self.icp_trim_dist,
-                             loss_fn=self.icp_loss_fn, dim=self.icp_dim)
+        loss_fn, trim_dist = self.icp_loss_fn, self.icp_trim_dist
+        # params["learn_icp"]: the training instance reads the parameters (and trains them); the inference instance keeps
+        # its hard gate and reads the learned metric and trim distance, detached -- the steepness has no meaning there
+        if "metric" in self.learn_icp:
+            loss_fn = dict(loss_fn, metric=self.icp_metric if self.training else self.icp_metric.detach())
+        if "trim_dist" in self.learn_icp:
+            trim_dist = self.icp_trim_dist_p if self.training else self.icp_trim_dist_p.detach()
+        if "tanh_steepness" in self.learn_icp and self.training:
+            alg.tanh_steepness = self.icp_tanh_steepness_p
+        icp_result = alg.icp(scan_pc, map_pc, T_init=T_init, weight=weights, trim_dist=trim_dist,
+                             loss_fn=loss_fn, dim=self.icp_dim)
         return icp_result["T"]
