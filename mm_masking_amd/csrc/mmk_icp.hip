@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "mmk_common.h"
 
@@ -1901,11 +1902,41 @@ __global__ void icp_bwd_target_final_kernel(const unsigned long long *__restrict
     }
 }
 
-// ------------------------------------------------------------------------------------------
+// ------------------------------------------------------------------------------------------ host
+// Run-time value -> template argument: f is called with a std::integral_constant per choice and instantiates the kernel.
+template <class F>
+auto with_bool(bool b, F &&f)
+{
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <class F>
+auto with_dim(int dim, F &&f)
+{
+    return dim == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 3>{});
+}
+
+template <class F>
+auto with_dim_type(int dim, int icp_type, F &&f)
+{
+    return with_dim(dim, [&](auto D) {
+        return icp_type == MMK_ICP_PT2PT ? f(D, std::integral_constant<int, MMK_ICP_PT2PT>{})
+                                         : f(D, std::integral_constant<int, MMK_ICP_PT2PL>{});
+    });
+}
+
+template <class F>
+auto with_bools(bool a, bool b, F &&f)
+{
+    return with_bool(a, [&](auto A) { return with_bool(b, [&](auto B) { return f(A, B); }); });
+}
+
+// Blocks of the per-point kernels (accumulate, backward sweep) per pair = rows of their block partials.
+inline int acc_blocks(int N) { return (N + ACC_THREADS - 1) / ACC_THREADS; }
+
 struct NNPlan {
     int Mpad, ntiles, nsb, ntu, tiles_per_unit, total_units, grid, P, ucap;
 };
-
 
 NNPlan nn_plan(int B, int N, int M, int dim)
 {
@@ -1952,23 +1983,19 @@ int launch_nn(int dim, const float *src, const float *tgtp, const float *Tk, con
     if (prev_idx == nullptr && seed_buf != nullptr && pl.Mpad >= 4 * NN_COARSE_STRIDE) {
         const dim3 grid((N + NN_COARSE_THREADS - 1) / NN_COARSE_THREADS, B);
         const int nn_pts = NN_THREADS * pl.P;
-        if (dim == 2)
-            hipLaunchKernelGGL(nn_coarse_seed_kernel<2>, grid, dim3(NN_COARSE_THREADS), 0, st, src, tgtp, Tk, active, allzero, zrep, nn_pts, pl.nsb, N,
-                               pl.Mpad, dec, seed_buf);
-        else
-            hipLaunchKernelGGL(nn_coarse_seed_kernel<3>, grid, dim3(NN_COARSE_THREADS), 0, st, src, tgtp, Tk, active, allzero, zrep, nn_pts, pl.nsb, N,
-                               pl.Mpad, dec, seed_buf);
+        with_dim(dim, [&](auto D) {
+            hipLaunchKernelGGL(nn_coarse_seed_kernel<D()>, grid, dim3(NN_COARSE_THREADS), 0, st, src, tgtp, Tk, active, allzero, zrep, nn_pts,
+                               pl.nsb, N, pl.Mpad, dec, seed_buf);
+        });
         MMK_LAUNCH_CHECK();
         prev_idx = seed_buf;
     }
     constexpr float U = 5.9604645e-8f;       // 2^-24
-    if (dim == 2) {
-        hipLaunchKernelGGL((nn_mfma_kernel<2>), dim3(pl.grid), dim3(NN_THREADS), 0, st, src, tgtp, Tk, active, prev_idx, ulist, ucnt,
-                           pl.ucap, B, N, pl.Mpad, pl.nsb, pl.ntu, pl.tiles_per_unit, pl.total_units, 360.0f * U, packed);
-    } else {
-        hipLaunchKernelGGL((nn_mfma_kernel<3>), dim3(pl.grid), dim3(NN_THREADS), 0, st, src, tgtp, Tk, active, prev_idx, ulist, ucnt,
-                           pl.ucap, B, N, pl.Mpad, pl.nsb, pl.ntu, pl.tiles_per_unit, pl.total_units, 496.0f * U, packed);
-    }
+    with_dim(dim, [&](auto D) {
+        hipLaunchKernelGGL((nn_mfma_kernel<D()>), dim3(pl.grid), dim3(NN_THREADS), 0, st, src, tgtp, Tk, active, prev_idx, ulist, ucnt,
+                           pl.ucap, B, N, pl.Mpad, pl.nsb, pl.ntu, pl.tiles_per_unit, pl.total_units, (D() == 2 ? 360.0f : 496.0f) * U,
+                           packed);
+    });
     MMK_LAUNCH_CHECK();
     if (rec) {
         MMK_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.n + 1], st));
@@ -1994,6 +2021,17 @@ int check_params(const mmk_icp_params *p)
     return MMK_OK;
 }
 
+// The robust-loss and trim arguments of the per-point kernels; k2 and trim2 are single fp32 products (I3).
+struct RobustArgs {
+    int loss;
+    float k, k2, trim2, trim_dist, trim_steep;
+};
+
+RobustArgs robust_args(const mmk_icp_params *p)
+{
+    return {p->loss, p->loss_k, p->loss_k * p->loss_k, p->trim_dist * p->trim_dist, p->trim_dist, p->trim_steep};
+}
+
 struct IcpWs {
     float *tgtp;
     unsigned long long *packed;  // 2 x (B,N) NN keys: read by iteration k's accumulate, armed for iteration k+1
@@ -2013,7 +2051,7 @@ struct IcpWs {
 IcpWs carve(const mmk_icp_params *p, void *ws, size_t cap)
 {
     const NNPlan pl = nn_plan(p->B, p->N, p->M, p->dim);
-    const int nblk = (p->N + ACC_THREADS - 1) / ACC_THREADS;
+    const int nblk = acc_blocks(p->N);
     mmk::Arena ar(ws, cap);
     IcpWs w;
     w.tgtp = ar.take<float>((size_t)p->B * p->dim * pl.Mpad);
@@ -2041,59 +2079,87 @@ IcpWs carve(const mmk_icp_params *p, void *ws, size_t cap)
     return w;
 }
 
-// Scratch of mmk_icp_backward_points: mmk_icp_backward's (carve above), then the target gradient's parts.
-struct IcpPtsWs {
-    float *rows;                 // (K,B,N,C): every point's contribution row, per iteration
-    unsigned long long *acc;     // (B,M,L): their fixed-point sums
-    unsigned *pmax;              // (B): float bits of the largest |entry| of a pair's rows
-    size_t bytes;
+// Workspace of the three backward entries, three parts in this order, each starting on a 256-byte boundary: the forward's
+// (carve), the target gradient's (with_target), the hyper-parameter gradient's (with_hyper).  A part that is not asked
+// for takes no room and leaves its pointers NULL, so mmk_icp_backward's workspace is the forward's.
+struct IcpBwdWs {
+    IcpWs w;
+    float *rows = nullptr;               // (K,B,N,C): every point's contribution row to the target gradient, per iteration
+    unsigned long long *acc = nullptr;   // (B,M,L): their fixed-point sums
+    unsigned *pmax = nullptr;            // (B): float bits of the largest |entry| of a pair's rows
+    double *hparts = nullptr;            // (K,B,nblk,3): block partials of (k̄, c̄, s̄), every entry written by the sweep
+    size_t bytes = 0;
 };
 
-IcpPtsWs carve_points(const mmk_icp_params *p, bool with_target, void *ws, size_t cap)
+IcpBwdWs carve_backward(const mmk_icp_params *p, bool with_target, bool with_hyper, void *ws, size_t cap)
 {
+    IcpBwdWs b;
+    b.w = carve(p, ws, cap);
     mmk::Arena ar(ws, cap);
-    ar.off = carve(p, nullptr, 0).bytes;
-    IcpPtsWs w{nullptr, nullptr, nullptr, 0};
+    ar.off = b.w.bytes;
     if (with_target) {
         const int C = tgt_row_cols(p->dim, p->icp_type);
-        w.rows = ar.take<float>((size_t)p->max_iter * p->B * p->N * C);
-        w.acc = ar.take<unsigned long long>((size_t)p->B * p->M * tgt_acc_cols(C));
-        w.pmax = ar.take<unsigned>((size_t)p->B);
+        b.rows = ar.take<float>((size_t)p->max_iter * p->B * p->N * C);
+        b.acc = ar.take<unsigned long long>((size_t)p->B * p->M * tgt_acc_cols(C));
+        b.pmax = ar.take<unsigned>((size_t)p->B);
     }
-    w.bytes = mmk::align_up(ar.off, 256);
-    return w;
+    if (with_hyper) b.hparts = ar.take<double>((size_t)p->max_iter * p->B * acc_blocks(p->N) * 3);
+    b.bytes = mmk::align_up(ar.off, 256);
+    return b;
 }
 
-// The hyper-parameter array of the _hp entries (I3'', I7'') and the scratch of its gradient: a workspace of its own BEHIND
-// mmk_icp_backward_points' (carve_points above), so that the older entries' layouts and sizes stay what they are.
-struct IcpHyper {
-    const float *hyper = nullptr;   // (1 | B, 3): k, trim_dist, trim_steep; NULL: the scalars of mmk_icp_params
-    int hstride = 0;                // 0 shared | 3 per pair
-    double *hparts = nullptr;       // (K,B,nblk,3): block partials of (k̄, c̄, s̄), every entry written by the sweep
-    float *grad_hyper = nullptr;    // (B,3) or NULL
-    size_t bytes = 0;               // whole workspace of mmk_icp_backward_hp
+// `code` is the entry's own: MMK_ERR_WORKSPACE, or MMK_ERR_ARG for mmk_icp_backward_points and mmk_icp_backward_hp.
+int check_workspace(const char *who, int code, const void *ws, size_t have, size_t need)
+{
+    if (ws != nullptr && need <= have) return MMK_OK;
+    mmk::set_error(code == MMK_ERR_ARG ? "%s: workspace too small (%zu < %zu bytes)" : "%s: workspace too small (%zu < %zu)", who, have,
+                   need);
+    return code;
+}
+
+// One dICP call as its entry received it, filled by position: an entry leaves out the tail it does not have.  The forward
+// writes the histories, the backward only reads them.
+struct IcpCall {
+    const float *source, *target, *weight;
+    int32_t *idx_hist;                     // (K | 1,B,N)
+    float *T_hist;                         // (K+1,B,16)
+    double *delta_hist, *A_hist;           // (K,B,6), (K,B,36)
+    int32_t *active_hist;                  // (K+1,B)
+    hipStream_t st;
+    const float *hyper = nullptr;          // (1 | B, 3): k, trim_dist, trim_steep; NULL: the scalars of mmk_icp_params
+    int hstride = 0;                       // 0 shared | 3 per pair
+    const float *grad_T = nullptr;
+    float *grad_weight = nullptr, *grad_T_init = nullptr;
+    float *grad_source = nullptr, *grad_target = nullptr;      // (B,N,3), (B,M,tgt_cols)
+    float *grad_hyper = nullptr;           // (B,3)
 };
 
-IcpHyper carve_hyper(const mmk_icp_params *p, bool with_target, bool with_hyper, void *ws, size_t cap)
+template <class T>
+T *writable(const T *p) { return const_cast<T *>(p); }
+
+// Bin `points` (B,M,cols) into the uniform grid of the exact searches (grid_nn_kernel, knn_normals_kernel).
+int build_grid(const float *points, int B, int M, int cols, int dim, int32_t *counts, int32_t *cursor, int32_t *starts,
+               float4 *sorted, hipStream_t st)
 {
-    mmk::Arena ar(ws, cap);
-    ar.off = carve_points(p, with_target, nullptr, 0).bytes;
-    IcpHyper h;
-    if (with_hyper) h.hparts = ar.take<double>((size_t)p->max_iter * p->B * ((p->N + ACC_THREADS - 1) / ACC_THREADS) * 3);
-    h.bytes = mmk::align_up(ar.off, 256);
-    return h;
+    MMK_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)B * GRID_NC * 2, st));   // counts and cursor
+    hipLaunchKernelGGL(grid_count_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, points, M, cols, counts);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(grid_scan_kernel, dim3(B), dim3(256), 0, st, counts, starts);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(grid_fill_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, points, M, cols, dim, starts, cursor, sorted);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
 }
 
 template <int DIM, int TYPE>
-int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight, float *T_hist,
-                int32_t *idx_hist, double *delta_hist, double *A_hist, int32_t *active_hist, const IcpWs &w,
-                int *iters_run, hipStream_t st, const float *hyper = nullptr, int hstride = 0)
+int run_forward(const mmk_icp_params *p, const IcpCall &c, const IcpWs &w, int *iters_run)
 {
     const int B = p->B, N = p->N, M = p->M;
+    const float *const src = c.source, *const tgt = c.target;
+    const hipStream_t st = c.st;
     const NNPlan pl = nn_plan(B, N, M, DIM);
-    const int nblk = (N + ACC_THREADS - 1) / ACC_THREADS;
-    const float k = p->loss_k, k2 = p->loss_k * p->loss_k, trim2 = p->trim_dist * p->trim_dist;
-    const float trim_dist = p->trim_dist, trim_steep = p->trim_steep;
+    const int nblk = acc_blocks(N);
+    const size_t idx_step = p->save_state ? (size_t)B * N : 0;     // without saved state every iteration reuses one (B,N) buffer
     int k_done = 0;
     // (keys, status word, zero-row representatives: icp_init_kernel in mmk_icp_forward)
     const bool use_grid = p->nn_method == MMK_NN_GRID;
@@ -2107,25 +2173,22 @@ int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, con
     }
     const int32_t *az = dedup ? w.allzero : nullptr, *zr = dedup ? w.zrep : nullptr;
     if (use_grid) {   // the target is fixed over the iterations: bin it once
-        MMK_CHECK_HIP(hipMemsetAsync(w.g_counts, 0, sizeof(int32_t) * (size_t)B * GRID_NC * 2, st));
-        hipLaunchKernelGGL(grid_count_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, tgt, M, p->tgt_cols, w.g_counts);
-        MMK_LAUNCH_CHECK();
-        hipLaunchKernelGGL(grid_scan_kernel, dim3(B), dim3(256), 0, st, w.g_counts, w.g_starts);
-        MMK_LAUNCH_CHECK();
-        hipLaunchKernelGGL(grid_fill_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, tgt, M, p->tgt_cols, DIM, w.g_starts,
-                           w.g_cursor, w.g_sorted);
-        MMK_LAUNCH_CHECK();
+        const int rc = build_grid(tgt, B, M, p->tgt_cols, DIM, w.g_counts, w.g_cursor, w.g_starts, w.g_sorted, st);
+        if (rc != MMK_OK) return rc;
     }
+    const RobustArgs r = robust_args(p);
+    const float *const hyper = c.hyper;
+    const int hstride = hyper ? c.hstride : 0;     // without `hyper` (HP = false) the launch gets NULL, stride 0 and no check
     for (int it = 0; it < p->max_iter; ++it) {
-        const float *Tk = T_hist + (size_t)it * B * 16;
-        const int32_t *act = active_hist + (size_t)it * B;
-        int32_t *idx = idx_hist + (p->save_state ? (size_t)it * B * N : 0);
+        const float *Tk = c.T_hist + (size_t)it * B * 16;
+        const int32_t *act = c.active_hist + (size_t)it * B;
+        int32_t *idx = c.idx_hist + it * idx_step;
+        // the correspondences of the previous iteration (still in the index buffer) bound the search / start the filter's bound
+        const int32_t *prev = (it > 0) ? c.idx_hist + (it - 1) * idx_step : nullptr;
         unsigned long long *keys = w.packed + (size_t)(it & 1) * B * N, *keys_next = w.packed + (size_t)((it + 1) & 1) * B * N;
         if (use_grid) {
             const bool rec = g_prof.on && g_prof.n < g_prof.cap;
             if (rec) MMK_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.n], st));
-            // the correspondences of the previous iteration (still in the index buffer) bound the search
-            const int32_t *prev = (it > 0) ? idx_hist + (p->save_state ? (size_t)(it - 1) * B * N : 0) : nullptr;
             hipLaunchKernelGGL(grid_nn_kernel<DIM>, dim3((N + 255) / 256, B), dim3(256), 0, st, src, Tk, act, w.g_starts,
                                w.g_sorted, N, M, tgt, p->tgt_cols, prev, keys);
             MMK_LAUNCH_CHECK();
@@ -2134,29 +2197,25 @@ int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, con
                 g_prof.n++;
             }
         } else {
-            // the correspondences of the previous iteration (still in the index buffer) start the filter's bound
-            const int32_t *prev = (it > 0) ? idx_hist + (p->save_state ? (size_t)(it - 1) * B * N : 0) : nullptr;
             int rc = launch_nn(DIM, src, w.tgtp, Tk, act, prev, dedup ? w.ulist : nullptr, w.ucnt, B, N, pl, keys, w.seed0, az, zr, w.tdec, st);
             if (rc != MMK_OK) return rc;
         }
-        if (hyper != nullptr)
-            hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE, true>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
-                               p->tgt_cols, weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, p->loss, k, k2, trim2, trim_dist,
-                               trim_steep, w.partials, w.status, hyper, hstride, it == 0 ? 1 : 0);
-        else
-            hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
-                               p->tgt_cols, weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, p->loss, k, k2, trim2, trim_dist,
-                               trim_steep, w.partials, w.status, static_cast<const float *>(nullptr), 0, 0);
+        const int hcheck = hyper && it == 0 ? 1 : 0;
+        with_bool(hyper != nullptr, [&](auto HP) {
+            hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE, HP()>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt, p->tgt_cols,
+                               c.weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, r.loss, r.k, r.k2, r.trim2,
+                               r.trim_dist, r.trim_steep, w.partials, w.status, hyper, hstride, hcheck);
+        });
         MMK_LAUNCH_CHECK();
         hipLaunchKernelGGL(icp_solve_kernel<DIM>, dim3(B), dim3(64), 0, st, w.partials, nblk, Tk,
-                           T_hist + (size_t)(it + 1) * B * 16, delta_hist + (size_t)it * B * 6,
-                           A_hist + (size_t)it * B * 36, act, active_hist + (size_t)(it + 1) * B, p->tolerance);
+                           c.T_hist + (size_t)(it + 1) * B * 16, c.delta_hist + (size_t)it * B * 6,
+                           c.A_hist + (size_t)it * B * 36, act, c.active_hist + (size_t)(it + 1) * B, p->tolerance);
         MMK_LAUNCH_CHECK();
         k_done = it + 1;
         if (p->check_every > 0 && (k_done % p->check_every) == 0 && k_done < p->max_iter) {
             static thread_local int32_t host_act[1 << 16];
             MMK_REQUIRE(B <= (1 << 16), "mmk_icp_forward: check_every needs B <= 65536");
-            MMK_CHECK_HIP(hipMemcpyAsync(host_act, active_hist + (size_t)k_done * B, sizeof(int32_t) * B,
+            MMK_CHECK_HIP(hipMemcpyAsync(host_act, c.active_hist + (size_t)k_done * B, sizeof(int32_t) * B,
                                          hipMemcpyDeviceToHost, st));
             MMK_CHECK_HIP(hipStreamSynchronize(st));
             bool any = false;
@@ -2166,105 +2225,77 @@ int run_forward(const mmk_icp_params *p, const float *src, const float *tgt, con
     }
     // iterations that were skipped after an early stop: carry the pose forward
     for (int it = k_done; it < p->max_iter; ++it) {
-        MMK_CHECK_HIP(hipMemcpyAsync(T_hist + (size_t)(it + 1) * B * 16, T_hist + (size_t)it * B * 16,
+        MMK_CHECK_HIP(hipMemcpyAsync(c.T_hist + (size_t)(it + 1) * B * 16, c.T_hist + (size_t)it * B * 16,
                                      sizeof(float) * B * 16, hipMemcpyDeviceToDevice, st));
-        MMK_CHECK_HIP(hipMemsetAsync(active_hist + (size_t)(it + 1) * B, 0, sizeof(int32_t) * B, st));
-        MMK_CHECK_HIP(hipMemsetAsync(delta_hist + (size_t)it * B * 6, 0, sizeof(double) * B * 6, st));
+        MMK_CHECK_HIP(hipMemsetAsync(c.active_hist + (size_t)(it + 1) * B, 0, sizeof(int32_t) * B, st));
+        MMK_CHECK_HIP(hipMemsetAsync(c.delta_hist + (size_t)it * B * 6, 0, sizeof(double) * B * 6, st));
     }
     if (iters_run) *iters_run = k_done;
     return MMK_OK;
 }
 
 template <int DIM, int TYPE>
-int run_backward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight,
-                 const int32_t *idx_hist, const float *T_hist, const double *delta_hist, const double *A_hist,
-                 const int32_t *active_hist, const float *grad_T, float *gw, float *grad_T_init, float *gsrc, float *gtgt,
-                 const IcpWs &w, const IcpPtsWs &pw, hipStream_t st, const IcpHyper &hy)
+int run_backward(const mmk_icp_params *p, const IcpCall &c, const IcpBwdWs &bw)
 {
     const int B = p->B, N = p->N, M = p->M;
-    const int nblk = (N + ACC_THREADS - 1) / ACC_THREADS;
-    const float k = p->loss_k, k2 = p->loss_k * p->loss_k, trim2 = p->trim_dist * p->trim_dist;
-    const float trim_dist = p->trim_dist, trim_steep = p->trim_steep;
+    const IcpWs &w = bw.w;
+    const hipStream_t st = c.st;
+    const int nblk = acc_blocks(N);
+    const RobustArgs r = robust_args(p);
     constexpr int C = tgt_row_cols(DIM, TYPE), L = tgt_acc_cols(C);
+    float *const gw = c.grad_weight, *const gsrc = c.grad_source, *const gtgt = c.grad_target;
     MMK_CHECK_HIP(hipMemsetAsync(gw, 0, sizeof(float) * (size_t)B * N, st));
     if (gsrc) MMK_CHECK_HIP(hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * N * 3, st));
     if (gtgt) {
-        MMK_CHECK_HIP(hipMemsetAsync(pw.acc, 0, sizeof(unsigned long long) * (size_t)B * M * L, st));
-        MMK_CHECK_HIP(hipMemsetAsync(pw.pmax, 0, sizeof(unsigned) * (size_t)B, st));
+        MMK_CHECK_HIP(hipMemsetAsync(bw.acc, 0, sizeof(unsigned long long) * (size_t)B * M * L, st));
+        MMK_CHECK_HIP(hipMemsetAsync(bw.pmax, 0, sizeof(unsigned) * (size_t)B, st));
     }
-    hipLaunchKernelGGL(f32_to_f64_kernel, dim3((B * 16 + 255) / 256), dim3(256), 0, st, grad_T, w.G0, B * 16);
+    hipLaunchKernelGGL(f32_to_f64_kernel, dim3((B * 16 + 255) / 256), dim3(256), 0, st, c.grad_T, w.G0, B * 16);
     MMK_LAUNCH_CHECK();
     double *Gin = w.G0, *Gout = w.G1;
     int nparts = 0;
+    // PTS: a cloud gradient is asked for; HP: the workspace has the hyper part, i.e. the entry was given `hyper`.  Without
+    // PTS gsrc, rows and bw.pmax are all NULL, without HP c.hyper and hparts are: one argument list serves the four kernels.
+    const bool pts = gsrc || gtgt, hp = bw.hparts != nullptr;
     for (int it = p->max_iter - 1; it >= 0; --it) {
-        const float *Tk = T_hist + (size_t)it * B * 16;
-        const int32_t *act = active_hist + (size_t)it * B;
-        hipLaunchKernelGGL(icp_bwd_pair_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, Tk,
-                           delta_hist + (size_t)it * B * 6, A_hist + (size_t)it * B * 36, act, Gout, w.lam);
+        const float *Tk = c.T_hist + (size_t)it * B * 16;
+        const int32_t *act = c.active_hist + (size_t)it * B;
+        const double *delta = c.delta_hist + (size_t)it * B * 6;
+        hipLaunchKernelGGL(icp_bwd_pair_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, Tk, delta,
+                           c.A_hist + (size_t)it * B * 36, act, Gout, w.lam);
         MMK_LAUNCH_CHECK();
-        const float *const nohyper = nullptr;
-        double *const noparts = nullptr;
-        double *hp = hy.hparts ? hy.hparts + (size_t)it * B * nblk * 3 : noparts;
-#define MMK_BWD_POINT(PTS_, HP_, GSRC, ROWS, PMAX, HYPER, HPARTS)                                                                      \
-    hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, PTS_, HP_>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt, p->tgt_cols,  \
-                       weight, Tk, act, idx_hist + (size_t)it * B * N, w.lam, delta_hist + (size_t)it * B * 6, N, M, p->loss, k, k2,   \
-                       trim2, trim_dist, trim_steep, gw, w.partials, GSRC, ROWS, PMAX, HYPER, hy.hstride, HPARTS)
-        float *const rows = gtgt ? pw.rows + (size_t)it * B * N * C : static_cast<float *>(nullptr);
-        if (hy.hparts != nullptr && (gsrc || gtgt))
-            MMK_BWD_POINT(true, true, gsrc, rows, pw.pmax, hy.hyper, hp);
-        else if (hy.hparts != nullptr)
-            MMK_BWD_POINT(false, true, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<unsigned *>(nullptr),
-                          hy.hyper, hp);
-        else if (gsrc || gtgt)
-            MMK_BWD_POINT(true, false, gsrc, rows, pw.pmax, nohyper, noparts);
-        else
-            MMK_BWD_POINT(false, false, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<unsigned *>(nullptr),
-                          nohyper, noparts);
-#undef MMK_BWD_POINT
+        float *rows = gtgt ? bw.rows + (size_t)it * B * N * C : nullptr;
+        double *hparts = hp ? bw.hparts + (size_t)it * B * nblk * 3 : nullptr;
+        with_bools(pts, hp, [&](auto PTS, auto HP) {
+            hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, PTS(), HP()>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, c.source,
+                               c.target, p->tgt_cols, c.weight, Tk, act, c.idx_hist + (size_t)it * B * N, w.lam, delta, N, M, r.loss, r.k,
+                               r.k2, r.trim2, r.trim_dist, r.trim_steep, gw, w.partials, gsrc, rows, bw.pmax, c.hyper, c.hstride,
+                               hparts);
+        });
         MMK_LAUNCH_CHECK();
         nparts = nblk;
-        double *t = Gin; Gin = Gout; Gout = t;
+        std::swap(Gin, Gout);
     }
-    if (grad_T_init) {
-        hipLaunchKernelGGL(bwd_final_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, grad_T_init);
+    if (c.grad_T_init) {
+        hipLaunchKernelGGL(bwd_final_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, c.grad_T_init);
         MMK_LAUNCH_CHECK();
     }
-    if (hy.grad_hyper) {
-        hipLaunchKernelGGL(icp_bwd_hyper_final_kernel, dim3(B), dim3(64), 0, st, hy.hparts, p->max_iter, B, nblk, hy.grad_hyper);
+    if (c.grad_hyper) {
+        hipLaunchKernelGGL(icp_bwd_hyper_final_kernel, dim3(B), dim3(64), 0, st, bw.hparts, p->max_iter, B, nblk, c.grad_hyper);
         MMK_LAUNCH_CHECK();
     }
     if (gtgt) {
         int cnt_bits = 0;
         while (((uint64_t)1 << cnt_bits) < (uint64_t)p->max_iter * (uint64_t)N) ++cnt_bits;
         const unsigned gx = (unsigned)(((size_t)N * L + ACC_THREADS - 1) / ACC_THREADS);
-        hipLaunchKernelGGL(icp_bwd_target_scatter_kernel<C>, dim3(gx, B, p->max_iter), dim3(ACC_THREADS), 0, st, pw.rows, idx_hist,
-                           active_hist, pw.pmax, B, N, M, cnt_bits, pw.acc);
+        hipLaunchKernelGGL(icp_bwd_target_scatter_kernel<C>, dim3(gx, B, p->max_iter), dim3(ACC_THREADS), 0, st, bw.rows, c.idx_hist,
+                           c.active_hist, bw.pmax, B, N, M, cnt_bits, bw.acc);
         MMK_LAUNCH_CHECK();
-        hipLaunchKernelGGL(icp_bwd_target_final_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, pw.acc, pw.pmax, cnt_bits, M, DIM, C,
+        hipLaunchKernelGGL(icp_bwd_target_final_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, bw.acc, bw.pmax, cnt_bits, M, DIM, C,
                            L, p->tgt_cols, gtgt);
         MMK_LAUNCH_CHECK();
     }
     return MMK_OK;
-}
-
-// mmk_icp_backward and mmk_icp_backward_points (gsrc / gtgt NULL: the former's launches exactly).
-int dispatch_backward(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight,
-                      const int32_t *idx_hist, const float *T_hist, const double *delta_hist, const double *A_hist,
-                      const int32_t *active_hist, const float *grad_T, float *gw, float *grad_T_init, float *gsrc,
-                      float *gtgt, const IcpWs &w, const IcpPtsWs &pw, hipStream_t st,
-                      const IcpHyper &hy = IcpHyper())
-{
-    if (p->dim == 2 && p->icp_type == MMK_ICP_PT2PT)
-        return run_backward<2, MMK_ICP_PT2PT>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
-                                              grad_T_init, gsrc, gtgt, w, pw, st, hy);
-    if (p->dim == 2)
-        return run_backward<2, MMK_ICP_PT2PL>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
-                                              grad_T_init, gsrc, gtgt, w, pw, st, hy);
-    if (p->icp_type == MMK_ICP_PT2PT)
-        return run_backward<3, MMK_ICP_PT2PT>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
-                                              grad_T_init, gsrc, gtgt, w, pw, st, hy);
-    return run_backward<3, MMK_ICP_PT2PL>(p, src, tgt, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, gw,
-                                          grad_T_init, gsrc, gtgt, w, pw, st, hy);
 }
 
 }  // namespace
@@ -2361,29 +2392,18 @@ extern "C" int mmk_knn_normals(const float *points, int32_t B, int32_t M, int32_
     MMK_REQUIRE((dim == 2 || dim == 3) && cols >= dim, "mmk_knn_normals: dim must be 2|3 and <= cols");
     MMK_REQUIRE(k >= 3 && k <= 32, "mmk_knn_normals: k must be in 3..32 (got %d)", k);
     const KnnWs w = knn_carve(B, M, workspace, workspace_bytes);
-    if (workspace == nullptr || w.bytes > workspace_bytes) {
-        mmk::set_error("mmk_knn_normals: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
+    int rc = check_workspace("mmk_knn_normals", MMK_ERR_WORKSPACE, workspace, workspace_bytes, w.bytes);
+    if (rc != MMK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // the grid of the ICP's exact search, built by the same kernels
-    MMK_CHECK_HIP(hipMemsetAsync(w.counts, 0, sizeof(int32_t) * (size_t)B * GRID_NC * 2, st));
-    hipLaunchKernelGGL(grid_count_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, points, M, cols, w.counts);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(grid_scan_kernel, dim3(B), dim3(256), 0, st, w.counts, w.starts);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(grid_fill_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, points, M, cols, dim, w.starts, w.cursor, w.sorted);
-    MMK_LAUNCH_CHECK();
-#define KNN_GO(D, KC) knn_launch<D, KC>(points, B, M, cols, k, max_radius, pad_val, viewpoint, w, normals, curvature, count, nbr_idx, st)
-    if (dim == 2) {
-        if (k <= 8) KNN_GO(2, 8);
-        else if (k <= 16) KNN_GO(2, 16);
-        else KNN_GO(2, 32);
-    } else {
-        if (k <= 8) KNN_GO(3, 8);
-        else if (k <= 16) KNN_GO(3, 16);
-        else KNN_GO(3, 32);
-    }
+    // the grid of the ICP's exact search
+    rc = build_grid(points, B, M, cols, dim, w.counts, w.cursor, w.starts, w.sorted, st);
+    if (rc != MMK_OK) return rc;
+#define KNN_GO(KC) knn_launch<D(), KC>(points, B, M, cols, k, max_radius, pad_val, viewpoint, w, normals, curvature, count, nbr_idx, st)
+    with_dim(dim, [&](auto D) {
+        if (k <= 8) KNN_GO(8);
+        else if (k <= 16) KNN_GO(16);
+        else KNN_GO(32);
+    });
 #undef KNN_GO
     MMK_LAUNCH_CHECK();
     return MMK_OK;
@@ -2423,54 +2443,39 @@ extern "C" int mmk_nn_profile_end(float *ms_out, int32_t max_out, int32_t *n_out
 extern "C" size_t mmk_icp_workspace_bytes(const mmk_icp_params *p)
 {
     if (check_params(p) != MMK_OK) return 0;
-    return carve(p, nullptr, 0).bytes;
+    return carve_backward(p, false, false, nullptr, 0).bytes;    // = carve's: the forward and mmk_icp_backward share it
 }
 
 namespace {
 // mmk_icp_forward (hyper NULL) and mmk_icp_forward_hp
-int forward_impl(const char *who, const mmk_icp_params *p, const float *source, const float *target, const float *weight,
-                 const float *T_init, float *T_out, int32_t *idx_hist, float *T_hist, double *delta_hist, double *A_hist,
-                 int32_t *active_hist, const float *hyper, int hstride, void *workspace, size_t workspace_bytes, int *iters_run,
-                 void *stream)
+int forward_impl(const char *who, const mmk_icp_params *p, const IcpCall &c, const float *T_init, float *T_out, void *workspace,
+                 size_t workspace_bytes, int *iters_run)
 {
     int rc = check_params(p);
     if (rc != MMK_OK) return rc;
-    MMK_REQUIRE(source && target && T_init && T_out && idx_hist && T_hist && delta_hist && A_hist && active_hist,
+    MMK_REQUIRE(c.source && c.target && T_init && T_out && c.idx_hist && c.T_hist && c.delta_hist && c.A_hist && c.active_hist,
                 "%s: NULL pointer", who);
     const IcpWs w = carve(p, workspace, workspace_bytes);
-    if (workspace == nullptr || w.bytes > workspace_bytes) {
-        mmk::set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
+    rc = check_workspace(who, MMK_ERR_WORKSPACE, workspace, workspace_bytes, w.bytes);
+    if (rc != MMK_OK) return rc;
+    const hipStream_t st = c.st;
     const int B = p->B;
     {
         const int Mpad = mmk_nn_padded_m(p->M);
-        hipLaunchKernelGGL(pack_target_kernel, dim3(Mpad / 256, B), dim3(256), 0, st, target, p->M, p->tgt_cols, p->dim, Mpad, w.tgtp,
+        hipLaunchKernelGGL(pack_target_kernel, dim3(Mpad / 256, B), dim3(256), 0, st, c.target, p->M, p->tgt_cols, p->dim, Mpad, w.tgtp,
                            w.tdec, NN_COARSE_STRIDE);
         MMK_LAUNCH_CHECK();
     }
     {
         const size_t nkeys = (size_t)2 * B * p->N;
         const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((nkeys + 255) / 256, (size_t)(B * 16 + 255) / 256), 2048);
-        hipLaunchKernelGGL(icp_init_kernel, dim3(blocks), dim3(256), 0, st, w.packed, nkeys, w.status, active_hist, T_init, T_hist, w.zrep, B,
-                           p->N);
+        hipLaunchKernelGGL(icp_init_kernel, dim3(blocks), dim3(256), 0, st, w.packed, nkeys, w.status, c.active_hist, T_init, c.T_hist,
+                           w.zrep, B, p->N);
         MMK_LAUNCH_CHECK();
     }
-    if (p->dim == 2 && p->icp_type == MMK_ICP_PT2PT)
-        rc = run_forward<2, MMK_ICP_PT2PT>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st, hyper,
-                                           hstride);
-    else if (p->dim == 2)
-        rc = run_forward<2, MMK_ICP_PT2PL>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st, hyper,
-                                           hstride);
-    else if (p->icp_type == MMK_ICP_PT2PT)
-        rc = run_forward<3, MMK_ICP_PT2PT>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st, hyper,
-                                           hstride);
-    else
-        rc = run_forward<3, MMK_ICP_PT2PL>(p, source, target, weight, T_hist, idx_hist, delta_hist, A_hist, active_hist, w, iters_run, st, hyper,
-                                           hstride);
+    rc = with_dim_type(p->dim, p->icp_type, [&](auto D, auto TYPE) { return run_forward<D(), TYPE()>(p, c, w, iters_run); });
     if (rc != MMK_OK) return rc;
-    MMK_CHECK_HIP(hipMemcpyAsync(T_out, T_hist + (size_t)p->max_iter * B * 16, sizeof(float) * B * 16,
+    MMK_CHECK_HIP(hipMemcpyAsync(T_out, c.T_hist + (size_t)p->max_iter * B * 16, sizeof(float) * B * 16,
                                  hipMemcpyDeviceToDevice, st));
     return MMK_OK;
 }
@@ -2481,8 +2486,8 @@ extern "C" int mmk_icp_forward(const mmk_icp_params *p, const float *source, con
                                float *T_hist, double *delta_hist, double *A_hist, int32_t *active_hist,
                                void *workspace, size_t workspace_bytes, int *iters_run, void *stream)
 {
-    return forward_impl("mmk_icp_forward", p, source, target, weight, T_init, T_out, idx_hist, T_hist, delta_hist, A_hist, active_hist,
-                        nullptr, 0, workspace, workspace_bytes, iters_run, stream);
+    const IcpCall c{source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, (hipStream_t)stream};
+    return forward_impl("mmk_icp_forward", p, c, T_init, T_out, workspace, workspace_bytes, iters_run);
 }
 
 extern "C" int mmk_icp_forward_hp(const mmk_icp_params *p, const float *source, const float *target,
@@ -2492,8 +2497,8 @@ extern "C" int mmk_icp_forward_hp(const mmk_icp_params *p, const float *source, 
                                   int *iters_run, void *stream)
 {
     MMK_REQUIRE(per_pair == 0 || per_pair == 1, "mmk_icp_forward_hp: per_pair must be 0 or 1 (got %d)", per_pair);
-    return forward_impl("mmk_icp_forward_hp", p, source, target, weight, T_init, T_out, idx_hist, T_hist, delta_hist, A_hist,
-                        active_hist, hyper, per_pair ? 3 : 0, workspace, workspace_bytes, iters_run, stream);
+    const IcpCall c{source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, (hipStream_t)stream, hyper, per_pair ? 3 : 0};
+    return forward_impl("mmk_icp_forward_hp", p, c, T_init, T_out, workspace, workspace_bytes, iters_run);
 }
 
 extern "C" int mmk_icp_status(const mmk_icp_params *p, const void *workspace, size_t workspace_bytes, int32_t *status_out,
@@ -2503,10 +2508,8 @@ extern "C" int mmk_icp_status(const mmk_icp_params *p, const void *workspace, si
     if (rc != MMK_OK) return rc;
     MMK_REQUIRE(status_out != nullptr, "mmk_icp_status: NULL status_out");
     const IcpWs w = carve(p, const_cast<void *>(workspace), workspace_bytes);
-    if (workspace == nullptr || w.bytes > workspace_bytes) {
-        mmk::set_error("mmk_icp_status: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
+    rc = check_workspace("mmk_icp_status", MMK_ERR_WORKSPACE, workspace, workspace_bytes, w.bytes);
+    if (rc != MMK_OK) return rc;
     MMK_CHECK_HIP(hipMemcpyAsync(status_out, w.status, sizeof(int32_t), hipMemcpyDefault, (hipStream_t)stream));
     return MMK_OK;
 }
@@ -2514,35 +2517,8 @@ extern "C" int mmk_icp_status(const mmk_icp_params *p, const void *workspace, si
 extern "C" size_t mmk_icp_partials_count(const mmk_icp_params *p)
 {
     if (check_params(p) != MMK_OK) return 0;
-    return (size_t)p->B * ((p->N + ACC_THREADS - 1) / ACC_THREADS) * nacc(p->dim);
+    return (size_t)p->B * acc_blocks(p->N) * nacc(p->dim);
 }
-
-namespace {
-template <int DIM, int TYPE>
-int run_accumulate(const mmk_icp_params *p, const float *src, const float *tgt, const float *weight, const float *T,
-                   const unsigned long long *keys, int32_t *idx, double *partials, int32_t *status, hipStream_t st)
-{
-    const int nblk = (p->N + ACC_THREADS - 1) / ACC_THREADS;
-    hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE>), dim3(nblk, p->B), dim3(ACC_THREADS), 0, st, src, tgt, p->tgt_cols, weight,
-                       T, static_cast<const int32_t *>(nullptr), keys, static_cast<unsigned long long *>(nullptr),
-                       static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr), 1, 1, idx, p->N, p->M, p->loss,
-                       p->loss_k, p->loss_k * p->loss_k, p->trim_dist * p->trim_dist, p->trim_dist, p->trim_steep, partials, status,
-                       static_cast<const float *>(nullptr), 0, 0);
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
-}
-
-template <int DIM>
-int run_solve_update(const mmk_icp_params *p, const double *partials, const float *T_in, float *T_out, double *delta, double *A,
-                     const int32_t *active_in, int32_t *active_out, hipStream_t st)
-{
-    const int nblk = (p->N + ACC_THREADS - 1) / ACC_THREADS;
-    hipLaunchKernelGGL(icp_solve_kernel<DIM>, dim3(p->B), dim3(64), 0, st, partials, nblk, T_in, T_out, delta, A, active_in, active_out,
-                       p->tolerance);
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
-}
-}  // namespace
 
 extern "C" int mmk_icp_accumulate(const mmk_icp_params *p, const float *source, const float *target, const float *weight,
                                   const float *T, const uint64_t *nn_keys, int32_t *idx_out, double *partials, int32_t *status,
@@ -2553,10 +2529,18 @@ extern "C" int mmk_icp_accumulate(const mmk_icp_params *p, const float *source, 
     MMK_REQUIRE(source && target && T && nn_keys && idx_out && partials && status, "mmk_icp_accumulate: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(nn_keys);
-    if (p->dim == 2 && p->icp_type == MMK_ICP_PT2PT) return run_accumulate<2, MMK_ICP_PT2PT>(p, source, target, weight, T, keys, idx_out, partials, status, st);
-    if (p->dim == 2) return run_accumulate<2, MMK_ICP_PT2PL>(p, source, target, weight, T, keys, idx_out, partials, status, st);
-    if (p->icp_type == MMK_ICP_PT2PT) return run_accumulate<3, MMK_ICP_PT2PT>(p, source, target, weight, T, keys, idx_out, partials, status, st);
-    return run_accumulate<3, MMK_ICP_PT2PL>(p, source, target, weight, T, keys, idx_out, partials, status, st);
+    const RobustArgs r = robust_args(p);
+    // one step on its own: every pair active, no keys to arm for a next search, no zero-row bookkeeping, no hyper array
+    const int32_t *const none = nullptr;
+    unsigned long long *const no_next = nullptr;
+    const float *const no_hyper = nullptr;
+    with_dim_type(p->dim, p->icp_type, [&](auto D, auto TYPE) {
+        hipLaunchKernelGGL((icp_accumulate_kernel<D(), TYPE(), false>), dim3(acc_blocks(p->N), p->B), dim3(ACC_THREADS), 0, st, source,
+                           target, p->tgt_cols, weight, T, none, keys, no_next, none, none, 1, 1, idx_out, p->N, p->M, r.loss, r.k, r.k2,
+                           r.trim2, r.trim_dist, r.trim_steep, partials, status, no_hyper, 0, 0);
+    });
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
 }
 
 extern "C" int mmk_icp_solve_update(const mmk_icp_params *p, const double *partials, const float *T_in, float *T_out,
@@ -2565,63 +2549,74 @@ extern "C" int mmk_icp_solve_update(const mmk_icp_params *p, const double *parti
     int rc = check_params(p);
     if (rc != MMK_OK) return rc;
     MMK_REQUIRE(partials && T_in && T_out && delta_out && A_out && active_in && active_out, "mmk_icp_solve_update: NULL pointer");
-    if (p->dim == 2) return run_solve_update<2>(p, partials, T_in, T_out, delta_out, A_out, active_in, active_out, (hipStream_t)stream);
-    return run_solve_update<3>(p, partials, T_in, T_out, delta_out, A_out, active_in, active_out, (hipStream_t)stream);
+    with_dim(p->dim, [&](auto D) {
+        hipLaunchKernelGGL(icp_solve_kernel<D()>, dim3(p->B), dim3(64), 0, (hipStream_t)stream, partials, acc_blocks(p->N), T_in, T_out,
+                           delta_out, A_out, active_in, active_out, p->tolerance);
+    });
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
 }
 
+namespace {
+// The three backward entries.  `per_pair` is mmk_icp_backward_hp's argument (0 from the others); a gradient output an entry
+// does not have is NULL in `c` and its check holds.  `ws_code`: what the entry returns for a short workspace.
+int backward_impl(const char *who, int ws_code, const mmk_icp_params *p, const IcpCall &c, int per_pair, void *workspace,
+                  size_t workspace_bytes)
+{
+    int rc = check_params(p);
+    if (rc != MMK_OK) return rc;
+    MMK_REQUIRE(p->save_state, "%s: forward must have run with save_state = 1", who);
+    MMK_REQUIRE(c.source && c.target && c.idx_hist && c.T_hist && c.delta_hist && c.A_hist && c.active_hist && c.grad_T && c.grad_weight,
+                "%s: NULL pointer", who);
+    MMK_REQUIRE(per_pair == 0 || per_pair == 1, "%s: per_pair must be 0 or 1 (got %d)", who, per_pair);
+    MMK_REQUIRE(c.grad_hyper == nullptr || c.hyper != nullptr, "%s: grad_hyper needs hyper", who);
+    MMK_REQUIRE(c.grad_target == nullptr || p->max_iter <= 65535, "%s: the target gradient needs max_iter <= 65535 (got %d)", who,
+                p->max_iter);
+    const IcpBwdWs bw = carve_backward(p, c.grad_target != nullptr, c.hyper != nullptr, workspace, workspace_bytes);
+    rc = check_workspace(who, ws_code, workspace, workspace_bytes, bw.bytes);
+    if (rc != MMK_OK) return rc;
+    return with_dim_type(p->dim, p->icp_type, [&](auto D, auto TYPE) { return run_backward<D(), TYPE()>(p, c, bw); });
+}
+}  // namespace
+
+// No cloud and no hyper-parameter gradients; a short workspace is MMK_ERR_WORKSPACE.
 extern "C" int mmk_icp_backward(const mmk_icp_params *p, const float *source, const float *target,
                                 const float *weight, const int32_t *idx_hist, const float *T_hist,
                                 const double *delta_hist, const double *A_hist, const int32_t *active_hist,
                                 const float *grad_T, float *grad_weight, float *grad_T_init, void *workspace,
                                 size_t workspace_bytes, void *stream)
 {
-    int rc = check_params(p);
-    if (rc != MMK_OK) return rc;
-    MMK_REQUIRE(p->save_state, "mmk_icp_backward: forward must have run with save_state = 1");
-    MMK_REQUIRE(source && target && idx_hist && T_hist && delta_hist && A_hist && active_hist && grad_T && grad_weight,
-                "mmk_icp_backward: NULL pointer");
-    const IcpWs w = carve(p, workspace, workspace_bytes);
-    if (workspace == nullptr || w.bytes > workspace_bytes) {
-        mmk::set_error("mmk_icp_backward: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
-    return dispatch_backward(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight,
-                             grad_T_init, nullptr, nullptr, w, IcpPtsWs{nullptr, nullptr, nullptr, 0}, (hipStream_t)stream);
+    const IcpCall c{source, target, weight, writable(idx_hist), writable(T_hist), writable(delta_hist), writable(A_hist),
+                    writable(active_hist), (hipStream_t)stream, nullptr, 0, grad_T, grad_weight, grad_T_init};
+    return backward_impl("mmk_icp_backward", MMK_ERR_WORKSPACE, p, c, 0, workspace, workspace_bytes);
 }
 
 extern "C" size_t mmk_icp_backward_points_workspace_bytes(const mmk_icp_params *p, int32_t with_target)
 {
     if (check_params(p) != MMK_OK) return 0;
-    return carve_points(p, with_target != 0, nullptr, 0).bytes;
+    return carve_backward(p, with_target != 0, false, nullptr, 0).bytes;
 }
 
+// No hyper-parameter array or gradient; a short workspace is MMK_ERR_ARG.
 extern "C" int mmk_icp_backward_points(const mmk_icp_params *p, const float *source, const float *target,
                                        const float *weight, const int32_t *idx_hist, const float *T_hist,
                                        const double *delta_hist, const double *A_hist, const int32_t *active_hist,
                                        const float *grad_T, float *grad_weight, float *grad_T_init, float *grad_source,
                                        float *grad_target, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_params(p);
-    if (rc != MMK_OK) return rc;
-    MMK_REQUIRE(p->save_state, "mmk_icp_backward_points: forward must have run with save_state = 1");
-    MMK_REQUIRE(source && target && idx_hist && T_hist && delta_hist && A_hist && active_hist && grad_T && grad_weight,
-                "mmk_icp_backward_points: NULL pointer");
-    MMK_REQUIRE(grad_target == nullptr || p->max_iter <= 65535,
-                "mmk_icp_backward_points: the target gradient needs max_iter <= 65535 (got %d)", p->max_iter);
-    const IcpPtsWs pw = carve_points(p, grad_target != nullptr, workspace, workspace_bytes);
-    MMK_REQUIRE(workspace != nullptr && pw.bytes <= workspace_bytes, "mmk_icp_backward_points: workspace too small (%zu < %zu bytes)",
-                workspace_bytes, pw.bytes);
-    const IcpWs w = carve(p, workspace, workspace_bytes);
-    return dispatch_backward(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight,
-                             grad_T_init, grad_source, grad_target, w, pw, (hipStream_t)stream);
+    const IcpCall c{source, target, weight, writable(idx_hist), writable(T_hist), writable(delta_hist), writable(A_hist),
+                    writable(active_hist), (hipStream_t)stream, nullptr, 0, grad_T, grad_weight, grad_T_init, grad_source, grad_target};
+    return backward_impl("mmk_icp_backward_points", MMK_ERR_ARG, p, c, 0, workspace, workspace_bytes);
 }
 
 extern "C" size_t mmk_icp_backward_hp_workspace_bytes(const mmk_icp_params *p, int32_t with_target, int32_t with_hyper)
 {
     if (check_params(p) != MMK_OK) return 0;
-    return carve_hyper(p, with_target != 0, with_hyper != 0, nullptr, 0).bytes;
+    return carve_backward(p, with_target != 0, with_hyper != 0, nullptr, 0).bytes;
 }
 
+// Every gradient the caller passes; hyper NULL: the scalars of p (grad_hyper then must be NULL).  A short workspace is
+// MMK_ERR_ARG.
 extern "C" int mmk_icp_backward_hp(const mmk_icp_params *p, const float *source, const float *target,
                                    const float *weight, const int32_t *idx_hist, const float *T_hist,
                                    const double *delta_hist, const double *A_hist, const int32_t *active_hist,
@@ -2629,23 +2624,8 @@ extern "C" int mmk_icp_backward_hp(const mmk_icp_params *p, const float *source,
                                    float *grad_target, const float *hyper, int32_t per_pair, float *grad_hyper,
                                    void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_params(p);
-    if (rc != MMK_OK) return rc;
-    MMK_REQUIRE(p->save_state, "mmk_icp_backward_hp: forward must have run with save_state = 1");
-    MMK_REQUIRE(source && target && idx_hist && T_hist && delta_hist && A_hist && active_hist && grad_T && grad_weight,
-                "mmk_icp_backward_hp: NULL pointer");
-    MMK_REQUIRE(per_pair == 0 || per_pair == 1, "mmk_icp_backward_hp: per_pair must be 0 or 1 (got %d)", per_pair);
-    MMK_REQUIRE(grad_hyper == nullptr || hyper != nullptr, "mmk_icp_backward_hp: grad_hyper needs hyper");
-    MMK_REQUIRE(grad_target == nullptr || p->max_iter <= 65535,
-                "mmk_icp_backward_hp: the target gradient needs max_iter <= 65535 (got %d)", p->max_iter);
-    IcpHyper hy = carve_hyper(p, grad_target != nullptr, hyper != nullptr, workspace, workspace_bytes);
-    MMK_REQUIRE(workspace != nullptr && hy.bytes <= workspace_bytes, "mmk_icp_backward_hp: workspace too small (%zu < %zu bytes)",
-                workspace_bytes, hy.bytes);
-    hy.hyper = hyper;
-    hy.hstride = per_pair ? 3 : 0;
-    hy.grad_hyper = grad_hyper;
-    const IcpPtsWs pw = carve_points(p, grad_target != nullptr, workspace, workspace_bytes);
-    const IcpWs w = carve(p, workspace, workspace_bytes);
-    return dispatch_backward(p, source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, grad_T, grad_weight,
-                             grad_T_init, grad_source, grad_target, w, pw, (hipStream_t)stream, hy);
+    const IcpCall c{source, target, weight, writable(idx_hist), writable(T_hist), writable(delta_hist), writable(A_hist),
+                    writable(active_hist), (hipStream_t)stream, hyper, per_pair ? 3 : 0, grad_T, grad_weight, grad_T_init,
+                    grad_source, grad_target, grad_hyper};
+    return backward_impl("mmk_icp_backward_hp", MMK_ERR_ARG, p, c, per_pair, workspace, workspace_bytes);
 }

@@ -177,22 +177,47 @@ def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False):
     st = _state_buffers(p, dev)
     T_out = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
     iters = ctypes.c_int(0)
+    args = [ctypes.byref(p), _lib.ptr(src, torch.float32, "source"), _lib.ptr(tgt, torch.float32, "target"),
+            _lib.ptr(weight, torch.float32, "weight"), _lib.ptr(T_init, torch.float32, "T_init"), _lib.ptr(T_out),
+            _lib.ptr(st["idx"]), _lib.ptr(st["T"]), _lib.ptr(st["delta"]), _lib.ptr(st["A"]), _lib.ptr(st["active"])]
+    entry = L.mmk_icp_forward
     if hyper is not None:
-        _lib.check(L.mmk_icp_forward_hp(ctypes.byref(p), _lib.ptr(src, torch.float32, "source"),
-                                        _lib.ptr(tgt, torch.float32, "target"), _lib.ptr(weight, torch.float32, "weight"),
-                                        _lib.ptr(T_init, torch.float32, "T_init"), _lib.ptr(T_out), _lib.ptr(st["idx"]),
-                                        _lib.ptr(st["T"]), _lib.ptr(st["delta"]), _lib.ptr(st["A"]), _lib.ptr(st["active"]),
-                                        _lib.ptr(hyper), 1 if per_pair else 0, _lib.ptr(ws), ws.numel(), ctypes.byref(iters),
-                                        _lib.stream_ptr(dev)))
-        _status.watch(p, ws, dev)
-        return T_out, st, iters.value
-    _lib.check(L.mmk_icp_forward(ctypes.byref(p), _lib.ptr(src, torch.float32, "source"),
-                                 _lib.ptr(tgt, torch.float32, "target"), _lib.ptr(weight, torch.float32, "weight"),
-                                 _lib.ptr(T_init, torch.float32, "T_init"), _lib.ptr(T_out), _lib.ptr(st["idx"]),
-                                 _lib.ptr(st["T"]), _lib.ptr(st["delta"]), _lib.ptr(st["A"]), _lib.ptr(st["active"]),
-                                 _lib.ptr(ws), ws.numel(), ctypes.byref(iters), _lib.stream_ptr(dev)))
+        entry = L.mmk_icp_forward_hp
+        args += [_lib.ptr(hyper), 1 if per_pair else 0]
+    _lib.check(entry(*args, _lib.ptr(ws), ws.numel(), ctypes.byref(iters), _lib.stream_ptr(dev)))
     _status.watch(p, ws, dev)
     return T_out, st, iters.value
+
+
+def _backward(ctx, grad_T, hyper, per_pair, need_h):
+    """The reverse sweep of both autograd functions -> (gw, gT0, gs, gt, gh); ``hyper`` None: a call with numbers only,
+    ``need_h``: a hyper-parameter gradient is asked for.  mmk_icp_backward on the cached workspace when neither a cloud nor
+    a hyper-parameter is involved; else mmk_icp_backward_points (no ``hyper``) or mmk_icp_backward_hp, whose scratch holds
+    per-point rows and fixed-point sums for the target as well and is sized per call, not cached."""
+    weight, src, tgt, idx, T_hist, delta, A, active = ctx.saved_tensors[:8]
+    p = ctx.p
+    L = _lib.lib()
+    dev = src.device
+    gT = grad_T.contiguous().float()
+    gw = torch.empty(p.B, p.N, dtype=torch.float32, device=dev)
+    gT0 = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
+    need_src, need_tgt = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+    state = [ctypes.byref(p)] + [_lib.ptr(t) for t in (src, tgt, weight, idx, T_hist, delta, A, active, gT, gw, gT0)]
+    if hyper is None and not (need_src or need_tgt):
+        ws = _workspace(L.mmk_icp_workspace_bytes(ctypes.byref(p)), dev)
+        _lib.check(L.mmk_icp_backward(*state, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return gw, gT0, None, None, None
+    if hyper is None:
+        entry, nbytes = L.mmk_icp_backward_points, L.mmk_icp_backward_points_workspace_bytes(state[0], 1 if need_tgt else 0)
+    else:
+        entry, nbytes = L.mmk_icp_backward_hp, L.mmk_icp_backward_hp_workspace_bytes(state[0], 1 if need_tgt else 0, 1)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    gs = torch.empty(p.B, p.N, 3, dtype=torch.float32, device=dev) if need_src else None
+    gt = torch.empty(p.B, p.M, p.tgt_cols, dtype=torch.float32, device=dev) if need_tgt else None
+    gh = torch.empty(p.B, 3, dtype=torch.float32, device=dev) if need_h else None
+    extra = [] if hyper is None else [_lib.ptr(hyper), 1 if per_pair else 0, _lib.ptr(gh)]
+    _lib.check(entry(*state, _lib.ptr(gs), _lib.ptr(gt), *extra, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    return gw, gT0, gs, gt, gh
 
 
 class _IcpFunction(torch.autograd.Function):
@@ -210,27 +235,7 @@ class _IcpFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_T):
-        weight, src, tgt, idx, T_hist, delta, A, active = ctx.saved_tensors
-        p = ctx.p
-        L = _lib.lib()
-        dev = src.device
-        gT = grad_T.contiguous().float()
-        gw = torch.empty(p.B, p.N, dtype=torch.float32, device=dev)
-        gT0 = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
-        need_src, need_tgt = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        state = [_lib.ptr(t) for t in (src, tgt, weight, idx, T_hist, delta, A, active, gT, gw, gT0)]
-        if not (need_src or need_tgt):
-            ws = _workspace(L.mmk_icp_workspace_bytes(ctypes.byref(p)), dev)
-            _lib.check(L.mmk_icp_backward(ctypes.byref(p), *state, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-            return gw, gT0, None, None, None
-        # the clouds' adjoints: the target's takes per-point rows and fixed-point sums as well (sized per call, not cached)
-        ws = torch.empty(int(L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(p), 1 if need_tgt else 0)),
-                         dtype=torch.uint8, device=dev)
-        gs = torch.empty(p.B, p.N, 3, dtype=torch.float32, device=dev) if need_src else None
-        gt = torch.empty(p.B, p.M, p.tgt_cols, dtype=torch.float32, device=dev) if need_tgt else None
-        _lib.check(L.mmk_icp_backward_points(ctypes.byref(p), *state, _lib.ptr(gs), _lib.ptr(gt), _lib.ptr(ws), ws.numel(),
-                                             _lib.stream_ptr(dev)))
-        return gw, gT0, gs, gt, None
+        return _backward(ctx, grad_T, None, False, False)[:4] + (None,)
 
 
 class _IcpHpFunction(torch.autograd.Function):
@@ -251,23 +256,9 @@ class _IcpHpFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_T):
-        weight, src, tgt, idx, T_hist, delta, A, active, hyper = ctx.saved_tensors
         p = ctx.p
-        L = _lib.lib()
-        dev = src.device
-        gT = grad_T.contiguous().float()
-        gw = torch.empty(p.B, p.N, dtype=torch.float32, device=dev)
-        gT0 = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
-        need_src, need_tgt = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         need_h = ctx.needs_input_grad[4:7]
-        state = [_lib.ptr(t) for t in (src, tgt, weight, idx, T_hist, delta, A, active, gT, gw, gT0)]
-        ws = torch.empty(int(L.mmk_icp_backward_hp_workspace_bytes(ctypes.byref(p), 1 if need_tgt else 0, 1)),
-                         dtype=torch.uint8, device=dev)
-        gs = torch.empty(p.B, p.N, 3, dtype=torch.float32, device=dev) if need_src else None
-        gt = torch.empty(p.B, p.M, p.tgt_cols, dtype=torch.float32, device=dev) if need_tgt else None
-        gh = torch.empty(p.B, 3, dtype=torch.float32, device=dev) if any(need_h) else None
-        _lib.check(L.mmk_icp_backward_hp(ctypes.byref(p), *state, _lib.ptr(gs), _lib.ptr(gt), _lib.ptr(hyper),
-                                         1 if ctx.per_pair else 0, _lib.ptr(gh), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        gw, gT0, gs, gt, gh = _backward(ctx, grad_T, ctx.saved_tensors[8], ctx.per_pair, any(need_h))
         gv = [None, None, None]
         for c in range(3):
             if need_h[c]:
@@ -321,14 +312,19 @@ class ICP:
         self.last_state = None
         self.last_iterations = None
 
-    def _trim_steep(self):
-        """mmk_icp_params.trim_steep of the instance's gate (attributes are assignable: validated at every use)."""
+    def _soft_gate(self):
+        """Whether the instance's gate is the tanh one (attributes are assignable: validated at every use)."""
         if self.trim not in ("hard", "tanh"):
             raise ValueError("dICP config: trim must be 'hard' or 'tanh' (got %r)" % (self.trim,))
+        return self.trim == "tanh"
+
+    def _trim_steep(self):
+        """mmk_icp_params.trim_steep of the instance's gate, validated like ``trim``."""
+        soft = self._soft_gate()
         steep = float(self.tanh_steepness)
         if not (steep > 0.0 and steep != float("inf")):
             raise ValueError("dICP config: tanh_steepness must be a finite number > 0 (got %r)" % (self.tanh_steepness,))
-        return steep if self.trim == "tanh" else 0.0
+        return steep if soft else 0.0
 
     def _params(self, B, N, M, tgt_cols, dim, loss_fn, trim_dist, save_state, on_device=False):
         """``on_device``: the metric, trim_dist and the steepness travel in the device array of the _hp entries; the struct
@@ -339,9 +335,7 @@ class ICP:
         if on_device:
             loss_k, trim_dist = 1.0, 0.0
             if isinstance(self.tanh_steepness, torch.Tensor):       # (no host validation of a tensor: the device flag replaces it)
-                if self.trim not in ("hard", "tanh"):
-                    raise ValueError("dICP config: trim must be 'hard' or 'tanh' (got %r)" % (self.trim,))
-                steep = 1.0 if self.trim == "tanh" else 0.0
+                steep = 1.0 if self._soft_gate() else 0.0
             else:
                 steep = self._trim_steep()
         else:
