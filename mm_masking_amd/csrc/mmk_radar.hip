@@ -1499,20 +1499,41 @@ inline int stream_blocks(size_t n) { return (int)std::min<size_t>((n + 2047) / 2
 }  // namespace
 
 // ================================================================================== C ABI
-extern "C" int mmk_cfar_mask(const float *raw, int32_t B, int32_t A, int32_t R, int32_t w2, int32_t guard,
-                             int32_t mincol, int32_t maxcol, float a_thresh, float b_thresh, int32_t diff,
-                             float steep_fact, float *mask, void *stream)
+static int check_workspace(const char *who, const void *ws, size_t have, size_t need)
 {
-    MMK_REQUIRE(raw && mask, "mmk_cfar_mask: NULL pointer");
-    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 1, "mmk_cfar_mask: raw_scans must be 3D with non-empty dims");
-    MMK_REQUIRE(w2 >= 1 && guard >= 0, "mmk_cfar_mask: bad window (w2=%d guard=%d)", w2, guard);
-    MMK_REQUIRE(mincol >= w2 + guard && maxcol <= R, "mmk_cfar_mask: column range [%d,%d) outside the row", mincol, maxcol);
-    const size_t smem = (size_t)(R + 1) * sizeof(double) + (size_t)R * sizeof(float);
-    MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask: R=%d does not fit the 160 KB LDS row buffer", R);
-    if (smem > 64 * 1024)
-        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)cfar_mask_kernel<CfarThVal>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int rows = A * B;
-    if (R <= 8 * CFAR_T && smem <= 40 * 1024) {
+    if (ws == nullptr || need > have) {
+        mmk::set_error("%s: workspace too small (%zu < %zu)", who, have, need);
+        return MMK_ERR_WORKSPACE;
+    }
+    return MMK_OK;
+}
+
+// What the four CFAR entries share: the scans, the window and the stream.
+struct CfarCall {
+    const float *raw;
+    int32_t B, A, R, w2, guard, mincol, maxcol;
+    float steep_fact;
+    hipStream_t st;
+    size_t smem;        // a row's dynamic LDS, the fp64 prefix array and the fp32 row: cfar_args fills it in
+};
+
+static int cfar_args(const char *who, CfarCall &c)
+{
+    MMK_REQUIRE(c.B >= 1 && c.A >= 1 && c.R >= 1, "%s: raw_scans must be 3D with non-empty dims", who);
+    MMK_REQUIRE(c.w2 >= 1 && c.guard >= 0, "%s: bad window (w2=%d guard=%d)", who, c.w2, c.guard);
+    MMK_REQUIRE(c.mincol >= c.w2 + c.guard && c.maxcol <= c.R, "%s: column range [%d,%d) outside the row", who, c.mincol, c.maxcol);
+    c.smem = (size_t)(c.R + 1) * sizeof(double) + (size_t)c.R * sizeof(float);
+    MMK_REQUIRE(c.smem <= 160 * 1024 - 64, "%s: R=%d does not fit the 160 KB LDS row buffer", who, c.R);
+    return MMK_OK;
+}
+
+template <class TH>
+static int launch_cfar_fwd(const CfarCall &c, TH thr, int32_t diff, float *mask)
+{
+    if (c.smem > 64 * 1024)
+        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)cfar_mask_kernel<TH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.smem));
+    const int rows = c.A * c.B;
+    if (c.R <= 8 * CFAR_T && c.smem <= 40 * 1024) {
         // persistent form: four blocks per CU (40 KB of LDS each), each with its next row in registers
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) {
@@ -1520,14 +1541,45 @@ extern "C" int mmk_cfar_mask(const float *raw, int32_t B, int32_t A, int32_t R, 
             if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
         }
         const int grid = std::min(rows, 4 * cus);
-        hipLaunchKernelGGL((cfar_mask_rows_kernel<8, CfarThVal>), dim3(grid), dim3(CFAR_T), smem, (hipStream_t)stream, raw, rows, R, w2,
-                           guard, mincol, maxcol, CfarThVal{a_thresh, b_thresh}, diff, steep_fact, mask);
+        hipLaunchKernelGGL((cfar_mask_rows_kernel<8, TH>), dim3(grid), dim3(CFAR_T), c.smem, c.st, c.raw, rows, c.R, c.w2, c.guard,
+                           c.mincol, c.maxcol, thr, diff, c.steep_fact, mask);
     } else {
-        hipLaunchKernelGGL(cfar_mask_kernel<CfarThVal>, dim3(A, B), dim3(CFAR_T), smem, (hipStream_t)stream, raw, R, w2, guard, mincol,
-                           maxcol, CfarThVal{a_thresh, b_thresh}, diff, steep_fact, mask);
+        hipLaunchKernelGGL(cfar_mask_kernel<TH>, dim3(c.A, c.B), dim3(CFAR_T), c.smem, c.st, c.raw, c.R, c.w2, c.guard, c.mincol,
+                           c.maxcol, thr, diff, c.steep_fact, mask);
     }
     MMK_LAUNCH_CHECK();
     return MMK_OK;
+}
+
+// grad_raw NULL (the pointer-threshold entry only): the kernel stops after its first pass.
+template <class TH>
+static int launch_cfar_bwd(const CfarCall &c, const float *grad_mask, TH thr, float *grad_raw)
+{
+    if (c.R <= 8 * CFAR_T) {
+        hipLaunchKernelGGL((cfar_mask_bwd_kernel<8, TH>), dim3(c.A, c.B), dim3(CFAR_T), c.smem, c.st, c.raw, grad_mask, c.R, c.w2,
+                           c.guard, c.mincol, c.maxcol, thr, c.steep_fact, grad_raw);
+    } else {
+        // the longest row of the LDS budget: (160 KB - 64) / 12 B = 13 648 cells = 26.7 per thread
+        constexpr int NLONG = 27;
+        static_assert((size_t)NLONG * CFAR_T * 12 >= 160 * 1024, "cfar_mask_bwd_kernel<NLONG> must hold every row the LDS admits");
+        if (c.smem > 64 * 1024)
+            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)(cfar_mask_bwd_kernel<NLONG, TH>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)c.smem));
+        hipLaunchKernelGGL((cfar_mask_bwd_kernel<NLONG, TH>), dim3(c.A, c.B), dim3(CFAR_T), c.smem, c.st, c.raw, grad_mask, c.R, c.w2,
+                           c.guard, c.mincol, c.maxcol, thr, c.steep_fact, grad_raw);
+    }
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_cfar_mask(const float *raw, int32_t B, int32_t A, int32_t R, int32_t w2, int32_t guard,
+                             int32_t mincol, int32_t maxcol, float a_thresh, float b_thresh, int32_t diff,
+                             float steep_fact, float *mask, void *stream)
+{
+    MMK_REQUIRE(raw && mask, "mmk_cfar_mask: NULL pointer");
+    CfarCall c{raw, B, A, R, w2, guard, mincol, maxcol, steep_fact, (hipStream_t)stream, 0};
+    if (int rc = cfar_args("mmk_cfar_mask", c)) return rc;
+    return launch_cfar_fwd(c, CfarThVal{a_thresh, b_thresh}, diff, mask);
 }
 
 extern "C" int mmk_cfar_mask_p(const float *raw, int32_t B, int32_t A, int32_t R, int32_t w2, int32_t guard, int32_t mincol,
@@ -1536,30 +1588,9 @@ extern "C" int mmk_cfar_mask_p(const float *raw, int32_t B, int32_t A, int32_t R
 {
     MMK_REQUIRE(raw && mask, "mmk_cfar_mask_p: NULL pointer");
     MMK_REQUIRE(a_thresh && b_thresh, "mmk_cfar_mask_p: NULL threshold pointer");
-    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 1, "mmk_cfar_mask_p: raw_scans must be 3D with non-empty dims");
-    MMK_REQUIRE(w2 >= 1 && guard >= 0, "mmk_cfar_mask_p: bad window (w2=%d guard=%d)", w2, guard);
-    MMK_REQUIRE(mincol >= w2 + guard && maxcol <= R, "mmk_cfar_mask_p: column range [%d,%d) outside the row", mincol, maxcol);
-    const size_t smem = (size_t)(R + 1) * sizeof(double) + (size_t)R * sizeof(float);
-    MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask_p: R=%d does not fit the 160 KB LDS row buffer", R);
-    if (smem > 64 * 1024)
-        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)cfar_mask_kernel<CfarThPtr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const CfarThPtr thr{a_thresh, b_thresh, per_scan ? 1 : 0, A, nullptr};
-    const int rows = A * B;
-    if (R <= 8 * CFAR_T && smem <= 40 * 1024) {                     // the same choice of kernel as mmk_cfar_mask
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        }
-        const int grid = std::min(rows, 4 * cus);
-        hipLaunchKernelGGL((cfar_mask_rows_kernel<8, CfarThPtr>), dim3(grid), dim3(CFAR_T), smem, (hipStream_t)stream, raw, rows, R, w2, guard,
-                           mincol, maxcol, thr, diff, steep_fact, mask);
-    } else {
-        hipLaunchKernelGGL(cfar_mask_kernel<CfarThPtr>, dim3(A, B), dim3(CFAR_T), smem, (hipStream_t)stream, raw, R, w2, guard, mincol,
-                           maxcol, thr, diff, steep_fact, mask);
-    }
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
+    CfarCall c{raw, B, A, R, w2, guard, mincol, maxcol, steep_fact, (hipStream_t)stream, 0};
+    if (int rc = cfar_args("mmk_cfar_mask_p", c)) return rc;
+    return launch_cfar_fwd(c, CfarThPtr{a_thresh, b_thresh, per_scan ? 1 : 0, A, nullptr}, diff, mask);
 }
 
 extern "C" size_t mmk_cfar_mask_bwd_p_ws_bytes(int32_t B, int32_t A)
@@ -1575,32 +1606,28 @@ extern "C" int mmk_cfar_mask_bwd_p(const float *raw, const float *grad_mask, int
 {
     MMK_REQUIRE(raw && grad_mask && grad_a && grad_b, "mmk_cfar_mask_bwd_p: NULL pointer");
     MMK_REQUIRE(a_thresh && b_thresh, "mmk_cfar_mask_bwd_p: NULL threshold pointer");
-    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 1, "mmk_cfar_mask_bwd_p: raw_scans must be 3D with non-empty dims");
-    MMK_REQUIRE(w2 >= 1 && guard >= 0, "mmk_cfar_mask_bwd_p: bad window (w2=%d guard=%d)", w2, guard);
-    MMK_REQUIRE(mincol >= w2 + guard && maxcol <= R, "mmk_cfar_mask_bwd_p: column range [%d,%d) outside the row", mincol, maxcol);
-    const size_t smem = (size_t)(R + 1) * sizeof(double) + (size_t)R * sizeof(float);
-    MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask_bwd_p: R=%d does not fit the 160 KB LDS row buffer", R);
-    const size_t need = mmk_cfar_mask_bwd_p_ws_bytes(B, A);
-    if (workspace == nullptr || need > workspace_bytes) {
-        mmk::set_error("mmk_cfar_mask_bwd_p: workspace too small (%zu < %zu)", workspace_bytes, need);
-        return MMK_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
+    CfarCall c{raw, B, A, R, w2, guard, mincol, maxcol, steep_fact, (hipStream_t)stream, 0};
+    if (int rc = cfar_args("mmk_cfar_mask_bwd_p", c)) return rc;
+    if (int rc = check_workspace("mmk_cfar_mask_bwd_p", workspace, workspace_bytes, mmk_cfar_mask_bwd_p_ws_bytes(B, A))) return rc;
     double *part = static_cast<double *>(workspace);
-    const CfarThPtr thr{a_thresh, b_thresh, per_scan ? 1 : 0, A, part};
-    if (R <= 8 * CFAR_T) {
-        hipLaunchKernelGGL((cfar_mask_bwd_kernel<8, CfarThPtr>), dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard, mincol,
-                           maxcol, thr, steep_fact, grad_raw);
-    } else {
-        constexpr int NLONG = 27;                                   // as in mmk_cfar_mask_bwd
-        if (smem > 64 * 1024)
-            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)(cfar_mask_bwd_kernel<NLONG, CfarThPtr>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)smem));
-        hipLaunchKernelGGL((cfar_mask_bwd_kernel<NLONG, CfarThPtr>), dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard,
-                           mincol, maxcol, thr, steep_fact, grad_raw);
-    }
+    if (int rc = launch_cfar_bwd(c, grad_mask, CfarThPtr{a_thresh, b_thresh, per_scan ? 1 : 0, A, part}, grad_raw)) return rc;
+    hipLaunchKernelGGL(cfar_param_sum_kernel, dim3(per_scan ? B : 1), dim3(RT), 0, c.st, part, per_scan ? A : A * B, grad_a, grad_b);
     MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cfar_param_sum_kernel, dim3(per_scan ? B : 1), dim3(RT), 0, st, part, per_scan ? A : A * B, grad_a, grad_b);
+    return MMK_OK;
+}
+
+// The marker placement of a mask into `w`: count, scan, emit.  The backward runs it on the same mask to find the forward's points.
+static int launch_peaks_placement(const char *who, const float *mask, int32_t B, int32_t A, int32_t R, float res, int32_t diff,
+                                  float steep_fact, const PeakWs &w, hipStream_t st)
+{
+    const size_t row_lds = (size_t)R * sizeof(float);
+    MMK_REQUIRE(row_lds <= 64 * 1024 - 64, "%s: R=%d does not fit the LDS row buffer", who, R);
+    hipLaunchKernelGGL(peaks_count_kernel, dim3(A, B), dim3(RT), row_lds, st, mask, R, res, diff, steep_fact, w.row_count);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(peaks_scan_kernel, dim3(B), dim3(RT), 0, st, w.row_count, A, w.row_off, w.total);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(peaks_emit_kernel, dim3(A, B), dim3(RT), row_lds, st, mask, R, res, diff, steep_fact, w.row_off, w.cap,
+                       w.mval, w.mrow);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -1621,20 +1648,9 @@ extern "C" int mmk_extract_peaks(const float *mask, int32_t B, int32_t A, int32_
     MMK_REQUIRE(mask && azimuths && out_pc && out_count, "mmk_extract_peaks: NULL pointer");
     MMK_REQUIRE(B >= 1 && A >= 1 && R >= 2 && max_pts >= 1, "mmk_extract_peaks: bad shape");
     const PeakWs w = carve_peaks(B, A, max_pts, workspace, workspace_bytes);
-    if (workspace == nullptr || w.bytes > workspace_bytes) {
-        mmk::set_error("mmk_extract_peaks: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
+    if (int rc = check_workspace("mmk_extract_peaks", workspace, workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t row_lds = (size_t)R * sizeof(float);
-    MMK_REQUIRE(row_lds <= 64 * 1024 - 64, "mmk_extract_peaks: R=%d does not fit the LDS row buffer", R);
-    hipLaunchKernelGGL(peaks_count_kernel, dim3(A, B), dim3(RT), row_lds, st, mask, R, res, diff, steep_fact, w.row_count);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(peaks_scan_kernel, dim3(B), dim3(RT), 0, st, w.row_count, A, w.row_off, w.total);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(peaks_emit_kernel, dim3(A, B), dim3(RT), row_lds, st, mask, R, res, diff, steep_fact, w.row_off, w.cap,
-                       w.mval, w.mrow);
-    MMK_LAUNCH_CHECK();
+    if (int rc = launch_peaks_placement("mmk_extract_peaks", mask, B, A, R, res, diff, steep_fact, w, st)) return rc;
     hipLaunchKernelGGL(peaks_pair_kernel, dim3((max_pts + 255) / 256, B), dim3(256), 0, st, w.mval, w.mrow, w.cap,
                        w.total, azimuths, T_ab, A, max_pts, out_pc, out_count);
     MMK_LAUNCH_CHECK();
@@ -1646,27 +1662,9 @@ extern "C" int mmk_cfar_mask_bwd(const float *raw, const float *grad_mask, int32
                                  float steep_fact, float *grad_raw, void *stream)
 {
     MMK_REQUIRE(raw && grad_mask && grad_raw, "mmk_cfar_mask_bwd: NULL pointer");
-    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 1, "mmk_cfar_mask_bwd: raw_scans must be 3D with non-empty dims");
-    MMK_REQUIRE(w2 >= 1 && guard >= 0, "mmk_cfar_mask_bwd: bad window (w2=%d guard=%d)", w2, guard);
-    MMK_REQUIRE(mincol >= w2 + guard && maxcol <= R, "mmk_cfar_mask_bwd: column range [%d,%d) outside the row", mincol, maxcol);
-    const size_t smem = (size_t)(R + 1) * sizeof(double) + (size_t)R * sizeof(float);
-    MMK_REQUIRE(smem <= 160 * 1024 - 64, "mmk_cfar_mask_bwd: R=%d does not fit the 160 KB LDS row buffer", R);
-    hipStream_t st = (hipStream_t)stream;
-    if (R <= 8 * CFAR_T) {
-        hipLaunchKernelGGL((cfar_mask_bwd_kernel<8, CfarThVal>), dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard, mincol,
-                           maxcol, CfarThVal{a_thresh, b_thresh}, steep_fact, grad_raw);
-    } else {
-        // the longest row of the LDS budget: (160 KB - 64) / 12 B = 13 648 cells = 26.7 per thread
-        constexpr int NLONG = 27;
-        static_assert((size_t)NLONG * CFAR_T * 12 >= 160 * 1024, "cfar_mask_bwd_kernel<NLONG> must hold every row the LDS admits");
-        if (smem > 64 * 1024)
-            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)(cfar_mask_bwd_kernel<NLONG, CfarThVal>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)smem));
-        hipLaunchKernelGGL((cfar_mask_bwd_kernel<NLONG, CfarThVal>), dim3(A, B), dim3(CFAR_T), smem, st, raw, grad_mask, R, w2, guard,
-                           mincol, maxcol, CfarThVal{a_thresh, b_thresh}, steep_fact, grad_raw);
-    }
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
+    CfarCall c{raw, B, A, R, w2, guard, mincol, maxcol, steep_fact, (hipStream_t)stream, 0};
+    if (int rc = cfar_args("mmk_cfar_mask_bwd", c)) return rc;
+    return launch_cfar_bwd(c, grad_mask, CfarThVal{a_thresh, b_thresh}, grad_raw);
 }
 
 extern "C" size_t mmk_extract_peaks_bwd_workspace_bytes(int32_t B, int32_t A, int32_t R, int32_t max_pts)
@@ -1683,29 +1681,34 @@ extern "C" int mmk_extract_peaks_bwd(const float *mask, int32_t B, int32_t A, in
     MMK_REQUIRE(mask && azimuths && grad_pc && grad_mask, "mmk_extract_peaks_bwd: NULL pointer");
     MMK_REQUIRE(B >= 1 && A >= 1 && R >= 2 && max_pts >= 1, "mmk_extract_peaks_bwd: bad shape");
     const PeakBwdWs w = carve_peaks_bwd(B, A, max_pts, workspace, workspace_bytes);
-    if (workspace == nullptr || w.bytes > workspace_bytes) {
-        mmk::set_error("mmk_extract_peaks_bwd: workspace too small (%zu < %zu)", workspace_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
+    if (int rc = check_workspace("mmk_extract_peaks_bwd", workspace, workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t row_lds = (size_t)R * sizeof(float);
-    MMK_REQUIRE(row_lds <= 64 * 1024 - 64, "mmk_extract_peaks_bwd: R=%d does not fit the LDS row buffer", R);
-    if (2 * row_lds > 64 * 1024)
-        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)peaks_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)(2 * row_lds)));
-    // the forward's own placement: same kernels, same arguments
-    hipLaunchKernelGGL(peaks_count_kernel, dim3(A, B), dim3(RT), row_lds, st, mask, R, res, diff, steep_fact, w.f.row_count);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(peaks_scan_kernel, dim3(B), dim3(RT), 0, st, w.f.row_count, A, w.f.row_off, w.f.total);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(peaks_emit_kernel, dim3(A, B), dim3(RT), row_lds, st, mask, R, res, diff, steep_fact, w.f.row_off, w.f.cap,
-                       w.f.mval, w.f.mrow);
-    MMK_LAUNCH_CHECK();
+    if (int rc = launch_peaks_placement("mmk_extract_peaks_bwd", mask, B, A, R, res, diff, steep_fact, w.f, st)) return rc;
     hipLaunchKernelGGL(peaks_bwd_points_kernel, dim3((max_pts + 255) / 256, B), dim3(256), 0, st, w.f.mrow, w.f.cap, w.f.total,
                        azimuths, T_ab, A, max_pts, grad_pc, w.gv);
     MMK_LAUNCH_CHECK();
+    const size_t row_lds = (size_t)R * sizeof(float);
+    if (2 * row_lds > 64 * 1024)
+        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)peaks_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)(2 * row_lds)));
     hipLaunchKernelGGL(peaks_bwd_rows_kernel, dim3(A, B), dim3(RT), 2 * row_lds, st, mask, R, res, diff, steep_fact, w.f.row_off,
                        w.f.cap, w.gv, grad_mask);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+// One image (polar2 and cart2 NULL) or two that share their azimuths, in one launch.
+static int launch_polar_to_cart(const char *who, const float *polar, const float *polar2, const float *azimuths,
+                                const float *range_grid, const float *angle_grid, int32_t B, int32_t A, int32_t R, int32_t W,
+                                float radar_resolution, int32_t interpolate_crossover, int32_t fix_wobble, float *cart, float *cart2,
+                                void *stream)
+{
+    MMK_REQUIRE(B >= 1 && A >= 2 && R >= 2 && W >= 1, "%s: bad shape", who);
+    MMK_REQUIRE((size_t)A * 4 <= 64 * 1024, "%s: too many azimuths (%d)", who, A);
+    const float half_res = (float)((double)radar_resolution / 2.0);
+    hipLaunchKernelGGL(polar_to_cart_kernel, dim3(((W + 31) / 32) * ((W + 7) / 8), B), dim3(256), (size_t)A * 4, (hipStream_t)stream,
+                       polar, azimuths, range_grid, angle_grid, A, R, W, radar_resolution, half_res,
+                       interpolate_crossover ? 1 : 0, fix_wobble ? 1 : 0, cart, polar2, cart2);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -1716,14 +1719,18 @@ extern "C" int mmk_polar_to_cart(const float *polar, const float *azimuths, cons
                                  void *stream)
 {
     MMK_REQUIRE(polar && azimuths && range_grid && angle_grid && cart, "mmk_polar_to_cart: NULL pointer");
-    MMK_REQUIRE(B >= 1 && A >= 2 && R >= 2 && W >= 1, "mmk_polar_to_cart: bad shape");
-    MMK_REQUIRE((size_t)A * 4 <= 64 * 1024, "mmk_polar_to_cart: too many azimuths (%d)", A);
-    const float half_res = (float)((double)radar_resolution / 2.0);
-    hipLaunchKernelGGL(polar_to_cart_kernel, dim3(((W + 31) / 32) * ((W + 7) / 8), B), dim3(256), (size_t)A * 4, (hipStream_t)stream,
-                       polar, azimuths, range_grid, angle_grid, A, R, W, radar_resolution, half_res,
-                       interpolate_crossover ? 1 : 0, fix_wobble ? 1 : 0, cart, (const float *)nullptr, (float *)nullptr);
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
+    return launch_polar_to_cart("mmk_polar_to_cart", polar, nullptr, azimuths, range_grid, angle_grid, B, A, R, W, radar_resolution,
+                                interpolate_crossover, fix_wobble, cart, nullptr, stream);
+}
+
+extern "C" int mmk_polar_to_cart_pair(const float *polar, const float *polar2, const float *azimuths, const float *range_grid,
+                                      const float *angle_grid, int32_t B, int32_t A, int32_t R, int32_t W,
+                                      float radar_resolution, int32_t interpolate_crossover, int32_t fix_wobble, float *cart,
+                                      float *cart2, void *stream)
+{
+    MMK_REQUIRE(polar && polar2 && azimuths && range_grid && angle_grid && cart && cart2, "mmk_polar_to_cart_pair: NULL pointer");
+    return launch_polar_to_cart("mmk_polar_to_cart_pair", polar, polar2, azimuths, range_grid, angle_grid, B, A, R, W,
+                                radar_resolution, interpolate_crossover, fix_wobble, cart, cart2, stream);
 }
 
 extern "C" int mmk_cart_to_polar(const double *cart, const double *sin_az, const double *cos_az, const double *range_coords,
@@ -1737,6 +1744,22 @@ extern "C" int mmk_cart_to_polar(const double *cart, const double *sin_az, const
                        range_coords, A, R, H, W, cart_resolution, polar);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
+}
+
+// What every fixed-point scatter starts from: no maximum yet, all sums zero.
+static int clear_fixed_sums(unsigned *pmax, int32_t B, unsigned long long *acc, size_t words_per_item, hipStream_t st)
+{
+    MMK_CHECK_HIP(hipMemsetAsync(pmax, 0, sizeof(unsigned) * (size_t)B, st));
+    MMK_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * (size_t)B * words_per_item, st));
+    return MMK_OK;
+}
+
+// cnt_bits of the scatters along the rays: a ray crosses the 2 x 2 tap neighbourhood of a pixel (diagonal 2 sqrt 2 pixels) in at
+// most per_ray samples, and A rays meet on the centre pixels.
+static int ray_taps_bits(int32_t A, int32_t R, double radar_resolution, double cart_resolution)
+{
+    const double per_ray = std::min((double)R, ceil(2.0 * sqrt(2.0) * cart_resolution / radar_resolution) + 1.0);
+    return ceil_log2((double)A * per_ray);
 }
 
 extern "C" size_t mmk_polar_to_cart_bwd_ws_bytes(int32_t B, int32_t A, int32_t R, int32_t W)
@@ -1754,16 +1777,12 @@ extern "C" int mmk_polar_to_cart_bwd(const float *grad_cart, const float *azimut
     MMK_REQUIRE(B >= 1 && B <= 65535 && A >= 2 && R >= 2 && W >= 1 && W <= 16384, "mmk_polar_to_cart_bwd: bad shape");
     MMK_REQUIRE((size_t)A * 4 <= 64 * 1024, "mmk_polar_to_cart_bwd: too many azimuths (%d)", A);
     const ResampleBwdWs w = carve_resample_bwd(B, (size_t)B * A * R, ws, ws_bytes);
-    if (ws == nullptr || w.bytes > ws_bytes) {
-        mmk::set_error("mmk_polar_to_cart_bwd: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
+    if (int rc = check_workspace("mmk_polar_to_cart_bwd", ws, ws_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t ncart = (size_t)W * W, npolar = (size_t)A * R;
     const int cnt_bits = ceil_log2(4.0 * (double)ncart);               // every tap of every pixel on one cell
     const float half_res = (float)((double)radar_resolution / 2.0);
-    MMK_CHECK_HIP(hipMemsetAsync(w.pmax, 0, sizeof(unsigned) * (size_t)B, st));
-    MMK_CHECK_HIP(hipMemsetAsync(w.acc, 0, sizeof(unsigned long long) * (size_t)B * npolar, st));
+    if (int rc = clear_fixed_sums(w.pmax, B, w.acc, npolar, st)) return rc;
     hipLaunchKernelGGL(absmax_bits_kernel<float>, dim3(stream_blocks(ncart), B), dim3(256), 0, st, grad_cart, ncart, w.pmax);
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(polar_to_cart_bwd_scatter_kernel, dim3(((W + 31) / 32) * ((W + 7) / 8), B), dim3(256), (size_t)A * 4, st,
@@ -1791,18 +1810,12 @@ extern "C" int mmk_cart_to_polar_bwd(const double *grad_polar, const double *sin
     MMK_REQUIRE(A <= 65535, "mmk_cart_to_polar_bwd: too many azimuths (%d)", A);
     MMK_REQUIRE(cart_resolution > 0.0 && radar_resolution > 0.0, "mmk_cart_to_polar_bwd: resolutions must be positive");
     const ResampleBwdWs w = carve_resample_bwd(B, 0, ws, ws_bytes);
-    if (ws == nullptr || w.bytes > ws_bytes) {
-        mmk::set_error("mmk_cart_to_polar_bwd: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
+    if (int rc = check_workspace("mmk_cart_to_polar_bwd", ws, ws_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t ncart = (size_t)H * W, npolar = (size_t)A * R;
-    // a ray crosses the 2 x 2 tap neighbourhood of a pixel (diagonal 2 sqrt 2 pixels) in at most this many samples
-    const double per_ray = std::min((double)R, ceil(2.0 * sqrt(2.0) * cart_resolution / radar_resolution) + 1.0);
-    const int cnt_bits = ceil_log2((double)A * per_ray);
+    const int cnt_bits = ray_taps_bits(A, R, radar_resolution, cart_resolution);
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(grad_cart);
-    MMK_CHECK_HIP(hipMemsetAsync(w.pmax, 0, sizeof(unsigned) * (size_t)B, st));
-    MMK_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * (size_t)B * ncart, st));
+    if (int rc = clear_fixed_sums(w.pmax, B, acc, ncart, st)) return rc;
     hipLaunchKernelGGL(absmax_bits_kernel<double>, dim3(stream_blocks(npolar), B), dim3(256), 0, st, grad_polar, npolar, w.pmax);
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(cart_to_polar_bwd_scatter_kernel, dim3((R + 255) / 256, A, B), dim3(256), 0, st, grad_polar, sin_az, cos_az,
@@ -1852,15 +1865,9 @@ extern "C" int mmk_mask_polar_scan_bwd(const float *grad_out, const float *scan,
         return MMK_OK;
     }
     const ResampleBwdWs w = carve_resample_bwd(B, (size_t)B * ncart, ws, ws_bytes);
-    if (ws == nullptr || w.bytes > ws_bytes) {
-        mmk::set_error("mmk_mask_polar_scan_bwd: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
-        return MMK_ERR_WORKSPACE;
-    }
-    // mmk_cart_to_polar_bwd's bound on the taps that meet on one pixel
-    const double per_ray = std::min((double)R, ceil(2.0 * sqrt(2.0) * cart_resolution / radar_resolution) + 1.0);
-    const int cnt_bits = ceil_log2((double)A * per_ray);
-    MMK_CHECK_HIP(hipMemsetAsync(w.pmax, 0, sizeof(unsigned) * (size_t)B, st));
-    MMK_CHECK_HIP(hipMemsetAsync(w.acc, 0, sizeof(unsigned long long) * (size_t)B * ncart, st));
+    if (int rc = check_workspace("mmk_mask_polar_scan_bwd", ws, ws_bytes, w.bytes)) return rc;
+    const int cnt_bits = ray_taps_bits(A, R, radar_resolution, cart_resolution);
+    if (int rc = clear_fixed_sums(w.pmax, B, w.acc, ncart, st)) return rc;
     hipLaunchKernelGGL(mask_polar_scan_absmax_kernel, dim3(stream_blocks(npolar), B), dim3(256), 0, st, grad_out, scan, npolar, w.pmax);
     MMK_LAUNCH_CHECK();
     hipLaunchKernelGGL(mask_polar_scan_bwd_kernel, cells, dim3(256), 0, st, grad_out, scan, mask_cart, sin_az, cos_az, range_coords, A,
@@ -1872,19 +1879,52 @@ extern "C" int mmk_mask_polar_scan_bwd(const float *grad_out, const float *scan,
     return MMK_OK;
 }
 
-extern "C" int mmk_polar_to_cart_pair(const float *polar, const float *polar2, const float *azimuths, const float *range_grid,
-                                      const float *angle_grid, int32_t B, int32_t A, int32_t R, int32_t W,
-                                      float radar_resolution, int32_t interpolate_crossover, int32_t fix_wobble, float *cart,
-                                      float *cart2, void *stream)
+// The chains of the ordered scatter, next | val | pix | res: one word per (point, tap) in each array.
+struct ChainWs {
+    int *next, *pix;
+    float *val, *res;
+    size_t bytes;
+};
+
+static ChainWs carve_chains(int32_t B, int32_t N, void *ws)
 {
-    MMK_REQUIRE(polar && polar2 && azimuths && range_grid && angle_grid && cart && cart2, "mmk_polar_to_cart_pair: NULL pointer");
-    MMK_REQUIRE(B >= 1 && A >= 2 && R >= 2 && W >= 1, "mmk_polar_to_cart_pair: bad shape");
-    MMK_REQUIRE((size_t)A * 4 <= 64 * 1024, "mmk_polar_to_cart_pair: too many azimuths (%d)", A);
-    const float half_res = (float)((double)radar_resolution / 2.0);
-    hipLaunchKernelGGL(polar_to_cart_kernel, dim3(((W + 31) / 32) * ((W + 7) / 8), B), dim3(256), (size_t)A * 4, (hipStream_t)stream,
-                       polar, azimuths, range_grid, angle_grid, A, R, W, radar_resolution, half_res,
-                       interpolate_crossover ? 1 : 0, fix_wobble ? 1 : 0, cart, polar2, cart2);
+    const size_t ne = (size_t)B * N * 4;
+    ChainWs c;
+    c.next = static_cast<int *>(ws);
+    c.val = reinterpret_cast<float *>(c.next + ne);
+    c.pix = reinterpret_cast<int *>(c.val + ne);
+    c.res = reinterpret_cast<float *>(c.pix + ne);
+    c.bytes = 4 * ne * sizeof(float);
+    return c;
+}
+
+// The ordered scatter of either sampler into its (B, rows, cols) image: link needs `lds_bytes` for what geom.stage brings in.
+template <class Geom>
+static int run_sample_weights_bwd(const char *who, const Geom &geom, int32_t rows, int32_t cols, size_t lds_bytes,
+                                  const float *grad_weights, const float *pc, int32_t B, int32_t N, int32_t pc_cols, float *grad_mask,
+                                  void *ws, size_t ws_bytes, hipStream_t st)
+{
+    MMK_REQUIRE((size_t)N * 4 < ((size_t)1 << 30) && (size_t)rows * cols < ((size_t)1 << 31), "%s: shape too large", who);
+    const ChainWs c = carve_chains(B, N, ws);
+    MMK_REQUIRE(ws_bytes >= c.bytes, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, c.bytes);
+    MMK_CHECK_HIP(hipMemsetAsync(grad_mask, 0, sizeof(float) * (size_t)B * rows * cols, st));
+    const dim3 grid((4 * N + 255) / 256, B);
+    hipLaunchKernelGGL(sample_weights_bwd_link_kernel<Geom>, grid, dim3(256), lds_bytes, st, grad_weights, pc, N, pc_cols, geom,
+                       grad_mask, c.next, c.val, c.pix);
     MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sample_weights_bwd_sum_kernel, grid, dim3(256), 0, st, N, rows, cols, grad_mask, c.next, c.val, c.pix, c.res);
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sample_weights_bwd_store_kernel, grid, dim3(256), 0, st, N, rows, cols, c.pix, c.res, grad_mask);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+// Argument checks shared by the three Cartesian sampler entries; on success `g` holds the launch's geometry.
+static int cart_weight_geom(const char *who, int32_t B, int32_t N, int32_t pc_cols, int32_t H, int32_t W, int32_t cart_pixel_width,
+                            float cart_resolution, CartWeightGeom &g)
+{
+    MMK_REQUIRE(B >= 1 && N >= 1 && pc_cols >= 2 && H >= 2 && W >= 2 && cart_pixel_width >= 2, "%s: bad shape", who);
+    g = CartWeightGeom{H, W, cart_pixel_width, cart_resolution};
     return MMK_OK;
 }
 
@@ -1893,17 +1933,17 @@ extern "C" int mmk_sample_weights_fwd(const float *mask, const float *pc, int32_
                                       float *weights, void *stream)
 {
     MMK_REQUIRE(mask && pc && weights, "mmk_sample_weights_fwd: NULL pointer");
-    MMK_REQUIRE(B >= 1 && N >= 1 && pc_cols >= 2 && H >= 2 && W >= 2 && cart_pixel_width >= 2,
-                "mmk_sample_weights_fwd: bad shape");
+    CartWeightGeom g;
+    if (int rc = cart_weight_geom("mmk_sample_weights_fwd", B, N, pc_cols, H, W, cart_pixel_width, cart_resolution, g)) return rc;
     hipLaunchKernelGGL(sample_weights_fwd_kernel, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, mask, pc, N,
-                       pc_cols, H, W, cart_pixel_width, cart_resolution, weights);
+                       pc_cols, g.H, g.W, g.cw, g.cres, weights);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
 
 extern "C" size_t mmk_sample_weights_bwd_ws_bytes(int32_t B, int32_t N)
 {
-    return B < 1 || N < 1 ? 0 : (size_t)B * N * 4 * 4 * sizeof(float);       // next | val | pix | res, one word per (point, tap) each
+    return B < 1 || N < 1 ? 0 : carve_chains(B, N, nullptr).bytes;
 }
 
 extern "C" int mmk_sample_weights_bwd(const float *grad_weights, const float *pc, int32_t B, int32_t N, int32_t pc_cols,
@@ -1911,28 +1951,10 @@ extern "C" int mmk_sample_weights_bwd(const float *grad_weights, const float *pc
                                       float *grad_mask, void *ws, size_t ws_bytes, void *stream)
 {
     MMK_REQUIRE(grad_weights && pc && grad_mask && ws, "mmk_sample_weights_bwd: NULL pointer");
-    MMK_REQUIRE(B >= 1 && N >= 1 && pc_cols >= 2 && H >= 2 && W >= 2 && cart_pixel_width >= 2,
-                "mmk_sample_weights_bwd: bad shape");
-    MMK_REQUIRE((size_t)N * 4 < ((size_t)1 << 30) && (size_t)H * W < ((size_t)1 << 31), "mmk_sample_weights_bwd: shape too large");
-    MMK_REQUIRE(ws_bytes >= mmk_sample_weights_bwd_ws_bytes(B, N), "mmk_sample_weights_bwd: workspace too small (%zu < %zu bytes)",
-                ws_bytes, mmk_sample_weights_bwd_ws_bytes(B, N));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t ne = (size_t)B * N * 4;
-    int *next = static_cast<int *>(ws);
-    float *val = reinterpret_cast<float *>(next + ne);
-    int *pix = reinterpret_cast<int *>(val + ne);
-    float *res = reinterpret_cast<float *>(pix + ne);
-    MMK_CHECK_HIP(hipMemsetAsync(grad_mask, 0, sizeof(float) * (size_t)B * H * W, st));
-    const dim3 grid((4 * N + 255) / 256, B);
-    const CartWeightGeom geom{H, W, cart_pixel_width, cart_resolution};
-    hipLaunchKernelGGL(sample_weights_bwd_link_kernel<CartWeightGeom>, grid, dim3(256), 0, st, grad_weights, pc, N, pc_cols, geom,
-                       grad_mask, next, val, pix);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sample_weights_bwd_sum_kernel, grid, dim3(256), 0, st, N, H, W, grad_mask, next, val, pix, res);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sample_weights_bwd_store_kernel, grid, dim3(256), 0, st, N, H, W, pix, res, grad_mask);
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
+    CartWeightGeom g;
+    if (int rc = cart_weight_geom("mmk_sample_weights_bwd", B, N, pc_cols, H, W, cart_pixel_width, cart_resolution, g)) return rc;
+    return run_sample_weights_bwd("mmk_sample_weights_bwd", g, H, W, 0, grad_weights, pc, B, N, pc_cols, grad_mask, ws, ws_bytes,
+                                  (hipStream_t)stream);
 }
 
 extern "C" int mmk_sample_weights_bwd_pc(const float *grad_weights, const float *mask, const float *pc, int32_t B, int32_t N,
@@ -1940,15 +1962,15 @@ extern "C" int mmk_sample_weights_bwd_pc(const float *grad_weights, const float 
                                          float *grad_pc, void *stream)
 {
     MMK_REQUIRE(grad_weights && mask && pc && grad_pc, "mmk_sample_weights_bwd_pc: NULL pointer");
-    MMK_REQUIRE(B >= 1 && N >= 1 && pc_cols >= 2 && H >= 2 && W >= 2 && cart_pixel_width >= 2,
-                "mmk_sample_weights_bwd_pc: bad shape");
+    CartWeightGeom g;
+    if (int rc = cart_weight_geom("mmk_sample_weights_bwd_pc", B, N, pc_cols, H, W, cart_pixel_width, cart_resolution, g)) return rc;
     hipLaunchKernelGGL(sample_weights_bwd_pc_kernel, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, grad_weights, mask,
-                       pc, N, pc_cols, H, W, cart_pixel_width, cart_resolution, grad_pc);
+                       pc, N, pc_cols, g.H, g.W, g.cw, g.cres, grad_pc);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
 
-// Argument checks shared by the three polar sampler entries; on success `g` holds the launch's geometry.
+// The same for the three polar sampler entries.
 static int polar_weight_geom(const char *who, const float *azimuths, int32_t B, int32_t N, int32_t pc_cols, int32_t A, int32_t R,
                              float radar_resolution, int32_t interpolate_crossover, int32_t fix_wobble, PolarWeightGeom &g)
 {
@@ -1991,26 +2013,8 @@ extern "C" int mmk_sample_weights_polar_bwd(const float *grad_weights, const flo
     if (int rc = polar_weight_geom("mmk_sample_weights_polar_bwd", azimuths, B, N, pc_cols, A, R, radar_resolution,
                                    interpolate_crossover, fix_wobble, g))
         return rc;
-    MMK_REQUIRE((size_t)N * 4 < ((size_t)1 << 30), "mmk_sample_weights_polar_bwd: shape too large");
-    MMK_REQUIRE(ws_bytes >= mmk_sample_weights_polar_bwd_ws_bytes(B, N),
-                "mmk_sample_weights_polar_bwd: workspace too small (%zu < %zu bytes)", ws_bytes,
-                mmk_sample_weights_polar_bwd_ws_bytes(B, N));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t ne = (size_t)B * N * 4;
-    int *next = static_cast<int *>(ws);
-    float *val = reinterpret_cast<float *>(next + ne);
-    int *pix = reinterpret_cast<int *>(val + ne);
-    float *res = reinterpret_cast<float *>(pix + ne);
-    MMK_CHECK_HIP(hipMemsetAsync(grad_mask, 0, sizeof(float) * (size_t)B * A * R, st));
-    const dim3 grid((4 * N + 255) / 256, B);
-    hipLaunchKernelGGL(sample_weights_bwd_link_kernel<PolarWeightGeom>, grid, dim3(256), (size_t)A * 4, st, grad_weights, pc, N,
-                       pc_cols, g, grad_mask, next, val, pix);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sample_weights_bwd_sum_kernel, grid, dim3(256), 0, st, N, A, R, grad_mask, next, val, pix, res);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sample_weights_bwd_store_kernel, grid, dim3(256), 0, st, N, A, R, pix, res, grad_mask);
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
+    return run_sample_weights_bwd("mmk_sample_weights_polar_bwd", g, A, R, (size_t)A * 4, grad_weights, pc, B, N, pc_cols, grad_mask,
+                                  ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int mmk_sample_weights_polar_bwd_pc(const float *grad_weights, const float *mask, const float *pc, const float *azimuths,

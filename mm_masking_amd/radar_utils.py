@@ -48,6 +48,21 @@ def _workspace(nbytes, device):
     return buf
 
 
+def _sized_workspace(size_fn, device, *dims):
+    """The workspace, at least as large as the entry's own ``*_ws_bytes(*dims)`` asks."""
+    return _workspace(int(size_fn(*dims)), device)
+
+
+def _remember(ctx, *inputs):
+    """For the backward: the dtype and device the gradient of each input goes back in, and its shape (None: a number)."""
+    ctx.like = [(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else None for t in inputs]
+
+
+def _grads_back(ctx, grads, n_rest):
+    """``grads`` (None: not computed) in their inputs' dtype and on their device, then None for the ``n_rest`` constants."""
+    return tuple(None if g is None else g.to(device=like[1], dtype=like[0]) for g, like in zip(grads, ctx.like)) + (None,) * n_rest
+
+
 # ----------------------------------------------------------------------------- host-only helpers
 def load_pc_from_file(file_path, to_type=None, to_device="cpu"):
     """radar_utils.py:10-18: float32 x 6 per point."""
@@ -166,7 +181,7 @@ class _CartToPolar(torch.autograd.Function):
         out = _cart_to_polar_forward(x, s_az, c_az, rc, cart_resolution)
         ctx.save_for_backward(s_az, c_az, rc)
         ctx.args = (tuple(x.shape), float(radar_resolution), float(cart_resolution))
-        ctx.like = cart.device
+        _remember(ctx, cart)
         return _back(out, cart)
 
     @staticmethod
@@ -177,13 +192,12 @@ class _CartToPolar(torch.autograd.Function):
         dev = s_az.device
         g = g.detach().to(device=dev, dtype=torch.float64).contiguous()
         L = _lib.lib()
-        nbytes = int(L.mmk_cart_to_polar_bwd_ws_bytes(B, A, R, H, W))
-        ws = _workspace(nbytes, dev)
+        ws = _sized_workspace(L.mmk_cart_to_polar_bwd_ws_bytes, dev, B, A, R, H, W)
         gx = torch.empty(B, H, W, dtype=torch.float64, device=dev)
         _lib.check(L.mmk_cart_to_polar_bwd(_lib.ptr(g), _lib.ptr(s_az), _lib.ptr(c_az), _lib.ptr(rc), B, A, R, H, W,
                                            radar_resolution, cart_resolution, _lib.ptr(gx), _lib.ptr(ws), ws.numel(),
                                            _lib.stream_ptr(dev)))
-        return (gx.to(ctx.like),) + (None,) * 6
+        return _grads_back(ctx, (gx,), 6)
 
 
 def radar_cartesian_to_polar(cart, azimuths, radar_resolution, cart_resolution=0.2384, polar_pixel_shape=(400, 3360)):
@@ -230,7 +244,7 @@ class _MaskPolarScan(torch.autograd.Function):
         out = _mask_polar_scan_forward(x, m, s_az, c_az, rc, cart_resolution)
         ctx.save_for_backward(x, m, s_az, c_az, rc)
         ctx.args = (float(radar_resolution), float(cart_resolution))
-        ctx.like = ((scan.dtype, scan.device), (mask.dtype, mask.device))
+        _remember(ctx, scan, mask)
         return _back(out, scan)
 
     @staticmethod
@@ -242,15 +256,13 @@ class _MaskPolarScan(torch.autograd.Function):
         g = _lib.dev_f32(g, dev)
         want_scan, want_mask = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         L = _lib.lib()
-        ws = _workspace(int(L.mmk_mask_polar_scan_bwd_ws_bytes(B, A, R, H, W)), dev) if want_mask else None
+        ws = _sized_workspace(L.mmk_mask_polar_scan_bwd_ws_bytes, dev, B, A, R, H, W) if want_mask else None
         gx = torch.empty_like(x) if want_scan else None
         gm = torch.empty_like(m) if want_mask else None
         _lib.check(L.mmk_mask_polar_scan_bwd(_lib.ptr(g), _lib.ptr(x), _lib.ptr(m), _lib.ptr(s_az), _lib.ptr(c_az), _lib.ptr(rc),
                                              B, A, R, H, W, radar_resolution, cart_resolution, _lib.ptr(gx), _lib.ptr(gm),
                                              _lib.ptr(ws), ws.numel() if want_mask else 0, _lib.stream_ptr(dev)))
-        (sd, sdev), (md, mdev) = ctx.like
-        return (gx.to(device=sdev, dtype=sd) if want_scan else None, gm.to(device=mdev, dtype=md) if want_mask else None) \
-            + (None,) * 6
+        return _grads_back(ctx, (gx, gm), 6)
 
 
 def mask_polar_scan(scan, mask, azimuths, radar_resolution, cart_resolution=0.2384):
@@ -283,12 +295,17 @@ def cfar_cols(n_range, res, width=101, minr=2.0, maxr=80.0, guard=5):
     return w2, mincol, maxcol
 
 
-def _cfar_forward(x, w2, guard, mincol, maxcol, a_thresh, b_thresh, diff, steep_fact):
+def _cfar_forward(x, cols, a, b, diff, steep_fact):
+    """Thresholds that are numbers go to mmk_cfar_mask; device tensors (both, of equal length) go to mmk_cfar_mask_p."""
     B, A, R = x.shape
+    w2, guard, mincol, maxcol = cols
     out = torch.empty_like(x)
-    _lib.check(_lib.lib().mmk_cfar_mask(_lib.ptr(x), B, A, R, w2, guard, mincol, max(mincol, maxcol),
-                                        float(a_thresh), float(b_thresh), 1 if diff else 0, float(steep_fact),
-                                        _lib.ptr(out), _lib.stream_ptr(x.device)))
+    head = (_lib.ptr(x), B, A, R, w2, guard, mincol, max(mincol, maxcol))
+    tail = (1 if diff else 0, float(steep_fact), _lib.ptr(out), _lib.stream_ptr(x.device))
+    if torch.is_tensor(a):
+        _lib.check(_lib.lib().mmk_cfar_mask_p(*head, _lib.ptr(a), _lib.ptr(b), 1 if a.numel() > 1 else 0, *tail))
+    else:
+        _lib.check(_lib.lib().mmk_cfar_mask(*head, float(a), float(b), *tail))
     return out
 
 
@@ -299,10 +316,10 @@ class _CfarMask(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw_scans, dev, cols, a_thresh, b_thresh, steep_fact):
         x = _lib.dev_f32(raw_scans, dev)
-        out = _cfar_forward(x, *cols, a_thresh, b_thresh, True, steep_fact)
+        out = _cfar_forward(x, cols, a_thresh, b_thresh, True, steep_fact)
         ctx.save_for_backward(x)
         ctx.args = (cols, float(a_thresh), float(b_thresh), float(steep_fact))
-        ctx.like = (raw_scans.dtype, raw_scans.device)
+        _remember(ctx, raw_scans)
         return _back(out, raw_scans)
 
     @staticmethod
@@ -314,7 +331,7 @@ class _CfarMask(torch.autograd.Function):
         gx = torch.empty_like(x)
         _lib.check(_lib.lib().mmk_cfar_mask_bwd(_lib.ptr(x), _lib.ptr(g), B, A, R, w2, guard, mincol, max(mincol, maxcol),
                                                 a_thresh, b_thresh, steep_fact, _lib.ptr(gx), _lib.stream_ptr(x.device)))
-        return gx.to(device=ctx.like[1], dtype=ctx.like[0]), None, None, None, None, None
+        return _grads_back(ctx, (gx,), 5)
 
 
 def _cfar_threshold_sizes(a_thresh, b_thresh, B):
@@ -340,15 +357,6 @@ def _cfar_threshold_dev(v, n, dev):
     return torch.full((n,), float(v), dtype=torch.float32, device=dev)
 
 
-def _cfar_forward_p(x, w2, guard, mincol, maxcol, a, b, diff, steep_fact):
-    B, A, R = x.shape
-    out = torch.empty_like(x)
-    _lib.check(_lib.lib().mmk_cfar_mask_p(_lib.ptr(x), B, A, R, w2, guard, mincol, max(mincol, maxcol), _lib.ptr(a), _lib.ptr(b),
-                                          1 if a.numel() > 1 else 0, 1 if diff else 0, float(steep_fact), _lib.ptr(out),
-                                          _lib.stream_ptr(x.device)))
-    return out
-
-
 class _CfarMaskP(torch.autograd.Function):
     """cfar_mask(diff=True) with tensor thresholds (mmk_cfar_mask_p / mmk_cfar_mask_bwd_p): the scan's gradient of _CfarMask
     and the gradients autograd takes through ``thres = a_thresh * stat + b_thresh`` (radar_utils.py:56) with respect to the
@@ -358,10 +366,10 @@ class _CfarMaskP(torch.autograd.Function):
     def forward(ctx, raw_scans, a_thresh, b_thresh, dev, cols, steep_fact, n):
         x = _lib.dev_f32(raw_scans, dev)
         a, b = _cfar_threshold_dev(a_thresh, n, dev), _cfar_threshold_dev(b_thresh, n, dev)
-        out = _cfar_forward_p(x, *cols, a, b, True, steep_fact)
+        out = _cfar_forward(x, cols, a, b, True, steep_fact)
         ctx.save_for_backward(x, a, b)
         ctx.args = (cols, float(steep_fact))
-        ctx.like = [(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else None for t in (raw_scans, a_thresh, b_thresh)]
+        _remember(ctx, raw_scans, a_thresh, b_thresh)
         return _back(out, raw_scans)
 
     @staticmethod
@@ -374,20 +382,16 @@ class _CfarMaskP(torch.autograd.Function):
         L = _lib.lib()
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None       # NULL: the kernel stops after its first pass
         ga, gb = torch.empty_like(a), torch.empty_like(b)
-        ws = _workspace(int(L.mmk_cfar_mask_bwd_p_ws_bytes(B, A)), dev)
+        ws = _sized_workspace(L.mmk_cfar_mask_bwd_p_ws_bytes, dev, B, A)
         _lib.check(L.mmk_cfar_mask_bwd_p(_lib.ptr(x), _lib.ptr(g), B, A, R, w2, guard, mincol, max(mincol, maxcol), _lib.ptr(a),
                                          _lib.ptr(b), 1 if a.numel() > 1 else 0, steep_fact, _lib.ptr(gx), _lib.ptr(ga),
                                          _lib.ptr(gb), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
         grads = []
-        for need, like, val in zip(ctx.needs_input_grad[:3], ctx.like, (gx, ga, gb)):
-            if not need:
-                grads.append(None)
-                continue
-            dtype, device, shape = like
-            if val.numel() != int(np.prod(shape)):                          # a single value broadcast over the scans
+        for need, like, val in zip(ctx.needs_input_grad, ctx.like, (gx, ga, gb)):
+            if need and val.numel() != int(np.prod(like[2])):               # a single value broadcast over the scans
                 val = val.sum()
-            grads.append(val.reshape(shape).to(device=device, dtype=dtype))
-        return tuple(grads) + (None,) * 4
+            grads.append(val.reshape(like[2]) if need else None)
+        return _grads_back(ctx, grads, 4)
 
 
 def cfar_mask(raw_scans, res, width=101, minr=2.0, maxr=80.0, guard=5,
@@ -405,16 +409,14 @@ def cfar_mask(raw_scans, res, width=101, minr=2.0, maxr=80.0, guard=5,
     n = _cfar_threshold_sizes(a_thresh, b_thresh, raw_scans.shape[0]) if tensors else 0
     dev = _hip_device(raw_scans)
     w2, mincol, maxcol = cfar_cols(raw_scans.shape[2], res, width, minr, maxr, guard)
+    cols = (w2, guard, mincol, maxcol)
+    if diff and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (raw_scans, a_thresh, b_thresh)):
+        if tensors:
+            return _CfarMaskP.apply(raw_scans, a_thresh, b_thresh, dev, cols, steep_fact, n)
+        return _CfarMask.apply(raw_scans, dev, cols, a_thresh, b_thresh, steep_fact)
     if tensors:
-        if diff and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (raw_scans, a_thresh, b_thresh)):
-            return _CfarMaskP.apply(raw_scans, a_thresh, b_thresh, dev, (w2, guard, mincol, maxcol), steep_fact, n)
-        x = _lib.dev_f32(raw_scans, dev)
-        a, b = _cfar_threshold_dev(a_thresh, n, dev), _cfar_threshold_dev(b_thresh, n, dev)
-        return _back(_cfar_forward_p(x, w2, guard, mincol, maxcol, a, b, diff, steep_fact), raw_scans)
-    if diff and torch.is_grad_enabled() and raw_scans.requires_grad:
-        return _CfarMask.apply(raw_scans, dev, (w2, guard, mincol, maxcol), a_thresh, b_thresh, steep_fact)
-    x = _lib.dev_f32(raw_scans, dev)
-    return _back(_cfar_forward(x, w2, guard, mincol, maxcol, a_thresh, b_thresh, diff, steep_fact), raw_scans)
+        a_thresh, b_thresh = _cfar_threshold_dev(a_thresh, n, dev), _cfar_threshold_dev(b_thresh, n, dev)
+    return _back(_cfar_forward(_lib.dev_f32(raw_scans, dev), cols, a_thresh, b_thresh, diff, steep_fact), raw_scans)
 
 
 # ----------------------------------------------------------------------------- R3 + R4
@@ -422,8 +424,7 @@ def _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts):
     B, A, R = m.shape
     dev = m.device
     L = _lib.lib()
-    nbytes = L.mmk_extract_peaks_workspace_bytes(B, A, R, int(max_pts))
-    ws = _workspace(nbytes, dev)
+    ws = _sized_workspace(L.mmk_extract_peaks_workspace_bytes, dev, B, A, R, int(max_pts))
     pc = torch.empty(B, int(max_pts), 3, dtype=torch.float32, device=dev)
     cnt = torch.empty(B, dtype=torch.int32, device=dev)
     _lib.check(L.mmk_extract_peaks(_lib.ptr(m), B, A, R, float(res), _lib.ptr(az), _lib.ptr(tm), _lib.ptr(Tab),
@@ -441,7 +442,7 @@ class _ExtractPeaks(torch.autograd.Function):
         pc, cnt = _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts)
         ctx.save_for_backward(m, az, Tab)
         ctx.args = (float(res), 1 if diff else 0, float(steep_fact), int(max_pts))
-        ctx.like = (thres_mask.dtype, thres_mask.device)
+        _remember(ctx, thres_mask)
         ctx.mark_non_differentiable(cnt)
         return pc, cnt
 
@@ -453,12 +454,11 @@ class _ExtractPeaks(torch.autograd.Function):
         dev = m.device
         gpc = _lib.dev_f32(gpc, dev)
         L = _lib.lib()
-        nbytes = L.mmk_extract_peaks_bwd_workspace_bytes(B, A, R, max_pts)
-        ws = _workspace(nbytes, dev)
+        ws = _sized_workspace(L.mmk_extract_peaks_bwd_workspace_bytes, dev, B, A, R, max_pts)
         gm = torch.empty_like(m)
         _lib.check(L.mmk_extract_peaks_bwd(_lib.ptr(m), B, A, R, res, _lib.ptr(az), _lib.ptr(Tab), diff, steep_fact, max_pts,
                                            _lib.ptr(gpc), _lib.ptr(gm), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        return (gm.to(device=ctx.like[1], dtype=ctx.like[0]),) + (None,) * 8
+        return _grads_back(ctx, (gm,), 8)
 
 
 def extract_pc_padded(thres_mask, res, azimuth_angles, azimuth_times, max_pts, T_ab=None, diff=True,
@@ -516,7 +516,7 @@ class _PolarToCart(torch.autograd.Function):
         out = _polar_to_cart_forward(x, az, W, radar_resolution, interpolate_crossover, fix_wobble)
         ctx.save_for_backward(az)
         ctx.args = (tuple(x.shape), W, float(radar_resolution), 1 if interpolate_crossover else 0, 1 if fix_wobble else 0)
-        ctx.like = (fft_data.dtype, fft_data.device)
+        _remember(ctx, fft_data)
         return _back(out, fft_data)
 
     @staticmethod
@@ -527,12 +527,11 @@ class _PolarToCart(torch.autograd.Function):
         g = _lib.dev_f32(g, dev)
         rg, ag = _device_grids(W, dev)
         L = _lib.lib()
-        nbytes = int(L.mmk_polar_to_cart_bwd_ws_bytes(B, A, R, W))
-        ws = _workspace(nbytes, dev)
+        ws = _sized_workspace(L.mmk_polar_to_cart_bwd_ws_bytes, dev, B, A, R, W)
         gx = torch.empty(B, A, R, dtype=torch.float32, device=dev)
         _lib.check(L.mmk_polar_to_cart_bwd(_lib.ptr(g), _lib.ptr(az), _lib.ptr(rg), _lib.ptr(ag), B, A, R, W, radar_resolution,
                                            crossover, wobble, _lib.ptr(gx), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        return (gx.to(device=ctx.like[1], dtype=ctx.like[0]),) + (None,) * 6
+        return _grads_back(ctx, (gx,), 6)
 
 
 def radar_polar_to_cartesian_diff(fft_data, azimuths, radar_resolution, cart_resolution=0.2384, cart_pixel_width=640,
@@ -595,10 +594,9 @@ class _SampleWeights(torch.autograd.Function):
         B, H, W = ctx.shape
         gw = gw.contiguous().float()
         gmask = torch.empty(B, H, W, dtype=torch.float32, device=gw.device)
-        nb = int(_lib.lib().mmk_sample_weights_bwd_ws_bytes(B, pc.shape[1]))
-        ws = _workspace(nb, gw.device)
-        _lib.check(_lib.lib().mmk_sample_weights_bwd(_lib.ptr(gw), _lib.ptr(pc), B, pc.shape[1], pc.shape[2], H, W,
-                                                     ctx.cw, ctx.cres, _lib.ptr(gmask), _lib.ptr(ws), nb, _lib.stream_ptr(gw.device)))
+        ws = _sized_workspace(_lib.lib().mmk_sample_weights_bwd_ws_bytes, gw.device, B, pc.shape[1])
+        _lib.check(_lib.lib().mmk_sample_weights_bwd(_lib.ptr(gw), _lib.ptr(pc), B, pc.shape[1], pc.shape[2], H, W, ctx.cw, ctx.cres,
+                                                     _lib.ptr(gmask), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(gw.device)))
         gpc = None
         if ctx.needs_input_grad[1]:
             gpc = torch.empty_like(pc)
@@ -634,19 +632,24 @@ class _WeightStats(torch.autograd.Function):
         return g_diff * (2.5 / w.shape[0]) * (1 - t * t) * real, None
 
 
-def _extract_weights_stats(mask, scan_pc):
-    """extract_weights plus the raw statistics vector of mmk_weight_stats (the policy takes its
-    mean_all_pts from it)."""
+def _sample_with_stats(mask, scan_pc, sample):
+    """What both extract_weights return, plus the raw statistics vector of mmk_weight_stats (the policy takes its
+    mean_all_pts from it); ``sample(m, pc, dev)`` gives the weights of the device copies of the mask and the points."""
     dev = _hip_device(mask)
     m = mask if (mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous()) else \
         mask.to(device=dev, dtype=torch.float32).contiguous()
     pc = scan_pc.to(device=dev, dtype=torch.float32).contiguous()      # not detached: differentiable in x, y
-    # point_to_cart_idx's defaults (0.2384 m, 640 px) whatever the mask's shape: radar_utils.py:112
-    weights = _SampleWeights.apply(m, pc, 0.2384, 640)
+    weights = sample(m, pc, dev)
     diff_mean_num_non0, st = _WeightStats.apply(weights, pc)
     if not mask.is_cuda:
         weights = weights.to(mask.device)
     return (weights, diff_mean_num_non0, st[1], st[2], st[3], st[4]), st
+
+
+def _extract_weights_stats(mask, scan_pc):
+    """extract_weights plus the raw statistics vector."""
+    # point_to_cart_idx's defaults (0.2384 m, 640 px) whatever the mask's shape: radar_utils.py:112
+    return _sample_with_stats(mask, scan_pc, lambda m, pc, dev: _SampleWeights.apply(m, pc, 0.2384, 640))
 
 
 def extract_weights(mask, scan_pc):
@@ -687,10 +690,9 @@ class _SampleWeightsPolar(torch.autograd.Function):
         gmask = None
         if ctx.needs_input_grad[0]:
             gmask = torch.empty(B, A, R, dtype=torch.float32, device=gw.device)
-            nb = int(L.mmk_sample_weights_polar_bwd_ws_bytes(B, N))
-            ws = _workspace(nb, gw.device)
+            ws = _sized_workspace(L.mmk_sample_weights_polar_bwd_ws_bytes, gw.device, B, N)
             _lib.check(L.mmk_sample_weights_polar_bwd(_lib.ptr(gw), _lib.ptr(pc), _lib.ptr(az), B, N, cols, A, R, *ctx.args,
-                                                      _lib.ptr(gmask), _lib.ptr(ws), nb, _lib.stream_ptr(gw.device)))
+                                                      _lib.ptr(gmask), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(gw.device)))
         gpc = None
         if ctx.needs_input_grad[1]:
             gpc = torch.empty_like(pc)
@@ -705,16 +707,8 @@ def _extract_weights_polar_stats(mask, scan_pc, azimuths, radar_resolution, inte
         raise ValueError("mask must be (B,A,R) and scan_pc (B,N,>=2) (got %s and %s)" % (tuple(mask.shape), tuple(scan_pc.shape)))
     if tuple(azimuths.shape) != (mask.shape[0], mask.shape[1]):
         raise ValueError("azimuths must be (B, %d) (got %s)" % (mask.shape[1], tuple(azimuths.shape)))
-    dev = _hip_device(mask)
-    m = mask if (mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous()) else \
-        mask.to(device=dev, dtype=torch.float32).contiguous()
-    pc = scan_pc.to(device=dev, dtype=torch.float32).contiguous()      # not detached: differentiable in x, y
-    az = _lib.dev_f32(azimuths, dev)
-    weights = _SampleWeightsPolar.apply(m, pc, az, radar_resolution, interpolate_crossover, fix_wobble)
-    diff_mean_num_non0, st = _WeightStats.apply(weights, pc)
-    if not mask.is_cuda:
-        weights = weights.to(mask.device)
-    return (weights, diff_mean_num_non0, st[1], st[2], st[3], st[4]), st
+    return _sample_with_stats(mask, scan_pc, lambda m, pc, dev: _SampleWeightsPolar.apply(
+        m, pc, _lib.dev_f32(azimuths, dev), radar_resolution, interpolate_crossover, fix_wobble))
 
 
 def extract_weights_polar(mask, scan_pc, azimuths, radar_resolution, interpolate_crossover=True, fix_wobble=True):
