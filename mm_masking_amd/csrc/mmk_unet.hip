@@ -93,6 +93,83 @@ __host__ __device__ constexpr int conv_cm(int cin, int cout)
     return cout >= 64 ? 64 : (cout <= 16 ? 16 : cout);
 }
 
+// ---- host side: run-time value -> template argument, and what every launcher does before it launches
+// f(integral_constant<int, V>) for the V of the list that equals v; NO_KERNEL when none does (the caller's table has no such
+// shape: it reports that under its own name).  Everything inlines: no allocation, no type erasure per launch.
+constexpr int NO_KERNEL = -0x7fffffff;
+template <int... Vs, class F>
+int with_int(int v, F &&f)
+{
+    int rc = NO_KERNEL;
+    (void)((v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+    return rc;
+}
+
+template <class F>
+auto with_bool(bool b, F &&f)
+{
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <class F>
+auto with_bools(bool a, bool b, F &&f)
+{
+    return with_bool(a, [&](auto A) { return with_bool(b, [&](auto B) { return f(A, B); }); });
+}
+
+// Raises the dynamic-LDS limit of ONE kernel instantiation to `bytes`, once per device (the flag is a static of this
+// instantiation of the helper: an attribute set for <.., POOLG = false> says nothing about <.., POOLG = true>).  `needed` is the
+// caller's own condition.
+template <auto Kernel>
+hipError_t raise_lds_limit(bool needed, size_t bytes)
+{
+    static bool done[64] = {};
+    if (!needed) return hipSuccess;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && !done[dev & 63]) {
+        e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        done[dev & 63] = e == hipSuccess;
+    }
+    return e;
+}
+
+// Resident blocks per CU of one kernel instantiation (registers / LDS), 1..cap: asked once per device, behind the LDS limit
+// the kernel needs beyond 64 KB.
+template <auto Kernel>
+hipError_t blocks_per_cu(int threads, size_t smem, int cap, int *per_cu)
+{
+    static int cached[64] = {};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (cached[dev & 63] == 0) {
+        if ((e = raise_lds_limit<Kernel>(smem > 64 * 1024, smem)) != hipSuccess) return e;
+        int nblk = 0;
+        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, Kernel, threads, smem)) != hipSuccess) return e;
+        cached[dev & 63] = nblk < 1 ? 1 : (nblk > cap ? cap : nblk);
+    }
+    *per_cu = cached[dev & 63];
+    return hipSuccess;
+}
+
+// XCD-contiguous persistent grid: the tiles of a launch in 8 contiguous ranges, one per XCD (32 CUs each), so that halo rows
+// shared by neighbouring tiles hit that XCD's L2; `nb` blocks per XCD and channel group walk a range (grid = 8 * nb x groups).
+struct XcdGrid {
+    int tiles, total, per_xcd, nb;      // tiles per image, in all, per XCD; blocks per XCD
+    int rounds() const { return (per_xcd + nb - 1) / nb; }
+};
+inline XcdGrid xcd_grid(int B, int H, int W, int tile_h, int tile_w, int groups, int per_cu)
+{
+    XcdGrid g;
+    g.tiles = ((W + tile_w - 1) / tile_w) * ((H + tile_h - 1) / tile_h);
+    g.total = g.tiles * B;
+    g.per_xcd = (g.total + 7) / 8;
+    const int nb = (32 * per_cu) / groups;
+    g.nb = nb < 1 ? 1 : (nb > g.per_xcd ? g.per_xcd : nb);
+    return g;
+}
+
 // (tap, channel offset inside the chunk) of the 8 consecutive k values lane `l` holds in k-step `s`.
 template <int CK>
 __device__ __forceinline__ void kslot(int s, int l, int &tap, int &ch)
@@ -392,15 +469,7 @@ template <int CK, int CM, bool LK = false>
 int launch_conv(const ConvArgs &a, hipStream_t st)
 {
     const size_t smem = ((size_t)HT * WT * lds_pitch(CK) + (size_t)ksteps(CK) * (CM / 16) * 512) * sizeof(bf16);
-    if (smem > 64 * 1024) {
-        static bool attr_set[64] = {};   // per template instantiation and device
-        int dev = 0;
-        MMK_CHECK_HIP(hipGetDevice(&dev));
-        if (!attr_set[dev & 63]) {
-            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_kernel<CK, CM, LK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            attr_set[dev & 63] = true;
-        }
-    }
+    MMK_CHECK_HIP((raise_lds_limit<conv3x3_kernel<CK, CM, LK>>(smem > 64 * 1024, smem)));
     const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
     const int groups = (a.COUT + CM - 1) / CM;
     // persistent grid: as many blocks as the LDS footprint lets a CU hold, on 256 CUs
@@ -890,26 +959,12 @@ int launch_conv_ring(const ConvArgs &a, hipStream_t st)
 #else
     const size_t smem = ((size_t)2 * HT * WT * lds_pitch(CK) + (size_t)ksteps(CK) * (CM / 16) * 512) * sizeof(bf16);
 #endif
-    static int per_cu[64] = {};     // resident blocks per CU (registers / LDS), per device
-    int dev = 0;
-    MMK_CHECK_HIP(hipGetDevice(&dev));
-    if (per_cu[dev & 63] == 0) {
-        if (smem > 64 * 1024)
-            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8, POOLG>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        int nblk = 0;
-        MMK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8, POOLG>, CONV_THREADS,
-                                                                   smem));
-        per_cu[dev & 63] = nblk < 1 ? 1 : (nblk > 8 ? 8 : nblk);
-    }
-    const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
+    constexpr auto kernel = conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8, POOLG>;
+    int per_cu = 0;
+    MMK_CHECK_HIP(blocks_per_cu<kernel>(CONV_THREADS, smem, 8, &per_cu));
     const int groups = (a.COUT + CM - 1) / CM;
-    const int total = tiles * a.B;
-    const int per_xcd = (total + 7) / 8;
-    int nb = (32 * per_cu[dev & 63]) / groups;                 // blocks per XCD (32 CUs each)
-    nb = nb < 1 ? 1 : (nb > per_xcd ? per_xcd : nb);
-    hipLaunchKernelGGL((conv3x3_ring_kernel<CK, CM, RD, EPI, POOL, C8, POOLG>), dim3(8 * nb, groups), dim3(CONV_THREADS), smem, st, a, total,
-                       per_xcd);
+    const XcdGrid g = xcd_grid(a.B, a.H, a.W, TH, TW, groups, per_cu);
+    hipLaunchKernelGGL(kernel, dim3(8 * g.nb, groups), dim3(CONV_THREADS), smem, st, a, g.total, g.per_xcd);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -985,6 +1040,13 @@ struct DeepCfg {
     static constexpr size_t smem(int wchunks) { return smem_core(wchunks); }
 #endif
 };
+
+// the persistent grid of a deep launch: one 8-wave block per CU
+template <int BM, int NT>
+XcdGrid deep_grid(int B, int H, int W, int cout)
+{
+    return xcd_grid(B, H, W, DeepCfg<BM, NT>::TH, DeepCfg<BM, NT>::TWD, (cout + BM - 1) / BM, 1);
+}
 
 // Round 5.  What the round-4 kernel's stages spent their cycles on (s_memtime stamps of a diagnostic build, scripts/deep_stamps.py,
 // 64 -> 64 at 160 x 160; per stage of ~11 500 cycles, with an epilogue every second stage): issuing the 12 prefetch loads of a
@@ -1478,23 +1540,12 @@ template <int BM, int NT, bool LK = false, bool SUBW = false, int ROLE = 0, bool
 int launch_conv_deep(const ConvArgs &a, hipStream_t st)
 {
     using C = DeepCfg<BM, NT>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    MMK_CHECK_HIP(hipGetDevice(&dev));
-    if (!attr_set[dev & 63]) {
-        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_deep_kernel<BM, NT, LK, SUBW, ROLE, WRES, POOLG>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev & 63] = true;
-    }
+    constexpr auto kernel = conv3x3_deep_kernel<BM, NT, LK, SUBW, ROLE, WRES, POOLG>;
+    MMK_CHECK_HIP(raise_lds_limit<kernel>(true, 160 * 1024));
     const size_t smem = C::smem(WRES ? a.CIN / 32 : 1);
     MMK_REQUIRE(smem <= (size_t)160 * 1024, "mmk_conv3x3: %zu bytes of LDS for CIN=%d COUT=%d", smem, a.CIN, a.COUT);
-    const int tiles = ((a.W + C::TWD - 1) / C::TWD) * ((a.H + C::TH - 1) / C::TH);
-    const int groups = (a.COUT + BM - 1) / BM;
-    const int total = tiles * a.B;
-    const int per_xcd = (total + 7) / 8;
-    int nb = 32 / groups;                                    // one 8-wave block per CU, 32 CUs per XCD
-    nb = nb < 1 ? 1 : (nb > per_xcd ? per_xcd : nb);
-    hipLaunchKernelGGL((conv3x3_deep_kernel<BM, NT, LK, SUBW, ROLE, WRES, POOLG>), dim3(8 * nb, groups), dim3(DEEP_THREADS), smem, st, a, total, per_xcd);
+    const XcdGrid g = deep_grid<BM, NT>(a.B, a.H, a.W, a.COUT);
+    hipLaunchKernelGGL(kernel, dim3(8 * g.nb, (a.COUT + BM - 1) / BM), dim3(DEEP_THREADS), smem, st, a, g.total, g.per_xcd);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -1503,16 +1554,25 @@ int launch_conv_deep(const ConvArgs &a, hipStream_t st)
 template <int BM, int NT>
 bool deep_weights_fit(int cin) { return DeepCfg<BM, NT>::smem(cin / 32) <= (size_t)160 * 1024; }
 
+// conv3x3_deep_kernel's table: output channels per block x tile width (NT = 3: 48-pixel tile rows waste less than NT = 5
+// where the rows are no longer than that)
+template <class F>
+int with_deep_cfg(int BM, bool narrow, F &&f)
+{
+    return with_int<16, 32, 64, 128>(BM, [&](auto M) {
+        return narrow ? f(M, std::integral_constant<int, 3>{}) : f(M, std::integral_constant<int, 5>{});
+    });
+}
+
 // Rounds of tiles the persistent grid of the plain launch walks (one 8-wave block per CU): blocks of an XCD share its
 // contiguous range of tiles.
-int deep_rounds(int B, int H, int W, int cout, int BM, int NT, int *tiles_per_image)
+int deep_rounds(int B, int H, int W, int cout, int BM, bool narrow, int *tiles_per_image)
 {
-    const int TH = BM >= 128 ? 4 : 8;
-    const int tpi = ((W + NT * 16 - 1) / (NT * 16)) * ((H + TH - 1) / TH);
-    const int groups = (cout + BM - 1) / BM;
-    const int nb = std::max(1, 32 / groups), per_xcd = (B * tpi + 7) / 8;
-    if (tiles_per_image) *tiles_per_image = tpi;
-    return (per_xcd + nb - 1) / nb;
+    return with_deep_cfg(BM, narrow, [&](auto M, auto NT) {
+        const XcdGrid g = deep_grid<M(), NT()>(B, H, W, cout);
+        if (tiles_per_image) *tiles_per_image = g.tiles;
+        return g.rounds();
+    });
 }
 
 int dispatch_conv_deep_plain(const ConvArgs &a, hipStream_t st);
@@ -1528,7 +1588,6 @@ int dispatch_conv_deep(const ConvArgs &a, hipStream_t st)
 {
     const int BM = conv_cm(a.CIN, a.COUT);
     const bool narrow = a.W <= 48;
-    const int NT = narrow ? 3 : 5;
     const char *split_env = getenv("MMK_CONV_SPLIT");       // MMK_CONV_SPLIT=0: always one launch (A/B, bit-identity test; read per call)
     const bool split_on = !(split_env && split_env[0] == '0');
     int tpi = 0;
@@ -1536,13 +1595,13 @@ int dispatch_conv_deep(const ConvArgs &a, hipStream_t st)
     // weight-gradient kernels of the side stream run there -- and the split cost the pass 0.15 ms instead of saving 0.01)
     const bool forward_role = a.relu != 0 && a.o1.relu_src == nullptr && a.o2.relu_src == nullptr && !a.o1.accumulate && !a.o2.accumulate;
     if (split_on && forward_role && a.slope == 0.f && (BM == 64 || BM == 128) && a.COUT % 32 == 0 && a.pool_y == nullptr && a.wpack_mtb == 0 &&
-        deep_rounds(a.B, a.H, a.W, a.COUT, BM, NT, &tpi) == 2) {
+        deep_rounds(a.B, a.H, a.W, a.COUT, BM, narrow, &tpi) == 2) {
         const int groups = (a.COUT + BM - 1) / BM, nb = std::max(1, 32 / groups);
         const int Bm = (8 * nb) / tpi;                      // images that fill one round
         const int Bt = a.B - Bm;
         const bool under_filled = (long)a.B * tpi * groups * 10 < (long)256 * 2 * 7;          // < 70 % of two rounds
-        if (Bm >= 1 && Bt >= 1 && under_filled && deep_rounds(Bm, a.H, a.W, a.COUT, BM, NT, nullptr) == 1 &&
-            deep_rounds(Bt, a.H, a.W, a.COUT, 32, NT, nullptr) == 1 && (a.o1.C % 32 == 0) && (a.o2.C % 32 == 0)) {
+        if (Bm >= 1 && Bt >= 1 && under_filled && deep_rounds(Bm, a.H, a.W, a.COUT, BM, narrow, nullptr) == 1 &&
+            deep_rounds(Bt, a.H, a.W, a.COUT, 32, narrow, nullptr) == 1 && (a.o1.C % 32 == 0) && (a.o2.C % 32 == 0)) {
             ConvArgs m = a;
             m.B = Bm;
             int rc = dispatch_conv_deep_plain(m, st);
@@ -1568,13 +1627,6 @@ int dispatch_conv_deep(const ConvArgs &a, hipStream_t st)
 
 int dispatch_conv_deep_plain(const ConvArgs &a, hipStream_t st)
 {
-    const int BM = conv_cm(a.CIN, a.COUT);
-    const bool narrow = a.W <= 48;          // NT = 3 (48-pixel tile rows) wastes less than NT = 5 there
-    if (a.slope > 0.f) {
-#define MMK_DEEP_CASE(M) if (BM == M) return narrow ? launch_conv_deep<M, 3, true>(a, st) : launch_conv_deep<M, 5, true>(a, st)
-        MMK_DEEP_CASE(16); MMK_DEEP_CASE(32); MMK_DEEP_CASE(64); MMK_DEEP_CASE(128);
-#undef MMK_DEEP_CASE
-    }
     // the epilogue's role (conv3x3_deep_kernel: ROLE): forward = activation, no epilogue operand; backward = no bias / activation /
     // dropout and at most ONE operand kind (ReLU source or accumulate target) per output half; anything else: the generic kernel
     const bool any_src = a.o1.relu_src != nullptr || (a.o2.C > 0 && a.o2.relu_src != nullptr);
@@ -1582,32 +1634,29 @@ int dispatch_conv_deep_plain(const ConvArgs &a, hipStream_t st)
     const bool both1 = a.o1.relu_src != nullptr && a.o1.accumulate != 0, both2 = a.o2.C > 0 && a.o2.relu_src != nullptr && a.o2.accumulate != 0;
     const int role = (a.relu != 0 && !any_src && !any_acc) ? 1
                    : ((a.relu == 0 && a.bias == nullptr && dropout_params(a.drop_p).thr == 0u && !both1 && !both2) ? 2 : 0);
-    if (a.x1_pool_arg != nullptr) {     // pooled gradient input: the data gradients of the encoder's >= 64-channel second convolutions
-#define MMK_DEEP_CASE(M)                                                                                                          \
-    if (BM == M && role == 2 && a.wpack_mtb == 0) {                                                                                \
-        if (M <= 64 && (narrow ? deep_weights_fit<M, 3>(a.CIN) : deep_weights_fit<M, 5>(a.CIN)))                                   \
-            return narrow ? launch_conv_deep<M, 3, false, false, 2, (M <= 64), true>(a, st)                                        \
-                          : launch_conv_deep<M, 5, false, false, 2, (M <= 64), true>(a, st);                                       \
-        if (M > 64)                                                                                                                \
-            return narrow ? launch_conv_deep<M, 3, false, false, 2, false, true>(a, st) : launch_conv_deep<M, 5, false, false, 2, false, true>(a, st); \
-    }
-        MMK_DEEP_CASE(64); MMK_DEEP_CASE(128);
-#undef MMK_DEEP_CASE
-        mmk::set_error("mmk_conv3x3: x1_pool_arg is not supported for this layer (CIN=%d COUT=%d)", a.CIN, a.COUT);
-        return MMK_ERR_ARG;
-    }
-#define MMK_DEEP_CASE(M, R)                                                                                                        \
-    if (BM == M && role == R) {                                                                                                    \
-        if (M <= 64 && a.wpack_mtb == 0 && (narrow ? deep_weights_fit<M, 3>(a.CIN) : deep_weights_fit<M, 5>(a.CIN)))               \
-            return narrow ? launch_conv_deep<M, 3, false, false, R, (M <= 64)>(a, st) : launch_conv_deep<M, 5, false, false, R, (M <= 64)>(a, st); \
-        return narrow ? launch_conv_deep<M, 3, false, false, R>(a, st) : launch_conv_deep<M, 5, false, false, R>(a, st);              \
-    }
-    MMK_DEEP_CASE(32, 1); MMK_DEEP_CASE(64, 1); MMK_DEEP_CASE(128, 1);
-    MMK_DEEP_CASE(32, 2); MMK_DEEP_CASE(64, 2); MMK_DEEP_CASE(128, 2);
-#undef MMK_DEEP_CASE
-#define MMK_DEEP_CASE(M) if (BM == M) return narrow ? launch_conv_deep<M, 3>(a, st) : launch_conv_deep<M, 5>(a, st)
-    MMK_DEEP_CASE(16); MMK_DEEP_CASE(32); MMK_DEEP_CASE(64); MMK_DEEP_CASE(128);
-#undef MMK_DEEP_CASE
+    const int rc = with_deep_cfg(conv_cm(a.CIN, a.COUT), a.W <= 48, [&](auto M, auto N) -> int {
+        constexpr int BM = M(), NT = N();
+        constexpr bool WRES = BM <= 64;         // (wider blocks leave no room for the weights of every chunk)
+        const bool resident = WRES && a.wpack_mtb == 0 && deep_weights_fit<BM, NT>(a.CIN);
+        if (a.slope > 0.f) return launch_conv_deep<BM, NT, true>(a, st);
+        if (a.x1_pool_arg != nullptr) {     // pooled gradient input: the data gradients of the encoder's >= 64-channel second convolutions
+            if constexpr (BM >= 64) {
+                if (role == 2 && a.wpack_mtb == 0) {
+                    if (resident) return launch_conv_deep<BM, NT, false, false, 2, WRES, true>(a, st);
+                    // (a plain `if`: the 64-wide instance is never launched, but it has always been one of the library's kernels)
+                    if (BM > 64) return launch_conv_deep<BM, NT, false, false, 2, false, true>(a, st);
+                }
+            }
+            mmk::set_error("mmk_conv3x3: x1_pool_arg is not supported for this layer (CIN=%d COUT=%d)", a.CIN, a.COUT);
+            return MMK_ERR_ARG;
+        }
+        if constexpr (BM >= 32) {
+            if (role == 1) return resident ? launch_conv_deep<BM, NT, false, false, 1, WRES>(a, st) : launch_conv_deep<BM, NT, false, false, 1>(a, st);
+            if (role == 2) return resident ? launch_conv_deep<BM, NT, false, false, 2, WRES>(a, st) : launch_conv_deep<BM, NT, false, false, 2>(a, st);
+        }
+        return launch_conv_deep<BM, NT>(a, st);
+    });
+    if (rc != NO_KERNEL) return rc;
     mmk::set_error("mmk_conv3x3: unsupported channel counts CIN=%d COUT=%d", a.CIN, a.COUT);
     return MMK_ERR_ARG;
 }
@@ -1617,6 +1666,18 @@ bool pool_fusable(int cin, int cout, int B, int H, int W)
 {
     const bool fits32 = (size_t)B * H * W * (size_t)std::max(cin, cout) < ((size_t)1 << 31);
     return cin == cout && (cin == 16 || cin == 32) && fits32 && H >= 2 && W >= 2;
+}
+
+// the thin kernels' table: input-channel chunk x output channels per block (32 -> 64 is a deep layer)
+template <class F>
+int with_thin_shape(int CK, int CM, F &&f)
+{
+    return with_int<8, 16, 32>(CK, [&](auto K) {
+        return with_int<16, 32, 64>(CM, [&](auto M) {
+            if constexpr (K() == 32 && M() == 64) return NO_KERNEL;
+            else return f(K, M);
+        });
+    });
 }
 
 int dispatch_conv(const ConvArgs &a, hipStream_t st)
@@ -1638,24 +1699,15 @@ int dispatch_conv(const ConvArgs &a, hipStream_t st)
     const bool fits32 = (size_t)a.B * a.H * a.W * (size_t)std::max(a.CIN, a.COUT) < ((size_t)1 << 31);
     // (the LeakyReLU variant of the network runs the thin layers on the plain pipelined kernel: the ring
     // kernel's straight-line epilogue is tuned for the reference's default configuration)
-    if (a.slope > 0.f) {
-#define MMK_CONV_CASE(K, M) if (CK == K && CM == M) return launch_conv<K, M, true>(a, st)
-        MMK_CONV_CASE(8, 16); MMK_CONV_CASE(8, 32); MMK_CONV_CASE(8, 64);
-        MMK_CONV_CASE(16, 16); MMK_CONV_CASE(16, 32); MMK_CONV_CASE(16, 64);
-        MMK_CONV_CASE(32, 16); MMK_CONV_CASE(32, 32);
-#undef MMK_CONV_CASE
-    }
-    if (a.CIN == CK && CM <= 32 && fits32) {
-#define MMK_RING_CASE(K, M) if (CK == K && CM == M) return launch_conv_ring_epi<K, M>(a, st)
-        MMK_RING_CASE(8, 16); MMK_RING_CASE(8, 32); MMK_RING_CASE(16, 16); MMK_RING_CASE(16, 32);
-        MMK_RING_CASE(32, 16); MMK_RING_CASE(32, 32);
-#undef MMK_RING_CASE
-    }
-#define MMK_CONV_CASE(K, M) if (CK == K && CM == M) return launch_conv<K, M>(a, st)
-    MMK_CONV_CASE(8, 16); MMK_CONV_CASE(8, 32); MMK_CONV_CASE(8, 64);
-    MMK_CONV_CASE(16, 16); MMK_CONV_CASE(16, 32); MMK_CONV_CASE(16, 64);
-    MMK_CONV_CASE(32, 16); MMK_CONV_CASE(32, 32);
-#undef MMK_CONV_CASE
+    const bool ring = a.CIN == CK && CM <= 32 && fits32;       // one chunk of input channels: the streaming kernel
+    const int rc = with_thin_shape(CK, CM, [&](auto K, auto M) -> int {
+        if (a.slope > 0.f) return launch_conv<K(), M(), true>(a, st);
+        if constexpr (M() <= 32) {
+            if (ring) return launch_conv_ring_epi<K(), M()>(a, st);
+        }
+        return launch_conv<K(), M()>(a, st);
+    });
+    if (rc != NO_KERNEL) return rc;
     mmk::set_error("mmk_conv3x3: unsupported channel counts CIN=%d COUT=%d", a.CIN, a.COUT);
     return MMK_ERR_ARG;
 }
@@ -1965,28 +2017,23 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_wgrad_kernel(const Wgrad
 
 // blocks along the pixel tiles (= partial slices of dW): what the 256 CUs hold at once (every extra
 // block costs one more pass over its dW slice); -1 on a HIP error
+// LDS of the weight-gradient kernels: the halo tile of x (CX channels) and the tile of g (CG channels; G8: 8 of a group of 16)
+constexpr size_t wgrad_smem(int CX, int CG)
+{
+    return ((size_t)(HT * WT + 8) * wg_pitch(CX) + (size_t)(TH * TW + 8) * wg_pitch(CG)) * sizeof(bf16);
+}
+
 template <int CK, int CM, bool G8>
 int wgrad_spatial(int cout, int cin, int B, int H, int W)
 {
-    const size_t smem = ((size_t)(HT * WT + 8) * wg_pitch(CK) + (size_t)(TH * TW + 8) * wg_pitch(G8 ? 8 : CM)) * sizeof(bf16);
-    static int per_cu[64] = {};      // resident blocks per CU (registers / LDS), per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    if (per_cu[dev & 63] == 0) {
-        if (smem > 64 * 1024 &&
-            hipFuncSetAttribute((const void *)conv3x3_wgrad_kernel<CK, CM, G8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return -1;
-        int nblk = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, conv3x3_wgrad_kernel<CK, CM, G8>, CONV_THREADS, smem) != hipSuccess)
-            return -1;
-        // (the 8/16-channel shapes share their slices -- one per block -- with the fused backward kernels, which hold 4 blocks
-        // per CU: with 6-8 slices per CU those run a second, half-empty round of blocks, 3-8 % slower)
-        const int cap = (CK <= 16 && CM == 16) ? 4 : 8;
-        per_cu[dev & 63] = nblk < 1 ? 1 : (nblk > cap ? cap : nblk);
-    }
+    // (the 8/16-channel shapes share their slices -- one per block -- with the fused backward kernels, which hold 4 blocks
+    // per CU: with 6-8 slices per CU those run a second, half-empty round of blocks, 3-8 % slower)
+    constexpr int cap = (CK <= 16 && CM == 16) ? 4 : 8;
+    int per_cu = 0;
+    if (blocks_per_cu<conv3x3_wgrad_kernel<CK, CM, G8>>(CONV_THREADS, wgrad_smem(CK, G8 ? 8 : CM), cap, &per_cu) != hipSuccess) return -1;
     const int tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * B;
     const int chunks = cin / CK, groups = (cout + CM - 1) / CM;
-    int spatial = (256 * per_cu[dev & 63]) / (chunks * groups);
+    int spatial = (256 * per_cu) / (chunks * groups);
     spatial = spatial < 1 ? 1 : (spatial > tiles ? tiles : spatial);
     return spatial >= 8 ? (spatial & ~7) : spatial;      // multiple of 8: XCD-contiguous tile walk
 }
@@ -1994,22 +2041,15 @@ int wgrad_spatial(int cout, int cin, int B, int H, int W)
 template <int CK, int CM, bool G8, bool POOLG = false>
 int launch_wgrad(const WgradArgs &a, hipStream_t st)
 {
-    const size_t smem = ((size_t)(HT * WT + 8) * wg_pitch(CK) + (size_t)(TH * TW + 8) * wg_pitch(G8 ? 8 : CM)) * sizeof(bf16);
+    constexpr size_t smem = wgrad_smem(CK, G8 ? 8 : CM);
     const int spatial = wgrad_spatial<CK, CM, G8>(a.COUT, a.CIN, a.B, a.H, a.W);
     if (spatial < 1) {
         mmk::set_error("mmk_conv3x3_wgrad: occupancy query failed");
         return MMK_ERR_HIP;
     }
     const int chunks = a.CIN / CK, groups = (a.COUT + CM - 1) / CM;
-    if constexpr (POOLG) {      // (the attribute is per instantiation; wgrad_spatial set it for the plain one)
-        static bool attr_set[64] = {};
-        int dev = 0;
-        MMK_CHECK_HIP(hipGetDevice(&dev));
-        if (smem > 64 * 1024 && !attr_set[dev & 63]) {
-            MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_wgrad_kernel<CK, CM, G8, POOLG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            attr_set[dev & 63] = true;
-        }
-    }
+    if constexpr (POOLG)        // (the limit is per instantiation; wgrad_spatial raised it for the plain one)
+        MMK_CHECK_HIP((raise_lds_limit<conv3x3_wgrad_kernel<CK, CM, G8, true>>(smem > 64 * 1024, smem)));
     hipLaunchKernelGGL((conv3x3_wgrad_kernel<CK, CM, G8, POOLG>), dim3(spatial, chunks, groups), dim3(CONV_THREADS), smem, st, a);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
@@ -2047,6 +2087,17 @@ struct BwdFusedArgs {
     const unsigned *g_arg = nullptr;   // POOLG: g is the POOLED gradient (B,H/2,W/2,CG), routed by these codes, times g_scale
     float g_scale = 1.f;
 };
+
+// the argument record of the four fused-backward entries (x2 / dx2: the second halves of mmk_conv16x8_bwd_fused, NULL elsewhere)
+BwdFusedArgs bwd_fused_args(const void *x, const void *x2, const void *g, const void *wpack_t, void *dx, void *dx2, float scale,
+                            int masked, int B, int H, int W, float *partials, int accumulate)
+{
+    BwdFusedArgs a = {};
+    a.x = (const bf16 *)x; a.x2 = (const bf16 *)x2; a.g = (const bf16 *)g; a.wpack_t = (const bf16 *)wpack_t;
+    a.dx = (bf16 *)dx; a.dx2 = (bf16 *)dx2; a.scale = scale; a.masked = masked;
+    a.B = B; a.H = H; a.W = W; a.partials = partials; a.acc_partials = accumulate;
+    return a;
+}
 
 // POOLG: the output gradient is the max-pool adjoint of a pooled gradient, taken through the codes (poolg_write)
 template <int CX, int CG, bool POOLG = false>
@@ -2620,19 +2671,29 @@ bool wgrad_is_deep(int cout, int cin, int c1) { return cin % 64 == 0 && cout % 6
 template <bool POOLG = false>
 int launch_wgrad_deep(const WgradArgs &a, hipStream_t st)
 {
-    const size_t smem = ((size_t)(HT * WT + 8) * wg_pitch(64) + (size_t)(TH * TW + 8) * wg_pitch(64)) * sizeof(bf16);
-    static bool attr_set[64] = {};
-    int dev = 0;
-    MMK_CHECK_HIP(hipGetDevice(&dev));
-    if (!attr_set[dev & 63]) {
-        MMK_CHECK_HIP(hipFuncSetAttribute((const void *)conv3x3_wgrad_deep_kernel<POOLG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set[dev & 63] = true;
-    }
+    constexpr size_t smem = wgrad_smem(64, 64);
+    MMK_CHECK_HIP(raise_lds_limit<conv3x3_wgrad_deep_kernel<POOLG>>(true, smem));
     const int spatial = wgrad_deep_slices(a.COUT, a.CIN, a.B, a.H, a.W);
     const int chunks = a.CIN / 64, groups = a.COUT / 64;
     hipLaunchKernelGGL(conv3x3_wgrad_deep_kernel<POOLG>, dim3(spatial, chunks, groups), dim3(WGD_THREADS), smem, st, a);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
+}
+
+// the thin weight-gradient kernels' table: input-channel chunk x output-channel group, and the G8 rule (8 output channels
+// stage 8 of their group of 16).  dispatch_wgrad and wgrad_slices both go through it: the slice count a caller sizes its
+// partials by is the grid of the kernel that gets launched.
+template <class F>
+int with_wgrad_shape(int cout, int cin, F &&f)
+{
+    return with_int<8, 16, 32, 64>(cin_chunk(cin), [&](auto K) {
+        return with_int<16, 32, 64>(cout_group(cout), [&](auto M) {
+            if constexpr (M() == 16) {
+                if (cout == 8) return f(K, M, std::true_type{});
+            }
+            return f(K, M, std::false_type{});
+        });
+    });
 }
 
 int dispatch_wgrad(const WgradArgs &a, hipStream_t st)
@@ -2644,13 +2705,8 @@ int dispatch_wgrad(const WgradArgs &a, hipStream_t st)
         return MMK_ERR_ARG;
     }
     if (wgrad_is_deep(a.COUT, a.CIN, a.C1)) return launch_wgrad_deep(a, st);
-    const int CK = cin_chunk(a.CIN), CM = cout_group(a.COUT);
-#define MMK_WG_CASE(K, M) if (CK == K && CM == M) return (M == 16 && a.COUT == 8) ? launch_wgrad<K, M, (M == 16)>(a, st) : launch_wgrad<K, M, false>(a, st)
-    MMK_WG_CASE(8, 16); MMK_WG_CASE(8, 32); MMK_WG_CASE(8, 64);
-    MMK_WG_CASE(16, 16); MMK_WG_CASE(16, 32); MMK_WG_CASE(16, 64);
-    MMK_WG_CASE(32, 16); MMK_WG_CASE(32, 32); MMK_WG_CASE(32, 64);
-    MMK_WG_CASE(64, 16); MMK_WG_CASE(64, 32); MMK_WG_CASE(64, 64);
-#undef MMK_WG_CASE
+    const int rc = with_wgrad_shape(a.COUT, a.CIN, [&](auto K, auto M, auto G8) { return launch_wgrad<K(), M(), G8()>(a, st); });
+    if (rc != NO_KERNEL) return rc;
     mmk::set_error("mmk_conv3x3_wgrad: unsupported channel counts CIN=%d COUT=%d", a.CIN, a.COUT);
     return MMK_ERR_ARG;
 }
@@ -2659,14 +2715,8 @@ int dispatch_wgrad(const WgradArgs &a, hipStream_t st)
 int wgrad_slices(int cout, int cin, int c1, int B, int H, int W)
 {
     if (wgrad_is_deep(cout, cin, c1)) return wgrad_deep_slices(cout, cin, B, H, W);
-    const int CK = cin_chunk(cin), CM = cout_group(cout);
-#define MMK_WG_CASE(K, M) if (CK == K && CM == M) return (M == 16 && cout == 8) ? wgrad_spatial<K, M, (M == 16)>(cout, cin, B, H, W) : wgrad_spatial<K, M, false>(cout, cin, B, H, W)
-    MMK_WG_CASE(8, 16); MMK_WG_CASE(8, 32); MMK_WG_CASE(8, 64);
-    MMK_WG_CASE(16, 16); MMK_WG_CASE(16, 32); MMK_WG_CASE(16, 64);
-    MMK_WG_CASE(32, 16); MMK_WG_CASE(32, 32); MMK_WG_CASE(32, 64);
-    MMK_WG_CASE(64, 16); MMK_WG_CASE(64, 32); MMK_WG_CASE(64, 64);
-#undef MMK_WG_CASE
-    return 0;
+    const int ns = with_wgrad_shape(cout, cin, [&](auto K, auto M, auto G8) { return wgrad_spatial<K(), M(), G8()>(cout, cin, B, H, W); });
+    return ns == NO_KERNEL ? 0 : ns;
 }
 
 struct UnpackBatch {
@@ -4334,9 +4384,7 @@ extern "C" int mmk_conv_bwd_fused(const void *x, const void *g, const void *wpac
     MMK_REQUIRE(x && g && wpack_t && dx && partials, "mmk_conv_bwd_fused: NULL pointer");
     MMK_REQUIRE(B >= 1 && H >= 2 && W >= 2 && (C == 8 || C == 16), "mmk_conv_bwd_fused: bad shape (8 or 16 channels)");
     MMK_REQUIRE((size_t)B * H * W * C < ((size_t)1 << 31), "mmk_conv_bwd_fused: tensor too large for 32-bit offsets");
-    BwdFusedArgs a = {};
-    a.x = (const bf16 *)x; a.g = (const bf16 *)g; a.wpack_t = (const bf16 *)wpack_t; a.dx = (bf16 *)dx; a.scale = scale; a.masked = 1;
-    a.B = B; a.H = H; a.W = W; a.partials = partials; a.acc_partials = accumulate;
+    const BwdFusedArgs a = bwd_fused_args(x, nullptr, g, wpack_t, dx, nullptr, scale, 1, B, H, W, partials, accumulate);
     return C == 8 ? launch_bwd_fused<8, 8>(a, 8, (hipStream_t)stream) : launch_bwd_fused<16, 16>(a, 16, (hipStream_t)stream);
 }
 
@@ -4347,9 +4395,7 @@ extern "C" int mmk_conv_bwd_fused_pooled(const void *x, const void *gy, const vo
     MMK_REQUIRE(x && gy && arg && wpack_t && dx && partials, "mmk_conv_bwd_fused_pooled: NULL pointer");
     MMK_REQUIRE(B >= 1 && H >= 2 && W >= 2 && C == 16, "mmk_conv_bwd_fused_pooled: bad shape (16 channels)");
     MMK_REQUIRE((size_t)B * H * W * C < ((size_t)1 << 31), "mmk_conv_bwd_fused_pooled: tensor too large for 32-bit offsets");
-    BwdFusedArgs a = {};
-    a.x = (const bf16 *)x; a.g = (const bf16 *)gy; a.wpack_t = (const bf16 *)wpack_t; a.dx = (bf16 *)dx; a.scale = scale; a.masked = 1;
-    a.B = B; a.H = H; a.W = W; a.partials = partials; a.acc_partials = accumulate;
+    BwdFusedArgs a = bwd_fused_args(x, nullptr, gy, wpack_t, dx, nullptr, scale, 1, B, H, W, partials, accumulate);
     a.g_arg = (const unsigned *)arg; a.g_scale = pool_scale;
     return launch_bwd_fused<16, 16, true>(a, 16, (hipStream_t)stream);
 }
@@ -4360,10 +4406,8 @@ extern "C" int mmk_conv8x16_bwd_fused(const void *x, const void *g, const void *
     MMK_REQUIRE(x && g && wpack_t && dx && partials, "mmk_conv8x16_bwd_fused: NULL pointer");
     MMK_REQUIRE(B >= 1 && H >= 2 && W >= 2, "mmk_conv8x16_bwd_fused: bad shape");
     MMK_REQUIRE((size_t)B * H * W * 16 < ((size_t)1 << 31), "mmk_conv8x16_bwd_fused: tensor too large for 32-bit offsets");
-    BwdFusedArgs a = {};
-    a.x = (const bf16 *)x; a.g = (const bf16 *)g; a.wpack_t = (const bf16 *)wpack_t; a.dx = (bf16 *)dx; a.scale = scale; a.masked = 1;
+    BwdFusedArgs a = bwd_fused_args(x, nullptr, g, wpack_t, dx, nullptr, scale, 1, B, H, W, partials, accumulate);
     a.accumulate_dx = 1;
-    a.B = B; a.H = H; a.W = W; a.partials = partials; a.acc_partials = accumulate;
     return launch_bwd_fused<8, 16>(a, 8, (hipStream_t)stream);
 }
 
@@ -4374,10 +4418,7 @@ extern "C" int mmk_conv16x8_bwd_fused(const void *x1, const void *x2, const void
     MMK_REQUIRE((x2 == nullptr) == (dx2 == nullptr), "mmk_conv16x8_bwd_fused: x2 and dx2 go together (both NULL: one 16-channel input / unmasked output)");
     MMK_REQUIRE(B >= 1 && H >= 2 && W >= 2, "mmk_conv16x8_bwd_fused: bad shape");
     MMK_REQUIRE((size_t)B * H * W * 16 < ((size_t)1 << 31), "mmk_conv16x8_bwd_fused: tensor too large for 32-bit offsets");
-    BwdFusedArgs a = {};
-    a.x = (const bf16 *)x1; a.x2 = (const bf16 *)x2; a.g = (const bf16 *)g; a.wpack_t = (const bf16 *)wpack_t;
-    a.dx = (bf16 *)dx1; a.dx2 = (bf16 *)dx2; a.scale = scale; a.masked = x2 != nullptr;
-    a.B = B; a.H = H; a.W = W; a.partials = partials; a.acc_partials = accumulate;
+    const BwdFusedArgs a = bwd_fused_args(x1, x2, g, wpack_t, dx1, dx2, scale, x2 != nullptr, B, H, W, partials, accumulate);
     return launch_bwd_fused<16, 8>(a, x2 ? 8 : 16, (hipStream_t)stream);
 }
 
@@ -4388,36 +4429,37 @@ extern "C" int32_t mmk_conv3x3_wgrad_slices(int32_t cout, int32_t cin, int32_t c
     return ns < 0 ? 0 : ns;
 }
 
-extern "C" int mmk_conv3x3_wgrad_partial(const void *x1, const void *x2, int32_t C1, int32_t C2, const void *g, int32_t cout,
-                                         int32_t B, int32_t H, int32_t W, float *partials, int32_t accumulate, void *stream)
+namespace {
+// one body for the two entries: `arg` set = g is the pooled gradient, routed by the codes (then the pooling needs H, W >= 2)
+int wgrad_partial(const char *who, const void *x1, const void *x2, int C1, int C2, const void *g, const void *arg, float pool_scale,
+                  bool pooled, int cout, int B, int H, int W, float *partials, int accumulate, void *stream)
 {
-    MMK_REQUIRE(x1 && g && partials, "mmk_conv3x3_wgrad_partial: NULL pointer");
-    MMK_REQUIRE(B >= 1 && H >= 1 && W >= 1, "mmk_conv3x3_wgrad_partial: bad shape");
+    MMK_REQUIRE(x1 && g && partials && (arg || !pooled), "%s: NULL pointer", who);
+    MMK_REQUIRE(B >= 1 && H >= (pooled ? 2 : 1) && W >= (pooled ? 2 : 1), "%s: bad shape", who);
     const int cin = C1 + C2;
-    MMK_REQUIRE(C1 % 8 == 0 && C2 % 8 == 0 && (C2 == 0 || x2), "mmk_conv3x3_wgrad_partial: bad input split %d+%d", C1, C2);
-    MMK_REQUIRE(chan_ok(cin) && chan_ok(cout), "mmk_conv3x3_wgrad_partial: unsupported channel counts %d -> %d", cin, cout);
+    MMK_REQUIRE(C1 % 8 == 0 && C2 % 8 == 0 && (C2 == 0 || x2), "%s: bad input split %d+%d", who, C1, C2);
+    MMK_REQUIRE(chan_ok(cin) && chan_ok(cout), "%s: unsupported channel counts %d -> %d", who, cin, cout);
     WgradArgs a;
     a.x1 = (const bf16 *)x1; a.x2 = (const bf16 *)x2; a.C1 = C1; a.C2 = C2; a.g = (const bf16 *)g;
     a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
     a.partials = partials; a.acc_partials = accumulate;
+    a.g_arg = (const unsigned *)arg; a.g_scale = pool_scale;
     return dispatch_wgrad(a, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int mmk_conv3x3_wgrad_partial(const void *x1, const void *x2, int32_t C1, int32_t C2, const void *g, int32_t cout,
+                                         int32_t B, int32_t H, int32_t W, float *partials, int32_t accumulate, void *stream)
+{
+    return wgrad_partial("mmk_conv3x3_wgrad_partial", x1, x2, C1, C2, g, nullptr, 1.f, false, cout, B, H, W, partials, accumulate, stream);
 }
 
 extern "C" int mmk_conv3x3_wgrad_partial_pooled(const void *x1, const void *x2, int32_t C1, int32_t C2, const void *gy, const void *arg,
                                                 float pool_scale, int32_t cout, int32_t B, int32_t H, int32_t W, float *partials,
                                                 int32_t accumulate, void *stream)
 {
-    MMK_REQUIRE(x1 && gy && arg && partials, "mmk_conv3x3_wgrad_partial_pooled: NULL pointer");
-    MMK_REQUIRE(B >= 1 && H >= 2 && W >= 2, "mmk_conv3x3_wgrad_partial_pooled: bad shape");
-    const int cin = C1 + C2;
-    MMK_REQUIRE(C1 % 8 == 0 && C2 % 8 == 0 && (C2 == 0 || x2), "mmk_conv3x3_wgrad_partial_pooled: bad input split %d+%d", C1, C2);
-    MMK_REQUIRE(chan_ok(cin) && chan_ok(cout), "mmk_conv3x3_wgrad_partial_pooled: unsupported channel counts %d -> %d", cin, cout);
-    WgradArgs a;
-    a.x1 = (const bf16 *)x1; a.x2 = (const bf16 *)x2; a.C1 = C1; a.C2 = C2; a.g = (const bf16 *)gy;
-    a.B = B; a.H = H; a.W = W; a.CIN = cin; a.COUT = cout;
-    a.partials = partials; a.acc_partials = accumulate;
-    a.g_arg = (const unsigned *)arg; a.g_scale = pool_scale;
-    return dispatch_wgrad(a, (hipStream_t)stream);
+    return wgrad_partial("mmk_conv3x3_wgrad_partial_pooled", x1, x2, C1, C2, gy, arg, pool_scale, true, cout, B, H, W, partials, accumulate,
+                         stream);
 }
 
 extern "C" int mmk_bn_forward_stats(const void *a, int64_t npix, int32_t C, const float *gamma, const float *beta, float eps,
@@ -4726,16 +4768,10 @@ extern "C" int mmk_upsample_bwd(const void *gy, int32_t B, int32_t Hs, int32_t W
     MMK_REQUIRE(Hs <= 65535 && B <= 65535, "mmk_upsample_bwd: shape exceeds the launch grid");
     const UpGeom ug = up_geom(Hs, Ws, C, Ho, Wo);
     const dim3 grid(nblk((size_t)Ws * (C / 8), 256), (Hs + UP_ROWS - 1) / UP_ROWS, B);
-#define MMK_UPB(P2, LKV, LG)                                                                                                   \
-    hipLaunchKernelGGL((upsample_bwd_kernel<P2, LKV>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16 *)gy, Hs, Ws, C, Ho, Wo, \
-                       ug.rh, ug.rw, LG, (const bf16 *)relu_src, scale, leaky_slope, (bf16 *)gx)
-    const bool lkv = leaky_slope > 0.f;
-    if (ug.lg >= 0) {
-        if (lkv) MMK_UPB(true, true, ug.lg); else MMK_UPB(true, false, ug.lg);
-    } else {
-        if (lkv) MMK_UPB(false, true, 0); else MMK_UPB(false, false, 0);
-    }
-#undef MMK_UPB
+    with_bools(ug.lg >= 0, leaky_slope > 0.f, [&](auto P2, auto LK) {
+        hipLaunchKernelGGL((upsample_bwd_kernel<P2(), LK()>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16 *)gy, Hs, Ws, C, Ho, Wo,
+                           ug.rh, ug.rw, P2() ? ug.lg : 0, (const bf16 *)relu_src, scale, leaky_slope, (bf16 *)gx);
+    });
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }
@@ -4749,21 +4785,28 @@ extern "C" int mmk_final_fwd(const void *x, const float *w, const float *bias, i
     return MMK_OK;
 }
 
+namespace {
+// the final layer's backward over `grid` blocks (9 partial sums each, in ws), then their reduction into dW, db
+int launch_final_bwd(dim3 grid, const void *x, const float *w, const float *mask, const float *gmask, size_t npix, const float *coef,
+                     float scale, float leaky_slope, void *gx, float *ws, float *dW, float *db, hipStream_t st)
+{
+    with_bool(leaky_slope > 0.f, [&](auto LK) {
+        hipLaunchKernelGGL(final_bwd_kernel<LK()>, grid, dim3(256), 0, st, (const bf16 *)x, w, mask, gmask, npix, coef, scale, leaky_slope,
+                           (bf16 *)gx, ws);
+    });
+    MMK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(final_bwd_reduce_kernel, dim3(1), dim3(288), 0, st, ws, (int)(grid.x * grid.y), dW, db);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+}  // namespace
+
 extern "C" int mmk_final_bwd(const void *x, const float *w, const float *mask, const float *gmask, int64_t npix, float scale,
                              float leaky_slope, void *gx, float *dW, float *db, float *ws /* MMK_FINAL_BWD_WS_FLOATS */, void *stream)
 {
     MMK_REQUIRE(x && w && mask && gmask && gx && dW && db && ws && npix >= 1, "mmk_final_bwd: bad argument");
     const unsigned blocks = (unsigned)std::min<size_t>(((size_t)npix + 255) / 256, 512);
-    if (leaky_slope > 0.f)
-        hipLaunchKernelGGL(final_bwd_kernel<true>, dim3(blocks, 1), dim3(256), 0, (hipStream_t)stream, (const bf16 *)x, w, mask, gmask,
-                           (size_t)npix, (const float *)nullptr, scale, leaky_slope, (bf16 *)gx, ws);
-    else
-        hipLaunchKernelGGL(final_bwd_kernel<false>, dim3(blocks, 1), dim3(256), 0, (hipStream_t)stream, (const bf16 *)x, w, mask, gmask,
-                           (size_t)npix, (const float *)nullptr, scale, leaky_slope, (bf16 *)gx, ws);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(final_bwd_reduce_kernel, dim3(1), dim3(288), 0, (hipStream_t)stream, ws, (int)blocks, dW, db);
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
+    return launch_final_bwd(dim3(blocks, 1), x, w, mask, gmask, (size_t)npix, nullptr, scale, leaky_slope, gx, ws, dW, db, (hipStream_t)stream);
 }
 
 extern "C" int mmk_mask_normalize(const float *mask, int32_t B, int64_t npix_per, float *part, float *mask_n, float *amax,
@@ -4794,14 +4837,5 @@ extern "C" int mmk_final_bwd_normalized(const void *x, const float *w, const flo
     // ~512 blocks in all (9 partial sums per block; per * B <= 512 + B <= MMK_FINAL_BWD_WS_FLOATS / 9 for B <= 1200)
     const unsigned per = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)npix_per + 255) / 256, (512 + B - 1) / B));
     MMK_REQUIRE((size_t)per * B * 9 <= MMK_FINAL_BWD_WS_FLOATS, "mmk_final_bwd_normalized: batch too large for the reduction workspace");
-    if (leaky_slope > 0.f)
-        hipLaunchKernelGGL(final_bwd_kernel<true>, dim3(per, B), dim3(256), 0, st, (const bf16 *)x, w, mask, gmask_n, (size_t)npix_per, coef,
-                           scale, leaky_slope, (bf16 *)gx, ws);
-    else
-        hipLaunchKernelGGL(final_bwd_kernel<false>, dim3(per, B), dim3(256), 0, st, (const bf16 *)x, w, mask, gmask_n, (size_t)npix_per, coef,
-                           scale, leaky_slope, (bf16 *)gx, ws);
-    MMK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(final_bwd_reduce_kernel, dim3(1), dim3(288), 0, st, ws, (int)(per * B), dW, db);
-    MMK_LAUNCH_CHECK();
-    return MMK_OK;
+    return launch_final_bwd(dim3(per, B), x, w, mask, gmask_n, (size_t)npix_per, coef, scale, leaky_slope, gx, ws, dW, db, st);
 }

@@ -16,8 +16,11 @@
 #include <string.h>
 
 #include "mmk_common.h"
+#include "mmk_unet_shared.h"
 
 namespace {
+
+using mmku::dropout_prob_ok;          // the probabilities the convolution entry accepts, checked before the first launch
 
 constexpr int NCONV = 23;                       // conv k: 0..11 encoder (2 per block), 12..21 decoder, 22 final
 const int ENC_CH[6] = {8, 16, 32, 64, 128, 256};
@@ -172,34 +175,27 @@ inline void *at(void *base, size_t off) { return static_cast<char *>(base) + off
         if (rc_ != MMK_OK) return rc_; \
     } while (0)
 
-struct ConvCall {
-    const void *x1 = nullptr, *x2 = nullptr;
-    int C1 = 0, C2 = 0;
-    const void *wpack = nullptr;
-    const float *bias = nullptr;
-    void *y1 = nullptr, *y2 = nullptr;
-    const void *src1 = nullptr, *src2 = nullptr;
-    int O1 = 0, O2 = 0, acc1 = 0, acc2 = 0;
-    float scale1 = 1.f, scale2 = 1.f;
-    int relu = 0;
-    float drop_p = 0.f;
-    unsigned seed = 0;
-    void *pool_y = nullptr, *pool_arg = nullptr;
-    const void *x1_arg = nullptr;           // x1 is a pooled gradient, routed by these codes times x1_scale (mmk_conv_desc.x1_pool_arg)
-    float x1_scale = 1.f;
-};
-
-int conv(const Plan &p, int h, int w, float slope, const ConvCall &c, void *stream)
+// What every convolution call of a pass starts from: a zeroed descriptor with the shape, the activation's slope and unit scales;
+// the call site fills in the rest and hands it to mmk_conv3x3.
+mmk_conv_desc conv_desc(const Plan &p, int h, int w, float slope)
 {
     mmk_conv_desc d;
     memset(&d, 0, sizeof(d));
-    d.x1 = c.x1; d.x2 = c.x2; d.C1 = c.C1; d.C2 = c.C2; d.wpack = c.wpack; d.bias = c.bias;
-    d.y1 = c.y1; d.relu_src1 = c.src1; d.O1 = c.O1; d.accumulate1 = c.acc1; d.scale1 = c.scale1;
-    d.y2 = c.y2; d.relu_src2 = c.src2; d.O2 = c.O2; d.accumulate2 = c.acc2; d.scale2 = c.scale2;
-    d.B = p.B; d.H = h; d.W = w; d.relu = c.relu; d.leaky_slope = slope; d.drop_p = c.drop_p; d.seed = c.seed;
-    d.pool_y = c.pool_y; d.pool_arg = c.pool_arg;
-    d.x1_pool_arg = c.x1_arg; d.x1_pool_scale = c.x1_scale;
-    return mmk_conv3x3(&d, stream);
+    d.B = p.B; d.H = h; d.W = w; d.leaky_slope = slope;
+    d.scale1 = d.scale2 = d.x1_pool_scale = 1.f;
+    return d;
+}
+
+// weights of the 21 3x3 layers -> bf16 MFMA-fragment order at base + offs[k] (transposed: the data-gradient operators), one launch
+int pack_all(const Plan &p, const mmk_unet_desc *d, int transposed, void *base, const size_t *offs, void *stream)
+{
+    const float *Wp[21];
+    void *Op[21];
+    for (int k = 1; k <= 21; ++k) {
+        Wp[k - 1] = d->params[2 * k];
+        Op[k - 1] = static_cast<char *>(base) + offs[k];
+    }
+    return mmk_conv3x3_pack_weights_batch(21, Wp, p.cout + 1, p.cinn + 1, transposed, Op, stream);
 }
 
 // Side stream of the backward pass: the 38 weight-gradient launches are leaves of the dependency graph (inputs:
@@ -270,15 +266,12 @@ int side_stream(SideStream **out)
     return MMK_OK;
 }
 
-// 1/keep as the kernels apply it (mmk_unet.hip: dropout_params)
-float dropout_scale(float p)
+// every bucket of a caller that hands over events has one
+int check_events(const char *who, void *const *bucket_events)
 {
-    const unsigned thr = (unsigned)(p * 65536.0f + 0.5f);
-    return thr ? 65536.0f / (float)(65536u - thr) : 1.0f;
+    for (int b = 0; b < MMK_UNET_GRAD_BUCKETS; ++b) MMK_REQUIRE(bucket_events[b] != nullptr, "%s: NULL event %d", who, b);
+    return MMK_OK;
 }
-
-// the probabilities the convolution entry accepts (mmk_unet_shared.h: dropout_prob_ok), checked before the first launch
-bool dropout_prob_ok(float p) { return p >= 0.f && p < 1.f && (unsigned)(p * 65536.0f + 0.5f) <= 65535u; }
 
 }  // namespace
 
@@ -339,34 +332,26 @@ extern "C" int mmk_unet_forward(const mmk_unet_desc *d, void *stream)
     auto Wk = [&](int k) { return d->params[2 * k]; };
     auto Bk = [&](int k) { return d->params[2 * k + 1]; };
     unsigned ctr = d->seed * 64u;
+    // convolution k of the network on x1 (| x2): bias + activation; `drop`: dropout with the pass's next seed (the second
+    // convolution of every block)
+    auto layer = [&](int k, const Tens &x1, const Tens *x2, const Tens &y, bool drop) {
+        mmk_conv_desc c = conv_desc(p, y.h, y.w, sl);
+        c.x1 = at(ws, x1.off); c.C1 = x1.c; c.wpack = at(ws, p.packs[k]); c.bias = Bk(k);
+        if (x2) { c.x2 = at(ws, x2->off); c.C2 = x2->c; }
+        c.y1 = at(ws, y.off); c.O1 = y.c; c.relu = 1;
+        if (drop) { c.drop_p = d->drop_p; c.seed = ++ctr; }
+        return c;
+    };
+    auto run = [&](const mmk_conv_desc &c) { return mmk_conv3x3(&c, stream); };
 
-    // weights of the 21 3x3 layers -> bf16 MFMA-fragment order, one launch
-    {
-        const float *Wp[21];
-        void *Op[21];
-        int32_t co[21], ci[21];
-        for (int k = 1; k <= 21; ++k) {
-            Wp[k - 1] = Wk(k); Op[k - 1] = at(ws, p.packs[k]); co[k - 1] = p.cout[k]; ci[k - 1] = p.cinn[k];
-        }
-        MMK_TRY(mmk_conv3x3_pack_weights_batch(21, Wp, co, ci, 0, Op, stream));
-    }
+    MMK_TRY(pack_all(p, d, 0, ws, p.packs, stream));
     // ---- encoder
     MMK_TRY(mmk_conv_first(d->x, p.cin, Wk(0), Bk(0), d->pre, B, p.H, p.W, sl, at(ws, p.a_enc[0].off), stream));
-    {
-        ConvCall c;
-        c.x1 = at(ws, p.a_enc[0].off); c.C1 = 8; c.wpack = at(ws, p.packs[1]); c.bias = Bk(1);
-        c.y1 = at(ws, p.d_enc[0].off); c.O1 = 8; c.relu = 1; c.drop_p = d->drop_p; c.seed = ++ctr;
-        MMK_TRY(conv(p, p.H, p.W, sl, c, stream));
-    }
+    MMK_TRY(run(layer(1, p.a_enc[0], nullptr, p.d_enc[0], true)));
     for (int i = 1; i < 6; ++i) {
         const int h = p.rh[i - 1], w = p.rw[i - 1], ch = ENC_CH[i];
-        ConvCall c;
-        c.x1 = at(ws, p.t[i - 1].off); c.C1 = ENC_CH[i - 1]; c.wpack = at(ws, p.packs[2 * i]); c.bias = Bk(2 * i);
-        c.y1 = at(ws, p.a_enc[i].off); c.O1 = ch; c.relu = 1;
-        MMK_TRY(conv(p, h, w, sl, c, stream));
-        ConvCall c2;
-        c2.x1 = at(ws, p.a_enc[i].off); c2.C1 = ch; c2.wpack = at(ws, p.packs[2 * i + 1]); c2.bias = Bk(2 * i + 1);
-        c2.y1 = at(ws, p.d_enc[i].off); c2.O1 = ch; c2.relu = 1; c2.drop_p = d->drop_p; c2.seed = ++ctr;
+        MMK_TRY(run(layer(2 * i, p.t[i - 1], nullptr, p.a_enc[i], false)));
+        mmk_conv_desc c2 = layer(2 * i + 1, p.a_enc[i], nullptr, p.d_enc[i], true);
         // ReLU network: the pooling leaves arg-max codes for the backward pass (mmk_maxpool2_bwd_arg), which then never reads
         // the block's pre-pool output d_enc[i]; where the second conv pools in the same pass it does not even write it
         // (desc.keep_full_res: it does, and a pooling pass over it makes the codes -- diagnostics)
@@ -374,7 +359,7 @@ extern "C" int mmk_unet_forward(const mmk_unet_desc *d, void *stream)
         const bool lean = fuse && !d->keep_full_res;
         if (fuse) c2.pool_y = at(ws, p.t[i].off);          // the second conv writes its 2x2 max-pool as well
         if (lean) { c2.pool_arg = at(ws, p.t_arg[i]); c2.y1 = nullptr; }
-        MMK_TRY(conv(p, h, w, sl, c2, stream));
+        MMK_TRY(run(c2));
         if (sl == 0.f) {
             if (!lean) MMK_TRY(mmk_maxpool2_fwd_arg(at(ws, p.d_enc[i].off), B, h, w, ch, at(ws, p.t[i].off), at(ws, p.t_arg[i]), stream));
         } else {
@@ -384,25 +369,12 @@ extern "C" int mmk_unet_forward(const mmk_unet_desc *d, void *stream)
     // ---- decoder (each block applied twice with shared weights: icp_weight_policy.py:178,182)
     const Tens *cur = &p.t[5];
     for (int j = 0; j < 5; ++j) {
-        const int cs = ENC_CH[4 - j], h = p.rh[4 - j], w = p.rw[4 - j];
         const int k0 = 12 + 2 * j, k1 = 13 + 2 * j;
-        MMK_TRY(mmk_upsample_fwd(at(ws, cur->off), B, cur->h, cur->w, cur->c, h, w, at(ws, p.u[j].off), stream));
-        ConvCall c;
-        c.x1 = at(ws, p.u[j].off); c.C1 = 2 * cs; c.wpack = at(ws, p.packs[k0]); c.bias = Bk(k0);
-        c.y1 = at(ws, p.a1[j].off); c.O1 = cs; c.relu = 1;
-        MMK_TRY(conv(p, h, w, sl, c, stream));
-        ConvCall c1;
-        c1.x1 = at(ws, p.a1[j].off); c1.C1 = cs; c1.wpack = at(ws, p.packs[k1]); c1.bias = Bk(k1);
-        c1.y1 = at(ws, p.d1[j].off); c1.O1 = cs; c1.relu = 1; c1.drop_p = d->drop_p; c1.seed = ++ctr;
-        MMK_TRY(conv(p, h, w, sl, c1, stream));
-        ConvCall c2;                                        // torch.cat([skip, d1]) without a copy
-        c2.x1 = at(ws, p.t[4 - j].off); c2.C1 = cs; c2.x2 = at(ws, p.d1[j].off); c2.C2 = cs;
-        c2.wpack = at(ws, p.packs[k0]); c2.bias = Bk(k0); c2.y1 = at(ws, p.a2[j].off); c2.O1 = cs; c2.relu = 1;
-        MMK_TRY(conv(p, h, w, sl, c2, stream));
-        ConvCall c3;
-        c3.x1 = at(ws, p.a2[j].off); c3.C1 = cs; c3.wpack = at(ws, p.packs[k1]); c3.bias = Bk(k1);
-        c3.y1 = at(ws, p.d2[j].off); c3.O1 = cs; c3.relu = 1; c3.drop_p = d->drop_p; c3.seed = ++ctr;
-        MMK_TRY(conv(p, h, w, sl, c3, stream));
+        MMK_TRY(mmk_upsample_fwd(at(ws, cur->off), B, cur->h, cur->w, cur->c, p.u[j].h, p.u[j].w, at(ws, p.u[j].off), stream));
+        MMK_TRY(run(layer(k0, p.u[j], nullptr, p.a1[j], false)));
+        MMK_TRY(run(layer(k1, p.a1[j], nullptr, p.d1[j], true)));
+        MMK_TRY(run(layer(k0, p.t[4 - j], &p.d1[j], p.a2[j], false)));       // torch.cat([skip, d1]) without a copy
+        MMK_TRY(run(layer(k1, p.a2[j], nullptr, p.d2[j], true)));
         cur = &p.d2[j];
     }
     // ---- final 1x1 + sigmoid (+ per-image amax normalisation)
@@ -447,7 +419,7 @@ extern "C" int mmk_unet_backward_buckets(const mmk_unet_desc *d, const float *gm
                                          size_t scratch_bytes, void *const *bucket_events, void *stream)
 {
     MMK_REQUIRE(bucket_events != nullptr, "mmk_unet_backward_buckets: NULL event array");
-    for (int b = 0; b < MMK_UNET_GRAD_BUCKETS; ++b) MMK_REQUIRE(bucket_events[b] != nullptr, "mmk_unet_backward_buckets: NULL event %d", b);
+    MMK_TRY(check_events("mmk_unet_backward_buckets", bucket_events));
     return unet_backward_impl(d, gmask, grads, scratch, scratch_bytes, bucket_events, stream);
 }
 
@@ -466,9 +438,7 @@ extern "C" int mmk_unet_backward_input(const mmk_unet_desc *d, const float *gmas
     // the statistics go where the first layer's weight gradient kept its partials (it is done with them by then)
     MMK_REQUIRE(mmk_conv_first_dgrad_ws_bytes(d->cin) <= mmk_conv_first_wgrad_ws_bytes(d->cin),
                 "mmk_unet_backward_input: no room for the statistics in scratch");
-    if (bucket_events)
-        for (int b = 0; b < MMK_UNET_GRAD_BUCKETS; ++b)
-            MMK_REQUIRE(bucket_events[b] != nullptr, "mmk_unet_backward_input: NULL event %d", b);
+    if (bucket_events) MMK_TRY(check_events("mmk_unet_backward_input", bucket_events));
     const InputGrad ig = {grad_x, norm_mode, norm_mode == MMK_NORM_MINMAX ? minmax : nullptr};
     return unet_backward_impl(d, gmask, grads, scratch, scratch_bytes, bucket_events, stream, &ig);
 }
@@ -486,26 +456,23 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
     for (int i = 0; i < 2 * NCONV; ++i) MMK_REQUIRE(d->params[i] && grads[i], "mmk_unet_backward: NULL parameter / gradient %d", i);
     void *ws = d->workspace, *sc = scratch;
     hipStream_t st = (hipStream_t)stream;
-    const float sl = d->leaky_slope, s = dropout_scale(d->drop_p);
+    const float sl = d->leaky_slope, s = mmku::dropout_params(d->drop_p).inv_keep;     // 1 / keep as the kernels apply it
     const int B = p.B;
     auto Wk = [&](int k) { return d->params[2 * k]; };
 
-    {
-        const float *Wp[21];
-        void *Op[21];
-        int32_t co[21], ci[21];
-        for (int k = 1; k <= 21; ++k) {
-            Wp[k - 1] = Wk(k); Op[k - 1] = at(sc, p.packs_t[k]); co[k - 1] = p.cout[k]; ci[k - 1] = p.cinn[k];
-        }
-        MMK_TRY(mmk_conv3x3_pack_weights_batch(21, Wp, co, ci, 1, Op, stream));
-    }
+    MMK_TRY(pack_all(p, d, 1, sc, p.packs_t, stream));
     SideStream *ss = nullptr;
     if (use_side_stream()) MMK_TRY(side_stream(&ss));
     void *wstream = ss ? (void *)ss->st : stream;          // where the weight-gradient launches go
-    if (ss) {       // everything enqueued so far (weight packing, zero fills) precedes the side stream's work
-        MMK_CHECK_HIP(hipEventRecord(ss->fork, st));
-        MMK_CHECK_HIP(hipStreamWaitEvent(ss->st, ss->fork, 0));
-    }
+    // the side stream's next launch waits for everything enqueued on the caller's stream so far
+    auto fork = [&]() -> int {
+        if (ss) {
+            MMK_CHECK_HIP(hipEventRecord(ss->fork, st));
+            MMK_CHECK_HIP(hipStreamWaitEvent(ss->st, ss->fork, 0));
+        }
+        return MMK_OK;
+    };
+    MMK_TRY(fork());        // (weight packing, the caller's zero fills)
     int part_used[NCONV] = {};      // sets of partial slices layer k has written so far (decoder layers: one per application)
     auto part_ptr = [&](int k) {
         float *ptr = static_cast<float *>(at(sc, p.part[k])) +
@@ -516,10 +483,7 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
     // parameter gradients of layers k0..k1: sum the slices / transpose, one launch on the weight-gradient stream, behind the
     // weight-gradient launches enqueued so far
     auto unpack = [&](int k0, int k1) -> int {
-        if (ss) {   // (some slices were written on the caller's stream: the fused 8 -> 8 backward launches)
-            MMK_CHECK_HIP(hipEventRecord(ss->fork, st));
-            MMK_CHECK_HIP(hipStreamWaitEvent(ss->st, ss->fork, 0));
-        }
+        MMK_TRY(fork());    // (some slices were written on the caller's stream: the fused 8 -> 8 backward launches)
         const float *src[21];
         int32_t slices[21], co[21], ci[21];
         float *dW[21], *db[21];
@@ -546,10 +510,7 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
         return mmk_conv_bwd_fused(x, g, at(sc, p.packs_t[k]), 1.f, B, h, w, ch, dx, part_ptr(k), 0, stream);
     };
     auto wgrad = [&](int k, const void *x1, int C1, const void *x2, int C2, const void *g, int h, int w, const void *g_arg = nullptr) -> int {
-        if (ss) {   // g was produced by the launch just enqueued on the caller's stream
-            MMK_CHECK_HIP(hipEventRecord(ss->fork, st));
-            MMK_CHECK_HIP(hipStreamWaitEvent(ss->st, ss->fork, 0));
-        }
+        MMK_TRY(fork());    // g was produced by the launch just enqueued on the caller's stream
         // (the plan sized the slices for an unsplit input; a split input must give the same count)
         if (mmk_conv3x3_wgrad_slices(p.cout[k], p.cinn[k], C1, B, h, w) != p.slices[k]) {
             mmk::set_error("mmk_unet_backward: partial-slice count of layer %d depends on the input split", k);
@@ -557,6 +518,17 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
         }
         if (g_arg) return mmk_conv3x3_wgrad_partial_pooled(x1, x2, C1, C2, g, g_arg, s, p.cout[k], B, h, w, part_ptr(k), 0, wstream);
         return mmk_conv3x3_wgrad_partial(x1, x2, C1, C2, g, p.cout[k], B, h, w, part_ptr(k), 0, wstream);
+    };
+    auto run = [&](const mmk_conv_desc &c) { return mmk_conv3x3(&c, stream); };
+    // Backward of a block's second convolution k (ch -> ch; input x, output gradient g, or the pooled gradient with its codes
+    // g_arg): the one-launch form where the layer has it, else the weight gradient beside a data gradient with x as ReLU source
+    auto second_conv_bwd = [&](int k, int ch, const void *x, const void *g, void *dx, int h, int w, const void *g_arg) -> int {
+        if (can_fuse(k, ch, h, w)) return bwd_fused(k, ch, x, g, dx, h, w, g_arg);
+        MMK_TRY(wgrad(k, x, ch, nullptr, 0, g, h, w, g_arg));
+        mmk_conv_desc c = conv_desc(p, h, w, sl);
+        c.x1 = g; c.C1 = ch; c.wpack = at(sc, p.packs_t[k]); c.y1 = dx; c.O1 = ch; c.relu_src1 = x;
+        if (g_arg) { c.x1_pool_arg = g_arg; c.x1_pool_scale = s; }
+        return run(c);
     };
 
     // ---- final layer
@@ -576,48 +548,31 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
         const int k0 = 12 + 2 * j, k1 = 13 + 2 * j;
         const void *skip = at(ws, p.t[4 - j].off);
         // second application
-        const bool fuse8 = can_fuse(k1, cs, h, w);
-        if (fuse8) {
-            MMK_TRY(bwd_fused(k1, cs, at(ws, p.a2[j].off), gz, at(sc, p.gz_a2[j].off), h, w));
-        } else {
-            MMK_TRY(wgrad(k1, at(ws, p.a2[j].off), cs, nullptr, 0, gz, h, w));
-            ConvCall c;
-            c.x1 = gz; c.C1 = cs; c.wpack = at(sc, p.packs_t[k1]); c.y1 = at(sc, p.gz_a2[j].off); c.O1 = cs;
-            c.src1 = at(ws, p.a2[j].off); c.scale1 = 1.f;
-            MMK_TRY(conv(p, h, w, sl, c, stream));
-        }
+        MMK_TRY(second_conv_bwd(k1, cs, at(ws, p.a2[j].off), gz, at(sc, p.gz_a2[j].off), h, w, nullptr));
         if (j == 4 && sl == 0.f && cs == 8 && p.slices[k0] > 0 && mmk_conv3x3_wgrad_slices(8, 16, 8, B, h, w) == p.slices[k0]) {
             // last decoder block: both halves of the data gradient are masked by the two halves of the weight gradient's input
             MMK_TRY(mmk_conv16x8_bwd_fused(skip, at(ws, p.d1[j].off), at(sc, p.gz_a2[j].off), at(sc, p.packs_t[k0]), s, B, h, w,
                                            at(sc, p.gsk[j].off), at(sc, p.gz_d1[j].off), part_ptr(k0), 0, stream));
         } else {
             MMK_TRY(wgrad(k0, skip, cs, at(ws, p.d1[j].off), cs, at(sc, p.gz_a2[j].off), h, w));
-            ConvCall c2;       // one pass, two outputs: the skip's gradient and the first application's output gradient
+            mmk_conv_desc c2 = conv_desc(p, h, w, sl);      // one pass, two outputs: the skip's gradient and the first application's output gradient
             c2.x1 = at(sc, p.gz_a2[j].off); c2.C1 = cs; c2.wpack = at(sc, p.packs_t[k0]);
             c2.y1 = at(sc, p.gsk[j].off); c2.O1 = cs; c2.scale1 = s;
-            c2.src1 = (j == 4) ? skip : nullptr;   // dec4's skip is the post-dropout activation of encoder block 0
-            c2.y2 = at(sc, p.gz_d1[j].off); c2.O2 = cs; c2.src2 = at(ws, p.d1[j].off); c2.scale2 = s;
-            MMK_TRY(conv(p, h, w, sl, c2, stream));
+            c2.relu_src1 = (j == 4) ? skip : nullptr;   // dec4's skip is the post-dropout activation of encoder block 0
+            c2.y2 = at(sc, p.gz_d1[j].off); c2.O2 = cs; c2.relu_src2 = at(ws, p.d1[j].off); c2.scale2 = s;
+            MMK_TRY(run(c2));
         }
         // first application
-        if (fuse8) {
-            MMK_TRY(bwd_fused(k1, cs, at(ws, p.a1[j].off), at(sc, p.gz_d1[j].off), at(sc, p.gz_a1[j].off), h, w));
-        } else {
-            MMK_TRY(wgrad(k1, at(ws, p.a1[j].off), cs, nullptr, 0, at(sc, p.gz_d1[j].off), h, w));
-            ConvCall c3;
-            c3.x1 = at(sc, p.gz_d1[j].off); c3.C1 = cs; c3.wpack = at(sc, p.packs_t[k1]); c3.y1 = at(sc, p.gz_a1[j].off); c3.O1 = cs;
-            c3.src1 = at(ws, p.a1[j].off); c3.scale1 = 1.f;
-            MMK_TRY(conv(p, h, w, sl, c3, stream));
-        }
+        MMK_TRY(second_conv_bwd(k1, cs, at(ws, p.a1[j].off), at(sc, p.gz_d1[j].off), at(sc, p.gz_a1[j].off), h, w, nullptr));
         if (j == 4 && sl == 0.f && cs == 8 && p.slices[k0] > 0 && mmk_conv3x3_wgrad_slices(8, 16, 16, B, h, w) == p.slices[k0]) {
             // (first application: the input is the up-sampled tensor, no ReLU source -- the launch shares the output gradient)
             MMK_TRY(mmk_conv16x8_bwd_fused(at(ws, p.u[j].off), nullptr, at(sc, p.gz_a1[j].off), at(sc, p.packs_t[k0]), 1.f, B, h, w,
                                            at(sc, p.g_u[j].off), nullptr, part_ptr(k0), 0, stream));
         } else {
             MMK_TRY(wgrad(k0, at(ws, p.u[j].off), 2 * cs, nullptr, 0, at(sc, p.gz_a1[j].off), h, w));
-            ConvCall c4;
+            mmk_conv_desc c4 = conv_desc(p, h, w, sl);
             c4.x1 = at(sc, p.gz_a1[j].off); c4.C1 = cs; c4.wpack = at(sc, p.packs_t[k0]); c4.y1 = at(sc, p.g_u[j].off); c4.O1 = 2 * cs;
-            MMK_TRY(conv(p, h, w, sl, c4, stream));
+            MMK_TRY(run(c4));
         }
         if (j > 0) {
             const Tens &pd2 = p.d2[j - 1];
@@ -658,16 +613,7 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
             else
                 MMK_TRY(mmk_maxpool2_bwd(at(ws, p.d_enc[i].off), g_t, B, h, w, ch, s, sl, at(sc, p.gz_d[i].off), stream));
         }
-        if (can_fuse(2 * i + 1, ch, h, w)) {
-            MMK_TRY(bwd_fused(2 * i + 1, ch, at(ws, p.a_enc[i].off), g_d, at(sc, p.gz_a[i].off), h, w, g_arg));
-        } else {
-            MMK_TRY(wgrad(2 * i + 1, at(ws, p.a_enc[i].off), ch, nullptr, 0, g_d, h, w, g_arg));
-            ConvCall c;
-            c.x1 = g_d; c.C1 = ch; c.wpack = at(sc, p.packs_t[2 * i + 1]); c.y1 = at(sc, p.gz_a[i].off); c.O1 = ch;
-            c.src1 = at(ws, p.a_enc[i].off); c.scale1 = 1.f;
-            c.x1_arg = g_arg; c.x1_scale = s;
-            MMK_TRY(conv(p, h, w, sl, c, stream));
-        }
+        MMK_TRY(second_conv_bwd(2 * i + 1, ch, at(ws, p.a_enc[i].off), g_d, at(sc, p.gz_a[i].off), h, w, g_arg));
         // data gradient accumulates into the skip gradient the decoder wrote for t[i-1]
         void *tgt = at(sc, p.gsk[5 - i].off);             // g_skip[i-1] was written by decoder block j = 4 - (i-1)
         if (i == 1 && sl == 0.f && ch == 16 && ENC_CH[0] == 8 && p.slices[2] > 0 &&
@@ -677,11 +623,11 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
                                            part_ptr(2), 0, stream));
         } else {
             MMK_TRY(wgrad(2 * i, at(ws, p.t[i - 1].off), ENC_CH[i - 1], nullptr, 0, at(sc, p.gz_a[i].off), h, w));
-            ConvCall c2;
+            mmk_conv_desc c2 = conv_desc(p, h, w, sl);
             c2.x1 = at(sc, p.gz_a[i].off); c2.C1 = ch; c2.wpack = at(sc, p.packs_t[2 * i]); c2.y1 = tgt; c2.O1 = ENC_CH[i - 1];
-            c2.acc1 = 1;
-            if (i == 1) { c2.src1 = at(ws, p.t[0].off); c2.scale1 = s; }   // t[0] is an activation: factor, then accumulate
-            MMK_TRY(conv(p, h, w, sl, c2, stream));
+            c2.accumulate1 = 1;
+            if (i == 1) { c2.relu_src1 = at(ws, p.t[0].off); c2.scale1 = s; }   // t[0] is an activation: factor, then accumulate
+            MMK_TRY(run(c2));
         }
         g_t = tgt;
         // the >= 64-channel encoder layers have their weight gradients enqueued: reduce their slices now (the reduction reads
@@ -693,15 +639,7 @@ int unet_backward_impl(const mmk_unet_desc *d, const float *gmask, float *const 
         }
     }
     // ---- encoder block 0
-    if (can_fuse(1, 8, p.H, p.W)) {
-        MMK_TRY(bwd_fused(1, 8, at(ws, p.a_enc[0].off), g_t, at(sc, p.gz_a[0].off), p.H, p.W));
-    } else {
-        MMK_TRY(wgrad(1, at(ws, p.a_enc[0].off), 8, nullptr, 0, g_t, p.H, p.W));
-        ConvCall c;
-        c.x1 = g_t; c.C1 = 8; c.wpack = at(sc, p.packs_t[1]); c.y1 = at(sc, p.gz_a[0].off); c.O1 = 8;
-        c.src1 = at(ws, p.a_enc[0].off); c.scale1 = 1.f;
-        MMK_TRY(conv(p, p.H, p.W, sl, c, stream));
-    }
+    MMK_TRY(second_conv_bwd(1, 8, at(ws, p.a_enc[0].off), g_t, at(sc, p.gz_a[0].off), p.H, p.W, nullptr));
     // ---- parameter gradients of the first five 3x3 layers (the rest was reduced on the way): on the weight-gradient stream,
     // beside the first layer's weight gradient
     MMK_TRY(unpack(1, 5));

@@ -19,6 +19,19 @@ def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+_sp = _lib.stream_ptr
+
+
+def _flat_grads(sizes, device):
+    """One zero-filled fp32 buffer for gradients of these sizes, each aligned to 4 floats (one fill instead of ~45; zeros, because
+    a DDP all-reduce sums the alignment gaps too): (buffer, [segment per size])."""
+    offs = [0]
+    for n in sizes:
+        offs.append(offs[-1] + (n + 3) // 4 * 4)
+    flat = torch.zeros(offs[-1], dtype=torch.float32, device=device)
+    return flat, [flat[o:o + n] for o, n in zip(offs, sizes)]
+
+
 def pack_weights(w, transposed=False):
     """fp32 (COUT,CIN,3,3) -> packed bf16 for mmk_conv3x3 (transposed: data-gradient operator)."""
     L = _lib.lib()
@@ -28,8 +41,8 @@ def pack_weights(w, transposed=False):
         raise _lib.MmkError("unsupported conv channel counts %d -> %d" % (cin, cout))
     out = torch.empty(n, dtype=BF16, device=w.device)
     wf = w.detach().float().contiguous()
-    _lib.check(L.mmk_conv3x3_pack_weights(_lib.ptr(wf), cout, cin, 1 if transposed else 0, _lib.ptr(out),
-                                          _lib.stream_ptr(w.device)))
+    _lib.check(L.mmk_conv3x3_pack_weights(_p(wf), cout, cin, 1 if transposed else 0, _p(out),
+                                          _sp(w.device)))
     return out
 
 
@@ -51,7 +64,7 @@ def pack_weights_batch(ws, transposed=False):
     Op = (ctypes.c_void_p * n)(*[base + 2 * o for o in offs[:-1]])
     co = (ctypes.c_int32 * n)(*[w.shape[0] for w in ws])
     ci = (ctypes.c_int32 * n)(*[w.shape[1] for w in ws])
-    _lib.check(L.mmk_conv3x3_pack_weights_batch(n, Wp, co, ci, tr, Op, _lib.stream_ptr(ws[0].device)))
+    _lib.check(L.mmk_conv3x3_pack_weights_batch(n, Wp, co, ci, tr, Op, _sp(ws[0].device)))
     return [buf[offs[i]:offs[i] + sizes[i]] for i in range(n)]
 
 
@@ -85,7 +98,7 @@ def conv3x3(x1, wpack, cout, bias=None, x2=None, relu=False, drop_p=0.0, seed=0,
                       drop_p=float(drop_p),
                       seed=int(seed) & 0xFFFFFFFF, pool_y=_p(pool_out), pool_arg=_p(pool_arg), x1_pool_arg=_p(x1_pool_arg),
                       x1_pool_scale=float(x1_pool_scale))
-    _lib.check(_lib.lib().mmk_conv3x3(ctypes.byref(d), _lib.stream_ptr(x1.device)))
+    _lib.check(_lib.lib().mmk_conv3x3(ctypes.byref(d), _sp(x1.device)))
     if pool_arg is not None:
         return None
     return (out, out2) if O2 > 0 else out
@@ -155,10 +168,10 @@ def conv3x3_wgrad_partial(x1, g, cout, partials, x2=None, accumulate=False, g_po
         assert g.shape == (B, H // 2, W // 2, cout) and g_pool_arg.shape == (B, H // 2, W // 2, cout // 2)
         _lib.check(_lib.lib().mmk_conv3x3_wgrad_partial_pooled(_p(x1), _p(x2), C1, C2, _p(g), _p(g_pool_arg), float(g_pool_scale),
                                                                cout, B, H, W, _p(partials), 1 if accumulate else 0,
-                                                               _lib.stream_ptr(x1.device)))
+                                                               _sp(x1.device)))
         return partials
     _lib.check(_lib.lib().mmk_conv3x3_wgrad_partial(_p(x1), _p(x2), C1, C2, _p(g), cout, B, H, W, _p(partials),
-                                                    1 if accumulate else 0, _lib.stream_ptr(x1.device)))
+                                                    1 if accumulate else 0, _sp(x1.device)))
     return partials
 
 
@@ -172,11 +185,11 @@ def conv_bwd_fused(x, g, wpack_t, scale, dx, partials, accumulate=False, g_pool_
         assert C == 16 and g.shape == (B, H // 2, W // 2, C) and g_pool_arg.shape == (B, H // 2, W // 2, C // 2) and dx.shape == x.shape
         _lib.check(_lib.lib().mmk_conv_bwd_fused_pooled(_p(x), _p(g), _p(g_pool_arg), float(g_pool_scale), _p(wpack_t), float(scale),
                                                         B, H, W, C, _p(dx), _p(partials), 1 if accumulate else 0,
-                                                        _lib.stream_ptr(x.device)))
+                                                        _sp(x.device)))
         return dx, partials
     assert C in (8, 16) and g.shape == x.shape and dx.shape == x.shape
     _lib.check(_lib.lib().mmk_conv_bwd_fused(_p(x), _p(g), _p(wpack_t), float(scale), B, H, W, C, _p(dx), _p(partials),
-                                             1 if accumulate else 0, _lib.stream_ptr(x.device)))
+                                             1 if accumulate else 0, _sp(x.device)))
     return dx, partials
 
 
@@ -186,7 +199,7 @@ def conv8x16_bwd_fused(x, g, wpack_t, scale, dx, partials, accumulate=False):
     B, H, W, C = x.shape
     assert C == 8 and g.shape == (B, H, W, 16) and dx.shape == x.shape
     _lib.check(_lib.lib().mmk_conv8x16_bwd_fused(_p(x), _p(g), _p(wpack_t), float(scale), B, H, W, _p(dx), _p(partials),
-                                                 1 if accumulate else 0, _lib.stream_ptr(x.device)))
+                                                 1 if accumulate else 0, _sp(x.device)))
     return dx, partials
 
 
@@ -200,7 +213,7 @@ def conv16x8_bwd_fused(x1, x2, g, wpack_t, scale, dx1, dx2, partials, accumulate
     else:
         assert C == 8 and x2.shape == x1.shape and g.shape == x1.shape and dx1.shape == x1.shape and dx2.shape == x1.shape
     _lib.check(_lib.lib().mmk_conv16x8_bwd_fused(_p(x1), _p(x2), _p(g), _p(wpack_t), float(scale), B, H, W, _p(dx1), _p(dx2),
-                                                 _p(partials), 1 if accumulate else 0, _lib.stream_ptr(x1.device)))
+                                                 _p(partials), 1 if accumulate else 0, _sp(x1.device)))
     return dx1, dx2, partials
 
 
@@ -230,15 +243,11 @@ def wgrad_unpack_batch(items):
     sl = (ctypes.c_int32 * n)(*slices)
     co = (ctypes.c_int32 * n)(*couts)
     ci = (ctypes.c_int32 * n)(*cins)
-    _lib.check(_lib.lib().mmk_conv3x3_wgrad_unpack_batch(n, Sp, sl, co, ci, Op, Dp, _lib.stream_ptr(dev)))
+    _lib.check(_lib.lib().mmk_conv3x3_wgrad_unpack_batch(n, Sp, sl, co, ci, Op, Dp, _sp(dev)))
     return [buf[offs[i]:offs[i] + sizes[i]].view(couts[i], cins[i], 3, 3) for i in range(n)]
 
 
 # ----------------------------------------------------------------------------- small wrappers
-def _sp(dev):
-    return _lib.stream_ptr(dev)
-
-
 def conv_first_wgrad(x, gz, pre, dW, db):
     """First layer's weight / bias gradient WRITTEN to dW (8,cin,3,3) and db (8,) (block partials + ordered reduction)."""
     L = _lib.lib()
@@ -516,21 +525,15 @@ class _UNet(torch.autograd.Function):
         def pkt(k):
             return packs_t[k]
 
-        # one zero-filled fp32 buffer for every gradient accumulator (one fill instead of ~45)
+        # one zero-filled fp32 buffer for every gradient accumulator
         cin0 = x.shape[1]
         sizes = [8 * cin0 * 9, 8]
         for k in range(1, 22):
             sizes += [9 * W(k).shape[0] * W(k).shape[1], W(k).shape[0]]
         sizes += [8, 1]
-        offs = [0]
-        for n in sizes:
-            offs.append(offs[-1] + (n + 3) // 4 * 4)
-        flat = torch.zeros(offs[-1], dtype=torch.float32, device=dev)
+        seg = _flat_grads(sizes, dev)[1]
 
-        def seg(i):
-            return flat[offs[i]:offs[i] + sizes[i]]
-
-        dB = {k: seg(2 * k + 1) for k in range(1, 22)}
+        dB = {k: seg[2 * k + 1] for k in range(1, 22)}
 
         part = {}        # layer -> partial-sum slices (weights + bias)
         part_sets = {}   # layer -> sets of slices written so far
@@ -552,7 +555,7 @@ class _UNet(torch.autograd.Function):
         # ---- final layer
         u4, a1_4, d1_4, a2_4, d2_4 = ctx.saved_dec[4]
         wf8 = W(22).float().reshape(8).contiguous()
-        g_fw, g_fb = seg(44), seg(45)
+        g_fw, g_fb = seg[44], seg[45]
         gz = torch.empty_like(d2_4)
         red = torch.empty(_lib.FINAL_BWD_WS_FLOATS, dtype=torch.float32, device=dev)
         if ctx.norm:
@@ -620,7 +623,7 @@ class _UNet(torch.autograd.Function):
         gz_d0 = g_t
         wgrad(1, a0, gz_d0)
         gz_a0 = conv3x3(gz_d0, pkt(1), 8, relu_src=a0, scale=1.0, slope=sl)
-        g_w0, g_b0 = seg(0).view(8, cin0, 3, 3), seg(1)
+        g_w0, g_b0 = seg[0].view(8, cin0, 3, 3), seg[1]
         conv_first_wgrad(x, gz_a0, ctx.pre, g_w0, g_b0)
         g_x = None
         if ctx.needs_input_grad[0]:       # the input image: the first layer's data gradient + the folded normalisation's adjoint
@@ -657,6 +660,24 @@ def workspace_tensor(ws, B, H, W, cin, tid):
     return ws[off.value:off.value + 2 * n].view(BF16).view(B, h.value, w.value, c.value)
 
 
+def _reported(nbytes):
+    """A buffer size the library reported; 0 is its refusal, raised with the reason."""
+    if nbytes == 0:
+        raise _lib.MmkError("libmmk_hip: %s" % _lib.lib().mmk_last_error().decode(errors="replace"))
+    return nbytes
+
+
+def _unet_desc(args, x, pre, P, ws, mask, keep_full_res=0):
+    """mmk_unet_desc of a pass from the values forward() keeps for backward() (ctx.desc_args)."""
+    B, H, W, cin, p_drop, seed, slope, norm = args
+    pp = (ctypes.c_void_p * len(P))(*[t.data_ptr() for t in P])
+    d = _lib.UNetDesc(B=B, H=H, W=W, cin=cin, x=x.data_ptr(), pre=None if pre is None else pre.data_ptr(), params=pp,
+                      drop_p=p_drop, seed=seed, leaky_slope=slope, norm=norm, workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+                      mask=mask.data_ptr(), keep_full_res=keep_full_res)
+    d.params_array = pp         # (lives as long as the descriptor)
+    return d
+
+
 class _UNetNative(torch.autograd.Function):
     """The same network through mmk_unet_forward / mmk_unet_backward: one C call per pass."""
 
@@ -668,16 +689,11 @@ class _UNetNative(torch.autograd.Function):
         x = x.contiguous().float()
         B, cin, H, W = x.shape
         P = [p.detach().float().contiguous() for p in params]
-        nbytes = L.mmk_unet_workspace_bytes(B, H, W, cin)
-        if nbytes == 0:
-            raise _lib.MmkError("libmmk_hip: %s" % L.mmk_last_error().decode(errors="replace"))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_reported(L.mmk_unet_workspace_bytes(B, H, W, cin)), dtype=torch.uint8, device=dev)
         mask = torch.empty(B, H, W, dtype=torch.float32, device=dev)
-        pp = (ctypes.c_void_p * len(P))(*[t.data_ptr() for t in P])
-        d = _lib.UNetDesc(B=B, H=H, W=W, cin=cin, x=x.data_ptr(), pre=None if pre is None else pre.data_ptr(), params=pp,
-                          drop_p=float(drop_p) if training else 0.0, seed=int(seed) & 0xFFFFFFFF, leaky_slope=float(slope),
-                          norm=1 if norm else 0, workspace=ws.data_ptr(), workspace_bytes=nbytes, mask=mask.data_ptr(),
-                          keep_full_res=1 if DEBUG is not None else 0)     # (the pre-pool outputs: only diagnostics read them)
+        ctx.desc_args = (B, H, W, cin, float(drop_p) if training else 0.0, int(seed) & 0xFFFFFFFF, float(slope), 1 if norm else 0)
+        d = _unet_desc(ctx.desc_args, x, pre, P, ws, mask,
+                       keep_full_res=1 if DEBUG is not None else 0)     # (the pre-pool outputs: only diagnostics read them)
         _lib.check(L.mmk_unet_forward(ctypes.byref(d), _sp(dev)))
         if DEBUG is not None:
             def tv(tid):
@@ -685,7 +701,6 @@ class _UNetNative(torch.autograd.Function):
             DEBUG["fwd"] = {"t": [tv(12 + i) for i in range(6)],
                             "enc": {"e%d" % i: (tv(i), tv(6 + i)) for i in range(6)},
                             "dec": [tuple(tv(18 + 5 * j + q) for q in range(5)) for j in range(5)]}
-        ctx.desc_args = (B, H, W, cin, float(drop_p) if training else 0.0, int(seed) & 0xFFFFFFFF, float(slope), 1 if norm else 0)
         ctx.x, ctx.pre, ctx.P, ctx.ws = x, pre, P, ws
         # an alias, not the output object itself (output -> grad_fn -> ctx -> output would be a reference cycle
         # that keeps the workspace alive until the cyclic GC runs)
@@ -695,25 +710,15 @@ class _UNetNative(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gmask):
         L = _lib.lib()
-        B, H, W, cin, p_drop, seed, slope, norm = ctx.desc_args
+        B, H, W, cin = ctx.desc_args[:4]
         x, P, ws = ctx.x, ctx.P, ctx.ws
         dev = x.device
         gmask = gmask.contiguous().float()
-        nscratch = L.mmk_unet_scratch_bytes(B, H, W, cin)
-        if nscratch == 0:
-            raise _lib.MmkError("libmmk_hip: %s" % L.mmk_last_error().decode(errors="replace"))
+        nscratch = _reported(L.mmk_unet_scratch_bytes(B, H, W, cin))
         scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
-        sizes = [p.numel() for p in P]
-        offs = [0]
-        for n in sizes:
-            offs.append(offs[-1] + (n + 3) // 4 * 4)
-        flat = torch.zeros(offs[-1], dtype=torch.float32, device=dev)   # (zeros: the alignment gaps are summed by a DDP all-reduce)
-        grads = [flat[offs[i]:offs[i] + sizes[i]].view(P[i].shape) for i in range(len(P))]
-        pp = (ctypes.c_void_p * len(P))(*[t.data_ptr() for t in P])
+        grads = [g.view(p.shape) for g, p in zip(_flat_grads([p.numel() for p in P], dev)[1], P)]
         gp = (ctypes.c_void_p * len(P))(*[t.data_ptr() for t in grads])
-        d = _lib.UNetDesc(B=B, H=H, W=W, cin=cin, x=x.data_ptr(), pre=None if ctx.pre is None else ctx.pre.data_ptr(), params=pp,
-                          drop_p=p_drop, seed=seed, leaky_slope=slope, norm=norm, workspace=ws.data_ptr(),
-                          workspace_bytes=ws.numel(), mask=ctx.mask.data_ptr())
+        d = _unet_desc(ctx.desc_args, x, ctx.pre, P, ws, ctx.mask)
         evs = GRAD_BUCKET_EVENTS
         ep = None
         if evs is not None:
