@@ -311,6 +311,20 @@ def ptr(t, dtype=None, name="tensor"):
     return ctypes.c_void_p(t.data_ptr())
 
 
+_ws_cache = {}
+
+
+def workspace(nbytes, device, tag):
+    """Scratch of at least ``nbytes`` for the kernels of one family (``tag``: callers under different tags never share a
+    buffer), one growing buffer per (device, stream, tag): calls enqueued on different streams must not share scratch."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, tag)
+    buf = _ws_cache.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+        _ws_cache[key] = buf
+    return buf
+
+
 def dev_f32(t, device):
     """Reference call sites hand over CPU or device tensors of any float type
     (icp_weight_policy.py:130-134 moves them itself); normalise to contiguous

@@ -22,6 +22,12 @@ import torch
 import torch.distributed as dist
 
 
+def job_size(process_group=None):
+    """The number of ranks of the job this process belongs to (of ``process_group``); 1 outside a job: a build without
+    torch.distributed, or no process group yet.  Asked when used: a group may be initialised after a model is built."""
+    return dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+
+
 class FlatGradSync:
     def __init__(self, module, process_group=None, overlap=False, force_collective=False):
         """``force_collective``: issue the collectives even in a one-rank group (the single-GPU rehearsal of the N-rank path:

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 from torch.nn import ModuleList
 
+from . import _lib
 from .dICP.ICP import ICP
 from .radar_utils import (_extract_weights_polar_stats, _extract_weights_stats, cfar_mask, extract_pc_padded, extract_weights, form_cart_range_angle_grid,
                           form_polar_range_grid, mask_polar_scan)
@@ -42,12 +43,28 @@ def weights_init(m):
 def _global_extrema(c_min, c_max):
     """min / max over the ranks of a data-parallel job (one MAX all-reduce of [-min, max]); the identity in a
     single-process run.  Same reduction as unet_hip.channel_minmax(global_reduce=True) on the HIP path."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+    from .ddp import dist, job_size
+    if job_size() == 1:
         return c_min, c_max
     t = torch.stack((-c_min.detach(), c_max.detach()))
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return -t[0], t[1]
+
+
+# scan mode and polar sampling: how the option reads in a message, the params setting that makes prepare_batch supply what
+# it reads, and what it does in a HIP kernel
+_BATCH_OPTIONS = {"scan": ("mask_target='scan'", "params['mask_target'] = 'scan'", "runs the radar front end in HIP kernels"),
+                  "polar": ("polar_sampling", "params['polar_sampling'] = True", "samples the mask in a HIP kernel")}
+
+
+def _check_batch(option, batch_scan, keys, device=None):
+    """What a forward with ``option`` needs: ``keys`` in batch_scan and, when ``device`` is given, a HIP device."""
+    what, setting, does = _BATCH_OPTIONS[option]
+    for key in keys:
+        if key not in batch_scan:
+            raise KeyError("%s needs batch_scan[%r] (prepare_batch with %s, or finish_batch(keep_polar=True))" % (what, key, setting))
+    if device is not None and torch.device(device).type != "cuda":
+        raise _lib.MmkError("%s %s with no CPU path: params['device'] must be a HIP device" % (what, does))
 
 
 class LearnICPWeightPolicy(nn.Module):
@@ -192,8 +209,8 @@ class LearnICPWeightPolicy(nn.Module):
         else "this process is a rank of a multi-rank job" -- asked when used, not when the model was built."""
         if self._global_minmax is not None:
             return self._global_minmax
-        import torch.distributed as dist
-        return bool(dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+        from .ddp import job_size
+        return job_size() > 1
 
     @global_minmax.setter
     def global_minmax(self, value):
@@ -265,6 +282,46 @@ class LearnICPWeightPolicy(nn.Module):
         logits = self.final_layer[0](input_data)
         return torch.sigmoid(logits.float()).squeeze(1)
 
+    def _unet_hip(self, raw_in):
+        """The mask of the raw network input (B, C, H, W) from the hand-written kernels (unet_hip.py / unet_hip_bn.py), with
+        the per-channel normalisation folded into the first layer's loads and, with norm_weights, the amax normalisation of
+        the mask inside the same autograd node."""
+        from . import unet_hip, unet_hip_bn
+        if not raw_in.is_cuda:
+            raise _lib.MmkError("the mask U-Net is a set of HIP kernels with no CPU path: params['device'] must be "
+                                "a HIP device (unet_backend='torch' is the CPU host-logic mirror used by tests)")
+        # any image of at least 32 x 32 (five floor-rounding poolings leave >= 1 pixel): the Cartesian
+        # 640 x 640 grid and the polar 400 x 3360 one (network_input_type "polar") alike
+        if raw_in.shape[1] > 4 or raw_in.shape[2] < 32 or raw_in.shape[3] < 32:
+            raise _lib.MmkError("mask U-Net: unsupported network input %s (1..4 channels, at least 32 x 32)"
+                                % (tuple(raw_in.shape),))
+        self._step += 1
+        # an image that requires grad receives its gradient from the network's autograd node; the statistics of a
+        # folded normalisation are computed outside the graph, so the node is told which ones they are (input_norm)
+        want_gx = torch.is_grad_enabled() and raw_in.requires_grad
+        mode = next((m for m in ("minmax", "standardize") if m in self.normalize_type), None)
+        if mode is None:
+            net_in, pre, mm = self._normalize_channels(raw_in), None, None
+        else:
+            # folded into the first layer's loads: one pass for (min, max), or two ordered ones for (mean, 1 / std) -- per
+            # rank under data parallelism, as the reference's torch.mean / torch.std of its own batch -- and no
+            # normalised copy of the image
+            net_in = raw_in.contiguous().float()
+            if mode == "standardize":
+                pre, mm = unet_hip.channel_meanstd(net_in), None
+            elif not want_gx:
+                pre, mm = unet_hip.channel_minmax(net_in, global_reduce=self.global_minmax), None
+            elif unet_hip.minmax_is_collective(self.global_minmax):
+                raise _lib.MmkError("the gradient with respect to the network input through min-max extrema that are "
+                                    "reduced over the ranks is not implemented: set params['global_minmax'] = False "
+                                    "or detach the input")
+            else:
+                pre, mm = unet_hip.channel_minmax(net_in, return_minmax=True)
+        # batch_norm: Conv, ReLU, BN, Conv, ReLU, BN, with BatchNorm kernels between the convolutions
+        return (unet_hip_bn if self.batch_norm else unet_hip).unet_mask(
+            self, net_in, self.training, self._step, norm=self.norm_weights, pre=pre, slope=0.1 if self.leaky else 0.0,
+            input_norm=(mode, mm) if want_gx and mode is not None else None)
+
     def forward(self, batch_scan, batch_map, T_init, binary=False, override_mask=None, neptune_run=None, epoch=0,
                 batch_idx=0, mask_only=False):
         fft_data = batch_scan["fft_data"].to(self.device)
@@ -272,86 +329,29 @@ class LearnICPWeightPolicy(nn.Module):
         scan_pc_raw = batch_scan["raw_pc"].to(self.device)
         map_pc = batch_map["pc"].to(self.device)
         if self.mask_target == "scan" and not mask_only:
-            from . import _lib
-            for key in (("azimuths",) if self.network_input_type == "polar" else ("fft_polar", "azimuths")):
-                if key not in batch_scan:
-                    raise KeyError("mask_target='scan' needs batch_scan[%r] (prepare_batch with params['mask_target'] = 'scan', "
-                                   "or finish_batch(keep_polar=True))" % key)
-            if torch.device(self.device).type != "cuda":
-                raise _lib.MmkError("mask_target='scan' runs the radar front end in HIP kernels with no CPU path: "
-                                    "params['device'] must be a HIP device")
-
+            _check_batch("scan", batch_scan, ("azimuths",) if self.network_input_type == "polar" else ("fft_polar", "azimuths"),
+                         self.device)
         if self.polar_sampling and not mask_only:
-            from . import _lib
-            if "azimuths" not in batch_scan:
-                raise KeyError("polar_sampling needs batch_scan['azimuths'] (prepare_batch with params['polar_sampling'] = True, "
-                               "or finish_batch(keep_polar=True))")
-            if torch.device(self.device).type != "cuda":
-                raise _lib.MmkError("polar_sampling samples the mask in a HIP kernel with no CPU path: "
-                                    "params['device'] must be a HIP device")
+            _check_batch("polar", batch_scan, ("azimuths",), self.device)
             n_az = batch_scan["azimuths"].shape[1]
             if override_mask is not None and (override_mask.ndim != 3 or override_mask.shape[0] != scan_pc_raw.shape[0] or
                                               override_mask.shape[1] != n_az):
                 raise ValueError("polar_sampling: override_mask must be a polar (B, %d, R) mask (got %s)"
                                  % (n_az, tuple(override_mask.shape)))
 
-        if override_mask is None:
+        normalised = False
+        if override_mask is not None:
+            weight_mask = override_mask.to(self.device)
+        else:
             raw_in = self._network_input(fft_data, fft_cfar, normalize=False)
             if self.unet_backend == "hip":
-                from . import _lib, unet_hip
-                if not raw_in.is_cuda:
-                    raise _lib.MmkError("the mask U-Net is a set of HIP kernels with no CPU path: params['device'] must be "
-                                        "a HIP device (unet_backend='torch' is the CPU host-logic mirror used by tests)")
-                # any image of at least 32 x 32 (five floor-rounding poolings leave >= 1 pixel): the Cartesian
-                # 640 x 640 grid and the polar 400 x 3360 one (network_input_type "polar") alike
-                if raw_in.shape[1] > 4 or raw_in.shape[2] < 32 or raw_in.shape[3] < 32:
-                    raise _lib.MmkError("mask U-Net: unsupported network input %s (1..4 channels, at least 32 x 32)"
-                                        % (tuple(raw_in.shape),))
-                self._step += 1
-                # an image that requires grad receives its gradient from the network's autograd node; the statistics of a
-                # folded normalisation are computed outside the graph, so the node is told which ones they are (input_norm)
-                want_gx = torch.is_grad_enabled() and raw_in.requires_grad
-                in_norm = None
-                if "minmax" in self.normalize_type:
-                    # min-max normalisation folded into the first layer's loads: one min/max pass, no
-                    # normalised copy of the image
-                    net_in = raw_in.contiguous().float()
-                    if want_gx:
-                        if unet_hip.minmax_is_collective(self.global_minmax):
-                            raise _lib.MmkError("the gradient with respect to the network input through min-max extrema that are "
-                                                "reduced over the ranks is not implemented: set params['global_minmax'] = False "
-                                                "or detach the input")
-                        pre, mm = unet_hip.channel_minmax(net_in, return_minmax=True)
-                        in_norm = ("minmax", mm)
-                    else:
-                        pre = unet_hip.channel_minmax(net_in, global_reduce=self.global_minmax)
-                elif "standardize" in self.normalize_type:
-                    # standardisation folded in the same way: (mean, 1 / std) per channel from two ordered passes, per
-                    # rank under data parallelism (as the reference's torch.mean / torch.std of its own batch)
-                    net_in = raw_in.contiguous().float()
-                    pre = unet_hip.channel_meanstd(net_in)
-                    in_norm = ("standardize", None) if want_gx else None
-                else:
-                    net_in, pre = self._normalize_channels(raw_in), None
-                # (the amax normalisation below rides inside the same autograd node)
-                if self.batch_norm:        # Conv, ReLU, BN, Conv, ReLU, BN: BatchNorm kernels between the convolutions
-                    from . import unet_hip_bn
-                    weight_mask = unet_hip_bn.unet_mask(self, net_in, self.training, self._step, norm=self.norm_weights, pre=pre,
-                                                        slope=0.1 if self.leaky else 0.0, input_norm=in_norm)
-                else:
-                    weight_mask = unet_hip.unet_mask(self, net_in, self.training, self._step, norm=self.norm_weights, pre=pre,
-                                                     slope=0.1 if self.leaky else 0.0, input_norm=in_norm)
-                normalised = self.norm_weights
+                weight_mask = self._unet_hip(raw_in)
+                normalised = self.norm_weights      # (the amax normalisation rides inside the network's autograd node)
+            elif raw_in.is_cuda:
+                raise _lib.MmkError("unet_backend='torch' is the CPU host-logic mirror (tests only); on a HIP device "
+                                    "the U-Net runs on the hand-written kernels (unet_backend='hip')")
             else:
-                if raw_in.is_cuda:
-                    from . import _lib
-                    raise _lib.MmkError("unet_backend='torch' is the CPU host-logic mirror (tests only); on a HIP device "
-                                        "the U-Net runs on the hand-written kernels (unet_backend='hip')")
                 weight_mask = self._unet(self._normalize_channels(raw_in))
-                normalised = False
-        else:
-            weight_mask = override_mask.to(self.device)
-            normalised = False
 
         if self.norm_weights and not normalised:
             weight_mask = weight_mask / torch.amax(weight_mask, dim=(1, 2), keepdim=True)

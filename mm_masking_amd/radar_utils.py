@@ -36,21 +36,9 @@ def _back(out, like):
     return out if like.is_cuda else out.to(like.device)
 
 
-_ws_cache = {}
-
-
-def _workspace(nbytes, device):
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream, "radar")
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
-    return buf
-
-
 def _sized_workspace(size_fn, device, *dims):
     """The workspace, at least as large as the entry's own ``*_ws_bytes(*dims)`` asks."""
-    return _workspace(int(size_fn(*dims)), device)
+    return _lib.workspace(int(size_fn(*dims)), device, "radar")
 
 
 def _remember(ctx, *inputs):

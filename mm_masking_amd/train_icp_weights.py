@@ -19,9 +19,10 @@ import time
 
 import torch
 
+from . import _lib
 from . import radar_utils as ru
 from . import synthetic
-from .icp_weight_policy import LearnICPWeightPolicy
+from .icp_weight_policy import LearnICPWeightPolicy, _check_batch
 
 
 def default_params(device=None):
@@ -90,90 +91,43 @@ def _const(kind, device, dtype):
 
 
 # ----------------------------------------------------------------------------- loss terms as single launches (HIP tensors)
-_BCE_WS = {}
+def _on_hip_f32(*tensors):
+    """What the loss kernels take: fp32 tensors on a HIP device (anything else keeps the PyTorch expression)."""
+    return all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
 
 
 class _PoseLossFn(torch.autograd.Function):
-    """(loss_rot, loss_trans) of the gt_eye form (train_icp_weights.py:193,197-200) in one launch, their gradient in another
-    (csrc/mmk_loss.hip) -- through PyTorch the two terms and their backward were ~25 launches of 2-5 us."""
+    """(loss_rot, loss_trans) of train_icp_weights.py:192-200 in one launch, their gradient w.r.t. T_pred in another
+    (csrc/mmk_loss.hip) -- through PyTorch the two terms and their backward were ~25 launches of 2-5 us.  ``T_gt=None`` is
+    the gt_eye form.  Against a ground-truth pose (gt_eye=False) the device takes a fp64 4x4 inverse per pair instead of
+    torch.inverse, which synchronises with the host, and ~15 launches of matmul / norm / mean; T_gt gets no gradient."""
 
     @staticmethod
-    def forward(ctx, T_pred):
-        from . import _lib
-        T = T_pred.contiguous().float()
-        out = torch.empty(2, dtype=torch.float32, device=T.device)
-        _lib.check(_lib.lib().mmk_pose_loss_fwd(_lib.ptr(T), T.shape[0], _lib.ptr(out), _lib.stream_ptr(T.device)))
-        ctx.save_for_backward(T)
-        return out[0], out[1]
-
-    @staticmethod
-    def backward(ctx, g_rot, g_trans):
-        from . import _lib
-        (T,) = ctx.saved_tensors
-        gT = torch.empty_like(T)
-        gr = None if g_rot is None else g_rot.contiguous().float()
-        gt = None if g_trans is None else g_trans.contiguous().float()
-        _lib.check(_lib.lib().mmk_pose_loss_bwd(_lib.ptr(T), T.shape[0], _lib.ptr(gr), _lib.ptr(gt), _lib.ptr(gT), _lib.stream_ptr(T.device)))
-        return gT
-
-
-class _BceMeanFn(torch.autograd.Function):
-    """torch.nn.BCELoss()(mask, target) (mean reduction, logs clamped at -100) as one pass + an ordered final sum, and its
-    gradient as one pass (csrc/mmk_loss.hip); deterministic.  (An input outside [0, 1] gives NaN here where torch raises.)"""
-
-    @staticmethod
-    def forward(ctx, mask, target):
-        from . import _lib
+    def forward(ctx, T_pred, T_gt=None):
         L = _lib.lib()
-        x, t = mask.contiguous().float(), target.contiguous().float()
-        if x.shape != t.shape:
-            raise _shape_mismatch(x, t)
-        key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
-        ws = _BCE_WS.get(key)
-        if ws is None:
-            ws = _BCE_WS[key] = torch.empty(int(L.mmk_bce_ws_bytes()), dtype=torch.uint8, device=x.device)
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.check(L.mmk_bce_mean_fwd(_lib.ptr(x), _lib.ptr(t), x.numel(), _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.stream_ptr(x.device)))
-        ctx.save_for_backward(x, t)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        from . import _lib
-        x, t = ctx.saved_tensors
-        gx = torch.empty_like(x)
-        _lib.check(_lib.lib().mmk_bce_mean_bwd(_lib.ptr(x), _lib.ptr(t), x.numel(), _lib.ptr(g.contiguous().float()), _lib.ptr(gx),
-                                               _lib.stream_ptr(x.device)))
-        return gx, None
-
-
-class _PoseLossGtFn(torch.autograd.Function):
-    """(loss_rot, loss_trans) against a ground-truth pose (gt_eye=False, train_icp_weights.py:192-200) in one launch, the
-    gradient w.r.t. T_pred in another (csrc/mmk_loss.hip): a fp64 4x4 inverse per pair on the device instead of torch.inverse,
-    which synchronises with the host, and ~15 launches of matmul / norm / mean.  T_gt gets no gradient."""
-
-    @staticmethod
-    def forward(ctx, T_pred, T_gt):
-        from . import _lib
         T = T_pred.contiguous().float()
-        Tg = _lib.dev_f32(T_gt, T.device)
-        if Tg.shape != T.shape:
-            raise ValueError("T_gt %s does not match T_pred %s" % (tuple(Tg.shape), tuple(T.shape)))
+        saved = (T,) if T_gt is None else (T, _lib.dev_f32(T_gt, T.device))
+        if T_gt is not None and saved[1].shape != T.shape:
+            raise ValueError("T_gt %s does not match T_pred %s" % (tuple(saved[1].shape), tuple(T.shape)))
         out = torch.empty(2, dtype=torch.float32, device=T.device)
-        _lib.check(_lib.lib().mmk_pose_loss_gt_fwd(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], _lib.ptr(out), _lib.stream_ptr(T.device)))
-        ctx.save_for_backward(T, Tg)
+        fwd = L.mmk_pose_loss_fwd if T_gt is None else L.mmk_pose_loss_gt_fwd
+        _lib.check(fwd(*map(_lib.ptr, saved), T.shape[0], _lib.ptr(out), _lib.stream_ptr(T.device)))
+        ctx.save_for_backward(*saved)
         return out[0], out[1]
 
     @staticmethod
     def backward(ctx, g_rot, g_trans):
-        from . import _lib
-        T, Tg = ctx.saved_tensors
+        L = _lib.lib()
+        saved = ctx.saved_tensors
+        T = saved[0]
         gT = torch.empty_like(T)
-        gr = None if g_rot is None else g_rot.contiguous().float()
-        gt = None if g_trans is None else g_trans.contiguous().float()
-        _lib.check(_lib.lib().mmk_pose_loss_gt_bwd(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], _lib.ptr(gr), _lib.ptr(gt), _lib.ptr(gT),
-                                                   _lib.stream_ptr(T.device)))
+        grads = [None if g is None else g.contiguous().float() for g in (g_rot, g_trans)]
+        bwd = L.mmk_pose_loss_bwd if len(saved) == 1 else L.mmk_pose_loss_gt_bwd
+        _lib.check(bwd(*map(_lib.ptr, saved), T.shape[0], *map(_lib.ptr, grads), _lib.ptr(gT), _lib.stream_ptr(T.device)))
         return gT, None
+
+
+_PoseLossGtFn = _PoseLossFn         # (T_pred, T_gt): the name its tests call
 
 
 def _shape_mismatch(x, t):
@@ -184,7 +138,6 @@ def _shape_mismatch(x, t):
 def fft_threshold_mask(fft_data):
     """torch.where(fft > 3 * mean_{H,W}(fft), 1, 0) per image of a fp32 (B,H,W) HIP tensor (train_icp_weights.py:204-206,
     312-316) in three launches (csrc/mmk_loss.hip)."""
-    from . import _lib
     L = _lib.lib()
     f = fft_data.contiguous()
     B = f.shape[0]
@@ -195,43 +148,71 @@ def fft_threshold_mask(fft_data):
     return out
 
 
-class _BceFftThresholdFn(torch.autograd.Function):
-    """_bce_mean(mask, fft_threshold_mask(fft)) without the target tensor: both passes compute the 0/1 target of each element
-    from fft and its image's threshold (csrc/mmk_loss.hip), the same bits as the two calls."""
+class _BceMeanFn(torch.autograd.Function):
+    """torch.nn.BCELoss()(mask, target) (mean reduction, logs clamped at -100) as one pass + an ordered final sum, and its
+    gradient as one pass (csrc/mmk_loss.hip); deterministic.  (An input outside [0, 1] gives NaN here where torch raises.)
+    ``from_fft``: ``target`` is the fft, and both passes compute the 0/1 target of each element from it and its image's
+    threshold -- _bce_mean(mask, fft_threshold_mask(fft)) without the target tensor, the same bits as the two calls."""
 
     @staticmethod
-    def forward(ctx, mask, fft_data):
-        from . import _lib
+    def forward(ctx, mask, target, from_fft=False):
         L = _lib.lib()
-        x, f = mask.contiguous().float(), fft_data.contiguous().float()
-        if x.shape != f.shape:
-            raise _shape_mismatch(x, f)
-        B = f.shape[0]
-        ws = torch.empty(int(L.mmk_fft_threshold_ws_bytes(B)), dtype=torch.uint8, device=x.device)
-        thr = torch.empty(B, dtype=torch.float32, device=x.device)
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.check(L.mmk_bce_fft_threshold_fwd(_lib.ptr(x), _lib.ptr(f), B, f.numel() // B, _lib.ptr(ws), ws.numel(), _lib.ptr(thr),
-                                               _lib.ptr(out), _lib.stream_ptr(x.device)))
-        ctx.save_for_backward(x, f, thr)
+        x, t = mask.contiguous().float(), target.contiguous().float()
+        if x.shape != t.shape:
+            raise _shape_mismatch(x, t)
+        if from_fft:
+            B = t.shape[0]
+            ws = torch.empty(int(L.mmk_fft_threshold_ws_bytes(B)), dtype=torch.uint8, device=x.device)
+            thr = torch.empty(B, dtype=torch.float32, device=x.device)     # a tensor of its own: the backward keeps it
+            out = torch.empty((), dtype=torch.float32, device=x.device)
+            _lib.check(L.mmk_bce_fft_threshold_fwd(_lib.ptr(x), _lib.ptr(t), B, t.numel() // B, _lib.ptr(ws), ws.numel(),
+                                                   _lib.ptr(thr), _lib.ptr(out), _lib.stream_ptr(x.device)))
+        else:
+            ws = _lib.workspace(int(L.mmk_bce_ws_bytes()), x.device, "loss")
+            thr = None
+            out = torch.empty((), dtype=torch.float32, device=x.device)
+            _lib.check(L.mmk_bce_mean_fwd(_lib.ptr(x), _lib.ptr(t), x.numel(), _lib.ptr(ws), ws.numel(), _lib.ptr(out),
+                                          _lib.stream_ptr(x.device)))
+        ctx.save_for_backward(x, t, thr)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
-        x, f, thr = ctx.saved_tensors
+        L = _lib.lib()
+        x, t, thr = ctx.saved_tensors
         gx = torch.empty_like(x)
-        B = f.shape[0]
-        _lib.check(_lib.lib().mmk_bce_fft_threshold_bwd(_lib.ptr(x), _lib.ptr(f), B, f.numel() // B, _lib.ptr(thr),
-                                                        _lib.ptr(g.contiguous().float()), _lib.ptr(gx), _lib.stream_ptr(x.device)))
-        return gx, None
+        g = g.contiguous().float()
+        if thr is None:
+            _lib.check(L.mmk_bce_mean_bwd(_lib.ptr(x), _lib.ptr(t), x.numel(), _lib.ptr(g), _lib.ptr(gx), _lib.stream_ptr(x.device)))
+        else:
+            B = t.shape[0]
+            _lib.check(L.mmk_bce_fft_threshold_bwd(_lib.ptr(x), _lib.ptr(t), B, t.numel() // B, _lib.ptr(thr), _lib.ptr(g),
+                                                   _lib.ptr(gx), _lib.stream_ptr(x.device)))
+        return gx, None, None
+
+
+class _BceFftThresholdFn(_BceMeanFn):
+    """_BceMeanFn(mask, fft_data, from_fft=True) under the name of the fft term."""
+
+    @staticmethod
+    def forward(ctx, mask, fft_data):
+        return _BceMeanFn.forward(ctx, mask, fft_data, True)
 
 
 def _bce_mean(mask, target):
     """mask_criterion(mask, target) of the reference (torch.nn.BCELoss, train_icp_weights.py:180): the fused kernels on a HIP
     device, PyTorch's own on the CPU (host-logic tests)."""
-    if mask.is_cuda and mask.dtype == torch.float32:
+    if _on_hip_f32(mask):
         return _BceMeanFn.apply(mask, target)
     return torch.nn.BCELoss()(mask, target)
+
+
+def _fft_target(fft_data):
+    """The fft term's target and generate_baseline's override mask (train_icp_weights.py:204-206, 312-316)."""
+    if _on_hip_f32(fft_data):
+        return fft_threshold_mask(fft_data)
+    mean_azimuth = torch.mean(fft_data, dim=(1, 2), keepdim=True)
+    return torch.where(fft_data > 3.0 * mean_azimuth, torch.ones_like(fft_data), torch.zeros_like(fft_data))
 
 
 def _map_pts_target(model, batch_scan, batch_map, device):
@@ -241,10 +222,32 @@ def _map_pts_target(model, batch_scan, batch_map, device):
     pc = batch_map["pc"].to(device)
     if not getattr(model, "polar_sampling", False):
         return ru.extract_bev_from_pts(pc)
-    if "azimuths" not in batch_scan:
-        raise KeyError("polar_sampling needs batch_scan['azimuths'] (prepare_batch with params['polar_sampling'] = True, "
-                       "or finish_batch(keep_polar=True))")
+    _check_batch("polar", batch_scan, ("azimuths",))
     return ru.polar_target_from_pts(pc, batch_scan["azimuths"], model.res, tuple(batch_scan["fft_data"].shape[1:]))
+
+
+def _xi_wedge(T_pred, T_gt, gt_eye):
+    """xi = T_pred T_gt^-1 - I of both loss functions (train_icp_weights.py:192-196, 256-260), T_gt = I with gt_eye."""
+    eye = _const("eye", T_pred.device, T_pred.dtype)
+    if gt_eye:
+        return T_pred - eye
+    return torch.matmul(T_pred, torch.inverse(T_gt)) - eye
+
+
+def _pose_terms(T_pred, T_gt, gt_eye):
+    """(loss_rot, loss_trans): one launch each way for fp32 HIP tensors (csrc/mmk_loss.hip; against T_gt without torch.inverse,
+    so without a host synchronisation), the reference's expression otherwise."""
+    if _on_hip_f32(T_pred) and (gt_eye or T_gt.dtype == torch.float32):
+        return _PoseLossFn.apply(T_pred) if gt_eye else _PoseLossFn.apply(T_pred, T_gt)
+    xi_wedge = _xi_wedge(T_pred, T_gt, gt_eye)
+    xi_r = xi_wedge[:, 0:2, 3]
+    xi_theta = xi_wedge[:, 1, 0].unsqueeze(-1)
+    return torch.norm(xi_theta, dim=1).mean(), torch.norm(xi_r, dim=1).mean()
+
+
+# (term, its key in loss_weights) in the reference's order of summation
+_LOSS_TERMS = (("rot", "icp_rot"), ("trans", "icp_trans"), ("fft", "fft"), ("mask_pts", "mask_pts"), ("cfar", "cfar"),
+               ("num_pts", "num_pts"))
 
 
 def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map, model, loss_weights=[],
@@ -254,35 +257,19 @@ def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map
     shape (1,) whenever one is); the switched-off terms are not multiplied and added on the GPU, though: they are a
     shared constant zero (x + 0 = x bit for bit), which takes ~20 two-microsecond launches out of a training step."""
     mask_criterion = _bce_mean
-    dev, dt = T_pred.device, T_pred.dtype
-    zero = _const("zero", dev, dt)
-    terms = {"rot": None, "trans": None, "fft": None, "mask_pts": None, "cfar": None, "num_pts": None}
-
-    if (loss_weights["icp_rot"] > 0.0 or loss_weights["icp_trans"] > 0.0) and gt_eye and T_pred.is_cuda and dt == torch.float32:
-        terms["rot"], terms["trans"] = _PoseLossFn.apply(T_pred)          # one launch each way (csrc/mmk_loss.hip)
-    elif (loss_weights["icp_rot"] > 0.0 or loss_weights["icp_trans"] > 0.0) and not gt_eye and T_pred.is_cuda and \
-            dt == torch.float32 and batch_T_gt.dtype == torch.float32:
-        terms["rot"], terms["trans"] = _PoseLossGtFn.apply(T_pred, batch_T_gt)     # no torch.inverse: no host synchronisation
-    elif loss_weights["icp_rot"] > 0.0 or loss_weights["icp_trans"] > 0.0:
-        eye = _const("eye", dev, dt)
-        if gt_eye:
-            xi_wedge = T_pred - eye
-        else:
-            xi_wedge = torch.matmul(T_pred, torch.inverse(batch_T_gt)) - eye
-        xi_r = xi_wedge[:, 0:2, 3]
-        xi_theta = xi_wedge[:, 1, 0].unsqueeze(-1)
-        terms["rot"] = torch.norm(xi_theta, dim=1).mean()
-        terms["trans"] = torch.norm(xi_r, dim=1).mean()
+    zero = _const("zero", T_pred.device, T_pred.dtype)
+    terms = {}
+    want_pose = loss_weights["icp_rot"] > 0.0 or loss_weights["icp_trans"] > 0.0
+    if want_pose:
+        terms["rot"], terms["trans"] = _pose_terms(T_pred, batch_T_gt, gt_eye)
     if icp_loss_only_iter <= 0 or (icp_loss_only_iter > 0 and epoch < icp_loss_only_iter) or \
             (loss_weights["icp_rot"] <= 0 and loss_weights["icp_trans"] <= 0):
         if loss_weights["fft"] > 0.0:
             fft_data = batch_scan["fft_data"].to(mask.device)
-            if mask.is_cuda and mask.dtype == torch.float32 and fft_data.dtype == torch.float32:
+            if _on_hip_f32(mask, fft_data):
                 terms["fft"] = _BceFftThresholdFn.apply(mask, fft_data)     # the target is never written
             else:
-                mean_azimuth = torch.mean(fft_data, dim=(1, 2), keepdim=True)
-                fft_mask = torch.where(fft_data > 3.0 * mean_azimuth, torch.ones_like(fft_data), torch.zeros_like(fft_data))
-                terms["fft"] = mask_criterion(mask, fft_mask)
+                terms["fft"] = mask_criterion(mask, _fft_target(fft_data))
         if loss_weights["cfar"] > 0.0:
             terms["cfar"] = mask_criterion(mask, batch_scan["fft_cfar"].to(mask.device))
         if loss_weights["mask_pts"] > 0.0:
@@ -291,16 +278,13 @@ def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map
         if loss_weights["num_pts"] > 0.0:
             terms["num_pts"] = model.mean_all_pts - num_non0
 
-    wkey = {"rot": "icp_rot", "trans": "icp_trans", "fft": "fft", "mask_pts": "mask_pts", "cfar": "cfar", "num_pts": "num_pts"}
     loss = None
     loss_components = {}
-    any_off = False
-    for name in ("rot", "trans", "fft", "mask_pts", "cfar", "num_pts"):     # the reference's order of summation
-        if terms[name] is None:
+    for name, wkey in _LOSS_TERMS:
+        if name not in terms:
             loss_components[name] = zero
-            any_off = True
             continue
-        w = loss_weights[wkey[name]]
+        w = loss_weights[wkey]
         # (a weight of exactly 1 -- the reference's defaults for the pose and map-point terms -- is not multiplied on the GPU:
         # 1.0 * x = x bit for bit, and the product and its backward were two ~5 us launches per term)
         t = terms[name] if (isinstance(w, (int, float)) and float(w) == 1.0) else w * terms[name]
@@ -308,7 +292,7 @@ def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map
         loss = t if loss is None else loss + t
     if loss is None:
         loss = zero.clone()
-    elif any_off and loss.dim() == 0:
+    elif len(terms) < len(_LOSS_TERMS) and loss.dim() == 0:     # a term is off: the reference's sum has its (1,) zero in it
         loss = loss.reshape(1)
     return loss, loss_components
 
@@ -317,19 +301,14 @@ def eval_validation_loss(T_pred, batch_T_gt, gt_eye=True):
     """train_icp_weights.py:255-273 -> [||(theta,x,y)||, |theta|, ||(x,y)||] batch means.  gt_eye=False on a HIP device:
     one launch (csrc/mmk_loss.hip) instead of torch.inverse, which synchronises with the host; the result carries no gradient,
     so a T_pred that needs one (the reference only calls this under no_grad) keeps the PyTorch expression."""
-    if not gt_eye and T_pred.is_cuda and T_pred.dtype == torch.float32 and batch_T_gt.dtype == torch.float32 and \
+    if not gt_eye and _on_hip_f32(T_pred) and batch_T_gt.dtype == torch.float32 and \
             not (torch.is_grad_enabled() and T_pred.requires_grad):
-        from . import _lib
         T = T_pred.detach().contiguous()
         Tg = _lib.dev_f32(batch_T_gt, T.device)
         out = torch.empty(3, dtype=torch.float32, device=T.device)
         _lib.check(_lib.lib().mmk_val_metric(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], _lib.ptr(out), _lib.stream_ptr(T.device)))
         return out
-    eye = _const("eye", T_pred.device, T_pred.dtype)
-    if gt_eye:
-        xi_wedge = T_pred - eye
-    else:
-        xi_wedge = torch.matmul(T_pred, torch.inverse(batch_T_gt)) - eye
+    xi_wedge = _xi_wedge(T_pred, batch_T_gt, gt_eye)
     xi_r = xi_wedge[:, 0:2, 3]
     xi_theta = xi_wedge[:, 1, 0].unsqueeze(-1)
     xi_stack = torch.cat((xi_theta, xi_r), dim=1)
@@ -337,10 +316,18 @@ def eval_validation_loss(T_pred, batch_T_gt, gt_eye=True):
                          torch.norm(xi_r, dim=1).mean()))
 
 
+def _unpack(batch, device):
+    """(batch_scan, batch_map, T_init, T_gt) of a batch of the reference's dict-of-dicts form, the poses on ``device``."""
+    batch_T = batch["transforms"]
+    batch_T_gt = batch_T["T_ml_gt"].to(device)
+    return batch["loc_data"], batch["map_data"], batch_T["T_ml_init"].to(device), batch_T_gt
+
+
 def train_step(model, batch, opt, loss_weights, device, gt_eye=True, epoch=None, icp_loss_only_iter=0,
                grad_sync=None):
     """Body of the reference's batch loop (train_icp_weights.py:31-58).  ``grad_sync``
     (optional callable) is where a data-parallel job all-reduces the gradients."""
+    # (not _unpack: the ground-truth pose of a host-resident batch is copied after the forward, as it always was)
     batch_scan, batch_map, batch_T = batch["loc_data"], batch["map_data"], batch["transforms"]
     batch_T_init = batch_T["T_ml_init"].to(device)
     if grad_sync is not None and hasattr(grad_sync, "zero_grad"):
@@ -396,9 +383,7 @@ def validate_policy(model, iterator, gt_eye=True, device="cpu", binary=False, ne
     n = 0
     with torch.no_grad():
         for batch in iterator:
-            batch_scan, batch_map, batch_T = batch["loc_data"], batch["map_data"], batch["transforms"]
-            batch_T_gt = batch_T["T_ml_gt"].to(device)
-            batch_T_init = batch_T["T_ml_init"].to(device)
+            batch_scan, batch_map, batch_T_init, batch_T_gt = _unpack(batch, device)
             T_pred, mask, _ = model(batch_scan, batch_map, batch_T_init, binary=binary)
             mean_num_pc += model.mean_num_pts
             max_w = model.max_w if model.max_w > max_w else max_w
@@ -417,18 +402,12 @@ def generate_baseline(model, iterator, baseline_type="train", device="cpu",
     loss_init_hist, loss_ones_hist = [], []
     with torch.no_grad():
         for batch in iterator:
-            batch_scan, batch_map, batch_T = batch["loc_data"], batch["map_data"], batch["transforms"]
-            batch_T_gt = batch_T["T_ml_gt"].to(device)
-            batch_T_init = batch_T["T_ml_init"].to(device)
+            batch_scan, batch_map, batch_T_init, batch_T_gt = _unpack(batch, device)
             fft_data = batch_scan["fft_data"].to(device)
             if loss_weights.get("cfar", 0.0) > 0.0:
                 ones_mask = batch_scan["fft_cfar"].to(device)
-            elif loss_weights.get("fft", 0.0) > 0.0 and fft_data.is_cuda and fft_data.dtype == torch.float32:
-                ones_mask = fft_threshold_mask(fft_data)
             elif loss_weights.get("fft", 0.0) > 0.0:
-                mean_azimuth = torch.mean(fft_data, dim=(1, 2), keepdim=True)
-                ones_mask = torch.where(fft_data > 3.0 * mean_azimuth, torch.ones_like(fft_data),
-                                        torch.zeros_like(fft_data))
+                ones_mask = _fft_target(fft_data)
             elif loss_weights.get("mask_pts", 0.0) > 0.0:
                 ones_mask = _map_pts_target(model, batch_scan, batch_map, device)
             else:
@@ -500,13 +479,16 @@ def fit(policy, training_iterator, validation_iterator, opt, params, checkpoint_
         os.makedirs(checkpoint_dir, exist_ok=True)
     best_path = os.path.join(checkpoint_dir, "best_policy.pt")
     hist = {"loss": [], "loss_comp": [], "acc": [], "epoch_train_time": [], "epoch_val_time": []}
+
+    def validate(epoch=None):
+        return _rank_mean(validate_policy(policy, validation_iterator, epoch=epoch, device=dev, binary=params["binary_inference"],
+                                          gt_eye=params["gt_eye"])[0])
     if start_epoch == 0:
         hist["train_baseline"] = generate_baseline(policy, training_iterator, baseline_type="train", device=dev, binary=False,
                                                    loss_weights=lw, gt_eye=params["gt_eye"])
         hist["val_baseline"] = generate_baseline(policy, validation_iterator, baseline_type="val", device=dev,
                                                  binary=params["binary_inference"], gt_eye=params["gt_eye"])
-        avg_norm = _rank_mean(validate_policy(policy, validation_iterator, device=dev, binary=params["binary_inference"],
-                                              gt_eye=params["gt_eye"], epoch=-1)[0])
+        avg_norm = validate(epoch=-1)
         best_norm = float(avg_norm[0, 0])
         log("Norm before training: %.6f" % best_norm)
     for epoch in range(start_epoch, params["num_epochs"]):
@@ -517,8 +499,7 @@ def fit(policy, training_iterator, validation_iterator, opt, params, checkpoint_
         mean_loss = float(mean_loss)
         t_train = time.time() - tic
         tic = time.time()
-        avg_norm = _rank_mean(validate_policy(policy, validation_iterator, epoch=epoch, device=dev, binary=params["binary_inference"],
-                                              gt_eye=params["gt_eye"])[0])
+        avg_norm = validate(epoch)
         t_val = time.time() - tic
         total = float(avg_norm[0, 0])
         if total < best_norm or epoch == 0:
@@ -540,8 +521,8 @@ def fit(policy, training_iterator, validation_iterator, opt, params, checkpoint_
     # may hold a collective (the global min-max normalisation), so a validation that only the main rank entered would
     # hang or pair with another rank's next collective.  The main rank reads best_policy.pt and its weights are
     # broadcast, so the ranks end the run with identical (best) parameters.
-    import torch.distributed as dist
-    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    from .ddp import dist, job_size
+    multi = job_size() > 1
     have_best = is_main and os.path.exists(best_path)
     if multi:
         flag = torch.tensor([1.0 if have_best else 0.0], device=dev)
@@ -554,8 +535,7 @@ def fit(policy, training_iterator, validation_iterator, opt, params, checkpoint_
             src = _main_rank(is_main, dev)
             for t in policy.state_dict().values():
                 dist.broadcast(t, src=src)
-        hist["final_acc"] = [float(v) for v in _rank_mean(validate_policy(policy, validation_iterator, device=dev,
-                                                                         binary=params["binary_inference"], gt_eye=params["gt_eye"])[0])[0]]
+        hist["final_acc"] = [float(v) for v in validate()[0]]
     return hist
 
 
@@ -563,18 +543,18 @@ def _rank_mean(t):
     """Mean over the ranks of a data-parallel job (identity in a single process): each rank validates its own shard of the
     validation set, and the reference selects its best policy on the WHOLE set (train_icp_weights.py:534-537) -- with equal
     shard sizes the mean of the shard means.  Every rank then takes the same best-policy decisions."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+    from .ddp import dist, job_size
+    if job_size() == 1:
         return t
     t = t.clone()
     dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    return t / dist.get_world_size()
+    return t / job_size()
 
 
 def _main_rank(is_main, dev):
     """The rank that passed is_main=True (the lowest one, should several have): found with one MIN all-reduce."""
-    import torch.distributed as dist
-    t = torch.tensor([float(dist.get_rank()) if is_main else float(dist.get_world_size())], device=dev)
+    from .ddp import dist, job_size
+    t = torch.tensor([float(dist.get_rank()) if is_main else float(job_size())], device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MIN)
     return int(t.item())
 

@@ -306,9 +306,9 @@ FORCE_COLLECTIVES = False     # one-rank rehearsal of the N-rank path (bench.py 
 
 def minmax_is_collective(global_reduce, process_group=None):
     """Whether channel_minmax(global_reduce=...) would reduce the extrema over the ranks (an all-reduce)."""
-    import torch.distributed as dist
-    return bool(global_reduce and dist.is_available() and dist.is_initialized()
-                and (dist.get_world_size(process_group) > 1 or FORCE_COLLECTIVES))
+    from .ddp import dist, job_size
+    forced = FORCE_COLLECTIVES and dist.is_available() and dist.is_initialized()        # (a one-rank group is still a group)
+    return bool(global_reduce and (job_size(process_group) > 1 or forced))
 
 
 def channel_minmax(x, process_group=None, global_reduce=False, return_minmax=False):

@@ -213,8 +213,12 @@ def _fit_worker(rank, world, port, out, ckpt_dir):
     # the model exists BEFORE the process group does: the global min-max default must still resolve to "on"
     model, p = _policy(seed=20 + rank)
     p.update({"num_epochs": 2, "loss_cfar_mask_weight": 1.0, "loss_map_pts_mask_weight": 0.0})
+    # one predicate says whether this process is a rank of a multi-rank job, before and after the group exists
+    from mm_masking_amd import unet_hip
+    assert ddp.job_size() == 1 and not model.global_minmax and not unet_hip.minmax_is_collective(True)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
+        assert ddp.job_size() == world and unet_hip.minmax_is_collective(True) and not unet_hip.minmax_is_collective(False)
         assert model.global_minmax
         n_forward = [0]
 

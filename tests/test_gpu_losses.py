@@ -44,10 +44,18 @@ def test_product_training_loss_golden_full(golden_dir, tag):
     np.testing.assert_allclose(v.cpu().numpy(), g["val_eye" if tag == "a" else "val_gt"], rtol=1e-5)
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 64), (3, 33, 7), (1, 640, 640)])
+def _bce_mean_fp64(x, t):
+    """mean(-(t max(log x, -100) + (1 - t) max(log(1 - x), -100))) of CPU tensors in fp64."""
+    x, t = x.double(), t.double()
+    return -(t * torch.log(x).clamp(min=-100.0) + (1.0 - t) * torch.log(1.0 - x).clamp(min=-100.0)).mean().item()
+
+
+@pytest.mark.parametrize("shape", [(2, 64, 64), (3, 33, 7), (1, 640, 640), (3, 1201, 1171)])
 def test_fused_bce_mean_matches_torch(shape):
     """_BceMeanFn == torch.nn.BCELoss() (train_icp_weights.py:180,223-226): value, gradient through an upstream factor, the
-    -100 clamp of the logs at x = 0 / 1, sizes that are not multiples of four."""
+    -100 clamp of the logs at x = 0 / 1, sizes that are not multiples of four.  (3, 1201, 1171): 1 054 778 float4 groups,
+    more than one pass of the forward's 2048 x 256 and of the backward's 4096 x 256 lanes, and a tail of one element; at that
+    size the value is compared with the formula in fp64, so that BCELoss's own fp32 summation error is not what is measured."""
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.rand(*shape, generator=g)
     x.view(-1)[:4] = torch.tensor([0.0, 1.0, 1e-30, 1.0 - 1e-7])
@@ -58,7 +66,7 @@ def test_fused_bce_mean_matches_torch(shape):
     la = trn._bce_mean(xa, t.to(DEV))
     lb = torch.nn.BCELoss()(xb, t.to(DEV))
     assert la.shape == lb.shape == ()
-    np.testing.assert_allclose(la.item(), lb.item(), rtol=2e-6)
+    np.testing.assert_allclose(la.item(), _bce_mean_fp64(x, t) if x.numel() > 4 * 2048 * 256 else lb.item(), rtol=2e-6)
     (0.37 * la).backward()
     (0.37 * lb).backward()
     np.testing.assert_allclose(xa.grad.cpu().numpy(), xb.grad.cpu().numpy(), rtol=2e-6, atol=1e-12)

@@ -51,6 +51,46 @@ def test_pose_entry_points_reject_bad_arguments(L):
     assert b"mmk_val_metric" in L.mmk_last_error()
 
 
+def test_gt_eye_pose_and_bce_entry_points_reject_bad_arguments(L):
+    a, o, g = _p(0x10000), _p(0x30000), _p(0x40000)
+    assert L.mmk_pose_loss_fwd(NULL, 4, o, NULL) == -1
+    assert L.mmk_pose_loss_fwd(a, 4, NULL, NULL) == -1
+    assert L.mmk_pose_loss_fwd(a, 0, o, NULL) == -1
+    assert b"mmk_pose_loss_fwd" in L.mmk_last_error()
+    assert L.mmk_pose_loss_bwd(NULL, 4, NULL, NULL, g, NULL) == -1
+    assert L.mmk_pose_loss_bwd(a, 4, NULL, NULL, NULL, NULL) == -1
+    assert L.mmk_pose_loss_bwd(a, -1, o, o, g, NULL) == -1
+    assert b"mmk_pose_loss_bwd" in L.mmk_last_error()
+    n, ws_bytes = 4097, L.mmk_bce_ws_bytes()
+    assert ws_bytes == 2048 * 8                              # one fp64 partial per block of the forward's grid
+    x, t, ws = _p(0x50000), _p(0x60000), _p(0x70000)
+    assert L.mmk_bce_mean_fwd(NULL, t, n, ws, ws_bytes, o, NULL) == -1
+    assert L.mmk_bce_mean_fwd(x, NULL, n, ws, ws_bytes, o, NULL) == -1
+    assert L.mmk_bce_mean_fwd(x, t, n, NULL, ws_bytes, o, NULL) == -1
+    assert L.mmk_bce_mean_fwd(x, t, n, ws, ws_bytes, NULL, NULL) == -1
+    assert L.mmk_bce_mean_fwd(x, t, 0, ws, ws_bytes, o, NULL) == -1
+    assert b"mmk_bce_mean_fwd: bad argument" in L.mmk_last_error()
+    assert L.mmk_bce_mean_fwd(x, t, n, ws, ws_bytes - 1, o, NULL) == -1
+    assert b"workspace" in L.mmk_last_error()
+    assert L.mmk_bce_mean_fwd(_p(0x50004), t, n, ws, ws_bytes - 1, o, NULL) == -1       # the workspace is examined first
+    assert b"workspace" in L.mmk_last_error()
+    assert L.mmk_bce_mean_fwd(_p(0x50004), t, n, ws, ws_bytes, o, NULL) == -1
+    assert b"aligned" in L.mmk_last_error()
+    L.mmk_bce_mean_fwd(x, t, 0, ws, ws_bytes, o, NULL)                                  # (a fresh message in between)
+    assert L.mmk_bce_mean_fwd(x, _p(0x60008), n, ws, ws_bytes, o, NULL) == -1
+    assert b"aligned" in L.mmk_last_error()
+    assert L.mmk_bce_mean_bwd(NULL, t, n, o, g, NULL) == -1
+    assert L.mmk_bce_mean_bwd(x, NULL, n, o, g, NULL) == -1
+    assert L.mmk_bce_mean_bwd(x, t, n, NULL, g, NULL) == -1
+    assert L.mmk_bce_mean_bwd(x, t, n, o, NULL, NULL) == -1
+    assert L.mmk_bce_mean_bwd(x, t, 0, o, g, NULL) == -1
+    assert b"mmk_bce_mean_bwd: bad argument" in L.mmk_last_error()
+    for bad in ((_p(0x50004), t, g), (x, _p(0x60008), g), (x, t, _p(0x4000c))):
+        L.mmk_bce_mean_bwd(x, t, 0, o, g, NULL)
+        assert L.mmk_bce_mean_bwd(bad[0], bad[1], n, o, bad[2], NULL) == -1
+        assert b"aligned" in L.mmk_last_error()
+
+
 def test_fft_threshold_entry_points_reject_bad_arguments(L):
     B, hw = 3, 640 * 640
     ws_bytes = L.mmk_fft_threshold_ws_bytes(B)
