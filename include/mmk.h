@@ -525,7 +525,8 @@ typedef struct {
                               (ReLU / dropout backward fused into the data-gradient pass)   */
     int32_t O1, accumulate1; /* accumulate: y1 += result                                    */
     float scale1;
-    void *y2;              /* bf16 (B,H,W,O2) or NULL: output channels [O1,O1+O2)           */
+    void *y2;              /* bf16 (B,H,W,O2) or NULL: output channels [O1,O1+O2); O1 a multiple of 8, and of 16
+                              where the layer has >= 64 output channels and >= 32 input channels (else refused) */
     const void *relu_src2;
     int32_t O2, accumulate2;
     float scale2;

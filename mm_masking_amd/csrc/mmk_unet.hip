@@ -1690,7 +1690,15 @@ int dispatch_conv(const ConvArgs &a, hipStream_t st)
         mmk::set_error("mmk_conv3x3: x1_pool_arg needs the ReLU network, a single input and H, W >= 2");
         return MMK_ERR_ARG;
     }
-    if (conv_is_deep(a.CIN, a.COUT)) return dispatch_conv_deep(a, st);
+    if (conv_is_deep(a.CIN, a.COUT)) {
+        // a lane of conv3x3_deep_kernel stores one run of 4 MT consecutive channels per pixel (16 where a block has >= 64) to the
+        // half its FIRST channel belongs to: a split inside such a run would put the rest of it into the wrong tensor, past its end
+        if (a.o2.C > 0 && conv_cm(a.CIN, a.COUT) >= 64 && a.o1.C % 16 != 0) {
+            mmk::set_error("mmk_conv3x3: output split %d+%d: layers of >= 64 output channels split at multiples of 16", a.o1.C, a.o2.C);
+            return MMK_ERR_ARG;
+        }
+        return dispatch_conv_deep(a, st);
+    }
     const int CK = conv_ck(a.CIN), CM = conv_cm(a.CIN, a.COUT);
     if (a.x1_pool_arg != nullptr && !(a.CIN == 32 && CM == 32 && (size_t)a.B * a.H * a.W * 32 < ((size_t)1 << 31))) {
         mmk::set_error("mmk_conv3x3: x1_pool_arg is not supported for this layer (CIN=%d COUT=%d)", a.CIN, a.COUT);
