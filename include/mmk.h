@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 502 /* 0.5.2: mmk_icp_params.trim_steep appended and mmk_icp_params_bytes (the soft tanh trim gate of the dICP; the struct grows at its end and 0 keeps the hard gate: additions only, the number stays), mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 502 /* 0.5.2: mmk_icp_soft, mmk_icp_forward_soft, mmk_icp_backward_soft (+ _workspace_bytes), mmk_knn_search (+ _workspace_bytes) (soft correspondences of the dICP; the option travels in a struct of its own, so mmk_icp_params keeps its size: additions only, the number stays), mmk_icp_params.trim_steep appended and mmk_icp_params_bytes (the soft tanh trim gate of the dICP; the struct grows at its end and 0 keeps the hard gate: additions only, the number stays), mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -169,6 +169,48 @@ int mmk_icp_backward_hp(const mmk_icp_params *p, const float *source, const floa
                         float *grad_source /*B,N,3 or NULL*/, float *grad_target /*B,M,tgt_cols or NULL*/,
                         const float *hyper /*1|B,3*/, int32_t per_pair, float *grad_hyper /*B,3 or NULL*/,
                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* Soft correspondences (DESIGN.md §3 I2', I3''', I7'''): every source point reads a VIRTUAL target row, the soft-min over
+ * its k nearest target rows, a_j = softmax_j(-(d_j - d_0) / temp), row = sum_j a_j row_j (xyz and, for pt2pl, the normal,
+ * which is not renormalised), and the backward differentiates the weights a_j in the points.  The option travels in a
+ * struct of its own (mmk_icp_params keeps its size, MMK_VERSION its number: additions only).  k in 2..8, M >= k, temp
+ * finite and > 0 (a squared length, m^2); anything else: MMK_ERR_ARG, workspace size 0.  The search is always the exact
+ * k-NN through the grid: p->nn_method is ignored.  Slot 0 of the k neighbours is the correspondent the hard searches return.
+ * mmk_icp_forward_soft: mmk_icp_forward's arguments; idx_hist is int32 (K,B,N,k) if save_state else (B,N,k), neighbours in key
+ * order.  Workspace: mmk_icp_soft_workspace_bytes(p, soft); mmk_icp_status reads its status word as usual.
+ * mmk_icp_backward_soft: mmk_icp_backward_points' arguments (grad_source and grad_target each optional: the entry serves
+ * both backward shapes).  Which k rows are the neighbours is a constant, like the freezes and the delta = 0 fallback;
+ * temp gets no gradient.  The target gradient is the same fixed-point scatter with K*N*k rows per pair (resolution max|row
+ * entry| * 2^(ceil(log2(K*N*k)) - 62)).  Workspace: mmk_icp_backward_soft_workspace_bytes(p, soft, grad_target != NULL);
+ * a short one is MMK_ERR_ARG.  Device-resident hyper-parameters (the _hp entries) are not combined with this mode.        */
+typedef struct {
+    int32_t k;          /* neighbours per point, 2..8                              */
+    float temp;         /* tau > 0, m^2: e_j = expf(-(d_j - d_0) / tau)            */
+} mmk_icp_soft;
+size_t mmk_icp_soft_workspace_bytes(const mmk_icp_params *p, const mmk_icp_soft *soft);
+int mmk_icp_forward_soft(const mmk_icp_params *p, const float *source /*B,N,3*/,
+                         const float *target /*B,M,tgt_cols*/, const float *weight /*B,N*/,
+                         const float *T_init /*B,16*/, float *T_out /*B,16*/,
+                         int32_t *idx_hist, float *T_hist, double *delta_hist, double *A_hist,
+                         int32_t *active_hist, const mmk_icp_soft *soft,
+                         void *workspace, size_t workspace_bytes, int *iters_run, void *stream);
+size_t mmk_icp_backward_soft_workspace_bytes(const mmk_icp_params *p, const mmk_icp_soft *soft, int32_t with_target);
+int mmk_icp_backward_soft(const mmk_icp_params *p, const float *source, const float *target,
+                          const float *weight, const int32_t *idx_hist /*K,B,N,k*/, const float *T_hist,
+                          const double *delta_hist, const double *A_hist,
+                          const int32_t *active_hist, const float *grad_T /*B,16*/,
+                          float *grad_weight /*B,N*/, float *grad_T_init /*B,16 or NULL*/,
+                          float *grad_source /*B,N,3 or NULL*/, float *grad_target /*B,M,tgt_cols or NULL*/,
+                          const mmk_icp_soft *soft, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Stage I2' on its own: the k (2..8, M >= k) nearest rows of `target` (B,M,tgt_cols, the first dim columns) to the source
+ * points under T (B,16), exact, through the per-call grid.  idx int32 (B,N,k) and d2 fp32 (B,N,k) in key order: ascending
+ * d2 (I2's expression), ties to the lowest index.  Workspace: mmk_knn_search_workspace_bytes(B, N, M, k) bytes (0 for
+ * arguments the search refuses).                                                                                         */
+size_t mmk_knn_search_workspace_bytes(int32_t B, int32_t N, int32_t M, int32_t k);
+int mmk_knn_search(const float *source /*B,N,3*/, const float *target /*B,M,tgt_cols*/, const float *T /*B,16*/,
+                   int32_t B, int32_t N, int32_t M, int32_t tgt_cols, int32_t dim, int32_t k,
+                   int32_t *idx /*B,N,k*/, float *d2 /*B,N,k*/, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The stages of one iteration on their own (SURVEY.md 8b names them; mmk_icp_forward is these in a loop behind the NN search).
  * mmk_icp_accumulate (stages I3 + I4): consumes nearest-neighbour keys ((bits of d2) << 32 | index, (B,N) uint64 -- the

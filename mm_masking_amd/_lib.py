@@ -48,6 +48,11 @@ class IcpParams(ctypes.Structure):
                 ("trim_steep", ctypes.c_float)]        # 0 (the default of a keyword construction): the hard trim gate
 
 
+class IcpSoft(ctypes.Structure):
+    """mmk_icp_soft of include/mmk.h: the soft correspondences' k (2..8) and temperature (m^2)."""
+    _fields_ = [("k", ctypes.c_int32), ("temp", ctypes.c_float)]
+
+
 class ConvDesc(ctypes.Structure):
     """mmk_conv_desc of include/mmk.h."""
     _fields_ = [("x1", ctypes.c_void_p), ("x2", ctypes.c_void_p), ("C1", ctypes.c_int32), ("C2", ctypes.c_int32),
@@ -126,6 +131,7 @@ def build(verbose=False):
 def _declare(lib):
     i32, f32, sz = ctypes.c_int32, ctypes.c_float, ctypes.c_size_t
     P = ctypes.POINTER(IcpParams)
+    S = ctypes.POINTER(IcpSoft)
     sig = {
         "mmk_version": (ctypes.c_int, []),
         "mmk_last_error": (ctypes.c_char_p, []),
@@ -139,6 +145,12 @@ def _declare(lib):
         "mmk_icp_forward_hp": (ctypes.c_int, [P] + [c_vp] * 10 + [c_vp, i32, c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
         "mmk_icp_backward_hp_workspace_bytes": (sz, [P, i32, i32]),
         "mmk_icp_backward_hp": (ctypes.c_int, [P] + [c_vp] * 13 + [c_vp, i32, c_vp, c_vp, sz, c_vp]),
+        "mmk_icp_soft_workspace_bytes": (sz, [P, S]),
+        "mmk_icp_forward_soft": (ctypes.c_int, [P] + [c_vp] * 10 + [S, c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
+        "mmk_icp_backward_soft_workspace_bytes": (sz, [P, S, i32]),
+        "mmk_icp_backward_soft": (ctypes.c_int, [P] + [c_vp] * 13 + [S, c_vp, sz, c_vp]),
+        "mmk_knn_search_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "mmk_knn_search": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, i32, c_vp, c_vp, c_vp, sz, c_vp]),
         "mmk_pose_loss_fwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp]),
         "mmk_pose_loss_bwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, c_vp]),
         "mmk_bce_ws_bytes": (sz, []),

@@ -1024,6 +1024,95 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_normals_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
+// I2' (DESIGN.md §3): the k (2..8) nearest target rows of every transformed source point, EXACT, for the soft
+// correspondences.  grid_nn_kernel's query (one transformed source point per thread, the pair's pose, the active flag) with
+// knn_normals_kernel's search: the top-8 packed keys in registers in descending order, every index a compile-time constant,
+// slots >= k switched off by predicates, each radius scanning only the annulus the previous square left out, the search over
+// once the k-th distance is below the ring bound, the exhaustive scan after GRID_RMAX.  No row is special: target_pad_val
+// rows are simply far away.  keys (B,N,k) in key order -- ascending d, ties to the lowest index -- so slot 0 is the
+// correspondent the hard searches return.  M >= k (the entries check it), so the exhaustive scan fills every slot.
+constexpr int SOFT_KMAX = 8;
+
+template <int DIM>
+__global__ __launch_bounds__(KNN_THREADS) void grid_knn_kernel(const float *__restrict__ src, const float *__restrict__ Tk,
+                                                               const int32_t *__restrict__ active,
+                                                               const int32_t *__restrict__ starts,
+                                                               const float4 *__restrict__ sorted, int N, int M, int k,
+                                                               unsigned long long *__restrict__ keys)
+{
+    constexpr int KC = SOFT_KMAX;
+    const int b = blockIdx.y;
+    if (active != nullptr && active[b] == 0) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    float T[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) T[q] = Tk[(size_t)b * 16 + q];
+    const float *sp = src + ((size_t)b * N + i) * 3;
+    const float s[3] = {sp[0], sp[1], sp[2]};
+    float p[DIM];
+    transform_point<DIM>(T, s, p);
+    const int cx = grid_coord(p[0]), cy = grid_coord(p[1]);
+    const int32_t *st = starts + (size_t)b * (GRID_NC + 1);
+    const float4 *pts = sorted + (size_t)b * M;
+
+    unsigned long long a[KC];   // descending: a[0] is the worst kept key, KNN_EMPTY while fewer than k are kept
+#pragma unroll
+    for (int j = 0; j < KC; ++j) a[j] = KNN_EMPTY;
+
+    // one scan site, as in knn_normals_kernel: steps 0..7 scan the annulus of their radius, step 8 every row
+    bool done = false;
+    int rp = -1;   // the square of radius rp has been scanned
+    for (int step = 0; step <= 8 && !done; ++step) {
+        const bool all = step == 8;
+        const int r = step == 0 ? 1 : step == 1 ? 2 : step == 2 ? 3 : step == 3 ? 5 : step == 4 ? 8 : step == 5 ? 12 : step == 6 ? 17 : GRID_RMAX;
+        if (all) {
+#pragma unroll
+            for (int j = 0; j < KC; ++j) a[j] = KNN_EMPTY;
+        }
+        for (int rc = 0; rc < (all ? 1 : 4); ++rc) {
+            int x0 = rc == 3 ? cx + rp + 1 : cx - r, x1 = rc == 2 ? cx - rp - 1 : cx + r;
+            int y0 = rc == 0 ? cy - r : rc == 1 ? cy + max(rp, 0) + 1 : cy - rp, y1 = rc == 0 ? cy - rp - 1 : rc == 1 ? cy + r : cy + rp;
+            x0 = max(x0, 0), y0 = max(y0, 0), x1 = min(x1, GRID_N - 1), y1 = min(y1, GRID_N - 1);
+            if (all) x0 = x1 = y0 = y1 = 0;
+            if (x0 > x1) continue;
+            for (int y = y0; y <= y1; ++y) {
+                const int k0 = all ? 0 : st[y * GRID_N + x0], k1 = all ? M : st[y * GRID_N + x1 + 1];
+                for (int kk = k0; kk < k1; kk += 8) {
+                    float4 t[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) t[u] = pts[min(kk + u, k1 - 1)];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const float d = nn_dist<DIM>(t[u].x, t[u].y, t[u].z, p);
+                        const unsigned long long key =
+                            ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)__float_as_uint(t[u].w);
+                        if (kk + u < k1 && key < a[0]) {
+                            a[0] = key;
+#pragma unroll
+                            for (int j = 0; j + 1 < KC; ++j) {
+                                const bool sw = (j + 1 < k) && a[j] < a[j + 1];
+                                const unsigned long long hi = sw ? a[j + 1] : a[j], lo = sw ? a[j] : a[j + 1];
+                                a[j] = hi;
+                                a[j + 1] = lo;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        rp = r;
+        const float lim = (float)r * GRID_CELL - 1e-3f;   // 1 mm of slack for the float cell assignment
+        done = all || (a[0] != KNN_EMPTY && __uint_as_float((unsigned)(a[0] >> 32)) < lim * lim);
+    }
+    // key order = slots k-1 .. 0
+    unsigned long long *out = keys + ((size_t)b * N + i) * k;
+#pragma unroll
+    for (int j = 0; j < KC; ++j)
+        if (j < k) out[k - 1 - j] = a[j];
+}
+
+// ------------------------------------------------------------------------------------------
 // I3 + I4 per-point terms (oracle: per_point_terms).
 template <int DIM, int TYPE>
 struct PointTerms {
@@ -1152,10 +1241,67 @@ __device__ __forceinline__ bool hyper_is_bad(const HyperVals &v, int loss, bool 
     return !ok;
 }
 
+// I3''' (DESIGN.md §3): the soft correspondent.  `nb` are the point's k neighbours in key order (I2'), p its transformed
+// position, temp the temperature tau (a squared length).  Per slot j, fp32, every operation rounded on its own:
+//      d_j = nn_dist(row_j, p) (I2's expression, recomputed from the row);  e_j = expf(-(d_j - d_0) / tau);
+//      S = sum_j e_j in slot order;  a_j = e_j / S.
+// Nothing is stored per slot: k is a run-time loop bound, a per-lane array indexed by j would live in scratch memory, so
+// each loop loads its row again (k rows of one point: L1 / L2 hits) and recomputes a_j.
+struct SoftArgs {
+    const unsigned long long *keys;      // (B,N,k) of grid_knn_kernel (the forward only)
+    int k;
+    float temp;
+};
+
+template <int DIM>
+__device__ __forceinline__ float soft_e(const float *row, const float p[DIM], float d0, float temp)
+{
+    const float d = nn_dist<DIM>(row[0], row[1], DIM == 3 ? row[2] : 0.f, p);
+    return expf(-(d - d0) / temp);
+}
+
+template <int DIM>
+__device__ __forceinline__ void soft_norm(const float *tgtb, int tgt_cols, const int32_t *nb, int k, const float p[DIM],
+                                          float temp, float &d0, float &S)
+{
+    const float *r0 = tgtb + (size_t)nb[0] * tgt_cols;
+    d0 = nn_dist<DIM>(r0[0], r0[1], DIM == 3 ? r0[2] : 0.f, p);
+    S = 0.f;
+    for (int j = 0; j < k; ++j) {
+        const float e = soft_e<DIM>(tgtb + (size_t)nb[j] * tgt_cols, p, d0, temp);
+        S = j == 0 ? e : S + e;
+    }
+}
+
+// The virtual target row vr[6] = sum_j a_j row_j in slot order (xyz; for pt2pl the normal too, NOT renormalised: the row
+// stays linear in a), each product and each sum rounded; it takes the target row's place in point_terms.
+template <int DIM, int TYPE>
+__device__ __forceinline__ void soft_virtual_row(const float *tgtb, int tgt_cols, const int32_t *nb, int k, const float p[DIM],
+                                                 float temp, float d0, float S, float vr[6])
+{
+#pragma unroll
+    for (int c = 0; c < 6; ++c) vr[c] = 0.f;
+    for (int j = 0; j < k; ++j) {
+        const float *row = tgtb + (size_t)nb[j] * tgt_cols;
+        const float a = soft_e<DIM>(row, p, d0, temp) / S;
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            const float v = a * row[c];
+            vr[c] = j == 0 ? v : vr[c] + v;
+            if constexpr (TYPE == MMK_ICP_PT2PL) {
+                const float vn = a * row[3 + c];
+                vr[3 + c] = j == 0 ? vn : vr[3 + c] + vn;
+            }
+        }
+    }
+}
+
 // Accumulate A (upper triangle, row-major) and b for one pair; one point per thread.
 // HP: k, trim_dist and the steepness come from `hyper` (I3'') instead of the launch's scalars; `hcheck` != 0 (the first
 // iteration of a call) has one thread per pair validate them.
-template <int DIM, int TYPE, bool HP = false>
+// SOFT (mmk_icp_forward_soft, I3'''): the point's k keys come from soft.keys, idx_out is (B,N,k), and the virtual row takes
+// the correspondent's place; `packed` and the zero-row bookkeeping are not used.  SOFT = false is the kernel it always was.
+template <int DIM, int TYPE, bool HP = false, bool SOFT = false>
 __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
     const float *__restrict__ src, const float *__restrict__ tgt, int tgt_cols,
     const float *__restrict__ weight, const float *__restrict__ Tk, const int32_t *__restrict__ active,
@@ -1163,7 +1309,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
     const int32_t *__restrict__ allzero, const int32_t *__restrict__ zrep, int nn_pts, int nn_nsb,
     int32_t *__restrict__ idx_out, int N, int M, int loss, float k,
     float k2, float trim2, float trim_dist, float trim_steep, double *__restrict__ partials, int32_t *__restrict__ status,
-    const float *__restrict__ hyper, int hstride, int hcheck)
+    const float *__restrict__ hyper, int hstride, int hcheck, SoftArgs soft)
 {
     constexpr int P = PointTerms<DIM, TYPE>::P;
     constexpr int NR = PointTerms<DIM, TYPE>::NR;
@@ -1185,24 +1331,45 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
         float T[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) T[q] = Tk[(size_t)b * 16 + q];
-        // consume the NN key; arm the OTHER key buffer for the next iteration's atomic mins (two buffers: a row of a
-        // skipped all-zero block reads the key of the pair's first zero row, which another workgroup owns)
-        int isrc = i;
-        if (allzero != nullptr && allzero[(size_t)b * nn_nsb + i / nn_pts] != 0 && zrep[b] < (i / nn_pts) * nn_pts) isrc = zrep[b];
-        const unsigned long long key = packed[(size_t)b * N + isrc];
-        if (packed_next != nullptr) packed_next[(size_t)b * N + i] = NN_KEY_INIT;
-        // An index outside the target can only come from a key nobody armed (every NN engine writes each row's key: range 0
-        // of the scan always does, also for non-finite points).  It must not become an address -- and it must not pass
-        // silently as correspondence 0 either: the launch raises MMK_ICP_STATUS_UNARMED_KEY in the caller's status word
-        // (mmk_icp_status; dICP/ICP.py turns it into an MmkError), then clamps so that the rest of the launch stays in bounds.
-        const unsigned jraw = (unsigned)(key & 0xffffffffull);
-        if ((key == NN_KEY_INIT || jraw >= (unsigned)M) && status != nullptr) atomicOr(status, (int32_t)MMK_ICP_STATUS_UNARMED_KEY);
-        const int j = (int)min(jraw, (unsigned)(M - 1));
-        idx_out[(size_t)b * N + i] = j;
-        const float omega = weight ? weight[(size_t)b * N + i] : 1.f;
         PointTerms<DIM, TYPE> t;
-        point_terms<DIM, TYPE>(t, T, src + ((size_t)b * N + i) * 3, tgt + ((size_t)b * M + j) * tgt_cols, omega,
-                               loss, k, k2, trim2, trim_dist, trim_steep);
+        if constexpr (SOFT) {
+            // the k keys -> idx_out (B,N,k), guarded like the single key below; then the virtual row
+            const unsigned long long *kp = soft.keys + ((size_t)b * N + i) * soft.k;
+            int32_t *nb = idx_out + ((size_t)b * N + i) * soft.k;
+            for (int j = 0; j < soft.k; ++j) {
+                const unsigned long long key = kp[j];
+                const unsigned jraw = (unsigned)(key & 0xffffffffull);
+                if ((key == NN_KEY_INIT || jraw >= (unsigned)M) && status != nullptr) atomicOr(status, (int32_t)MMK_ICP_STATUS_UNARMED_KEY);
+                nb[j] = (int)min(jraw, (unsigned)(M - 1));
+            }
+            const float *srow = src + ((size_t)b * N + i) * 3;
+            const float s[3] = {srow[0], srow[1], srow[2]};
+            float p[DIM], vr[6], d0, S;
+            transform_point<DIM>(T, s, p);
+            const float *tgtb = tgt + (size_t)b * M * tgt_cols;
+            soft_norm<DIM>(tgtb, tgt_cols, nb, soft.k, p, soft.temp, d0, S);
+            soft_virtual_row<DIM, TYPE>(tgtb, tgt_cols, nb, soft.k, p, soft.temp, d0, S, vr);
+            const float omega = weight ? weight[(size_t)b * N + i] : 1.f;
+            point_terms<DIM, TYPE>(t, T, srow, vr, omega, loss, k, k2, trim2, trim_dist, trim_steep);
+        } else {
+            // consume the NN key; arm the OTHER key buffer for the next iteration's atomic mins (two buffers: a row of a
+            // skipped all-zero block reads the key of the pair's first zero row, which another workgroup owns)
+            int isrc = i;
+            if (allzero != nullptr && allzero[(size_t)b * nn_nsb + i / nn_pts] != 0 && zrep[b] < (i / nn_pts) * nn_pts) isrc = zrep[b];
+            const unsigned long long key = packed[(size_t)b * N + isrc];
+            if (packed_next != nullptr) packed_next[(size_t)b * N + i] = NN_KEY_INIT;
+            // An index outside the target can only come from a key nobody armed (every NN engine writes each row's key: range 0
+            // of the scan always does, also for non-finite points).  It must not become an address -- and it must not pass
+            // silently as correspondence 0 either: the launch raises MMK_ICP_STATUS_UNARMED_KEY in the caller's status word
+            // (mmk_icp_status; dICP/ICP.py turns it into an MmkError), then clamps so that the rest of the launch stays in bounds.
+            const unsigned jraw = (unsigned)(key & 0xffffffffull);
+            if ((key == NN_KEY_INIT || jraw >= (unsigned)M) && status != nullptr) atomicOr(status, (int32_t)MMK_ICP_STATUS_UNARMED_KEY);
+            const int j = (int)min(jraw, (unsigned)(M - 1));
+            idx_out[(size_t)b * N + i] = j;
+            const float omega = weight ? weight[(size_t)b * N + i] : 1.f;
+            point_terms<DIM, TYPE>(t, T, src + ((size_t)b * N + i) * 3, tgt + ((size_t)b * M + j) * tgt_cols, omega,
+                                   loss, k, k2, trim2, trim_dist, trim_steep);
+        }
         int a = 0;
 #pragma unroll
         for (int m = 0; m < P; ++m) {
@@ -1557,6 +1724,40 @@ __global__ __launch_bounds__(64) void icp_bwd_pair_kernel(
 __host__ __device__ constexpr int tgt_row_cols(int dim, int type) { return type == MMK_ICP_PT2PL ? 2 * dim : dim; }
 __host__ __device__ constexpr int tgt_acc_cols(int c) { return c <= 2 ? 2 : (c <= 4 ? 4 : 8); }
 
+// The adjoint of the target row a point read (I7): q̄ (dim), then n̄ (dim) for pt2pl, the soft gate's path gev included.
+template <int DIM, int TYPE>
+__device__ __forceinline__ void target_row_adjoint(const PointTerms<DIM, TYPE> &t, const float *ebar,
+                                                   const float (*Jbar)[PointTerms<DIM, TYPE>::P], const float *gev,
+                                                   float trim_steep, float *q)
+{
+    constexpr int P = PointTerms<DIM, TYPE>::P;
+    if constexpr (TYPE == MMK_ICP_PT2PT) {
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) q[c] = ebar[c];               // e = q − p
+    } else {
+        const float eb = ebar[0];                                   // e = n·(q − p), J = nᵀG
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            q[c] = t.n[c] * eb;
+            q[DIM + c] = eb * t.ev[c] + Jbar[0][c];
+        }
+        if constexpr (DIM == 2) {        // J[2] = ny·px − nx·py
+            q[DIM + 0] -= t.p[1] * Jbar[0][2];
+            q[DIM + 1] += t.p[0] * Jbar[0][2];
+        } else {                         // J[3:6] = p × n: n̄ += J̄rot × p (as p̄ += n × J̄rot above)
+            const float px = t.p[0], py = t.p[1], pz = t.p[DIM - 1];
+            const float j3 = Jbar[0][P - 3], j4 = Jbar[0][P - 2], j5 = Jbar[0][P - 1];
+            q[DIM + 0] += j4 * pz - j5 * py;
+            q[DIM + 1] += j5 * px - j3 * pz;
+            q[DIM + DIM - 1] += j3 * py - j4 * px;
+        }
+    }
+    if (trim_steep > 0.f) {     // the gate's path into the correspondent's xyz (the normals get nothing from it)
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) q[c] += gev[c];
+    }
+}
+
 // I7 backward, per-point part: dL/dweight and the point path of dL/dT_k.
 // PTS (mmk_icp_backward_points): also the adjoints of the clouds -- gsrc (B,N,3, may be NULL) += R_kᵀ p̄ in place (each
 // thread owns its point, iterations are ordered launches), and the point's contribution to its correspondent's target
@@ -1565,7 +1766,10 @@ __host__ __device__ constexpr int tgt_acc_cols(int c) { return c <= 2 ? 2 : (c <
 // HP (mmk_icp_backward_hp, I7''): k, trim_dist and the steepness come from `hyper` as in the forward, and the block's fp64
 // sums of the per-point adjoints (k̄, c̄, s̄) go to `hparts` (nblk,B rows of 3 for this iteration) by the reduction of the pose
 // parts: wave shuffle -> LDS -> one partial per block, no atomics.  A frozen pair's blocks write exact zeros.
-template <int DIM, int TYPE, bool PTS, bool HP = false>
+// SOFT (mmk_icp_backward_soft, I7'''): idx is (B,N,k), the virtual row is rebuilt as in the forward, the per-point code below
+// yields its adjoint, and a last loop over the slots turns that into the k target rows (`rows` is (B,N*k,C)) and the
+// softmin's share of p̄.  SOFT = false is the kernel it always was.
+template <int DIM, int TYPE, bool PTS, bool HP = false, bool SOFT = false>
 __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     const float *__restrict__ src, const float *__restrict__ tgt, int tgt_cols,
     const float *__restrict__ weight, const float *__restrict__ Tk, const int32_t *__restrict__ active,
@@ -1573,7 +1777,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     int M, int loss, float k, float k2, float trim2, float trim_dist, float trim_steep, float *__restrict__ gw,
     double *__restrict__ pparts,
     float *__restrict__ gsrc, float *__restrict__ rows, unsigned *__restrict__ pmax,
-    const float *__restrict__ hyper, int hstride, double *__restrict__ hparts)
+    const float *__restrict__ hyper, int hstride, double *__restrict__ hparts, SoftArgs soft)
 {
     constexpr int P = PointTerms<DIM, TYPE>::P;
     constexpr int NR = PointTerms<DIM, TYPE>::NR;
@@ -1602,11 +1806,25 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
             lam[q] = (float)lam64[(size_t)b * 6 + q];
             dl[q] = (float)delta64[(size_t)b * 6 + q];
         }
-        const int j = idx[(size_t)b * N + i];
+        int j = 0;
+        if constexpr (!SOFT) j = idx[(size_t)b * N + i];
         const float omega = weight ? weight[(size_t)b * N + i] : 1.f;
         PointTerms<DIM, TYPE> t;
-        point_terms<DIM, TYPE>(t, T, src + ((size_t)b * N + i) * 3, tgt + ((size_t)b * M + j) * tgt_cols, omega,
-                               loss, k, k2, trim2, trim_dist, trim_steep);
+        float sd0 = 0.f, sS = 1.f;           // SOFT: d_0 and S of the point
+        if constexpr (SOFT) {
+            const float *srow = src + ((size_t)b * N + i) * 3;
+            const float s[3] = {srow[0], srow[1], srow[2]};
+            float p[DIM], vr[6];
+            transform_point<DIM>(T, s, p);
+            const float *tgtb = tgt + (size_t)b * M * tgt_cols;
+            const int32_t *nb = idx + ((size_t)b * N + i) * soft.k;
+            soft_norm<DIM>(tgtb, tgt_cols, nb, soft.k, p, soft.temp, sd0, sS);
+            soft_virtual_row<DIM, TYPE>(tgtb, tgt_cols, nb, soft.k, p, soft.temp, sd0, sS, vr);
+            point_terms<DIM, TYPE>(t, T, srow, vr, omega, loss, k, k2, trim2, trim_dist, trim_steep);
+        } else {
+            point_terms<DIM, TYPE>(t, T, src + ((size_t)b * N + i) * 3, tgt + ((size_t)b * M + j) * tgt_cols, omega,
+                                   loss, k, k2, trim2, trim_dist, trim_steep);
+        }
         float wbar = 0.f;
         float ebar[NR];
         float Jbar[NR][P];
@@ -1696,6 +1914,57 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
                 acc[NP + 2] = (double)(keepbar * (-g * (t.d - trim_dist)));
             }
         }
+        if constexpr (SOFT) {
+            // I7''': q holds the adjoint of the virtual row [q̃̄ ; ñ̄].  Per slot ā_j = q̃̄·q_j (+ ñ̄·n_j); m = sum_l a_l ā_l in
+            // slot order (first loop); then z̄_j = a_j (ā_j - m), d̄_j = -z̄_j / tau, the slot's target row a_j [q̃̄ ; ñ̄] with
+            // 2 d̄_j (q_j - p) added to its xyz, and the same vector taken off p̄ (second loop).  Which rows are the
+            // neighbours is a constant, and tau gets no gradient.
+            float q[C];
+            target_row_adjoint<DIM, TYPE>(t, ebar, Jbar, gev, trim_steep, q);
+            const float *tgtb = tgt + (size_t)b * M * tgt_cols;
+            const int32_t *nb = idx + ((size_t)b * N + i) * soft.k;
+            auto abar = [&](const float *row) {
+                float v = q[0] * row[0];
+#pragma unroll
+                for (int c = 1; c < DIM; ++c) v += q[c] * row[c];
+                if constexpr (TYPE == MMK_ICP_PT2PL) {
+#pragma unroll
+                    for (int c = 0; c < DIM; ++c) v += q[DIM + c] * row[3 + c];
+                }
+                return v;
+            };
+            float m = 0.f;
+            for (int j = 0; j < soft.k; ++j) {
+                const float *row = tgtb + (size_t)nb[j] * tgt_cols;
+                const float a = soft_e<DIM>(row, t.p, sd0, soft.temp) / sS;
+                const float v = a * abar(row);
+                m = j == 0 ? v : m + v;
+            }
+            for (int j = 0; j < soft.k; ++j) {
+                const float *row = tgtb + (size_t)nb[j] * tgt_cols;
+                const float a = soft_e<DIM>(row, t.p, sd0, soft.temp) / sS;
+                const float zbar = a * (abar(row) - m);
+                const float g = 2.f * (-zbar / soft.temp);
+                float out[C];
+#pragma unroll
+                for (int c = 0; c < DIM; ++c) {
+                    const float h = g * (row[c] - t.p[c]);
+                    out[c] = a * q[c] + h;
+                    pbar[c] -= h;
+                    if constexpr (TYPE == MMK_ICP_PT2PL) out[DIM + c] = a * q[DIM + c];
+                }
+                if constexpr (PTS) {
+                    if (rows != nullptr) {
+                        float *orow = rows + (((size_t)b * N + i) * soft.k + j) * C;
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {
+                            orow[c] = out[c];
+                            mbits = max(mbits, __float_as_uint(fabsf(out[c])));
+                        }
+                    }
+                }
+            }
+        }
         // p = R s + t
 #pragma unroll
         for (int r = 0; r < DIM; ++r) {
@@ -1714,33 +1983,9 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
                     gs[c] += v;
                 }
             }
-            if (rows != nullptr) {
+            if (!SOFT && rows != nullptr) {
                 float q[C];                 // ∂L/∂(correspondent's xyz), then ∂L/∂(its normal) for pt2pl
-                if constexpr (TYPE == MMK_ICP_PT2PT) {
-#pragma unroll
-                    for (int c = 0; c < DIM; ++c) q[c] = ebar[c];               // e = q − p
-                } else {
-                    const float eb = ebar[0];                                   // e = n·(q − p), J = nᵀG
-#pragma unroll
-                    for (int c = 0; c < DIM; ++c) {
-                        q[c] = t.n[c] * eb;
-                        q[DIM + c] = eb * t.ev[c] + Jbar[0][c];
-                    }
-                    if constexpr (DIM == 2) {        // J[2] = ny·px − nx·py
-                        q[DIM + 0] -= t.p[1] * Jbar[0][2];
-                        q[DIM + 1] += t.p[0] * Jbar[0][2];
-                    } else {                         // J[3:6] = p × n: n̄ += J̄rot × p (as p̄ += n × J̄rot above)
-                        const float px = t.p[0], py = t.p[1], pz = t.p[DIM - 1];
-                        const float j3 = Jbar[0][P - 3], j4 = Jbar[0][P - 2], j5 = Jbar[0][P - 1];
-                        q[DIM + 0] += j4 * pz - j5 * py;
-                        q[DIM + 1] += j5 * px - j3 * pz;
-                        q[DIM + DIM - 1] += j3 * py - j4 * px;
-                    }
-                }
-                if (trim_steep > 0.f) {     // the gate's path into the correspondent's xyz (the normals get nothing from it)
-#pragma unroll
-                    for (int c = 0; c < DIM; ++c) q[c] += gev[c];
-                }
+                target_row_adjoint<DIM, TYPE>(t, ebar, Jbar, gev, trim_steep, q);
                 float *row = rows + ((size_t)b * N + i) * C;
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
@@ -2079,8 +2324,9 @@ IcpWs carve(const mmk_icp_params *p, void *ws, size_t cap)
     return w;
 }
 
-// Workspace of the three backward entries, three parts in this order, each starting on a 256-byte boundary: the forward's
-// (carve), the target gradient's (with_target), the hyper-parameter gradient's (with_hyper).  A part that is not asked
+// Workspace of the backward entries, four parts in this order, each starting on a 256-byte boundary: the forward's
+// (carve), the target gradient's (with_target), the hyper-parameter gradient's (with_hyper), the soft correspondences'
+// (soft_k > 0; mmk_icp_forward_soft's workspace is the forward's part and this one).  A part that is not asked
 // for takes no room and leaves its pointers NULL, so mmk_icp_backward's workspace is the forward's.
 struct IcpBwdWs {
     IcpWs w;
@@ -2088,10 +2334,13 @@ struct IcpBwdWs {
     unsigned long long *acc = nullptr;   // (B,M,L): their fixed-point sums
     unsigned *pmax = nullptr;            // (B): float bits of the largest |entry| of a pair's rows
     double *hparts = nullptr;            // (K,B,nblk,3): block partials of (k̄, c̄, s̄), every entry written by the sweep
+    unsigned long long *soft_keys = nullptr;     // (B,N,k): the k-NN keys of the iteration in flight (soft correspondences)
     size_t bytes = 0;
 };
 
-IcpBwdWs carve_backward(const mmk_icp_params *p, bool with_target, bool with_hyper, void *ws, size_t cap)
+// soft_k > 0 (the _soft entries; p->nn_method is MMK_NN_GRID there): the target part holds k rows per point and the soft
+// part, the last one, the keys of grid_knn_kernel.
+IcpBwdWs carve_backward(const mmk_icp_params *p, bool with_target, bool with_hyper, void *ws, size_t cap, int soft_k = 0)
 {
     IcpBwdWs b;
     b.w = carve(p, ws, cap);
@@ -2099,11 +2348,12 @@ IcpBwdWs carve_backward(const mmk_icp_params *p, bool with_target, bool with_hyp
     ar.off = b.w.bytes;
     if (with_target) {
         const int C = tgt_row_cols(p->dim, p->icp_type);
-        b.rows = ar.take<float>((size_t)p->max_iter * p->B * p->N * C);
+        b.rows = ar.take<float>((size_t)p->max_iter * p->B * p->N * std::max(soft_k, 1) * C);
         b.acc = ar.take<unsigned long long>((size_t)p->B * p->M * tgt_acc_cols(C));
         b.pmax = ar.take<unsigned>((size_t)p->B);
     }
     if (with_hyper) b.hparts = ar.take<double>((size_t)p->max_iter * p->B * acc_blocks(p->N) * 3);
+    if (soft_k > 0) b.soft_keys = ar.take<unsigned long long>((size_t)p->B * p->N * soft_k);
     b.bytes = mmk::align_up(ar.off, 256);
     return b;
 }
@@ -2132,7 +2382,19 @@ struct IcpCall {
     float *grad_weight = nullptr, *grad_T_init = nullptr;
     float *grad_source = nullptr, *grad_target = nullptr;      // (B,N,3), (B,M,tgt_cols)
     float *grad_hyper = nullptr;           // (B,3)
+    int soft_k = 0;                        // > 0: soft correspondences (I2', I3''', I7'''); idx_hist is then (K | 1,B,N,k)
+    float soft_temp = 0.f;
 };
+
+// mmk_icp_soft as the _soft entries accept it: k in 2..8 with M >= k, temp finite and > 0.
+int check_soft(const char *who, const mmk_icp_soft *s, int M)
+{
+    MMK_REQUIRE(s != nullptr, "%s: soft is NULL", who);
+    MMK_REQUIRE(s->k >= 2 && s->k <= SOFT_KMAX, "%s: soft.k must be in 2..%d (got %d)", who, SOFT_KMAX, s->k);
+    MMK_REQUIRE(M >= s->k, "%s: the target must have at least soft.k = %d rows (got M = %d)", who, s->k, M);
+    MMK_REQUIRE(std::isfinite(s->temp) && s->temp > 0.f, "%s: soft.temp must be finite and > 0 (got %g)", who, (double)s->temp);
+    return MMK_OK;
+}
 
 template <class T>
 T *writable(const T *p) { return const_cast<T *>(p); }
@@ -2152,14 +2414,17 @@ int build_grid(const float *points, int B, int M, int cols, int dim, int32_t *co
 }
 
 template <int DIM, int TYPE>
-int run_forward(const mmk_icp_params *p, const IcpCall &c, const IcpWs &w, int *iters_run)
+int run_forward(const mmk_icp_params *p, const IcpCall &c, const IcpWs &w, int *iters_run, unsigned long long *soft_keys = nullptr)
 {
     const int B = p->B, N = p->N, M = p->M;
     const float *const src = c.source, *const tgt = c.target;
     const hipStream_t st = c.st;
     const NNPlan pl = nn_plan(B, N, M, DIM);
     const int nblk = acc_blocks(N);
-    const size_t idx_step = p->save_state ? (size_t)B * N : 0;     // without saved state every iteration reuses one (B,N) buffer
+    const bool soft = c.soft_k > 0;
+    const SoftArgs sa{soft_keys, c.soft_k, c.soft_temp};
+    // without saved state every iteration reuses one (B,N) buffer ((B,N,k) with soft correspondences)
+    const size_t idx_step = p->save_state ? (size_t)B * N * (soft ? c.soft_k : 1) : 0;
     int k_done = 0;
     // (keys, status word, zero-row representatives: icp_init_kernel in mmk_icp_forward)
     const bool use_grid = p->nn_method == MMK_NN_GRID;
@@ -2189,8 +2454,12 @@ int run_forward(const mmk_icp_params *p, const IcpCall &c, const IcpWs &w, int *
         if (use_grid) {
             const bool rec = g_prof.on && g_prof.n < g_prof.cap;
             if (rec) MMK_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.n], st));
-            hipLaunchKernelGGL(grid_nn_kernel<DIM>, dim3((N + 255) / 256, B), dim3(256), 0, st, src, Tk, act, w.g_starts,
-                               w.g_sorted, N, M, tgt, p->tgt_cols, prev, keys);
+            if (soft)
+                hipLaunchKernelGGL(grid_knn_kernel<DIM>, dim3((N + KNN_THREADS - 1) / KNN_THREADS, B), dim3(KNN_THREADS), 0, st, src, Tk,
+                                   act, w.g_starts, w.g_sorted, N, M, c.soft_k, soft_keys);
+            else
+                hipLaunchKernelGGL(grid_nn_kernel<DIM>, dim3((N + 255) / 256, B), dim3(256), 0, st, src, Tk, act, w.g_starts,
+                                   w.g_sorted, N, M, tgt, p->tgt_cols, prev, keys);
             MMK_LAUNCH_CHECK();
             if (rec) {
                 MMK_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.n + 1], st));
@@ -2201,10 +2470,11 @@ int run_forward(const mmk_icp_params *p, const IcpCall &c, const IcpWs &w, int *
             if (rc != MMK_OK) return rc;
         }
         const int hcheck = hyper && it == 0 ? 1 : 0;
-        with_bool(hyper != nullptr, [&](auto HP) {
-            hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE, HP()>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt, p->tgt_cols,
-                               c.weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, r.loss, r.k, r.k2, r.trim2,
-                               r.trim_dist, r.trim_steep, w.partials, w.status, hyper, hstride, hcheck);
+        with_bools(hyper != nullptr, soft, [&](auto HP, auto SOFT) {
+            if constexpr (!(HP() && SOFT()))        // (no entry combines the two)
+                hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE, HP(), SOFT()>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
+                                   p->tgt_cols, c.weight, Tk, act, keys, keys_next, az, zr, nn_pts, pl.nsb, idx, N, M, r.loss, r.k, r.k2,
+                                   r.trim2, r.trim_dist, r.trim_steep, w.partials, w.status, hyper, hstride, hcheck, sa);
         });
         MMK_LAUNCH_CHECK();
         hipLaunchKernelGGL(icp_solve_kernel<DIM>, dim3(B), dim3(64), 0, st, w.partials, nblk, Tk,
@@ -2257,6 +2527,9 @@ int run_backward(const mmk_icp_params *p, const IcpCall &c, const IcpBwdWs &bw)
     // PTS: a cloud gradient is asked for; HP: the workspace has the hyper part, i.e. the entry was given `hyper`.  Without
     // PTS gsrc, rows and bw.pmax are all NULL, without HP c.hyper and hparts are: one argument list serves the four kernels.
     const bool pts = gsrc || gtgt, hp = bw.hparts != nullptr;
+    const bool soft = c.soft_k > 0;                 // (never with hp: mmk_icp_backward_soft has no `hyper`)
+    const int rpp = soft ? c.soft_k : 1;            // target rows (and saved indices) per point
+    const SoftArgs sa{nullptr, c.soft_k, c.soft_temp};
     for (int it = p->max_iter - 1; it >= 0; --it) {
         const float *Tk = c.T_hist + (size_t)it * B * 16;
         const int32_t *act = c.active_hist + (size_t)it * B;
@@ -2264,13 +2537,17 @@ int run_backward(const mmk_icp_params *p, const IcpCall &c, const IcpBwdWs &bw)
         hipLaunchKernelGGL(icp_bwd_pair_kernel<DIM>, dim3(B), dim3(64), 0, st, Gin, w.partials, nparts, Tk, delta,
                            c.A_hist + (size_t)it * B * 36, act, Gout, w.lam);
         MMK_LAUNCH_CHECK();
-        float *rows = gtgt ? bw.rows + (size_t)it * B * N * C : nullptr;
+        float *rows = gtgt ? bw.rows + (size_t)it * B * N * rpp * C : nullptr;
         double *hparts = hp ? bw.hparts + (size_t)it * B * nblk * 3 : nullptr;
+        const int32_t *idx = c.idx_hist + (size_t)it * B * N * rpp;
         with_bools(pts, hp, [&](auto PTS, auto HP) {
-            hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, PTS(), HP()>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, c.source,
-                               c.target, p->tgt_cols, c.weight, Tk, act, c.idx_hist + (size_t)it * B * N, w.lam, delta, N, M, r.loss, r.k,
-                               r.k2, r.trim2, r.trim_dist, r.trim_steep, gw, w.partials, gsrc, rows, bw.pmax, c.hyper, c.hstride,
-                               hparts);
+            with_bool(soft, [&](auto SOFT) {
+                if constexpr (!(HP() && SOFT()))    // (no entry combines the two)
+                    hipLaunchKernelGGL((icp_bwd_point_kernel<DIM, TYPE, PTS(), HP(), SOFT()>), dim3(nblk, B), dim3(ACC_THREADS), 0, st,
+                                       c.source, c.target, p->tgt_cols, c.weight, Tk, act, idx, w.lam, delta, N, M, r.loss, r.k, r.k2,
+                                       r.trim2, r.trim_dist, r.trim_steep, gw, w.partials, gsrc, rows, bw.pmax, c.hyper, c.hstride,
+                                       hparts, sa);
+            });
         });
         MMK_LAUNCH_CHECK();
         nparts = nblk;
@@ -2286,10 +2563,11 @@ int run_backward(const mmk_icp_params *p, const IcpCall &c, const IcpBwdWs &bw)
     }
     if (gtgt) {
         int cnt_bits = 0;
-        while (((uint64_t)1 << cnt_bits) < (uint64_t)p->max_iter * (uint64_t)N) ++cnt_bits;
-        const unsigned gx = (unsigned)(((size_t)N * L + ACC_THREADS - 1) / ACC_THREADS);
+        const int NR = N * rpp;                    // rows per pair and iteration: the scatter is flat over them
+        while (((uint64_t)1 << cnt_bits) < (uint64_t)p->max_iter * (uint64_t)NR) ++cnt_bits;
+        const unsigned gx = (unsigned)(((size_t)NR * L + ACC_THREADS - 1) / ACC_THREADS);
         hipLaunchKernelGGL(icp_bwd_target_scatter_kernel<C>, dim3(gx, B, p->max_iter), dim3(ACC_THREADS), 0, st, bw.rows, c.idx_hist,
-                           c.active_hist, bw.pmax, B, N, M, cnt_bits, bw.acc);
+                           c.active_hist, bw.pmax, B, NR, M, cnt_bits, bw.acc);
         MMK_LAUNCH_CHECK();
         hipLaunchKernelGGL(icp_bwd_target_final_kernel, dim3((M + 255) / 256, B), dim3(256), 0, st, bw.acc, bw.pmax, cnt_bits, M, DIM, C,
                            L, p->tgt_cols, gtgt);
@@ -2447,16 +2725,26 @@ extern "C" size_t mmk_icp_workspace_bytes(const mmk_icp_params *p)
 }
 
 namespace {
-// mmk_icp_forward (hyper NULL) and mmk_icp_forward_hp
-int forward_impl(const char *who, const mmk_icp_params *p, const IcpCall &c, const float *T_init, float *T_out, void *workspace,
+// The params a call runs with: soft correspondences always search through the grid, whatever nn_method says.
+mmk_icp_params effective_params(const mmk_icp_params *p, int soft_k)
+{
+    mmk_icp_params e = *p;
+    if (soft_k > 0) e.nn_method = MMK_NN_GRID;
+    return e;
+}
+
+// mmk_icp_forward (hyper NULL), mmk_icp_forward_hp and mmk_icp_forward_soft (c.soft_k > 0, already checked)
+int forward_impl(const char *who, const mmk_icp_params *p_in, const IcpCall &c, const float *T_init, float *T_out, void *workspace,
                  size_t workspace_bytes, int *iters_run)
 {
-    int rc = check_params(p);
+    int rc = check_params(p_in);
     if (rc != MMK_OK) return rc;
     MMK_REQUIRE(c.source && c.target && T_init && T_out && c.idx_hist && c.T_hist && c.delta_hist && c.A_hist && c.active_hist,
                 "%s: NULL pointer", who);
-    const IcpWs w = carve(p, workspace, workspace_bytes);
-    rc = check_workspace(who, MMK_ERR_WORKSPACE, workspace, workspace_bytes, w.bytes);
+    const mmk_icp_params eff = effective_params(p_in, c.soft_k), *const p = &eff;
+    const IcpBwdWs fw = carve_backward(p, false, false, workspace, workspace_bytes, c.soft_k);     // the forward's part (+ the soft part)
+    const IcpWs &w = fw.w;
+    rc = check_workspace(who, MMK_ERR_WORKSPACE, workspace, workspace_bytes, fw.bytes);
     if (rc != MMK_OK) return rc;
     const hipStream_t st = c.st;
     const int B = p->B;
@@ -2473,7 +2761,7 @@ int forward_impl(const char *who, const mmk_icp_params *p, const IcpCall &c, con
                            w.zrep, B, p->N);
         MMK_LAUNCH_CHECK();
     }
-    rc = with_dim_type(p->dim, p->icp_type, [&](auto D, auto TYPE) { return run_forward<D(), TYPE()>(p, c, w, iters_run); });
+    rc = with_dim_type(p->dim, p->icp_type, [&](auto D, auto TYPE) { return run_forward<D(), TYPE()>(p, c, w, iters_run, fw.soft_keys); });
     if (rc != MMK_OK) return rc;
     MMK_CHECK_HIP(hipMemcpyAsync(T_out, c.T_hist + (size_t)p->max_iter * B * 16, sizeof(float) * B * 16,
                                  hipMemcpyDeviceToDevice, st));
@@ -2499,6 +2787,29 @@ extern "C" int mmk_icp_forward_hp(const mmk_icp_params *p, const float *source, 
     MMK_REQUIRE(per_pair == 0 || per_pair == 1, "mmk_icp_forward_hp: per_pair must be 0 or 1 (got %d)", per_pair);
     const IcpCall c{source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, (hipStream_t)stream, hyper, per_pair ? 3 : 0};
     return forward_impl("mmk_icp_forward_hp", p, c, T_init, T_out, workspace, workspace_bytes, iters_run);
+}
+
+extern "C" size_t mmk_icp_soft_workspace_bytes(const mmk_icp_params *p, const mmk_icp_soft *soft)
+{
+    if (check_params(p) != MMK_OK || check_soft("mmk_icp_soft_workspace_bytes", soft, p->M) != MMK_OK) return 0;
+    const mmk_icp_params eff = effective_params(p, soft->k);
+    return carve_backward(&eff, false, false, nullptr, 0, soft->k).bytes;
+}
+
+extern "C" int mmk_icp_forward_soft(const mmk_icp_params *p, const float *source, const float *target,
+                                    const float *weight, const float *T_init, float *T_out, int32_t *idx_hist,
+                                    float *T_hist, double *delta_hist, double *A_hist, int32_t *active_hist,
+                                    const mmk_icp_soft *soft, void *workspace, size_t workspace_bytes, int *iters_run,
+                                    void *stream)
+{
+    int rc = check_params(p);
+    if (rc != MMK_OK) return rc;
+    rc = check_soft("mmk_icp_forward_soft", soft, p->M);
+    if (rc != MMK_OK) return rc;
+    IcpCall c{source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, (hipStream_t)stream};
+    c.soft_k = soft->k;
+    c.soft_temp = soft->temp;
+    return forward_impl("mmk_icp_forward_soft", p, c, T_init, T_out, workspace, workspace_bytes, iters_run);
 }
 
 extern "C" int mmk_icp_status(const mmk_icp_params *p, const void *workspace, size_t workspace_bytes, int32_t *status_out,
@@ -2537,7 +2848,7 @@ extern "C" int mmk_icp_accumulate(const mmk_icp_params *p, const float *source, 
     with_dim_type(p->dim, p->icp_type, [&](auto D, auto TYPE) {
         hipLaunchKernelGGL((icp_accumulate_kernel<D(), TYPE(), false>), dim3(acc_blocks(p->N), p->B), dim3(ACC_THREADS), 0, st, source,
                            target, p->tgt_cols, weight, T, none, keys, no_next, none, none, 1, 1, idx_out, p->N, p->M, r.loss, r.k, r.k2,
-                           r.trim2, r.trim_dist, r.trim_steep, partials, status, no_hyper, 0, 0);
+                           r.trim2, r.trim_dist, r.trim_steep, partials, status, no_hyper, 0, 0, SoftArgs{nullptr, 0, 0.f});
     });
     MMK_LAUNCH_CHECK();
     return MMK_OK;
@@ -2560,11 +2871,12 @@ extern "C" int mmk_icp_solve_update(const mmk_icp_params *p, const double *parti
 namespace {
 // The three backward entries.  `per_pair` is mmk_icp_backward_hp's argument (0 from the others); a gradient output an entry
 // does not have is NULL in `c` and its check holds.  `ws_code`: what the entry returns for a short workspace.
-int backward_impl(const char *who, int ws_code, const mmk_icp_params *p, const IcpCall &c, int per_pair, void *workspace,
+int backward_impl(const char *who, int ws_code, const mmk_icp_params *p_in, const IcpCall &c, int per_pair, void *workspace,
                   size_t workspace_bytes)
 {
-    int rc = check_params(p);
+    int rc = check_params(p_in);
     if (rc != MMK_OK) return rc;
+    const mmk_icp_params eff = effective_params(p_in, c.soft_k), *const p = &eff;
     MMK_REQUIRE(p->save_state, "%s: forward must have run with save_state = 1", who);
     MMK_REQUIRE(c.source && c.target && c.idx_hist && c.T_hist && c.delta_hist && c.A_hist && c.active_hist && c.grad_T && c.grad_weight,
                 "%s: NULL pointer", who);
@@ -2572,7 +2884,7 @@ int backward_impl(const char *who, int ws_code, const mmk_icp_params *p, const I
     MMK_REQUIRE(c.grad_hyper == nullptr || c.hyper != nullptr, "%s: grad_hyper needs hyper", who);
     MMK_REQUIRE(c.grad_target == nullptr || p->max_iter <= 65535, "%s: the target gradient needs max_iter <= 65535 (got %d)", who,
                 p->max_iter);
-    const IcpBwdWs bw = carve_backward(p, c.grad_target != nullptr, c.hyper != nullptr, workspace, workspace_bytes);
+    const IcpBwdWs bw = carve_backward(p, c.grad_target != nullptr, c.hyper != nullptr, workspace, workspace_bytes, c.soft_k);
     rc = check_workspace(who, ws_code, workspace, workspace_bytes, bw.bytes);
     if (rc != MMK_OK) return rc;
     return with_dim_type(p->dim, p->icp_type, [&](auto D, auto TYPE) { return run_backward<D(), TYPE()>(p, c, bw); });
@@ -2628,4 +2940,92 @@ extern "C" int mmk_icp_backward_hp(const mmk_icp_params *p, const float *source,
                     writable(active_hist), (hipStream_t)stream, hyper, per_pair ? 3 : 0, grad_T, grad_weight, grad_T_init,
                     grad_source, grad_target, grad_hyper};
     return backward_impl("mmk_icp_backward_hp", MMK_ERR_ARG, p, c, per_pair, workspace, workspace_bytes);
+}
+
+extern "C" size_t mmk_icp_backward_soft_workspace_bytes(const mmk_icp_params *p, const mmk_icp_soft *soft, int32_t with_target)
+{
+    if (check_params(p) != MMK_OK || check_soft("mmk_icp_backward_soft_workspace_bytes", soft, p->M) != MMK_OK) return 0;
+    const mmk_icp_params eff = effective_params(p, soft->k);
+    return carve_backward(&eff, with_target != 0, false, nullptr, 0, soft->k).bytes;
+}
+
+// The reverse sweep of a mmk_icp_forward_soft call (I7'''): grad_source and grad_target each optional, idx_hist (K,B,N,k).
+// A short workspace is MMK_ERR_ARG.
+extern "C" int mmk_icp_backward_soft(const mmk_icp_params *p, const float *source, const float *target,
+                                     const float *weight, const int32_t *idx_hist, const float *T_hist,
+                                     const double *delta_hist, const double *A_hist, const int32_t *active_hist,
+                                     const float *grad_T, float *grad_weight, float *grad_T_init, float *grad_source,
+                                     float *grad_target, const mmk_icp_soft *soft, void *workspace, size_t workspace_bytes,
+                                     void *stream)
+{
+    int rc = check_params(p);
+    if (rc != MMK_OK) return rc;
+    rc = check_soft("mmk_icp_backward_soft", soft, p->M);
+    if (rc != MMK_OK) return rc;
+    IcpCall c{source, target, weight, writable(idx_hist), writable(T_hist), writable(delta_hist), writable(A_hist),
+              writable(active_hist), (hipStream_t)stream, nullptr, 0, grad_T, grad_weight, grad_T_init, grad_source, grad_target};
+    c.soft_k = soft->k;
+    c.soft_temp = soft->temp;
+    return backward_impl("mmk_icp_backward_soft", MMK_ERR_ARG, p, c, 0, workspace, workspace_bytes);
+}
+
+namespace {
+struct KnnSearchWs {
+    KnnWs grid;
+    unsigned long long *keys;      // (B,N,k)
+    size_t bytes;
+};
+
+KnnSearchWs knn_search_carve(int32_t B, int32_t N, int32_t M, int32_t k, void *workspace, size_t workspace_bytes)
+{
+    KnnSearchWs w;
+    w.grid = knn_carve(B, M, workspace, workspace_bytes);
+    mmk::Arena ar(workspace, workspace_bytes);
+    ar.off = w.grid.bytes;
+    w.keys = ar.take<unsigned long long>((size_t)B * N * k);
+    w.bytes = mmk::align_up(ar.off, 256);
+    return w;
+}
+
+int check_knn_search(const char *who, int32_t B, int32_t N, int32_t M, int32_t k)
+{
+    MMK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && M >= 1, "%s: B must be in 1..65535, N and M >= 1 (got %d, %d, %d)", who, B, N, M);
+    MMK_REQUIRE(k >= 2 && k <= SOFT_KMAX, "%s: k must be in 2..%d (got %d)", who, SOFT_KMAX, k);
+    MMK_REQUIRE(M >= k, "%s: the target must have at least k = %d rows (got M = %d)", who, k, M);
+    return MMK_OK;
+}
+}  // namespace
+
+extern "C" size_t mmk_knn_search_workspace_bytes(int32_t B, int32_t N, int32_t M, int32_t k)
+{
+    if (check_knn_search("mmk_knn_search_workspace_bytes", B, N, M, k) != MMK_OK) return 0;
+    return knn_search_carve(B, N, M, k, nullptr, 0).bytes;
+}
+
+// I2' on its own: the k nearest rows of `target` (B,M,tgt_cols) to the transformed source points, in key order.
+extern "C" int mmk_knn_search(const float *source, const float *target, const float *T, int32_t B, int32_t N, int32_t M,
+                              int32_t tgt_cols, int32_t dim, int32_t k, int32_t *idx, float *d2, void *workspace,
+                              size_t workspace_bytes, void *stream)
+{
+    MMK_REQUIRE(source && target && T && idx && d2, "mmk_knn_search: NULL pointer");
+    MMK_REQUIRE((dim == 2 || dim == 3) && tgt_cols >= dim, "mmk_knn_search: dim must be 2|3 and <= tgt_cols");
+    int rc = check_knn_search("mmk_knn_search", B, N, M, k);
+    if (rc != MMK_OK) return rc;
+    MMK_REQUIRE((size_t)B * N * k <= 0x7fffffffu, "mmk_knn_search: B * N * k must fit 31 bits");
+    const KnnSearchWs w = knn_search_carve(B, N, M, k, workspace, workspace_bytes);
+    rc = check_workspace("mmk_knn_search", MMK_ERR_WORKSPACE, workspace, workspace_bytes, w.bytes);
+    if (rc != MMK_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = build_grid(target, B, M, tgt_cols, dim, w.grid.counts, w.grid.cursor, w.grid.starts, w.grid.sorted, st);
+    if (rc != MMK_OK) return rc;
+    const int32_t *const every_pair = nullptr;
+    with_dim(dim, [&](auto D) {
+        hipLaunchKernelGGL(grid_knn_kernel<D()>, dim3((N + KNN_THREADS - 1) / KNN_THREADS, B), dim3(KNN_THREADS), 0, st, source, T,
+                           every_pair, w.grid.starts, w.grid.sorted, N, M, k, w.keys);
+    });
+    MMK_LAUNCH_CHECK();
+    const int n = B * N * k;
+    hipLaunchKernelGGL(nn_unpack_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w.keys, n, idx, d2);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
 }

@@ -45,6 +45,18 @@ synchronisation: the kernels raise ``MMK_ICP_STATUS_BAD_HYPER`` for a value the 
 range (metric > 0 under Cauchy / Huber, trim_dist >= 0, steepness > 0 under the tanh gate), and the next ICP call, or
 ``check_errors()``, turns it into an MmkError.  Nothing here keeps a learned value in range, and ``tolerance`` and
 ``target_pad_val`` get no gradient.
+
+Soft correspondences (``parameters.correspondence: softmin`` in the YAML, or ``icp.correspondence = "softmin"``; DESIGN.md §3
+I2', I3''', I7'''): a differentiable call -- ``differentiable=True`` with grad enabled -- matches every source point to a
+VIRTUAL target row, the soft-min over its ``softmin_k`` (2..8, default 4) nearest target rows with temperature
+``softmin_temp`` (m^2, default 0.25): a_j = softmax_j(-(d_j - d_0) / temp), row = sum_j a_j row_j, for pt2pl the normal
+columns too, which are NOT renormalised.  The backward differentiates the a_j in the points, so a gradient can tell a point
+that it would be better served by the neighbour next to its correspondent; which k rows are the neighbours stays a constant
+and the temperature gets no gradient.  The search of such a call is always the exact k-NN through the grid: ``nn_search``
+is ignored there.  Any other call of the instance (``differentiable=False``, or under ``torch.no_grad()``) keeps nearest
+correspondences, bit for bit -- upstream's split, as with the gate.  ``trim: tanh`` combines with it; a tensor
+hyper-parameter does not (ValueError before the device is touched), and the target needs at least ``softmin_k`` rows.
+``correspondence: nearest``, or the keys absent, is the call it always was.
 """
 import ctypes
 import os
@@ -71,10 +83,11 @@ def _workspace(nbytes, device):
     return buf
 
 
-def _state_buffers(p, device):
+def _state_buffers(p, device, soft=None):
     K, B, N = p.max_iter, p.B, p.N
+    per_point = () if soft is None else (soft.k,)          # soft correspondences: k neighbours per point, in key order
     return {
-        "idx": torch.empty((K if p.save_state else 1, B, N), dtype=torch.int32, device=device),
+        "idx": torch.empty((K if p.save_state else 1, B, N) + per_point, dtype=torch.int32, device=device),
         "T": torch.empty((K + 1, B, 16), dtype=torch.float32, device=device),
         "delta": torch.empty((K, B, 6), dtype=torch.float64, device=device),
         "A": torch.empty((K, B, 36), dtype=torch.float64, device=device),
@@ -169,12 +182,15 @@ def _hyper_array(values, per_pair, B, dev):
     return torch.stack(cols, dim=1).contiguous()
 
 
-def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False):
+def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False, soft=None):
     L = _lib.lib()
     dev = src.device
     _status.check()
-    ws = _workspace(L.mmk_icp_workspace_bytes(ctypes.byref(p)), dev)
-    st = _state_buffers(p, dev)
+    nbytes = L.mmk_icp_workspace_bytes(ctypes.byref(p)) if soft is None else L.mmk_icp_soft_workspace_bytes(ctypes.byref(p), ctypes.byref(soft))
+    if nbytes == 0:
+        raise _lib.MmkError("libmmk_hip: %s" % L.mmk_last_error().decode(errors="replace"))
+    ws = _workspace(nbytes, dev)
+    st = _state_buffers(p, dev, soft)
     T_out = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
     iters = ctypes.c_int(0)
     args = [ctypes.byref(p), _lib.ptr(src, torch.float32, "source"), _lib.ptr(tgt, torch.float32, "target"),
@@ -184,16 +200,20 @@ def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False):
     if hyper is not None:
         entry = L.mmk_icp_forward_hp
         args += [_lib.ptr(hyper), 1 if per_pair else 0]
+    elif soft is not None:
+        entry = L.mmk_icp_forward_soft
+        args += [ctypes.byref(soft)]
     _lib.check(entry(*args, _lib.ptr(ws), ws.numel(), ctypes.byref(iters), _lib.stream_ptr(dev)))
     _status.watch(p, ws, dev)
     return T_out, st, iters.value
 
 
-def _backward(ctx, grad_T, hyper, per_pair, need_h):
-    """The reverse sweep of both autograd functions -> (gw, gT0, gs, gt, gh); ``hyper`` None: a call with numbers only,
+def _backward(ctx, grad_T, hyper, per_pair, need_h, soft=None):
+    """The reverse sweep of the autograd functions -> (gw, gT0, gs, gt, gh); ``hyper`` None: a call with numbers only,
     ``need_h``: a hyper-parameter gradient is asked for.  mmk_icp_backward on the cached workspace when neither a cloud nor
     a hyper-parameter is involved; else mmk_icp_backward_points (no ``hyper``) or mmk_icp_backward_hp, whose scratch holds
-    per-point rows and fixed-point sums for the target as well and is sized per call, not cached."""
+    per-point rows and fixed-point sums for the target as well and is sized per call, not cached.  ``soft``: the call had
+    soft correspondences -- mmk_icp_backward_soft, with or without the clouds."""
     weight, src, tgt, idx, T_hist, delta, A, active = ctx.saved_tensors[:8]
     p = ctx.p
     L = _lib.lib()
@@ -203,11 +223,13 @@ def _backward(ctx, grad_T, hyper, per_pair, need_h):
     gT0 = torch.empty(p.B, 4, 4, dtype=torch.float32, device=dev)
     need_src, need_tgt = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
     state = [ctypes.byref(p)] + [_lib.ptr(t) for t in (src, tgt, weight, idx, T_hist, delta, A, active, gT, gw, gT0)]
-    if hyper is None and not (need_src or need_tgt):
+    if hyper is None and soft is None and not (need_src or need_tgt):
         ws = _workspace(L.mmk_icp_workspace_bytes(ctypes.byref(p)), dev)
         _lib.check(L.mmk_icp_backward(*state, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
         return gw, gT0, None, None, None
-    if hyper is None:
+    if soft is not None:
+        entry, nbytes = L.mmk_icp_backward_soft, L.mmk_icp_backward_soft_workspace_bytes(state[0], ctypes.byref(soft), 1 if need_tgt else 0)
+    elif hyper is None:
         entry, nbytes = L.mmk_icp_backward_points, L.mmk_icp_backward_points_workspace_bytes(state[0], 1 if need_tgt else 0)
     else:
         entry, nbytes = L.mmk_icp_backward_hp, L.mmk_icp_backward_hp_workspace_bytes(state[0], 1 if need_tgt else 0, 1)
@@ -216,6 +238,8 @@ def _backward(ctx, grad_T, hyper, per_pair, need_h):
     gt = torch.empty(p.B, p.M, p.tgt_cols, dtype=torch.float32, device=dev) if need_tgt else None
     gh = torch.empty(p.B, 3, dtype=torch.float32, device=dev) if need_h else None
     extra = [] if hyper is None else [_lib.ptr(hyper), 1 if per_pair else 0, _lib.ptr(gh)]
+    if soft is not None:
+        extra = [ctypes.byref(soft)]
     _lib.check(entry(*state, _lib.ptr(gs), _lib.ptr(gt), *extra, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
     return gw, gT0, gs, gt, gh
 
@@ -236,6 +260,23 @@ class _IcpFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_T):
         return _backward(ctx, grad_T, None, False, False)[:4] + (None,)
+
+
+class _IcpSoftFunction(torch.autograd.Function):
+    """_IcpFunction for a call with soft correspondences (mmk_icp_forward_soft / mmk_icp_backward_soft): the saved
+    correspondences are (K,B,N,k)."""
+
+    @staticmethod
+    def forward(ctx, weight, T_init, src, tgt, p, soft):
+        T_out, st, _ = _forward(p, src, tgt, weight, T_init, soft=soft)
+        _IcpFunction.last_active = st["active"]
+        ctx.p, ctx.soft = p, soft
+        ctx.save_for_backward(weight, src, tgt, st["idx"], st["T"], st["delta"], st["A"], st["active"])
+        return T_out
+
+    @staticmethod
+    def backward(ctx, grad_T):
+        return _backward(ctx, grad_T, None, False, False, soft=ctx.soft)[:4] + (None, None)
 
 
 class _IcpHpFunction(torch.autograd.Function):
@@ -309,6 +350,13 @@ class ICP:
         self.trim = str((cfg.get("parameters") or {}).get("trim", "hard"))
         self.tanh_steepness = float((cfg.get("parameters") or {}).get("tanh_steepness", 10.0))
         self._trim_steep()
+        # the correspondences of a differentiable call: "nearest" the single nearest target row (a constant of the
+        # backward), "softmin" the soft-min over the softmin_k nearest rows at temperature softmin_temp (DESIGN.md §3
+        # I2', I3''', I7'''); every other call keeps "nearest"
+        self.correspondence = str((cfg.get("parameters") or {}).get("correspondence", "nearest"))
+        self.softmin_k = (cfg.get("parameters") or {}).get("softmin_k", 4)
+        self.softmin_temp = (cfg.get("parameters") or {}).get("softmin_temp", 0.25)
+        self._softmin()
         self.last_state = None
         self.last_iterations = None
 
@@ -325,6 +373,18 @@ class ICP:
         if not (steep > 0.0 and steep != float("inf")):
             raise ValueError("dICP config: tanh_steepness must be a finite number > 0 (got %r)" % (self.tanh_steepness,))
         return steep if soft else 0.0
+
+    def _softmin(self):
+        """mmk_icp_soft of the instance's correspondences, or None for "nearest" (attributes are assignable: validated at
+        every use)."""
+        if self.correspondence not in ("nearest", "softmin"):
+            raise ValueError("dICP config: correspondence must be 'nearest' or 'softmin' (got %r)" % (self.correspondence,))
+        k, temp = self.softmin_k, self.softmin_temp
+        if isinstance(k, bool) or not isinstance(k, int) or not 2 <= k <= 8:
+            raise ValueError("dICP config: softmin_k must be an integer in 2..8 (got %r)" % (k,))
+        if isinstance(temp, (bool, torch.Tensor)) or not isinstance(temp, (int, float)) or not (0.0 < float(temp) < float("inf")):
+            raise ValueError("dICP config: softmin_temp must be a finite number > 0 (got %r)" % (temp,))
+        return _lib.IcpSoft(k=k, temp=float(temp)) if self.correspondence == "softmin" else None
 
     def _params(self, B, N, M, tgt_cols, dim, loss_fn, trim_dist, save_state, on_device=False):
         """``on_device``: the metric, trim_dist and the steepness travel in the device array of the _hp entries; the struct
@@ -359,6 +419,15 @@ class ICP:
             raise ValueError("dim must be 2 or 3")
         values = (1.0 if loss_fn is None else loss_fn.get("metric", 1.0), trim_dist, self.tanh_steepness)
         per_pair = _hyper_sizes(values, source.shape[0])            # None: numbers only, the call it always was
+        soft = self._softmin()
+        if not (self.differentiable and torch.is_grad_enabled()):
+            soft = None                                             # only a differentiable call has soft correspondences
+        if soft is not None and per_pair is not None:
+            raise ValueError("correspondence='softmin' does not combine with a tensor hyper-parameter (%s given as a tensor)"
+                             % ", ".join(n for n, v in zip(HYPER_NAMES, values) if isinstance(v, torch.Tensor)))
+        if soft is not None and target.shape[1] < soft.k:
+            raise ValueError("correspondence='softmin' needs a target of at least softmin_k = %d rows (got %d)"
+                             % (soft.k, target.shape[1]))
         if source.is_cuda:
             dev = source.device
         elif torch.cuda.is_available():
@@ -385,10 +454,14 @@ class ICP:
             (w is not None and w.requires_grad) or T0.requires_grad or src.requires_grad or tgt.requires_grad or
             any(isinstance(v, torch.Tensor) and v.requires_grad for v in values))
         p = self._params(B, N, M, tgt.shape[-1], dim, loss_fn, trim_dist, save_state=need_grad, on_device=per_pair is not None)
+        if soft is not None:
+            p.nn_method = _lib.NN_METHODS["grid"]                   # the k-NN goes through the grid; nn_search is ignored
         if need_grad:
             if w is None:
                 w = torch.ones(B, N, dtype=torch.float32, device=dev)
-            if per_pair is None:
+            if soft is not None:
+                T = _IcpSoftFunction.apply(w, T0, src, tgt, p, soft)
+            elif per_pair is None:
                 T = _IcpFunction.apply(w, T0, src, tgt, p)
             else:
                 T = _IcpHpFunction.apply(w, T0, src, tgt, values[0], values[1], values[2], p, per_pair)
@@ -396,7 +469,7 @@ class ICP:
         else:
             with torch.no_grad():
                 hyper = None if per_pair is None else _hyper_array(values, per_pair, B, dev)
-                T, st, iters = _forward(p, src, tgt, None if w is None else w.detach(), T0.detach(), hyper, bool(per_pair))
+                T, st, iters = _forward(p, src, tgt, None if w is None else w.detach(), T0.detach(), hyper, bool(per_pair), soft)
             self.last_state = st
             self.last_iterations = iters
         return {"T": T if T.device == out_device else T.to(out_device)}

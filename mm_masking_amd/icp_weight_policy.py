@@ -123,6 +123,25 @@ class LearnICPWeightPolicy(nn.Module):
         if "icp_tanh_steepness" in params:
             self.ICP_alg.tanh_steepness = self.icp_tanh_steepness
         self.ICP_alg_inference.trim = "hard"
+        # params["icp_correspondence"] / ["icp_softmin_k"] / ["icp_softmin_temp"] (absent upstream): the correspondences of the
+        # TRAINING instance, "nearest" or the "softmin" over the k nearest target rows that the backward differentiates
+        # (dICP/ICP.py); the inference instance keeps nearest correspondences.  Works with mask_target="scan" (that mode
+        # runs unweighted: the mask acts through the points); does not combine with learn_icp (tensor hyper-parameters).
+        self.icp_correspondence = params.get("icp_correspondence", "nearest")
+        if self.icp_correspondence not in ("nearest", "softmin"):
+            raise ValueError("icp_correspondence must be 'nearest' or 'softmin' (got %r)" % (self.icp_correspondence,))
+        learn = params.get("learn_icp", ()) or ()
+        if self.icp_correspondence == "softmin" and len((learn,) if isinstance(learn, str) else tuple(learn)) > 0:
+            raise ValueError("icp_correspondence='softmin' does not combine with learn_icp (tensor hyper-parameters)")
+        if "icp_correspondence" in params:          # (absent: whatever the dICP configuration says, "nearest" by default)
+            self.ICP_alg.correspondence = self.icp_correspondence
+        if "icp_softmin_k" in params:
+            self.ICP_alg.softmin_k = params["icp_softmin_k"]
+        if "icp_softmin_temp" in params:
+            self.ICP_alg.softmin_temp = params["icp_softmin_temp"]
+        self.ICP_alg._softmin()                     # validates k (2..8) and the temperature (> 0): ValueError
+        self.icp_softmin_k, self.icp_softmin_temp = self.ICP_alg.softmin_k, self.ICP_alg.softmin_temp
+        self.ICP_alg_inference.correspondence = "nearest"
         # "hip" (the product path): hand-written NHWC bf16 kernels (csrc/mmk_unet.hip), fp32 masters;
         # "torch": the nn.Module tree evaluated by PyTorch on the CPU -- host-logic mirror for tests only
         self.unet_backend = params.get("unet_backend", "hip")
