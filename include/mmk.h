@@ -180,7 +180,7 @@ int mmk_icp_backward_hp(const mmk_icp_params *p, const float *source, const floa
  * order.  Workspace: mmk_icp_soft_workspace_bytes(p, soft); mmk_icp_status reads its status word as usual.
  * mmk_icp_backward_soft: mmk_icp_backward_points' arguments (grad_source and grad_target each optional: the entry serves
  * both backward shapes).  Which k rows are the neighbours is a constant, like the freezes and the delta = 0 fallback;
- * temp gets no gradient.  The target gradient is the same fixed-point scatter with K*N*k rows per pair (resolution max|row
+ * temp gets no gradient here (the _soft_t entries below give it one).  The target gradient is the same fixed-point scatter with K*N*k rows per pair (resolution max|row
  * entry| * 2^(ceil(log2(K*N*k)) - 62)).  Workspace: mmk_icp_backward_soft_workspace_bytes(p, soft, grad_target != NULL);
  * a short one is MMK_ERR_ARG.  Device-resident hyper-parameters (the _hp entries) are not combined with this mode.        */
 typedef struct {
@@ -202,6 +202,37 @@ int mmk_icp_backward_soft(const mmk_icp_params *p, const float *source, const fl
                           float *grad_weight /*B,N*/, float *grad_T_init /*B,16 or NULL*/,
                           float *grad_source /*B,N,3 or NULL*/, float *grad_target /*B,M,tgt_cols or NULL*/,
                           const mmk_icp_soft *soft, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The soft entries with the temperature read ON THE DEVICE (DESIGN.md §3 I3'''', I7''''): temp fp32 (1) (per_pair = 0, shared
+ * by the batch) or (B) (per_pair = 1).  soft->k is used; soft->temp must still pass the struct's validation (pass 1.0) and is
+ * not read.  The expression is that of I3''', e_j = expf(-(d_j - d_0) / tau_b), so a call whose array holds the fp32 value of a
+ * mmk_icp_forward_soft call is bit-identical to it.  Nothing is read back: on the first iteration one thread per pair
+ * validates tau_b, and a non-finite or <= 0 value raises MMK_ICP_STATUS_BAD_HYPER in the status word (mmk_icp_status); the
+ * arithmetic runs on (indices come from the k-NN, never from tau: nothing leaves its bounds).
+ * mmk_icp_forward_soft_t: temp == NULL is mmk_icp_forward_soft exactly.  Workspace: mmk_icp_soft_workspace_bytes(p, soft).
+ * mmk_icp_backward_soft_t: grad_temp (B -- one row per pair also when temp is shared: the caller adds the rows -- or NULL)
+ * = dL/dtau.  Per point and active iteration in fp32: u = sum_j zbar_j (d_j - d_0) in slot order (slot 0 adds exactly 0),
+ * tau-bar_i = u / (tau_b * tau_b); summed per pair in fp64 by block partials in a fixed order, as grad_hyper is (no float
+ * atomics: bit-reproducible; a pair's frozen iterations add exactly 0).  temp == NULL with grad_temp == NULL is
+ * mmk_icp_backward_soft exactly.  Workspace: mmk_icp_backward_soft_t_workspace_bytes(p, soft, grad_target != NULL,
+ * grad_temp != NULL) -- the older entries' sizes are unchanged.  per_pair other than 0 / 1, grad_temp without temp and a
+ * short workspace: MMK_ERR_ARG.                                                                                           */
+int mmk_icp_forward_soft_t(const mmk_icp_params *p, const float *source /*B,N,3*/,
+                           const float *target /*B,M,tgt_cols*/, const float *weight /*B,N*/,
+                           const float *T_init /*B,16*/, float *T_out /*B,16*/,
+                           int32_t *idx_hist, float *T_hist, double *delta_hist, double *A_hist,
+                           int32_t *active_hist, const mmk_icp_soft *soft, const float *temp /*1|B*/, int32_t per_pair,
+                           void *workspace, size_t workspace_bytes, int *iters_run, void *stream);
+size_t mmk_icp_backward_soft_t_workspace_bytes(const mmk_icp_params *p, const mmk_icp_soft *soft, int32_t with_target,
+                                               int32_t with_temp);
+int mmk_icp_backward_soft_t(const mmk_icp_params *p, const float *source, const float *target,
+                            const float *weight, const int32_t *idx_hist /*K,B,N,k*/, const float *T_hist,
+                            const double *delta_hist, const double *A_hist,
+                            const int32_t *active_hist, const float *grad_T /*B,16*/,
+                            float *grad_weight /*B,N*/, float *grad_T_init /*B,16 or NULL*/,
+                            float *grad_source /*B,N,3 or NULL*/, float *grad_target /*B,M,tgt_cols or NULL*/,
+                            const mmk_icp_soft *soft, const float *temp /*1|B*/, int32_t per_pair,
+                            float *grad_temp /*B or NULL*/, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Stage I2' on its own: the k (2..8, M >= k) nearest rows of `target` (B,M,tgt_cols, the first dim columns) to the source
  * points under T (B,16), exact, through the per-call grid.  idx int32 (B,N,k) and d2 fp32 (B,N,k) in key order: ascending

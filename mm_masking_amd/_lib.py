@@ -149,6 +149,9 @@ def _declare(lib):
         "mmk_icp_forward_soft": (ctypes.c_int, [P] + [c_vp] * 10 + [S, c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
         "mmk_icp_backward_soft_workspace_bytes": (sz, [P, S, i32]),
         "mmk_icp_backward_soft": (ctypes.c_int, [P] + [c_vp] * 13 + [S, c_vp, sz, c_vp]),
+        "mmk_icp_forward_soft_t": (ctypes.c_int, [P] + [c_vp] * 10 + [S, c_vp, i32, c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
+        "mmk_icp_backward_soft_t_workspace_bytes": (sz, [P, S, i32, i32]),
+        "mmk_icp_backward_soft_t": (ctypes.c_int, [P] + [c_vp] * 13 + [S, c_vp, i32, c_vp, c_vp, sz, c_vp]),
         "mmk_knn_search_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "mmk_knn_search": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, i32, c_vp, c_vp, c_vp, sz, c_vp]),
         "mmk_pose_loss_fwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp]),

@@ -1247,11 +1247,26 @@ __device__ __forceinline__ bool hyper_is_bad(const HyperVals &v, int loss, bool 
 //      S = sum_j e_j in slot order;  a_j = e_j / S.
 // Nothing is stored per slot: k is a run-time loop bound, a per-lane array indexed by j would live in scratch memory, so
 // each loop loads its row again (k rows of one point: L1 / L2 hits) and recomputes a_j.
+// I3⁗ / I7⁗ (the _soft_t entries): with `tptr` the pair's tau is tptr[b * tstride] (tstride 0 shared | 1 per pair), read
+// once per block -- b is blockIdx.y, the load is uniform -- and `temp` is not looked at; the expressions below are the same,
+// so an array that holds a number call's fp32 value gives that call's bits.
 struct SoftArgs {
     const unsigned long long *keys;      // (B,N,k) of grid_knn_kernel (the forward only)
     int k;
     float temp;
+    const float *tptr = nullptr;         // (1 | B) device tau; NULL: `temp`
+    int tstride = 0;
+    int tcheck = 0;                      // the forward's first iteration: one thread per pair validates tau_b
+    double *tparts = nullptr;            // the backward: (B,nblk) block partials of tau-bar for this iteration, or NULL
 };
+
+__device__ __forceinline__ float soft_temp(const SoftArgs &soft, int b)
+{
+    return soft.tptr != nullptr ? soft.tptr[(size_t)b * soft.tstride] : soft.temp;
+}
+
+// A device tau that is non-finite or <= 0: MMK_ICP_STATUS_BAD_HYPER.  (NaN fails every comparison.)
+__device__ __forceinline__ bool soft_temp_is_bad(float tau) { return !(tau > 0.f && tau <= 3.4028234663852886e38f); }
 
 template <int DIM>
 __device__ __forceinline__ float soft_e(const float *row, const float p[DIM], float d0, float temp)
@@ -1301,6 +1316,8 @@ __device__ __forceinline__ void soft_virtual_row(const float *tgtb, int tgt_cols
 // iteration of a call) has one thread per pair validate them.
 // SOFT (mmk_icp_forward_soft, I3'''): the point's k keys come from soft.keys, idx_out is (B,N,k), and the virtual row takes
 // the correspondent's place; `packed` and the zero-row bookkeeping are not used.  SOFT = false is the kernel it always was.
+// With soft.tptr (mmk_icp_forward_soft_t, I3⁗) tau is the pair's device value, and `soft.tcheck` != 0 (the first iteration
+// of a call) has one thread per pair validate it.
 template <int DIM, int TYPE, bool HP = false, bool SOFT = false>
 __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
     const float *__restrict__ src, const float *__restrict__ tgt, int tgt_cols,
@@ -1321,6 +1338,12 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
         if (hcheck != 0 && blockIdx.x == 0 && threadIdx.x == 0 && status != nullptr && hyper_is_bad(hv, loss, trim_steep > 0.f))
             atomicOr(status, (int32_t)MMK_ICP_STATUS_BAD_HYPER);
         k = hv.k, k2 = hv.k2, trim2 = hv.trim2, trim_dist = hv.trim_dist, trim_steep = hv.trim_steep;
+    }
+    float stemp = 0.f;
+    if constexpr (SOFT) {
+        stemp = soft_temp(soft, b);
+        if (soft.tcheck != 0 && blockIdx.x == 0 && threadIdx.x == 0 && status != nullptr && soft_temp_is_bad(stemp))
+            atomicOr(status, (int32_t)MMK_ICP_STATUS_BAD_HYPER);
     }
     const int i = blockIdx.x * ACC_THREADS + threadIdx.x;
     double acc[NACC];
@@ -1347,8 +1370,8 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_accumulate_kernel(
             float p[DIM], vr[6], d0, S;
             transform_point<DIM>(T, s, p);
             const float *tgtb = tgt + (size_t)b * M * tgt_cols;
-            soft_norm<DIM>(tgtb, tgt_cols, nb, soft.k, p, soft.temp, d0, S);
-            soft_virtual_row<DIM, TYPE>(tgtb, tgt_cols, nb, soft.k, p, soft.temp, d0, S, vr);
+            soft_norm<DIM>(tgtb, tgt_cols, nb, soft.k, p, stemp, d0, S);
+            soft_virtual_row<DIM, TYPE>(tgtb, tgt_cols, nb, soft.k, p, stemp, d0, S, vr);
             const float omega = weight ? weight[(size_t)b * N + i] : 1.f;
             point_terms<DIM, TYPE>(t, T, srow, vr, omega, loss, k, k2, trim2, trim_dist, trim_steep);
         } else {
@@ -1768,7 +1791,10 @@ __device__ __forceinline__ void target_row_adjoint(const PointTerms<DIM, TYPE> &
 // parts: wave shuffle -> LDS -> one partial per block, no atomics.  A frozen pair's blocks write exact zeros.
 // SOFT (mmk_icp_backward_soft, I7'''): idx is (B,N,k), the virtual row is rebuilt as in the forward, the per-point code below
 // yields its adjoint, and a last loop over the slots turns that into the k target rows (`rows` is (B,N*k,C)) and the
-// softmin's share of p̄.  SOFT = false is the kernel it always was.
+// softmin's share of p̄.  SOFT = false is the kernel it always was.  With soft.tparts (mmk_icp_backward_soft_t with
+// grad_temp, I7⁗) the second slot loop also forms u = sum_j z̄_j (d_j - d_0), the point's tau-bar = u / (tau_b tau_b) goes
+// through the reduction of the pose parts as one more fp64 accumulator, and the block's sum lands in soft.tparts (B,nblk);
+// a frozen pair's blocks write exact zeros.  Without it that accumulator is neither summed nor stored.
 template <int DIM, int TYPE, bool PTS, bool HP = false, bool SOFT = false>
 __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     const float *__restrict__ src, const float *__restrict__ tgt, int tgt_cols,
@@ -1782,7 +1808,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     constexpr int P = PointTerms<DIM, TYPE>::P;
     constexpr int NR = PointTerms<DIM, TYPE>::NR;
     constexpr int NP = npose(DIM);
-    constexpr int NH = HP ? 3 : 0;
+    constexpr int NH = HP ? 3 : (SOFT ? 1 : 0);     // SOFT: tau-bar (I7⁗), summed only when soft.tparts is given
     constexpr int C = tgt_row_cols(DIM, TYPE);
     const int b = blockIdx.y;
     const int i = blockIdx.x * ACC_THREADS + threadIdx.x;
@@ -1795,6 +1821,8 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     }
     const bool act = active[b] != 0;
     unsigned mbits = 0u;
+    float stemp = 0.f;
+    if constexpr (SOFT) stemp = soft_temp(soft, b);
 
     if (act && i < N) {
         float T[16];
@@ -1818,8 +1846,8 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
             transform_point<DIM>(T, s, p);
             const float *tgtb = tgt + (size_t)b * M * tgt_cols;
             const int32_t *nb = idx + ((size_t)b * N + i) * soft.k;
-            soft_norm<DIM>(tgtb, tgt_cols, nb, soft.k, p, soft.temp, sd0, sS);
-            soft_virtual_row<DIM, TYPE>(tgtb, tgt_cols, nb, soft.k, p, soft.temp, sd0, sS, vr);
+            soft_norm<DIM>(tgtb, tgt_cols, nb, soft.k, p, stemp, sd0, sS);
+            soft_virtual_row<DIM, TYPE>(tgtb, tgt_cols, nb, soft.k, p, stemp, sd0, sS, vr);
             point_terms<DIM, TYPE>(t, T, srow, vr, omega, loss, k, k2, trim2, trim_dist, trim_steep);
         } else {
             point_terms<DIM, TYPE>(t, T, src + ((size_t)b * N + i) * 3, tgt + ((size_t)b * M + j) * tgt_cols, omega,
@@ -1918,7 +1946,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
             // I7''': q holds the adjoint of the virtual row [q̃̄ ; ñ̄].  Per slot ā_j = q̃̄·q_j (+ ñ̄·n_j); m = sum_l a_l ā_l in
             // slot order (first loop); then z̄_j = a_j (ā_j - m), d̄_j = -z̄_j / tau, the slot's target row a_j [q̃̄ ; ñ̄] with
             // 2 d̄_j (q_j - p) added to its xyz, and the same vector taken off p̄ (second loop).  Which rows are the
-            // neighbours is a constant, and tau gets no gradient.
+            // neighbours is a constant; tau gets its gradient from the same z̄_j when soft.tparts is given (I7⁗).
             float q[C];
             target_row_adjoint<DIM, TYPE>(t, ebar, Jbar, gev, trim_steep, q);
             const float *tgtb = tgt + (size_t)b * M * tgt_cols;
@@ -1933,18 +1961,23 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
                 }
                 return v;
             };
-            float m = 0.f;
+            float m = 0.f, tu = 0.f;
             for (int j = 0; j < soft.k; ++j) {
                 const float *row = tgtb + (size_t)nb[j] * tgt_cols;
-                const float a = soft_e<DIM>(row, t.p, sd0, soft.temp) / sS;
+                const float a = soft_e<DIM>(row, t.p, sd0, stemp) / sS;
                 const float v = a * abar(row);
                 m = j == 0 ? v : m + v;
             }
             for (int j = 0; j < soft.k; ++j) {
                 const float *row = tgtb + (size_t)nb[j] * tgt_cols;
-                const float a = soft_e<DIM>(row, t.p, sd0, soft.temp) / sS;
+                const float a = soft_e<DIM>(row, t.p, sd0, stemp) / sS;
                 const float zbar = a * (abar(row) - m);
-                const float g = 2.f * (-zbar / soft.temp);
+                const float g = 2.f * (-zbar / stemp);
+                if (soft.tparts != nullptr) {       // I7⁗: u = sum_j z̄_j (d_j - d_0) in slot order; slot 0 adds exactly 0
+                    const float dj = nn_dist<DIM>(row[0], row[1], DIM == 3 ? row[2] : 0.f, t.p);
+                    const float v = zbar * (dj - sd0);
+                    tu = j == 0 ? v : tu + v;
+                }
                 float out[C];
 #pragma unroll
                 for (int c = 0; c < DIM; ++c) {
@@ -1964,6 +1997,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
                     }
                 }
             }
+            if (soft.tparts != nullptr) acc[NP] = (double)(tu / (stemp * stemp));
         }
         // p = R s + t
 #pragma unroll
@@ -2006,6 +2040,7 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
     }
 #pragma unroll
     for (int a = 0; a < NP + NH; ++a) {
+        if (SOFT && a == NP && soft.tparts == nullptr) continue;        // (uniform over the grid)
         double v = wave_sum(acc[a]);
         if (lane == 0) red[wv][a] = v;
     }
@@ -2033,26 +2068,37 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
             hparts[((size_t)b * gridDim.x + blockIdx.x) * 3 + c] = v;
         }
     }
+    if constexpr (SOFT) {
+        if (soft.tparts != nullptr && threadIdx.x == 64) {          // (a wave of its own, as above)
+            double v = 0.0;
+#pragma unroll
+            for (int w = 0; w < ACC_THREADS / 64; ++w) v += red[w][NP];
+            soft.tparts[(size_t)b * gridDim.x + blockIdx.x] = v;
+        }
+    }
 }
 
 // grad_hyper (B,3) = the ordered sum of a pair's block partials over the iterations and blocks: `hparts` is (K,B,nblk,3).
 // One wave per pair: lane l adds the rows l, l + 64, ... in index order, then the lanes are added by the fixed shuffle tree
-// -- the same order in every run.
+// -- the same order in every run.  NC = 1: grad_temp (B) from the tau-bar partials (K,B,nblk) of the _soft_t entry (I7⁗).
+template <int NC = 3>
 __global__ __launch_bounds__(64) void icp_bwd_hyper_final_kernel(const double *__restrict__ hparts, int K, int B, int nblk,
                                                                  float *__restrict__ grad_hyper)
 {
     const int b = blockIdx.x, lane = threadIdx.x;
-    double v[3] = {0.0, 0.0, 0.0};
+    double v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = 0.0;
     for (int e = lane; e < K * nblk; e += 64) {
         const int it = e / nblk, blk = e % nblk;
-        const double *row = hparts + (((size_t)it * B + b) * nblk + blk) * 3;
+        const double *row = hparts + (((size_t)it * B + b) * nblk + blk) * NC;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] += row[c];
+        for (int c = 0; c < NC; ++c) v[c] += row[c];
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < NC; ++c) {
         const double s = wave_sum(v[c]);
-        if (lane == 0) grad_hyper[(size_t)b * 3 + c] = (float)s;
+        if (lane == 0) grad_hyper[(size_t)b * NC + c] = (float)s;
     }
 }
 
@@ -2324,9 +2370,10 @@ IcpWs carve(const mmk_icp_params *p, void *ws, size_t cap)
     return w;
 }
 
-// Workspace of the backward entries, four parts in this order, each starting on a 256-byte boundary: the forward's
+// Workspace of the backward entries, five parts in this order, each starting on a 256-byte boundary: the forward's
 // (carve), the target gradient's (with_target), the hyper-parameter gradient's (with_hyper), the soft correspondences'
-// (soft_k > 0; mmk_icp_forward_soft's workspace is the forward's part and this one).  A part that is not asked
+// (soft_k > 0; mmk_icp_forward_soft's workspace is the forward's part and this one), the temperature gradient's
+// (with_temp).  A part that is not asked
 // for takes no room and leaves its pointers NULL, so mmk_icp_backward's workspace is the forward's.
 struct IcpBwdWs {
     IcpWs w;
@@ -2335,12 +2382,14 @@ struct IcpBwdWs {
     unsigned *pmax = nullptr;            // (B): float bits of the largest |entry| of a pair's rows
     double *hparts = nullptr;            // (K,B,nblk,3): block partials of (k̄, c̄, s̄), every entry written by the sweep
     unsigned long long *soft_keys = nullptr;     // (B,N,k): the k-NN keys of the iteration in flight (soft correspondences)
+    double *tparts = nullptr;            // (K,B,nblk): block partials of tau-bar (mmk_icp_backward_soft_t with grad_temp)
     size_t bytes = 0;
 };
 
 // soft_k > 0 (the _soft entries; p->nn_method is MMK_NN_GRID there): the target part holds k rows per point and the soft
 // part, the last one, the keys of grid_knn_kernel.
-IcpBwdWs carve_backward(const mmk_icp_params *p, bool with_target, bool with_hyper, void *ws, size_t cap, int soft_k = 0)
+IcpBwdWs carve_backward(const mmk_icp_params *p, bool with_target, bool with_hyper, void *ws, size_t cap, int soft_k = 0,
+                        bool with_temp = false)
 {
     IcpBwdWs b;
     b.w = carve(p, ws, cap);
@@ -2354,6 +2403,7 @@ IcpBwdWs carve_backward(const mmk_icp_params *p, bool with_target, bool with_hyp
     }
     if (with_hyper) b.hparts = ar.take<double>((size_t)p->max_iter * p->B * acc_blocks(p->N) * 3);
     if (soft_k > 0) b.soft_keys = ar.take<unsigned long long>((size_t)p->B * p->N * soft_k);
+    if (with_temp) b.tparts = ar.take<double>((size_t)p->max_iter * p->B * acc_blocks(p->N));
     b.bytes = mmk::align_up(ar.off, 256);
     return b;
 }
@@ -2384,6 +2434,9 @@ struct IcpCall {
     float *grad_hyper = nullptr;           // (B,3)
     int soft_k = 0;                        // > 0: soft correspondences (I2', I3''', I7'''); idx_hist is then (K | 1,B,N,k)
     float soft_temp = 0.f;
+    const float *temp = nullptr;           // (1 | B): the device tau of the _soft_t entries; NULL: soft_temp
+    int tstride = 0;                       // 0 shared | 1 per pair
+    float *grad_temp = nullptr;            // (B)
 };
 
 // mmk_icp_soft as the _soft entries accept it: k in 2..8 with M >= k, temp finite and > 0.
@@ -2422,7 +2475,7 @@ int run_forward(const mmk_icp_params *p, const IcpCall &c, const IcpWs &w, int *
     const NNPlan pl = nn_plan(B, N, M, DIM);
     const int nblk = acc_blocks(N);
     const bool soft = c.soft_k > 0;
-    const SoftArgs sa{soft_keys, c.soft_k, c.soft_temp};
+    SoftArgs sa{soft_keys, c.soft_k, c.soft_temp, c.temp, c.temp ? c.tstride : 0};
     // without saved state every iteration reuses one (B,N) buffer ((B,N,k) with soft correspondences)
     const size_t idx_step = p->save_state ? (size_t)B * N * (soft ? c.soft_k : 1) : 0;
     int k_done = 0;
@@ -2470,6 +2523,7 @@ int run_forward(const mmk_icp_params *p, const IcpCall &c, const IcpWs &w, int *
             if (rc != MMK_OK) return rc;
         }
         const int hcheck = hyper && it == 0 ? 1 : 0;
+        sa.tcheck = c.temp && it == 0 ? 1 : 0;
         with_bools(hyper != nullptr, soft, [&](auto HP, auto SOFT) {
             if constexpr (!(HP() && SOFT()))        // (no entry combines the two)
                 hipLaunchKernelGGL((icp_accumulate_kernel<DIM, TYPE, HP(), SOFT()>), dim3(nblk, B), dim3(ACC_THREADS), 0, st, src, tgt,
@@ -2529,7 +2583,7 @@ int run_backward(const mmk_icp_params *p, const IcpCall &c, const IcpBwdWs &bw)
     const bool pts = gsrc || gtgt, hp = bw.hparts != nullptr;
     const bool soft = c.soft_k > 0;                 // (never with hp: mmk_icp_backward_soft has no `hyper`)
     const int rpp = soft ? c.soft_k : 1;            // target rows (and saved indices) per point
-    const SoftArgs sa{nullptr, c.soft_k, c.soft_temp};
+    SoftArgs sa{nullptr, c.soft_k, c.soft_temp, c.temp, c.temp ? c.tstride : 0};
     for (int it = p->max_iter - 1; it >= 0; --it) {
         const float *Tk = c.T_hist + (size_t)it * B * 16;
         const int32_t *act = c.active_hist + (size_t)it * B;
@@ -2540,6 +2594,7 @@ int run_backward(const mmk_icp_params *p, const IcpCall &c, const IcpBwdWs &bw)
         float *rows = gtgt ? bw.rows + (size_t)it * B * N * rpp * C : nullptr;
         double *hparts = hp ? bw.hparts + (size_t)it * B * nblk * 3 : nullptr;
         const int32_t *idx = c.idx_hist + (size_t)it * B * N * rpp;
+        sa.tparts = bw.tparts ? bw.tparts + (size_t)it * B * nblk : nullptr;
         with_bools(pts, hp, [&](auto PTS, auto HP) {
             with_bool(soft, [&](auto SOFT) {
                 if constexpr (!(HP() && SOFT()))    // (no entry combines the two)
@@ -2558,7 +2613,11 @@ int run_backward(const mmk_icp_params *p, const IcpCall &c, const IcpBwdWs &bw)
         MMK_LAUNCH_CHECK();
     }
     if (c.grad_hyper) {
-        hipLaunchKernelGGL(icp_bwd_hyper_final_kernel, dim3(B), dim3(64), 0, st, bw.hparts, p->max_iter, B, nblk, c.grad_hyper);
+        hipLaunchKernelGGL(icp_bwd_hyper_final_kernel<3>, dim3(B), dim3(64), 0, st, bw.hparts, p->max_iter, B, nblk, c.grad_hyper);
+        MMK_LAUNCH_CHECK();
+    }
+    if (c.grad_temp) {
+        hipLaunchKernelGGL(icp_bwd_hyper_final_kernel<1>, dim3(B), dim3(64), 0, st, bw.tparts, p->max_iter, B, nblk, c.grad_temp);
         MMK_LAUNCH_CHECK();
     }
     if (gtgt) {
@@ -2812,6 +2871,26 @@ extern "C" int mmk_icp_forward_soft(const mmk_icp_params *p, const float *source
     return forward_impl("mmk_icp_forward_soft", p, c, T_init, T_out, workspace, workspace_bytes, iters_run);
 }
 
+// mmk_icp_forward_soft with tau on the device (I3⁗): `temp` (1 | B), per_pair 0 | 1.  temp NULL: mmk_icp_forward_soft.
+extern "C" int mmk_icp_forward_soft_t(const mmk_icp_params *p, const float *source, const float *target,
+                                      const float *weight, const float *T_init, float *T_out, int32_t *idx_hist,
+                                      float *T_hist, double *delta_hist, double *A_hist, int32_t *active_hist,
+                                      const mmk_icp_soft *soft, const float *temp, int32_t per_pair, void *workspace,
+                                      size_t workspace_bytes, int *iters_run, void *stream)
+{
+    int rc = check_params(p);
+    if (rc != MMK_OK) return rc;
+    rc = check_soft("mmk_icp_forward_soft_t", soft, p->M);
+    if (rc != MMK_OK) return rc;
+    MMK_REQUIRE(per_pair == 0 || per_pair == 1, "mmk_icp_forward_soft_t: per_pair must be 0 or 1 (got %d)", per_pair);
+    IcpCall c{source, target, weight, idx_hist, T_hist, delta_hist, A_hist, active_hist, (hipStream_t)stream};
+    c.soft_k = soft->k;
+    c.soft_temp = soft->temp;
+    c.temp = temp;
+    c.tstride = per_pair ? 1 : 0;
+    return forward_impl("mmk_icp_forward_soft_t", p, c, T_init, T_out, workspace, workspace_bytes, iters_run);
+}
+
 extern "C" int mmk_icp_status(const mmk_icp_params *p, const void *workspace, size_t workspace_bytes, int32_t *status_out,
                               void *stream)
 {
@@ -2882,9 +2961,11 @@ int backward_impl(const char *who, int ws_code, const mmk_icp_params *p_in, cons
                 "%s: NULL pointer", who);
     MMK_REQUIRE(per_pair == 0 || per_pair == 1, "%s: per_pair must be 0 or 1 (got %d)", who, per_pair);
     MMK_REQUIRE(c.grad_hyper == nullptr || c.hyper != nullptr, "%s: grad_hyper needs hyper", who);
+    MMK_REQUIRE(c.grad_temp == nullptr || c.temp != nullptr, "%s: grad_temp needs temp", who);
     MMK_REQUIRE(c.grad_target == nullptr || p->max_iter <= 65535, "%s: the target gradient needs max_iter <= 65535 (got %d)", who,
                 p->max_iter);
-    const IcpBwdWs bw = carve_backward(p, c.grad_target != nullptr, c.hyper != nullptr, workspace, workspace_bytes, c.soft_k);
+    const IcpBwdWs bw = carve_backward(p, c.grad_target != nullptr, c.hyper != nullptr, workspace, workspace_bytes, c.soft_k,
+                                       c.grad_temp != nullptr);
     rc = check_workspace(who, ws_code, workspace, workspace_bytes, bw.bytes);
     if (rc != MMK_OK) return rc;
     return with_dim_type(p->dim, p->icp_type, [&](auto D, auto TYPE) { return run_backward<D(), TYPE()>(p, c, bw); });
@@ -2967,6 +3048,38 @@ extern "C" int mmk_icp_backward_soft(const mmk_icp_params *p, const float *sourc
     c.soft_k = soft->k;
     c.soft_temp = soft->temp;
     return backward_impl("mmk_icp_backward_soft", MMK_ERR_ARG, p, c, 0, workspace, workspace_bytes);
+}
+
+extern "C" size_t mmk_icp_backward_soft_t_workspace_bytes(const mmk_icp_params *p, const mmk_icp_soft *soft, int32_t with_target,
+                                                          int32_t with_temp)
+{
+    if (check_params(p) != MMK_OK || check_soft("mmk_icp_backward_soft_t_workspace_bytes", soft, p->M) != MMK_OK) return 0;
+    const mmk_icp_params eff = effective_params(p, soft->k);
+    return carve_backward(&eff, with_target != 0, false, nullptr, 0, soft->k, with_temp != 0).bytes;
+}
+
+// The reverse sweep of a mmk_icp_forward_soft_t call (I7⁗): mmk_icp_backward_soft plus the device tau and grad_temp (B, one
+// row per pair also when tau is shared; optional).  temp NULL and grad_temp NULL: mmk_icp_backward_soft.  A short workspace
+// is MMK_ERR_ARG.
+extern "C" int mmk_icp_backward_soft_t(const mmk_icp_params *p, const float *source, const float *target,
+                                       const float *weight, const int32_t *idx_hist, const float *T_hist,
+                                       const double *delta_hist, const double *A_hist, const int32_t *active_hist,
+                                       const float *grad_T, float *grad_weight, float *grad_T_init, float *grad_source,
+                                       float *grad_target, const mmk_icp_soft *soft, const float *temp, int32_t per_pair,
+                                       float *grad_temp, void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_params(p);
+    if (rc != MMK_OK) return rc;
+    rc = check_soft("mmk_icp_backward_soft_t", soft, p->M);
+    if (rc != MMK_OK) return rc;
+    IcpCall c{source, target, weight, writable(idx_hist), writable(T_hist), writable(delta_hist), writable(A_hist),
+              writable(active_hist), (hipStream_t)stream, nullptr, 0, grad_T, grad_weight, grad_T_init, grad_source, grad_target};
+    c.soft_k = soft->k;
+    c.soft_temp = soft->temp;
+    c.temp = temp;
+    c.tstride = per_pair ? 1 : 0;
+    c.grad_temp = grad_temp;
+    return backward_impl("mmk_icp_backward_soft_t", MMK_ERR_ARG, p, c, per_pair, workspace, workspace_bytes);
 }
 
 namespace {

@@ -52,11 +52,22 @@ VIRTUAL target row, the soft-min over its ``softmin_k`` (2..8, default 4) neares
 ``softmin_temp`` (m^2, default 0.25): a_j = softmax_j(-(d_j - d_0) / temp), row = sum_j a_j row_j, for pt2pl the normal
 columns too, which are NOT renormalised.  The backward differentiates the a_j in the points, so a gradient can tell a point
 that it would be better served by the neighbour next to its correspondent; which k rows are the neighbours stays a constant
-and the temperature gets no gradient.  The search of such a call is always the exact k-NN through the grid: ``nn_search``
+(the temperature's gradient: below).  The search of such a call is always the exact k-NN through the grid: ``nn_search``
 is ignored there.  Any other call of the instance (``differentiable=False``, or under ``torch.no_grad()``) keeps nearest
 correspondences, bit for bit -- upstream's split, as with the gate.  ``trim: tanh`` combines with it; a tensor
 hyper-parameter does not (ValueError before the device is touched), and the target needs at least ``softmin_k`` rows.
 ``correspondence: nearest``, or the keys absent, is the call it always was.
+
+``icp.softmin_temp`` may also be a floating-point tensor of shape ``()``, ``(1,)`` (one temperature for the batch) or
+``(B,)`` (one per pair); any other shape, or an integer dtype, is a ValueError before the device is touched.  The call then
+goes through ``mmk_icp_forward_soft_t`` / ``mmk_icp_backward_soft_t`` (DESIGN.md §3 I3⁗, I7⁗): the kernels read tau on the
+device with the expression they always had, so a tensor that holds the fp32 value of a number call gives that call's bits.
+A tensor that requires grad gets its gradient in its own shape, dtype and device -- a shared value the fp64 sum of the pairs'
+rows, rounded once -- and ``T`` requires grad when it does; a differentiable call in which nothing requires grad runs the
+state-less soft forward with the device tau.  A tensor is not validated on the host: a non-finite or <= 0 value raises
+``MMK_ICP_STATUS_BAD_HYPER`` as the other device-resident values do, and nothing here keeps a learned temperature positive.
+A call that is not differentiable keeps nearest correspondences and does not look at the tensor.  The refusals above hold
+with a tensor temperature too.
 """
 import ctypes
 import os
@@ -135,10 +146,10 @@ class _StatusWatch:
             raise _lib.MmkError("dICP: a source row reached the accumulation stage with a nearest-neighbour key that no search "
                                 "kernel wrote (MMK_ICP_STATUS_UNARMED_KEY) -- internal error, the poses of that call are invalid")
         if bad & ICP_STATUS_BAD_HYPER:
-            raise _lib.MmkError("dICP: a device-resident hyper-parameter of an ICP call (loss_fn['metric'], trim_dist or "
-                                "tanh_steepness given as a tensor) was non-finite or out of range: the metric must be > 0, "
-                                "trim_dist >= 0, the steepness > 0 (MMK_ICP_STATUS_BAD_HYPER); the poses of that call are what "
-                                "the arithmetic gave with it")
+            raise _lib.MmkError("dICP: a device-resident hyper-parameter of an ICP call (loss_fn['metric'], trim_dist, "
+                                "tanh_steepness or softmin_temp given as a tensor) was non-finite or out of range: the metric "
+                                "must be > 0, trim_dist >= 0, the steepness > 0, softmin_temp > 0 (MMK_ICP_STATUS_BAD_HYPER); "
+                                "the poses of that call are what the arithmetic gave with it")
         if bad:
             raise _lib.MmkError("dICP: the ICP kernels raised status bits 0x%x" % bad)
 
@@ -170,6 +181,22 @@ def _hyper_sizes(values, B):
     return per_pair if any_tensor else None
 
 
+def _temp_size(temp, B):
+    """Validate a tensor ``softmin_temp`` (shape (), (1,) or (B,), floating point) without touching the device.  Returns
+    whether the device array takes one value per pair."""
+    if tuple(temp.shape) not in ((), (1,), (B,)):
+        raise ValueError("softmin_temp must be a number or a tensor of shape (), (1,) or (B,) = (%d,) (got shape %s)"
+                         % (B, tuple(temp.shape)))
+    if not temp.is_floating_point():
+        raise ValueError("softmin_temp: a tensor must have a floating-point dtype (got %s)" % (temp.dtype,))
+    return temp.ndim == 1 and temp.shape[0] == B and B > 1
+
+
+def _temp_array(temp, per_pair, B, dev):
+    """(1 | B,) fp32 on the device; nothing is read back."""
+    return temp.detach().to(device=dev, dtype=torch.float32).reshape(-1).expand(B if per_pair else 1).contiguous()
+
+
 def _hyper_array(values, per_pair, B, dev):
     """(1 | B, 3) fp32 on the device: tensors moved / cast, numbers broadcast there; nothing is read back."""
     n = B if per_pair else 1
@@ -182,7 +209,8 @@ def _hyper_array(values, per_pair, B, dev):
     return torch.stack(cols, dim=1).contiguous()
 
 
-def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False, soft=None):
+def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False, soft=None, temp=None):
+    """``temp``: the (1 | B,) device temperature of a soft call (``per_pair`` then is its stride), mmk_icp_forward_soft_t."""
     L = _lib.lib()
     dev = src.device
     _status.check()
@@ -200,6 +228,9 @@ def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False, soft=None)
     if hyper is not None:
         entry = L.mmk_icp_forward_hp
         args += [_lib.ptr(hyper), 1 if per_pair else 0]
+    elif soft is not None and temp is not None:
+        entry = L.mmk_icp_forward_soft_t
+        args += [ctypes.byref(soft), _lib.ptr(temp), 1 if per_pair else 0]
     elif soft is not None:
         entry = L.mmk_icp_forward_soft
         args += [ctypes.byref(soft)]
@@ -208,12 +239,13 @@ def _forward(p, src, tgt, weight, T_init, hyper=None, per_pair=False, soft=None)
     return T_out, st, iters.value
 
 
-def _backward(ctx, grad_T, hyper, per_pair, need_h, soft=None):
+def _backward(ctx, grad_T, hyper, per_pair, need_h, soft=None, temp=None):
     """The reverse sweep of the autograd functions -> (gw, gT0, gs, gt, gh); ``hyper`` None: a call with numbers only,
     ``need_h``: a hyper-parameter gradient is asked for.  mmk_icp_backward on the cached workspace when neither a cloud nor
     a hyper-parameter is involved; else mmk_icp_backward_points (no ``hyper``) or mmk_icp_backward_hp, whose scratch holds
     per-point rows and fixed-point sums for the target as well and is sized per call, not cached.  ``soft``: the call had
-    soft correspondences -- mmk_icp_backward_soft, with or without the clouds."""
+    soft correspondences -- mmk_icp_backward_soft, with or without the clouds; with ``temp``, the device temperature,
+    mmk_icp_backward_soft_t, and gh is then (B,) = dL/dtau per pair when ``need_h``."""
     weight, src, tgt, idx, T_hist, delta, A, active = ctx.saved_tensors[:8]
     p = ctx.p
     L = _lib.lib()
@@ -227,7 +259,10 @@ def _backward(ctx, grad_T, hyper, per_pair, need_h, soft=None):
         ws = _workspace(L.mmk_icp_workspace_bytes(ctypes.byref(p)), dev)
         _lib.check(L.mmk_icp_backward(*state, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
         return gw, gT0, None, None, None
-    if soft is not None:
+    if soft is not None and temp is not None:
+        entry, nbytes = L.mmk_icp_backward_soft_t, L.mmk_icp_backward_soft_t_workspace_bytes(
+            state[0], ctypes.byref(soft), 1 if need_tgt else 0, 1 if need_h else 0)
+    elif soft is not None:
         entry, nbytes = L.mmk_icp_backward_soft, L.mmk_icp_backward_soft_workspace_bytes(state[0], ctypes.byref(soft), 1 if need_tgt else 0)
     elif hyper is None:
         entry, nbytes = L.mmk_icp_backward_points, L.mmk_icp_backward_points_workspace_bytes(state[0], 1 if need_tgt else 0)
@@ -236,10 +271,12 @@ def _backward(ctx, grad_T, hyper, per_pair, need_h, soft=None):
     ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
     gs = torch.empty(p.B, p.N, 3, dtype=torch.float32, device=dev) if need_src else None
     gt = torch.empty(p.B, p.M, p.tgt_cols, dtype=torch.float32, device=dev) if need_tgt else None
-    gh = torch.empty(p.B, 3, dtype=torch.float32, device=dev) if need_h else None
+    gh = torch.empty((p.B,) if temp is not None else (p.B, 3), dtype=torch.float32, device=dev) if need_h else None
     extra = [] if hyper is None else [_lib.ptr(hyper), 1 if per_pair else 0, _lib.ptr(gh)]
     if soft is not None:
         extra = [ctypes.byref(soft)]
+        if temp is not None:
+            extra += [_lib.ptr(temp), 1 if per_pair else 0, _lib.ptr(gh)]
     _lib.check(entry(*state, _lib.ptr(gs), _lib.ptr(gt), *extra, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
     return gw, gT0, gs, gt, gh
 
@@ -277,6 +314,33 @@ class _IcpSoftFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_T):
         return _backward(ctx, grad_T, None, False, False, soft=ctx.soft)[:4] + (None, None)
+
+
+class _IcpSoftTempFunction(torch.autograd.Function):
+    """_IcpSoftFunction with the temperature on the device (mmk_icp_forward_soft_t / mmk_icp_backward_soft_t): ``tau`` is
+    the tensor as given; when it requires grad it gets the pair sums of I7⁗ -- its own row each for a (B,) tensor, their
+    fp64 sum, rounded once, for a shared one."""
+
+    @staticmethod
+    def forward(ctx, weight, T_init, src, tgt, tau, p, soft, per_pair):
+        temp = _temp_array(tau, per_pair, p.B, src.device)
+        T_out, st, _ = _forward(p, src, tgt, weight, T_init, per_pair=per_pair, soft=soft, temp=temp)
+        _IcpFunction.last_active = st["active"]
+        ctx.p, ctx.soft, ctx.per_pair = p, soft, per_pair
+        ctx.meta = (tuple(tau.shape), tau.dtype, tau.device)
+        ctx.save_for_backward(weight, src, tgt, st["idx"], st["T"], st["delta"], st["A"], st["active"], temp)
+        return T_out
+
+    @staticmethod
+    def backward(ctx, grad_T):
+        need_t = ctx.needs_input_grad[4]
+        gw, gT0, gs, gt, gh = _backward(ctx, grad_T, None, ctx.per_pair, need_t, soft=ctx.soft, temp=ctx.saved_tensors[8])
+        gtau = None
+        if need_t:
+            shape, dtype, device = ctx.meta
+            g = gh if ctx.per_pair else gh.double().sum()       # a shared value: the sum over the pairs, rounded once
+            gtau = g.to(device=device, dtype=dtype).reshape(shape)
+        return gw, gT0, gs, gt, gtau, None, None, None
 
 
 class _IcpHpFunction(torch.autograd.Function):
@@ -382,7 +446,11 @@ class ICP:
         k, temp = self.softmin_k, self.softmin_temp
         if isinstance(k, bool) or not isinstance(k, int) or not 2 <= k <= 8:
             raise ValueError("dICP config: softmin_k must be an integer in 2..8 (got %r)" % (k,))
-        if isinstance(temp, (bool, torch.Tensor)) or not isinstance(temp, (int, float)) or not (0.0 < float(temp) < float("inf")):
+        if isinstance(temp, torch.Tensor):
+            # shape and dtype are validated against the call's B (_temp_size), the values on the device (the status flag);
+            # the struct carries a placeholder that passes its validation and is not read
+            return _lib.IcpSoft(k=k, temp=1.0) if self.correspondence == "softmin" else None
+        if isinstance(temp, bool) or not isinstance(temp, (int, float)) or not (0.0 < float(temp) < float("inf")):
             raise ValueError("dICP config: softmin_temp must be a finite number > 0 (got %r)" % (temp,))
         return _lib.IcpSoft(k=k, temp=float(temp)) if self.correspondence == "softmin" else None
 
@@ -425,6 +493,8 @@ class ICP:
         if soft is not None and per_pair is not None:
             raise ValueError("correspondence='softmin' does not combine with a tensor hyper-parameter (%s given as a tensor)"
                              % ", ".join(n for n, v in zip(HYPER_NAMES, values) if isinstance(v, torch.Tensor)))
+        tau = self.softmin_temp if soft is not None and isinstance(self.softmin_temp, torch.Tensor) else None
+        tau_per_pair = False if tau is None else _temp_size(tau, source.shape[0])
         if soft is not None and target.shape[1] < soft.k:
             raise ValueError("correspondence='softmin' needs a target of at least softmin_k = %d rows (got %d)"
                              % (soft.k, target.shape[1]))
@@ -452,14 +522,16 @@ class ICP:
             w = weight.to(device=dev, dtype=torch.float32).contiguous()
         need_grad = self.differentiable and torch.is_grad_enabled() and (
             (w is not None and w.requires_grad) or T0.requires_grad or src.requires_grad or tgt.requires_grad or
-            any(isinstance(v, torch.Tensor) and v.requires_grad for v in values))
+            any(isinstance(v, torch.Tensor) and v.requires_grad for v in values) or (tau is not None and tau.requires_grad))
         p = self._params(B, N, M, tgt.shape[-1], dim, loss_fn, trim_dist, save_state=need_grad, on_device=per_pair is not None)
         if soft is not None:
             p.nn_method = _lib.NN_METHODS["grid"]                   # the k-NN goes through the grid; nn_search is ignored
         if need_grad:
             if w is None:
                 w = torch.ones(B, N, dtype=torch.float32, device=dev)
-            if soft is not None:
+            if tau is not None:
+                T = _IcpSoftTempFunction.apply(w, T0, src, tgt, tau, p, soft, tau_per_pair)
+            elif soft is not None:
                 T = _IcpSoftFunction.apply(w, T0, src, tgt, p, soft)
             elif per_pair is None:
                 T = _IcpFunction.apply(w, T0, src, tgt, p)
@@ -469,7 +541,9 @@ class ICP:
         else:
             with torch.no_grad():
                 hyper = None if per_pair is None else _hyper_array(values, per_pair, B, dev)
-                T, st, iters = _forward(p, src, tgt, None if w is None else w.detach(), T0.detach(), hyper, bool(per_pair), soft)
+                temp = None if tau is None else _temp_array(tau, tau_per_pair, B, dev)
+                T, st, iters = _forward(p, src, tgt, None if w is None else w.detach(), T0.detach(), hyper,
+                                        bool(per_pair) if tau is None else tau_per_pair, soft, temp)
             self.last_state = st
             self.last_iterations = iters
         return {"T": T if T.device == out_device else T.to(out_device)}

@@ -126,13 +126,18 @@ class LearnICPWeightPolicy(nn.Module):
         # params["icp_correspondence"] / ["icp_softmin_k"] / ["icp_softmin_temp"] (absent upstream): the correspondences of the
         # TRAINING instance, "nearest" or the "softmin" over the k nearest target rows that the backward differentiates
         # (dICP/ICP.py); the inference instance keeps nearest correspondences.  Works with mask_target="scan" (that mode
-        # runs unweighted: the mask acts through the points); does not combine with learn_icp (tensor hyper-parameters).
+        # runs unweighted: the mask acts through the points); of learn_icp's names it combines with "softmin_temp" only (the
+        # other three are tensor hyper-parameters of the hard-correspondence entries).
         self.icp_correspondence = params.get("icp_correspondence", "nearest")
         if self.icp_correspondence not in ("nearest", "softmin"):
             raise ValueError("icp_correspondence must be 'nearest' or 'softmin' (got %r)" % (self.icp_correspondence,))
         learn = params.get("learn_icp", ()) or ()
-        if self.icp_correspondence == "softmin" and len((learn,) if isinstance(learn, str) else tuple(learn)) > 0:
+        learn = (learn,) if isinstance(learn, str) else tuple(learn)
+        if self.icp_correspondence == "softmin" and any(name != "softmin_temp" for name in learn):
             raise ValueError("icp_correspondence='softmin' does not combine with learn_icp (tensor hyper-parameters)")
+        if "softmin_temp" in learn and self.icp_correspondence != "softmin":
+            raise ValueError("learn_icp: 'softmin_temp' needs icp_correspondence='softmin': nearest correspondences have no "
+                             "temperature")
         if "icp_correspondence" in params:          # (absent: whatever the dICP configuration says, "nearest" by default)
             self.ICP_alg.correspondence = self.icp_correspondence
         if "icp_softmin_k" in params:
@@ -203,14 +208,17 @@ class LearnICPWeightPolicy(nn.Module):
         # the ICP becomes a scalar parameter (one value for the batch), read by the training instance on the device and
         # trained through the ICP's hyper-parameter gradients (dICP/ICP.py).  They start from icp_loss_fn["metric"],
         # icp_trim_dist and icp_tanh_steepness.  Nothing keeps a learned value in range: the ICP's status flag reports one
-        # that left it.
+        # that left it.  "softmin_temp" (with icp_correspondence="softmin", checked above): the soft-min temperature becomes
+        # the scalar parameter icp_softmin_temp_p, started from icp_softmin_temp and trained through the ICP's temperature
+        # gradient (DESIGN.md §3 I7⁗); the inference instance keeps nearest correspondences and never reads it.
         learn_icp = params.get("learn_icp", ())
         if isinstance(learn_icp, str):
             learn_icp = (learn_icp,)
         self.learn_icp = tuple(learn_icp)
         for name in self.learn_icp:
-            if name not in ("metric", "trim_dist", "tanh_steepness"):
-                raise ValueError("learn_icp: unknown name %r (choose from 'metric', 'trim_dist', 'tanh_steepness')" % (name,))
+            if name not in ("metric", "trim_dist", "tanh_steepness", "softmin_temp"):
+                raise ValueError("learn_icp: unknown name %r (choose from 'metric', 'trim_dist', 'tanh_steepness', 'softmin_temp')"
+                                 % (name,))
             if name in ("trim_dist", "tanh_steepness") and self.icp_trim != "tanh":
                 raise ValueError("learn_icp: %r needs icp_trim='tanh': the hard gate is a constant of the backward" % (name,))
             if name == "metric" and (self.icp_loss_fn is None or self.icp_loss_fn.get("name") not in ("cauchy", "huber")):
@@ -221,6 +229,8 @@ class LearnICPWeightPolicy(nn.Module):
             self.icp_trim_dist_p = nn.Parameter(torch.tensor(float(self.icp_trim_dist), dtype=torch.float32))
         if "tanh_steepness" in self.learn_icp:
             self.icp_tanh_steepness_p = nn.Parameter(torch.tensor(self.icp_tanh_steepness, dtype=torch.float32))
+        if "softmin_temp" in self.learn_icp:
+            self.icp_softmin_temp_p = nn.Parameter(torch.tensor(float(self.icp_softmin_temp), dtype=torch.float32))
 
     @property
     def global_minmax(self):
@@ -438,6 +448,8 @@ class LearnICPWeightPolicy(nn.Module):
             trim_dist = self.icp_trim_dist_p if self.training else self.icp_trim_dist_p.detach()
         if "tanh_steepness" in self.learn_icp and self.training:
             alg.tanh_steepness = self.icp_tanh_steepness_p
+        if "softmin_temp" in self.learn_icp and self.training:
+            alg.softmin_temp = self.icp_softmin_temp_p
         icp_result = alg.icp(scan_pc, map_pc, T_init=T_init, weight=weights, trim_dist=trim_dist,
                              loss_fn=loss_fn, dim=self.icp_dim)
         return icp_result["T"]
