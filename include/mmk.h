@@ -44,6 +44,8 @@ extern "C" {
 #define MMK_LOSS_NONE 0
 #define MMK_LOSS_CAUCHY 1
 #define MMK_LOSS_HUBER 2
+#define MMK_LOSS_GEMAN_MCCLURE 3 /* rho = c c, c = 1 / (1 + r2 / k^2) */
+#define MMK_LOSS_WELSCH 4        /* rho = exp(-(r2 / k^2))                              */
 
 int mmk_version(void);
 const char *mmk_last_error(void);
@@ -60,8 +62,10 @@ typedef struct {
     int32_t tgt_cols;   /* 3 (xyz) or 6 (xyz|normal): icp_weight_dataset.py:397-398 */
     int32_t dim;        /* 2 or 3 (reference passes dim=2)                        */
     int32_t icp_type;   /* MMK_ICP_PT2PT | MMK_ICP_PT2PL (ctor icp_type)          */
-    int32_t loss;       /* MMK_LOSS_* from loss_fn["name"]                        */
-    float loss_k;       /* loss_fn["metric"]                                      */
+    int32_t loss;       /* MMK_LOSS_* from loss_fn["name"]: none | cauchy | huber |
+                           geman_mcclure | welsch                                 */
+    float loss_k;       /* loss_fn["metric"]: the robust scale k, > 0 under every
+                           code but MMK_LOSS_NONE                                 */
     float trim_dist;    /* trim_dist (5.0 at icp_weight_policy.py:279)            */
     float tolerance;    /* ctor tolerance: a pair freezes once ||delta|| < tol    */
     int32_t max_iter;   /* ctor max_iterations (K)                                */

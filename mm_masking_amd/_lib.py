@@ -78,7 +78,7 @@ class UNetDesc(ctypes.Structure):
 FINAL_BWD_WS_FLOATS = 16384        # MMK_FINAL_BWD_WS_FLOATS of include/mmk.h
 NORM_MODES = {None: 0, "none": 0, "minmax": 1, "standardize": 2}      # MMK_NORM_* of include/mmk.h
 ICP_TYPES = {"pt2pt": 0, "pt2pl": 1}
-LOSSES = {None: 0, "none": 0, "l2": 0, "cauchy": 1, "huber": 2}
+LOSSES = {None: 0, "none": 0, "l2": 0, "cauchy": 1, "huber": 2, "geman_mcclure": 3, "welsch": 4}
 NN_METHODS = {"brute": 0, "grid": 1}
 
 

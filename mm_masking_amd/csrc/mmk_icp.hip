@@ -1204,6 +1204,11 @@ __device__ __forceinline__ void point_terms(PointTerms<DIM, TYPE> &t, const floa
     } else if (loss == MMK_LOSS_HUBER) {
         const float r = sqrtf(t.r2);
         rho = (r <= k) ? 1.f : k / r;
+    } else if (loss == MMK_LOSS_GEMAN_MCCLURE) {
+        const float c = 1.0f / (1.0f + t.r2 / k2);      // Cauchy's expression
+        rho = c * c;
+    } else if (loss == MMK_LOSS_WELSCH) {
+        rho = expf(-(t.r2 / k2));
     }
     t.rho = rho;
     t.omega = omega;
@@ -1878,17 +1883,27 @@ __global__ __launch_bounds__(ACC_THREADS) void icp_bwd_point_kernel(
             r2bar = rhobar * (-(t.rho * t.rho) / k2);
         } else if (loss == MMK_LOSS_HUBER) {
             if (sqrtf(t.r2) > k) r2bar = rhobar * (-t.rho / (2.f * t.r2));
+        } else if (loss == MMK_LOSS_GEMAN_MCCLURE) {    // rho = c c: c by the forward's expression
+            const float c = 1.0f / (1.0f + t.r2 / k2);
+            r2bar = rhobar * (-(2.f * (c * t.rho)) / k2);
+        } else if (loss == MMK_LOSS_WELSCH) {
+            r2bar = rhobar * (-t.rho / k2);
         }
 #pragma unroll
         for (int r = 0; r < NR; ++r) ebar[r] += 2.f * t.er[r] * r2bar;
         gw[(size_t)b * N + i] += gomega;
-        if constexpr (HP) {             // k̄ (I7''): rho = 1 / (1 + r2 / k2) | k / r past the knee
+        if constexpr (HP) {             // k̄ (I7''): rho = 1 / (1 + r2 / k2) | k / r past the knee | c c | exp(-(r2 / k2))
             float kbar = 0.f;
             if (loss == MMK_LOSS_CAUCHY) {
                 kbar = rhobar * ((2.f * t.r2 * (t.rho * t.rho)) / (k * k2));
             } else if (loss == MMK_LOSS_HUBER) {
                 const float r = sqrtf(t.r2);
                 if (r > k) kbar = rhobar / r;
+            } else if (loss == MMK_LOSS_GEMAN_MCCLURE) {
+                const float c = 1.0f / (1.0f + t.r2 / k2);
+                kbar = rhobar * ((4.f * t.r2 * (c * t.rho)) / (k * k2));
+            } else if (loss == MMK_LOSS_WELSCH) {
+                kbar = rhobar * ((2.f * t.r2 * t.rho) / (k * k2));
             }
             acc[NP + 0] = (double)kbar;
         }
@@ -2303,7 +2318,7 @@ int check_params(const mmk_icp_params *p)
     MMK_REQUIRE(p->tgt_cols == 3 || p->tgt_cols == 6, "mmk_icp: target must have 3 or 6 columns (got %d)", p->tgt_cols);
     MMK_REQUIRE(p->icp_type == MMK_ICP_PT2PT || p->icp_type == MMK_ICP_PT2PL, "mmk_icp: bad icp_type %d", p->icp_type);
     MMK_REQUIRE(p->icp_type != MMK_ICP_PT2PL || p->tgt_cols == 6, "mmk_icp: pt2pl needs target normals (B,M,6)");
-    MMK_REQUIRE(p->loss >= MMK_LOSS_NONE && p->loss <= MMK_LOSS_HUBER, "mmk_icp: bad loss %d", p->loss);
+    MMK_REQUIRE(p->loss >= MMK_LOSS_NONE && p->loss <= MMK_LOSS_WELSCH, "mmk_icp: bad loss %d", p->loss);
     MMK_REQUIRE(p->max_iter >= 1, "mmk_icp: max_iter must be >= 1");
     MMK_REQUIRE(p->loss == MMK_LOSS_NONE || p->loss_k > 0.f, "mmk_icp: loss metric must be > 0");
     MMK_REQUIRE(p->nn_method == MMK_NN_BRUTE || p->nn_method == MMK_NN_GRID, "mmk_icp: bad nn_method %d", p->nn_method);

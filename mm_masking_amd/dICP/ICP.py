@@ -7,8 +7,12 @@ Keeps the call contract the reference relies on
         max_iterations=int, tolerance=float)
     .target_pad_val
     .icp(source (B,N,3), target (B,M,6|3), T_init=(B,4,4), weight=(B,N),
-         trim_dist=5.0, loss_fn={"name": "cauchy"|"huber", "metric": k}, dim=2|3)
+         trim_dist=5.0, loss_fn={"name": "cauchy"|"huber"|"geman_mcclure"|"welsch", "metric": k}, dim=2|3)
         -> {"T": (B,4,4)}
+
+``geman_mcclure`` (rho = c c, c = 1 / (1 + r2 / k^2)) and ``welsch`` (rho = exp(-(r2 / k^2))) are absent upstream: the two
+strongly redescending kernels.  They go through every path Cauchy and Huber have, and their metric
+may be a number or a tensor like Cauchy's (below).
 
 pt2pl takes its normals from the target's columns 3..5; with ``parameters.target_normals:
 estimate`` in the YAML an xyz-only target gets them from ``normals.estimate_normals`` per call.
@@ -42,7 +46,7 @@ is bit-identical to it.  Each tensor that requires grad gets its gradient in its
 value the sum over the pairs -- and ``T`` requires grad when one of them does.  The hard gate gives ``trim_dist`` and the
 steepness exactly 0, no robust loss gives the metric exactly 0.  A tensor cannot be validated on the host without a
 synchronisation: the kernels raise ``MMK_ICP_STATUS_BAD_HYPER`` for a value the call uses that is non-finite or out of
-range (metric > 0 under Cauchy / Huber, trim_dist >= 0, steepness > 0 under the tanh gate), and the next ICP call, or
+range (metric > 0 under a robust loss, trim_dist >= 0, steepness > 0 under the tanh gate), and the next ICP call, or
 ``check_errors()``, turns it into an MmkError.  Nothing here keeps a learned value in range, and ``tolerance`` and
 ``target_pad_val`` get no gradient.
 

@@ -221,8 +221,10 @@ class LearnICPWeightPolicy(nn.Module):
                                  % (name,))
             if name in ("trim_dist", "tanh_steepness") and self.icp_trim != "tanh":
                 raise ValueError("learn_icp: %r needs icp_trim='tanh': the hard gate is a constant of the backward" % (name,))
-            if name == "metric" and (self.icp_loss_fn is None or self.icp_loss_fn.get("name") not in ("cauchy", "huber")):
-                raise ValueError("learn_icp: 'metric' needs a robust loss (icp_loss_fn name 'cauchy' or 'huber')")
+            if name == "metric" and (self.icp_loss_fn is None or self.icp_loss_fn.get("name") not in
+                                     ("cauchy", "huber", "geman_mcclure", "welsch")):
+                raise ValueError("learn_icp: 'metric' needs a robust loss (icp_loss_fn name 'cauchy', 'huber', "
+                                 "'geman_mcclure' or 'welsch')")
         if "metric" in self.learn_icp:
             self.icp_metric = nn.Parameter(torch.tensor(float(self.icp_loss_fn.get("metric", 1.0)), dtype=torch.float32))
         if "trim_dist" in self.learn_icp:
