@@ -1,8 +1,8 @@
 """GPU: the HIP dICP with its robust scale k, trim distance and steepness on the device, one value for the batch or one per
 pair, and their gradients (mmk_icp_forward_hp / mmk_icp_backward_hp; DESIGN.md §3 I3'', I7'') against the restatement
-tests/dicp_hyper_ref.py.
+tests/dicp_restatement.py.
 
-Shapes, cases and replay discipline are those of tests/test_gpu_soft_trim.py (imported from it): B = 2, 300 + 20 source rows,
+Shapes, cases and replay discipline are those of tests/dicp_cases.py (imported from it): B = 2, 300 + 20 source rows,
 700 + 30 target rows, K = 4, trim_dist 0.6, both NN engines; the reference replays the device's idx_hist.  In the per-pair
 runs pair 1 uses k x 1.3, trim_dist x 1.15, steepness x 0.8.
 
@@ -12,9 +12,9 @@ the "is this gradient awake" condition of each parameter is made of it -- max_b 
 magnitudes of pair b's contributions -- next to the soft-trim test's own conditions (band share, Huber past its knee, no pair
 frozen).  All are asserted on the reference's values and printed.
 
-Tolerances: pose 2e-6 absolute, gradients 2e-3 of the reference's largest magnitude per parameter (``_close`` of the soft-trim
-test).  Equalities are exact: tensors holding the values of a float call give that call's bits; a shared value's gradient is
-the fp32 rounding of the fp64 sum of the pairs' gradients; the hard gate gives trim_dist and the steepness 0, no robust loss
+Tolerances: pose 2e-6 absolute, gradients 2e-3 of the reference's largest magnitude per parameter (``close`` of
+tests/dicp_cases.py).  Equalities are exact: tensors holding the values of a float call give that call's bits; a shared value's
+gradient is the fp32 rounding of the fp64 sum of the pairs' gradients; the hard gate gives trim_dist and the steepness 0, no robust loss
 gives k 0, a pair's frozen iterations add 0; two runs agree in every bit.
 
 Measured on an MI355X (both engines, all cases): pose within 2.4e-7 of the replay; gradients within 9.5e-6 of the reference's
@@ -29,89 +29,25 @@ from mm_masking_amd import _lib
 from mm_masking_amd.dICP.ICP import ICP, check_errors
 
 import icp_freeze_cases as fz
-from dicp_hyper_ref import ICPHyperRef
-from test_gpu_soft_trim import (B, CASES, DEV, IDS, K, N, NAMES, TOL, TRIM, _assert_gate_is_awake, _close, _inputs,
-                                nn_engine)  # noqa: F401
+from dicp_cases import (B, GATE_CASES as CASES, GATE_IDS as IDS, GATE_TRIM as TRIM, HNAMES, K, MULT, NAMES, TOL, assert_gate_awake,
+                        assert_hyper_awake, close, gpu, inputs, nn_engine, reference, same)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
 
-HNAMES = ("k", "trim_dist", "trim_steep")
-MULT = (1.3, 1.15, 0.8)             # pair 1's values over pair 0's
 ALL7 = NAMES + HNAMES
 
 
 def _values(case, per_pair):
     """(k, trim_dist, steepness) of a case as floats (pair 0's) and as fp32 tensors: (B,) with pair 1 scaled, or equal."""
-    k = 1.0 if case[1] is None else case[1][1]
-    base = (k, TRIM, case[4])
+    base = (1.0 if case[1] is None else case[1][1], TRIM, case[4])
     m = MULT if per_pair else (1.0, 1.0, 1.0)
     return base, [torch.tensor([v, v * mm], dtype=torch.float32) for v, mm in zip(base, m)]
 
 
-def _loss_fn(case, metric):
-    """The case's loss with ``metric``; a case without a robust loss still hands the metric over (name "l2": rho = 1)."""
-    return {"name": "l2" if case[1] is None else case[1][0], "metric": metric}
-
-
-def _gpu(case, inp, hyper, need=ALL7, gate="tanh", K_=K, tol=TOL):
-    """One forward + backward.  ``hyper``: (k, trim_dist, steepness), each a float or a CPU tensor (moved to the device and,
-    if named in ``need``, requiring grad)."""
-    icp = ICP(icp_type=case[0], differentiable=True, max_iterations=K_, tolerance=tol)
-    h = [v.clone().to(DEV).requires_grad_(n in need) if isinstance(v, torch.Tensor) else v for n, v in zip(HNAMES, hyper)]
-    icp.trim, icp.tanh_steepness = gate, h[2]
-    x = [v.clone().to(DEV).requires_grad_(name in need) for name, v in zip(NAMES, inp["x"])]
-    T = icp.icp(x[0], x[1], T_init=x[3], weight=x[2], trim_dist=h[1], loss_fn=_loss_fn(case, h[0]), dim=case[2])["T"]
-    saved = T.grad_fn.saved_tensors                 # weight, src, tgt, idx, T_hist, delta, A, active(, hyper)
-    (T * inp["G"].to(DEV)).sum().backward()
-    torch.cuda.synchronize()
-    grads = {name: (v.grad.cpu() if v.grad is not None else None) for name, v in zip(NAMES, x)}
-    for n, v in zip(HNAMES, h):
-        grads[n] = v.grad.cpu() if isinstance(v, torch.Tensor) and v.grad is not None else None
-        if grads[n] is not None:
-            assert grads[n].shape == v.shape and v.grad.dtype == v.dtype and v.grad.device == v.device
-    return {"T": T.detach().cpu(), "idx": saved[3].cpu(), "active": saved[7].cpu(), "grads": grads, "fn": type(T.grad_fn).__name__}
-
-
-def _same(a, b, names):
-    assert torch.equal(a["T"], b["T"]) and torch.equal(a["idx"], b["idx"]) and torch.equal(a["active"], b["active"])
-    for name in names:
-        assert torch.equal(a["grads"][name], b["grads"][name]), name
-
-
-_ref_cache = {}
-
-
-def _reference(ci, inp, idx_hist):
-    """Autograd through the fp32 restatement replaying ``idx_hist`` with the per-pair values as (B,N) leaves; once per key."""
-    key = (ci, idx_hist.numpy().tobytes())
-    if key not in _ref_cache:
-        case = CASES[ci]
-        _, vals = _values(case, True)
-        leaves = [v.clone().requires_grad_(True) for v in inp["x"]]
-        hl = [v[:, None].expand(B, N).contiguous().requires_grad_(True) for v in vals]
-        ref = ICPHyperRef(case[0], differentiable=True, max_iterations=K, tolerance=TOL, soft=True)
-        out = ref.icp(leaves[0], leaves[1], T_init=leaves[3], weight=leaves[2], k=hl[0], trim_dist=hl[1], trim_steep=hl[2],
-                      loss_name=None if case[1] is None else case[1][0], dim=case[2], fixed_idx=[idx_hist[k].long() for k in range(K)])
-        (out["T"] * inp["G"]).sum().backward()
-        grads = {name: v.grad for name, v in zip(NAMES, leaves)}
-        points = {n: (v.grad.double() if v.grad is not None else None) for n, v in zip(HNAMES, hl)}
-        for n in HNAMES:
-            grads[n] = None if points[n] is None else points[n].sum(1)
-        _ref_cache[key] = {"T": out["T"].detach(), "hist": out["hist"], "num_iter": out["num_iter"], "grads": grads, "points": points}
-    return _ref_cache[key]
-
-
-def _assert_hyper_is_awake(ci, ref):
-    """No parameter's gradient is the rounding noise of a cancellation: for each, some pair's |g_b| is at least 0.03 of the
-    sum of the magnitudes of its per-point contributions."""
-    for n in HNAMES:
-        p = ref["points"][n]
-        if p is None:
-            assert n == "k" and CASES[ci][1] is None
-            continue
-        ratios = (p.sum(1).abs() / p.abs().sum(1)).tolist()
-        print("AWAKE %-10s |g_b| / S_b per pair: %s" % (n, ["%.3f" % r for r in ratios]))
-        assert max(ratios) >= 0.03, (n, ratios)
+def _gpu(case, inp, hyper, need=ALL7, gate="tanh", **kw):
+    """One forward + backward.  ``hyper``: (k, trim_dist, steepness), each a float or a CPU tensor."""
+    return gpu(case, inp, hyper[1], need=need, gate=gate, k=hyper[0], steep=hyper[2], **kw)
 
 
 # ----------------------------------------------------------------------------- 1. same values, same bits
@@ -119,7 +55,7 @@ def _assert_hyper_is_awake(ci, ref):
 @pytest.mark.parametrize("ci", range(len(CASES)), ids=IDS)
 def test_tensors_with_a_float_calls_values_give_its_bits(nn_engine, ci, gate):
     case = CASES[ci]
-    inp = _inputs(case)
+    inp = inputs(case)
     base, vals = _values(case, False)
     for need in (NAMES, ("weight", "T_init")):                  # both backward shapes
         plain = _gpu(case, inp, base, need=need, gate=gate)
@@ -129,7 +65,7 @@ def test_tensors_with_a_float_calls_values_give_its_bits(nn_engine, ci, gate):
             for with_grad in (need, need + HNAMES):
                 got = _gpu(case, inp, hyper, need=with_grad, gate=gate)
                 assert got["fn"] == "_IcpHpFunctionBackward"
-                _same(got, plain, need)
+                same(got, plain, need)
                 assert all(got["grads"][n] is None for n in NAMES if n not in need)
 
 
@@ -137,13 +73,13 @@ def test_tensors_with_a_float_calls_values_give_its_bits(nn_engine, ci, gate):
 @pytest.mark.parametrize("ci", range(len(CASES)), ids=IDS)
 def test_per_pair_values_match_the_restatement(nn_engine, ci):
     case = CASES[ci]
-    inp = _inputs(case)
+    inp = inputs(case)
     _, vals = _values(case, True)
     run = _gpu(case, inp, vals)
     assert run["active"][:K].all()
-    ref = _reference(ci, inp, run["idx"])
-    _assert_gate_is_awake(ci, ref)
-    _assert_hyper_is_awake(ci, ref)
+    ref = reference(case, TRIM, fixed_idx=run["idx"], mult=MULT)
+    assert_gate_awake(case, ref)
+    assert_hyper_awake(case, ref)
     err = (run["T"].double() - ref["T"].double()).abs().max().item()
     print("POSE max abs diff = %.3e" % err)
     np.testing.assert_allclose(run["T"].numpy(), ref["T"].numpy(), atol=2e-6, rtol=0)
@@ -154,10 +90,10 @@ def test_per_pair_values_match_the_restatement(nn_engine, ci):
             assert ref["grads"][name] is None and g.shape == (B,) and (g == 0).all()       # 4. no robust loss: exactly 0
             continue
         assert g.shape == ref["grads"][name].shape
-        _close(g, ref["grads"][name], name)
+        close(g, ref["grads"][name], name)
     # the other backward shape (no cloud requires grad): the same hyper-parameter gradients, bit for bit
     two = _gpu(case, inp, vals, need=("weight", "T_init") + HNAMES)
-    _same(two, run, ("weight", "T_init") + HNAMES)
+    same(two, run, ("weight", "T_init") + HNAMES)
     # a parameter alone, the others numbers of pair 0: still its own (B,) gradient
     base, _ = _values(case, False)
     if case[1] is not None:
@@ -168,7 +104,7 @@ def test_per_pair_values_match_the_restatement(nn_engine, ci):
     per = _gpu(case, inp, equal)
     for shape in ((), (1,)):
         shared = _gpu(case, inp, [v[0].reshape(shape) for v in equal])
-        _same(shared, per, NAMES)
+        same(shared, per, NAMES)
         for n in HNAMES:
             want = per["grads"][n].double().sum().float()
             assert shared["grads"][n].shape == shape and torch.equal(shared["grads"][n].reshape(()), want), n
@@ -180,7 +116,7 @@ def test_per_pair_values_match_the_restatement(nn_engine, ci):
         assert hard["grads"]["k"].abs().min() > 0
     # 5. run to run, all seven
     again = _gpu(case, inp, vals)
-    _same(again, run, ALL7)
+    same(again, run, ALL7)
 
 
 # ----------------------------------------------------------------------------- 4. a frozen pair's frozen iterations
@@ -216,7 +152,7 @@ def test_frozen_iterations_contribute_exactly_zero(nn_engine, gate):
 # ----------------------------------------------------------------------------- 6. the status bit
 def test_bad_value_on_the_device_raises_the_status_bit_and_nothing_else():
     case = CASES[0]
-    inp = _inputs(case)
+    inp = inputs(case)
     base, _ = _values(case, False)
     check_errors(wait=True)
     icp = ICP(icp_type=case[0], differentiable=False, max_iterations=2, tolerance=TOL)

@@ -1,12 +1,11 @@
 """GPU: the Geman-McClure and Welsch kernels of the HIP dICP (MMK_LOSS_GEMAN_MCCLURE, MMK_LOSS_WELSCH; DESIGN.md §3 I3, I7,
-I7'') through every path Cauchy and Huber have, against the restatement tests/dicp_robust_ref.py: nearest correspondences on
+I7'') through every path Cauchy and Huber have, against the restatement tests/dicp_restatement.py: nearest correspondences on
 both NN engines and both backward shapes, the device-resident scale and its gradient, soft correspondences with the
 temperature a number and a tensor, the stand-alone accumulate stage, the status bit and the policy.
 
-Shapes, inputs and ``_close`` are those of tests/test_gpu_softmin.py (imported from it): B = 2, 300 + 20 zero source rows (one
-full and one partial 256-thread block), 700 + 30 target_pad_val rows, K = 4, T_init shifted by 0.2 m, trim_dist 1.0; the
-launch helpers are those of tests/test_gpu_softmin.py (numbers), tests/test_gpu_icp_hyper.py (tensor hyper-parameters) and
-tests/test_gpu_softmin_temp.py (a tensor temperature).  In the per-pair runs pair 1 uses k x 1.3.
+Shapes, inputs, ``close`` and the launch helper ``gpu`` are those of tests/dicp_cases.py (imported from it): B = 2, 300 + 20
+zero source rows (one full and one partial 256-thread block), 700 + 30 target_pad_val rows, K = 4, T_init shifted by 0.2 m,
+trim_dist 1.0.  In the per-pair runs pair 1 uses k x 1.3.
 
 The reference REPLAYS the device's idx_hist: device and host expf may differ in the last bit, and a flipped near-tie of a later
 search must not turn that into a failure.  idx_hist[0], found before any rho is evaluated, is compared bit for bit with the
@@ -46,103 +45,13 @@ import torch
 from mm_masking_amd import _lib
 from mm_masking_amd.dICP.ICP import ICP, check_errors
 
-from dicp_robust_ref import ICPRobustRef, per_point_terms
-from dicp_softmin_ref import knn_ref_batch
-from oracle.dicp_ref import transform_points
-from test_gpu_icp_hyper import _gpu as _gpu_hp
-from test_gpu_softmin import (B, DEV, K, M, M_REAL, N, N_REAL, NAMES, TAU, TOL, TRIM, _close, _inputs, _soft,
-                              nn_engine)  # noqa: F401
-from test_gpu_softmin import _gpu as _gpu_number
-from test_gpu_softmin_temp import _gpu as _gpu_tau
+from dicp_cases import (B, HARD_STEEP, K, M, M_REAL, N, N_REAL, NAMES, PER_PAIR_TAU, REAL, ROBUST_CASES as CASES, ROBUST_IDS as IDS,
+                        ROBUST_TRIM as TRIM, K_MULT, TAU, TOL, assert_awake, close, first_neighbours, gpu, inputs, nn_engine,
+                        reference, same)  # noqa: F401
+from dicp_restatement import per_point_terms
 
 pytestmark = pytest.mark.gpu
-
-#        type     loss (k)                  dim noise tanh steepness (0: the hard gate)
-CASES = [("pt2pt", ("geman_mcclure", 0.5), 2, 0.01, 0.0),
-         ("pt2pl", ("welsch", 0.2), 2, 0.15, 0.0),
-         ("pt2pt", ("welsch", 0.5), 3, 0.01, 0.0),
-         ("pt2pl", ("geman_mcclure", 0.5), 3, 0.15, 0.0),
-         ("pt2pl", ("geman_mcclure", 0.2), 2, 0.15, 4.0),
-         ("pt2pt", ("welsch", 0.5), 2, 0.01, 4.0)]
-IDS = ["%s-%s-d%d%s" % (c[0], c[1][0], c[2], "-tanh" if c[4] else "") for c in CASES]
-K_MULT = 1.3                        # pair 1's scale over pair 0's in the per-pair runs
-PER_PAIR_TAU = (0.25, 0.4)
-HARD_STEEP = 10.0                   # the instance's default steepness: not read under the hard gate
-
-
-def k_values(case, per_pair):
-    """(k of pair 0, k of pair 1) as an fp32 tensor."""
-    k0 = case[1][1]
-    return torch.tensor([k0, k0 * K_MULT if per_pair else k0], dtype=torch.float32)
-
-
-def bn_leaf(values):
-    """(B,) values -> a (B,N) leaf: its gradient is every point's contribution to its pair's sum."""
-    return values.to(torch.float32)[:, None].expand(B, N).contiguous().requires_grad_(True)
-
-
-def reference(case, inp, ks, fixed_idx=None, soft_k=None, taus=None, hyper_leaves=False, differentiable=True):
-    """Autograd through the fp32 restatement: nearest correspondences, or soft ones over ``soft_k`` rows with the per-pair
-    temperatures ``taus``; ``fixed_idx`` (K, ...) is replayed, None runs free.  ``hyper_leaves``: trim_dist and the steepness
-    are (B,N) leaves too (the tanh cases)."""
-    icp_type, (name, _), dim, _, steep = case
-    leaves = [v.clone().requires_grad_(differentiable) for v in inp["x"]]
-    kl = bn_leaf(ks)
-    hl = {"k": kl}
-    trim, st = TRIM, (steep if steep > 0 else HARD_STEEP)
-    if hyper_leaves:
-        hl["trim_dist"], hl["trim_steep"] = bn_leaf(torch.full((B,), TRIM)), bn_leaf(torch.full((B,), steep))
-        trim, st = hl["trim_dist"], hl["trim_steep"]
-    ref = ICPRobustRef(icp_type, differentiable=differentiable, max_iterations=K, tolerance=TOL, soft=steep > 0)
-    kw = dict(T_init=leaves[3], weight=leaves[2], k=kl, trim_dist=trim, trim_steep=st, loss_name=name, dim=dim,
-              fixed_idx=None if fixed_idx is None else [fixed_idx[it].long() for it in range(K)])
-    if soft_k is None:
-        out = ref.icp(leaves[0], leaves[1], **kw)
-    else:
-        hl["tau"] = bn_leaf(torch.tensor(taus))
-        out = ref.icp_soft(leaves[0], leaves[1], hl["tau"], softmin_k=soft_k, **kw)
-    res = {"T": out["T"].detach(), "hist": out["hist"], "num_iter": out["num_iter"]}
-    if differentiable:
-        (out["T"] * inp["G"]).sum().backward()
-        res["grads"] = {n: v.grad for n, v in zip(NAMES, leaves)}
-        res["points"] = {n: v.grad.double() for n, v in hl.items()}
-        for n, p in res["points"].items():
-            res["grads"][n] = p.sum(1)
-    return res
-
-
-_ref_cache = {}
-
-
-def _reference(ci, inp, idx_hist, ks, **kw):
-    """``reference`` replaying ``idx_hist``; computed once per key and left unchanged."""
-    key = (ci, tuple(ks.tolist()), idx_hist.numpy().tobytes(), tuple(sorted((k, str(v)) for k, v in kw.items())))
-    if key not in _ref_cache:
-        _ref_cache[key] = reference(CASES[ci], inp, ks, fixed_idx=idx_hist, **kw)
-    return _ref_cache[key]
-
-
-def awake_figures(ref):
-    """(smallest band share over the iterations, the scale's awake ratio per pair, smallest step norm) of a reference run."""
-    real = torch.zeros(B, N, dtype=torch.bool)
-    real[:, :N_REAL] = True
-    h = ref["hist"]
-    shares = [float(((kp > 0.5) & (rho > 0.05) & (rho < 0.95))[real].double().mean()) for kp, rho in zip(h["keep"], h["rho"])]
-    p = ref["points"]["k"]
-    ratios = (p.sum(1).abs() / p.abs().sum(1)).tolist()
-    step = min(float(d.norm(dim=1).min()) for d in h["delta"])
-    return shares, ratios, step
-
-
-def assert_awake(ref, what):
-    """No case passes with a pair frozen, the kernel off or saturated, or the scale's gradient asleep."""
-    assert ref["num_iter"] == K and all(bool(a.all()) for a in ref["hist"]["active"]), what      # no pair froze
-    shares, ratios, step = awake_figures(ref)
-    print("AWAKE %s: band share per iteration %s, |g_b| / S_b per pair %s, smallest step %.4f"
-          % (what, ["%.2f" % s for s in shares], ["%.3f" % r for r in ratios], step))
-    assert min(shares) >= 0.30, (what, shares)
-    assert max(ratios) >= 0.03, (what, ratios)
-    return shares, ratios, step
+DEV = torch.device("cuda:0")
 
 
 def _pose(run, ref):
@@ -151,15 +60,19 @@ def _pose(run, ref):
     np.testing.assert_allclose(run["T"].numpy(), ref["T"].numpy(), atol=2e-6, rtol=0)
 
 
-def _same(a, b, names):
-    assert torch.equal(a["T"], b["T"]) and torch.equal(a["idx"], b["idx"]) and torch.equal(a["active"], b["active"])
-    for name in names:
-        assert torch.equal(a["grads"][name], b["grads"][name]), name
+def k_values(case, per_pair):
+    """(k of pair 0, k of pair 1) as an fp32 tensor."""
+    k0 = case[1][1]
+    return torch.tensor([k0, k0 * K_MULT if per_pair else k0], dtype=torch.float32)
+
+
+def _gpu_hp(case, inp, hyper, need, gate):
+    return gpu(case, inp, hyper[1], need=need, gate=gate, k=hyper[0], steep=hyper[2])
 
 
 def _hyper(case, ks, tensors):
-    """The (k, trim_dist, steepness) triple and the gate of tests/test_gpu_icp_hyper.py's launch helper; ``tensors``: trim_dist
-    and the steepness as (B,) tensors of the case's values (the tanh cases)."""
+    """The (k, trim_dist, steepness) triple and the gate of a launch with the scale on the device; ``tensors``: trim_dist and
+    the steepness as (B,) tensors of the case's values (the tanh cases)."""
     steep = case[4]
     if steep > 0:
         if tensors:
@@ -173,21 +86,21 @@ def _hyper(case, ks, tensors):
 def test_nearest_matches_the_restatement(nn_engine, ci):
     case = CASES[ci]
     icp_type, _, dim, _, _ = case
-    inp = _inputs(case)
-    run = _gpu_number(case, inp)                                 # all four: mmk_icp_backward_points
+    inp = inputs(case)
+    run = gpu(case, inp, TRIM)                                 # all four: mmk_icp_backward_points
     assert run["fn"].startswith("_IcpFunction") and tuple(run["idx"].shape) == (K, B, N) and run["active"][:K].all()
-    free = reference(case, inp, k_values(case, False), differentiable=False)
+    free = reference(case, TRIM, differentiable=False)
     assert torch.equal(run["idx"][0].long(), free["hist"]["idx"][0].long())
-    ref = _reference(ci, inp, run["idx"], k_values(case, False))
+    ref = reference(case, TRIM, fixed_idx=run["idx"])
     assert_awake(ref, "%s nearest" % IDS[ci])
     _pose(run, ref)
     for name in NAMES:
-        _close(run["grads"][name], ref["grads"][name], name)
-    two = _gpu_number(case, inp, need=("weight", "T_init"))     # without the clouds: mmk_icp_backward
+        close(run["grads"][name], ref["grads"][name], name)
+    two = gpu(case, inp, TRIM, need=("weight", "T_init"))     # without the clouds: mmk_icp_backward
     assert torch.equal(two["T"], run["T"]) and torch.equal(two["idx"], run["idx"])
     assert two["grads"]["source"] is None and two["grads"]["target"] is None
     for name in ("weight", "T_init"):
-        _close(two["grads"][name], ref["grads"][name], name + " (no clouds)")
+        close(two["grads"][name], ref["grads"][name], name + " (no clouds)")
     # structural zeros
     gs, gt, gw = run["grads"]["source"], run["grads"]["target"], run["grads"]["weight"]
     if dim == 2:
@@ -203,8 +116,8 @@ def test_nearest_matches_the_restatement(nn_engine, ci):
     assert (gs[:, N_REAL:] == 0).all()                                           # zero-weight rows
     assert torch.isfinite(gw).all() and torch.isfinite(gt).all() and torch.isfinite(gs).all()
     # run to run
-    again = _gpu_number(case, inp)
-    _same(again, run, NAMES)
+    again = gpu(case, inp, TRIM)
+    same(again, run, NAMES)
 
 
 # ----------------------------------------------------------------------------- 2. the scale on the device
@@ -212,13 +125,13 @@ def test_nearest_matches_the_restatement(nn_engine, ci):
 def test_device_scale_and_its_gradient(ci):
     case = CASES[ci]
     tanh = case[4] > 0
-    inp = _inputs(case)
+    inp = inputs(case)
     # a (B,) tensor with the number call's values gives the number call's bits
-    plain = _gpu_number(case, inp)
+    plain = gpu(case, inp, TRIM)
     hyper, gate = _hyper(case, k_values(case, False), False)
     per = _gpu_hp(case, inp, hyper, need=NAMES + ("k",), gate=gate)
     assert per["fn"] == "_IcpHpFunctionBackward"
-    _same(per, plain, NAMES)
+    same(per, plain, NAMES)
     # per-pair values against the restatement, the metric's gradient included; under the tanh gate trim_dist's and the
     # steepness's too
     ks = k_values(case, True)
@@ -226,23 +139,23 @@ def test_device_scale_and_its_gradient(ci):
     need = NAMES + (("k", "trim_dist", "trim_steep") if tanh else ("k",))
     run = _gpu_hp(case, inp, hyper, need=need, gate=gate)
     assert run["active"][:K].all() and not torch.equal(run["T"][1], plain["T"][1])
-    ref = _reference(ci, inp, run["idx"], ks, hyper_leaves=tanh)
+    ref = reference(case, TRIM, fixed_idx=run["idx"], mult=(K_MULT, 1.0, 1.0))
     assert_awake(ref, "%s per-pair k" % IDS[ci])
     _pose(run, ref)
     for name in need:
         assert run["grads"][name].shape == ref["grads"][name].shape
-        _close(run["grads"][name], ref["grads"][name], name)
+        close(run["grads"][name], ref["grads"][name], name)
     two = _gpu_hp(case, inp, hyper, need=("weight", "T_init", "k"), gate=gate)      # the other backward shape
-    _same(two, run, ("weight", "T_init", "k"))
+    same(two, run, ("weight", "T_init", "k"))
     # a shared value gets the fp32 rounding of the fp64 sum of the pairs' rows
     want = per["grads"]["k"].double().sum().float()
     for shape in ((), (1,)):
         hyper, gate = _hyper(case, k_values(case, False)[0].reshape(shape), False)
         shared = _gpu_hp(case, inp, hyper, need=NAMES + ("k",), gate=gate)
-        _same(shared, per, NAMES)
+        same(shared, per, NAMES)
         assert shared["grads"]["k"].shape == shape and torch.equal(shared["grads"]["k"].reshape(()), want)
     again = _gpu_hp(case, inp, _hyper(case, ks, True)[0], need=need, gate=gate)
-    _same(again, run, need)
+    same(again, run, need)
 
 
 # ----------------------------------------------------------------------------- 3. soft correspondences
@@ -250,41 +163,38 @@ def test_device_scale_and_its_gradient(ci):
 @pytest.mark.parametrize("ci", range(len(CASES)), ids=IDS)
 def test_soft_correspondences_match_the_restatement(ci, k):
     case = CASES[ci]
-    dim = case[2]
-    inp = _inputs(case)
-    ks = k_values(case, False)
-    p = torch.stack(transform_points(inp["x"][0], inp["x"][3], dim), dim=-1)
-    free0 = torch.from_numpy(knn_ref_batch(p.numpy(), inp["x"][1][..., :dim].numpy(), k, dim)[0])
+    inp = inputs(case)
+    free0 = first_neighbours(case, k)
     # tau a number
-    run = _gpu_number(case, inp, configure=_soft(k))
+    run = gpu(case, inp, TRIM, softmin_k=k)
     assert run["fn"].startswith("_IcpSoftFunction") and tuple(run["idx"].shape) == (K, B, N, k) and run["active"][:K].all()
     assert torch.equal(run["idx"][0].long(), free0)
-    ref = _reference(ci, inp, run["idx"], ks, soft_k=k, taus=(TAU, TAU))
+    ref = reference(case, TRIM, fixed_idx=run["idx"], soft_k=k)
     assert_awake(ref, "%s softmin k=%d tau=%g" % (IDS[ci], k, TAU))
     _pose(run, ref)
     for name in NAMES:
-        _close(run["grads"][name], ref["grads"][name], name)
-    two = _gpu_number(case, inp, need=("weight", "T_init"), configure=_soft(k))
+        close(run["grads"][name], ref["grads"][name], name)
+    two = gpu(case, inp, TRIM, need=("weight", "T_init"), softmin_k=k)
     assert torch.equal(two["T"], run["T"]) and torch.equal(two["idx"], run["idx"])
     for name in ("weight", "T_init"):
         assert torch.equal(two["grads"][name], run["grads"][name])
     # tau a (B,) tensor
-    ten = _gpu_tau(case, inp, k, torch.tensor(PER_PAIR_TAU))
+    ten = gpu(case, inp, TRIM, need=NAMES + ("tau",), softmin_k=k, tau=torch.tensor(PER_PAIR_TAU))
     assert ten["fn"] == "_IcpSoftTempFunctionBackward" and ten["active"][:K].all()
     assert torch.equal(ten["idx"][0].long(), free0)
-    tref = _reference(ci, inp, ten["idx"], ks, soft_k=k, taus=PER_PAIR_TAU)
+    tref = reference(case, TRIM, fixed_idx=ten["idx"], soft_k=k, taus=PER_PAIR_TAU)
     assert_awake(tref, "%s softmin k=%d tau=%s" % (IDS[ci], k, PER_PAIR_TAU))
     _pose(ten, tref)
     for name in NAMES + ("tau",):
         assert ten["grads"][name].shape == tref["grads"][name].shape
-        _close(ten["grads"][name], tref["grads"][name], name)
+        close(ten["grads"][name], tref["grads"][name], name)
 
 
 # ----------------------------------------------------------------------------- 4. the stand-alone stage
 def test_accumulate_stage_with_geman_mcclure():
     case = CASES[0]
     icp_type, (name, k0), dim, _, steep = case
-    inp = _inputs(case)
+    inp = inputs(case)
     L = _lib.lib()
     s, t, wt, T0 = (v.to(DEV).contiguous() for v in inp["x"])
     Tt = T0.reshape(B, 16).contiguous()
@@ -322,9 +232,7 @@ def test_accumulate_stage_with_geman_mcclure():
     one = torch.ones(1, 1)
     J, e, wref, _, aux = per_point_terms(src, tgt, T0c, idx_out.cpu().long(), w, icp_type, name, one * k0, one * TRIM,
                                          one * HARD_STEEP, dim, False)
-    real = torch.zeros(B, N, dtype=torch.bool)
-    real[:, :N_REAL] = True
-    band = float(((aux["keep"] > 0.5) & (aux["rho"] > 0.05) & (aux["rho"] < 0.95))[real].double().mean())
+    band = float(((aux["keep"] > 0.5) & (aux["rho"] > 0.05) & (aux["rho"] < 0.95))[REAL].double().mean())
     assert band >= 0.30, band
     Jd, ed = J.double(), e.double()
     wJ = (wref[..., None, None] * J).double()
@@ -353,7 +261,7 @@ def test_accumulate_stage_with_geman_mcclure():
 @pytest.mark.parametrize("name", ["geman_mcclure", "welsch"])
 def test_bad_scale_on_the_device_raises_the_status_bit_and_nothing_else(name):
     case = CASES[0]
-    inp = _inputs(case)
+    inp = inputs(case)
     check_errors(wait=True)
     icp = ICP(icp_type=case[0], differentiable=False, max_iterations=2, tolerance=TOL)
     s, t, w, T0 = (v.to(DEV) for v in inp["x"])

@@ -1,5 +1,5 @@
 """GPU: the soft (tanh) trim gate of the HIP dICP (mmk_icp_params.trim_steep; DESIGN.md §3 I3', I7') against the restatement
-tests/dicp_soft_trim_ref.py: forward, the gradients of source, target, weight and T_init from both backward entries,
+tests/dicp_restatement.py: forward, the gradients of source, target, weight and T_init from both backward entries,
 structural zeros, bit reproducibility, the untouched hard gate, the stand-alone accumulate stage, a coincident point and the
 policy's params["icp_trim"].
 
@@ -27,125 +27,15 @@ import numpy as np
 import pytest
 import torch
 
-from mm_masking_amd import _lib, synthetic
+from mm_masking_amd import _lib
 from mm_masking_amd.dICP.ICP import ICP
 
-from dicp_soft_trim_ref import ICPSoftRef, band_share, per_point_terms
+from dicp_cases import (B, GATE_CASES as CASES, GATE_IDS as IDS, GATE_TRIM as TRIM, K, M, M_REAL, N, N_REAL, NAMES, REAL, TOL,
+                        assert_gate_awake, close, gpu, inputs, nn_engine, reference)  # noqa: F401
+from dicp_restatement import as_bn, band_share, per_point_terms
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-B, N_REAL, N_ZERO, M_REAL, M_PAD, K, TOL, TRIM = 2, 300, 20, 700, 30, 4, 1e-9, 0.6
-N, M = N_REAL + N_ZERO, M_REAL + M_PAD
-
-#        type     loss (k)          dim noise steepness
-CASES = [("pt2pt", ("cauchy", 0.5), 2, 0.01, 4.0),
-         ("pt2pl", ("huber", 0.1), 2, 0.15, 4.0),
-         ("pt2pt", ("huber", 0.5), 3, 0.01, 4.0),
-         ("pt2pl", ("cauchy", 0.5), 3, 0.15, 4.0),
-         ("pt2pl", None, 2, 0.15, 4.0),
-         ("pt2pt", None, 2, 0.01, 10.0)]
-IDS = ["%s-%s-d%d-s%g" % (c[0], c[1][0] if c[1] else "none", c[2], c[4]) for c in CASES]
-NAMES = ("source", "target", "weight", "T_init")
-
-
-@pytest.fixture(params=["brute", "grid"])
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
-
-
-def _inputs(case, coincident=False):
-    icp_type, loss, dim, noise, steep = case
-    S, Tg = [], []
-    for b in range(B):
-        s, t, _ = synthetic.simple_cloud_pair(77 + dim + b, N_REAL, M_REAL, dim=dim, noise=noise, pad_n=N_ZERO, pad_m=M_PAD,
-                                              yaw=0.02 + 0.01 * b, trans=(0.6, -0.4 + 0.1 * b, 0.1))
-        S.append(s), Tg.append(t)
-    src, tgt = np.stack(S), np.stack(Tg)
-    w = np.random.default_rng(2).uniform(0.2, 1.0, (B, N)).astype(np.float32)
-    w[:, N_REAL:] = 0.0
-    T0 = torch.eye(4).repeat(B, 1, 1)
-    if coincident:
-        src[:, 5] = tgt[:, 11, :3]          # d == 0 under T_init = I
-    else:
-        T0[:, 0, 3] += 0.2
-    G = torch.from_numpy(np.random.default_rng(3).normal(size=(B, 4, 4)).astype(np.float32))
-    loss_fn = None if loss is None else {"name": loss[0], "metric": loss[1]}
-    return {"x": [torch.from_numpy(src), torch.from_numpy(tgt), torch.from_numpy(w), T0], "G": G, "loss_fn": loss_fn}
-
-
-def _gpu(case, inp, need=NAMES, configure=None):
-    """One forward + backward of the HIP dICP: T, idx_hist (K,B,N), active_hist (K+1,B), gradients by name."""
-    icp_type, _, dim, _, steep = case
-    icp = ICP(icp_type=icp_type, differentiable=True, max_iterations=K, tolerance=TOL)
-    if configure is None:
-        icp.trim, icp.tanh_steepness = "tanh", steep
-    else:
-        icp = configure(icp) or icp
-    x = [v.clone().to(DEV).requires_grad_(name in need) for name, v in zip(NAMES, inp["x"])]
-    T = icp.icp(x[0], x[1], T_init=x[3], weight=x[2], trim_dist=TRIM, loss_fn=inp["loss_fn"], dim=dim)["T"]
-    saved = T.grad_fn.saved_tensors                 # weight, src, tgt, idx, T_hist, delta, A, active
-    (T * inp["G"].to(DEV)).sum().backward()
-    torch.cuda.synchronize()
-    grads = {name: (v.grad.cpu() if v.grad is not None else None) for name, v in zip(NAMES, x)}
-    return {"T": T.detach().cpu(), "idx": saved[3].cpu(), "active": saved[7].cpu(), "grads": grads}
-
-
-_ref_cache = {}
-
-
-def _reference(ci, inp, idx_hist):
-    """Autograd through the fp32 restatement replaying ``idx_hist``; computed once per (case, correspondences)."""
-    key = (ci, idx_hist.numpy().tobytes())
-    if key not in _ref_cache:
-        icp_type, _, dim, _, steep = CASES[ci]
-        leaves = [v.clone().requires_grad_(True) for v in inp["x"]]
-        ref = ICPSoftRef(icp_type, differentiable=True, max_iterations=K, tolerance=TOL, trim_steep=steep)
-        out = ref.icp(leaves[0], leaves[1], T_init=leaves[3], weight=leaves[2], trim_dist=TRIM, loss_fn=inp["loss_fn"], dim=dim,
-                      fixed_idx=[idx_hist[k].long() for k in range(K)])
-        (out["T"] * inp["G"]).sum().backward()
-        _ref_cache[key] = {"T": out["T"].detach(), "hist": out["hist"], "num_iter": out["num_iter"],
-                           "grads": {name: v.grad for name, v in zip(NAMES, leaves)}}
-    return _ref_cache[key]
-
-
-_free_cache = {}
-
-
-def _free_idx0(ci, inp):
-    """Correspondences of the first iteration of the free-running reference."""
-    if ci not in _free_cache:
-        icp_type, _, dim, _, steep = CASES[ci]
-        ref = ICPSoftRef(icp_type, differentiable=False, max_iterations=1, tolerance=TOL, trim_steep=steep)
-        out = ref.icp(inp["x"][0], inp["x"][1], T_init=inp["x"][3], weight=inp["x"][2], trim_dist=TRIM, loss_fn=inp["loss_fn"], dim=dim)
-        _free_cache[ci] = out["hist"]["idx"][0]
-    return _free_cache[ci]
-
-
-def _close(g, ref, name, rel=2e-3):
-    g, ref = g.detach().cpu().double().numpy(), ref.detach().double().numpy()
-    scale = np.abs(ref).max()
-    assert scale > 0, name
-    err = np.abs(g - ref).max()
-    print("GRAD %-7s err/scale = %.3e (scale %.3e)" % (name, err / scale, scale))
-    assert err <= rel * scale, (name, err, scale)
-
-
-def _assert_gate_is_awake(ci, ref):
-    """Conditions on the reference's own values: no case passes with the gate or the Huber branch asleep."""
-    loss = CASES[ci][1]
-    real = torch.zeros(B, N, dtype=torch.bool)
-    real[:, :N_REAL] = True
-    assert ref["num_iter"] == K and all(bool(a.all()) for a in ref["hist"]["active"])          # all pairs active
-    shares = [band_share(k, real) for k in ref["hist"]["keep"]]
-    print("BAND SHARE per iteration: %s" % ["%.2f" % s for s in shares])
-    assert min(shares) >= 0.10, shares
-    if loss is not None and loss[0] == "huber":
-        hub = [float(h[real].double().mean()) for h in ref["hist"]["huber_out"]]
-        print("HUBER r > k share per iteration: %s" % ["%.2f" % s for s in hub])
-        assert float(torch.stack(ref["hist"]["huber_out"])[:, real].double().mean()) >= 0.3, hub
 
 
 # ----------------------------------------------------------------------------- 1. - 4. forward, gradients, zeros, run-to-run
@@ -153,24 +43,24 @@ def _assert_gate_is_awake(ci, ref):
 def test_soft_gate_matches_the_restatement(nn_engine, ci):
     case = CASES[ci]
     icp_type, _, dim, _, _ = case
-    inp = _inputs(case)
-    run = _gpu(case, inp)
+    inp = inputs(case)
+    run = gpu(case, inp, TRIM)
     assert run["active"][:K].all()
     # 1. forward: the first search is the free-running reference's; the pose is the replay's
-    assert torch.equal(run["idx"][0].long(), _free_idx0(ci, inp).long())
-    ref = _reference(ci, inp, run["idx"])
-    _assert_gate_is_awake(ci, ref)
+    assert torch.equal(run["idx"][0].long(), reference(case, TRIM, differentiable=False, K_=1)["hist"]["idx"][0].long())
+    ref = reference(case, TRIM, fixed_idx=run["idx"])
+    assert_gate_awake(case, ref)
     err = (run["T"].double() - ref["T"].double()).abs().max().item()
     print("POSE max abs diff = %.3e" % err)
     np.testing.assert_allclose(run["T"].numpy(), ref["T"].numpy(), atol=2e-6, rtol=0)
     # 2. gradients: mmk_icp_backward_points (all four), mmk_icp_backward (weight and T_init only)
     for name in NAMES:
-        _close(run["grads"][name], ref["grads"][name], name)
-    two = _gpu(case, inp, need=("weight", "T_init"))
+        close(run["grads"][name], ref["grads"][name], name)
+    two = gpu(case, inp, TRIM, need=("weight", "T_init"))
     assert torch.equal(two["T"], run["T"]) and torch.equal(two["idx"], run["idx"])
     assert two["grads"]["source"] is None and two["grads"]["target"] is None
     for name in ("weight", "T_init"):
-        _close(two["grads"][name], ref["grads"][name], name + " (mmk_icp_backward)")
+        close(two["grads"][name], ref["grads"][name], name + " (mmk_icp_backward)")
         assert torch.equal(two["grads"][name], run["grads"][name])
     # 3. structural zeros, as with the hard gate
     gs, gt, gw = run["grads"]["source"], run["grads"]["target"], run["grads"]["weight"]
@@ -188,7 +78,7 @@ def test_soft_gate_matches_the_restatement(nn_engine, ci):
     assert (gs[:, N_REAL:] == 0).all()                                           # zero-weight rows: nothing through omega
     assert torch.isfinite(gw).all()
     # 4. run to run
-    again = _gpu(case, inp)
+    again = gpu(case, inp, TRIM)
     assert torch.equal(again["T"], run["T"]) and torch.equal(again["idx"], run["idx"])
     for name in NAMES:
         assert torch.equal(again["grads"][name], run["grads"][name]), name
@@ -198,8 +88,8 @@ def test_soft_gate_matches_the_restatement(nn_engine, ci):
 @pytest.mark.parametrize("ci", [1, 2], ids=[IDS[1], IDS[2]])
 def test_gate_off_is_bit_identical_to_a_call_that_never_mentions_it(nn_engine, ci, tmp_path):
     case = CASES[ci]
-    inp = _inputs(case)
-    plain = _gpu(case, inp, configure=lambda icp: None)                 # never mentions the option
+    inp = inputs(case)
+    plain = gpu(case, inp, TRIM, gate=False)                                            # never mentions the option
 
     def hard_attr(icp):
         icp.trim, icp.tanh_steepness = "hard", 4.0
@@ -223,12 +113,12 @@ def test_gate_off_is_bit_identical_to_a_call_that_never_mentions_it(nn_engine, c
         return new
 
     for configure in (hard_attr, hard_yaml, zero_steep):
-        got = _gpu(case, inp, configure=configure)
+        got = gpu(case, inp, TRIM, gate=False, configure=configure)
         assert torch.equal(got["T"], plain["T"]) and torch.equal(got["idx"], plain["idx"]), configure.__name__
         assert torch.equal(got["active"], plain["active"])
         for name in NAMES:
             assert torch.equal(got["grads"][name], plain["grads"][name]), (configure.__name__, name)
-    soft = _gpu(case, inp)
+    soft = gpu(case, inp, TRIM)
     assert not torch.equal(soft["T"], plain["T"])                       # and the option is not a no-op
 
 
@@ -237,7 +127,7 @@ def test_gate_off_is_bit_identical_to_a_call_that_never_mentions_it(nn_engine, c
 def test_accumulate_stage_with_the_soft_gate(ci):
     case = CASES[ci]
     icp_type, _, dim, _, steep = case
-    inp = _inputs(case)
+    inp = inputs(case)
     L = _lib.lib()
     s, t, wt, T0 = (v.to(DEV).contiguous() for v in inp["x"])
     Tt = T0.reshape(B, 16).contiguous()
@@ -274,12 +164,10 @@ def test_accumulate_stage_with_the_soft_gate(ci):
 
     src, tgt, w, T0c = inp["x"]
     ic = idx_out.cpu().long()
-    loss_name = None if inp["loss_fn"] is None else inp["loss_fn"]["name"]
-    loss_k = 1.0 if inp["loss_fn"] is None else inp["loss_fn"]["metric"]
-    J, e, wref, _, aux = per_point_terms(src, tgt, T0c, ic, w, icp_type, loss_name, loss_k, TRIM, dim, steep)
-    real = torch.zeros(B, N, dtype=torch.bool)
-    real[:, :N_REAL] = True
-    assert band_share(aux["keep"], real) >= 0.10
+    loss_name, loss_k = (None, 1.0) if case[1] is None else case[1]
+    kk, cc, ss = (as_bn(v, B, torch.float32) for v in (loss_k, TRIM, steep))
+    J, e, wref, _, aux = per_point_terms(src, tgt, T0c, ic, w, icp_type, loss_name, kk, cc, ss, dim, True)
+    assert band_share(aux["keep"], REAL) >= 0.10
     Jd, ed = J.double(), e.double()
     wJ = (wref[..., None, None] * J).double()
     A_ref = torch.einsum("bnrp,bnrq->bpq", wJ, Jd)
@@ -308,8 +196,8 @@ def test_accumulate_stage_with_the_soft_gate(ci):
 @pytest.mark.parametrize("ci", [0, 1, 3], ids=[IDS[0], IDS[1], IDS[3]])
 def test_coincident_point_keeps_every_gradient_finite(nn_engine, ci):
     case = CASES[ci]
-    inp = _inputs(case, coincident=True)
-    run = _gpu(case, inp)
+    inp = inputs(case, coincident=True)
+    run = gpu(case, inp, TRIM)
     assert (run["idx"][0][:, 5] == 11).all()                    # d == 0 in the first iteration
     for name in NAMES:
         g = run["grads"][name]

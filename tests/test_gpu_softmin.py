@@ -1,5 +1,5 @@
 """GPU: soft correspondences of the HIP dICP (mmk_icp_forward_soft / mmk_icp_backward_soft, mmk_knn_search; DESIGN.md §3 I2',
-I3''', I7''') against the restatement tests/dicp_softmin_ref.py: the stand-alone k-NN element for element, the forward and the
+I3''', I7''') against the restatement tests/dicp_restatement.py: the stand-alone k-NN element for element, the forward and the
 gradients of source, target, weight and T_init from both backward shapes, structural zeros, bit reproducibility, the nearest
 limit against the hard call, the untouched `nearest` mode and the policy's params["icp_correspondence"].
 
@@ -7,7 +7,7 @@ The reference REPLAYS the neighbours of the GPU run (fixed_idx): device and host
 flipped near-tie of a later search must not turn that into a failure.  idx_hist[0], found before the first solve, is compared
 bit for bit with the free-running reference.
 
-Shapes (those of tests/test_gpu_soft_trim.py): B = 2, 300 + 20 zero source rows (one full and one partial 256-thread block),
+Shapes (tests/dicp_cases.py): B = 2, 300 + 20 zero source rows (one full and one partial 256-thread block),
 700 + 30 target_pad_val rows, K = 4, T_init shifted by 0.2 m, trim_dist 1.0, tau = 0.25 m^2, k in {4, 8}.  Every case asserts
 on the reference's own values that the soft-min is awake (a_0 < 0.9 for 30 % at least of the real points in every iteration),
 that 30 % of the real points pass the gate in every iteration, that Huber is past its knee for 30 % of them, and that no pair
@@ -28,119 +28,16 @@ import numpy as np
 import pytest
 import torch
 
-from mm_masking_amd import _lib, synthetic
+from mm_masking_amd import _lib
 from mm_masking_amd.dICP.ICP import ICP
 from oracle.dicp_ref import transform_points
 
-from dicp_softmin_ref import ICPSoftminRef, knn_ref_batch
+from dicp_cases import (B, K, M, M_REAL, N, N_REAL, NAMES, SOFTMIN_CASES as CASES, SOFTMIN_IDS as IDS, SOFTMIN_TRIM as TRIM, TAU, TOL,
+                        assert_softmin_awake, close, first_neighbours, gpu, inputs, nn_engine, reference)  # noqa: F401
+from dicp_restatement import knn_ref_batch
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-B, N_REAL, N_ZERO, M_REAL, M_PAD, K, TOL, TRIM, TAU = 2, 300, 20, 700, 30, 4, 1e-9, 1.0, 0.25
-N, M = N_REAL + N_ZERO, M_REAL + M_PAD
-
-#        type     loss (k)          dim noise tanh steepness (0: the hard gate)
-CASES = [("pt2pt", ("cauchy", 0.5), 2, 0.01, 0.0),
-         ("pt2pl", ("huber", 0.1), 2, 0.15, 0.0),
-         ("pt2pt", ("huber", 0.5), 3, 0.01, 0.0),
-         ("pt2pl", ("cauchy", 0.5), 3, 0.15, 0.0),
-         ("pt2pl", None, 2, 0.15, 4.0)]
-IDS = ["%s-%s-d%d%s" % (c[0], c[1][0] if c[1] else "none", c[2], "-tanh" if c[4] else "") for c in CASES]
-NAMES = ("source", "target", "weight", "T_init")
-
-
-def _inputs(case):
-    icp_type, loss, dim, noise, steep = case
-    S, Tg = [], []
-    for b in range(B):
-        s, t, _ = synthetic.simple_cloud_pair(77 + dim + b, N_REAL, M_REAL, dim=dim, noise=noise, pad_n=N_ZERO, pad_m=M_PAD,
-                                              yaw=0.02 + 0.01 * b, trans=(0.6, -0.4 + 0.1 * b, 0.1))
-        S.append(s), Tg.append(t)
-    src, tgt = np.stack(S), np.stack(Tg)
-    w = np.random.default_rng(2).uniform(0.2, 1.0, (B, N)).astype(np.float32)
-    w[:, N_REAL:] = 0.0
-    T0 = torch.eye(4).repeat(B, 1, 1)
-    T0[:, 0, 3] += 0.2
-    G = torch.from_numpy(np.random.default_rng(3).normal(size=(B, 4, 4)).astype(np.float32))
-    loss_fn = None if loss is None else {"name": loss[0], "metric": loss[1]}
-    return {"x": [torch.from_numpy(src), torch.from_numpy(tgt), torch.from_numpy(w), T0], "G": G, "loss_fn": loss_fn}
-
-
-def _soft(k, tau=TAU):
-    def configure(icp):
-        icp.correspondence, icp.softmin_k, icp.softmin_temp = "softmin", k, tau
-    return configure
-
-
-def _gpu(case, inp, need=NAMES, configure=None, trim_dist=TRIM):
-    """One forward + backward of the HIP dICP: T, idx_hist, T_hist (K+1,B,16), active_hist (K+1,B), gradients by name."""
-    icp_type, _, dim, _, steep = case
-    icp = ICP(icp_type=icp_type, differentiable=True, max_iterations=K, tolerance=TOL)
-    if steep > 0:
-        icp.trim, icp.tanh_steepness = "tanh", steep
-    if configure is not None:
-        icp = configure(icp) or icp
-    x = [v.clone().to(DEV).requires_grad_(name in need) for name, v in zip(NAMES, inp["x"])]
-    T = icp.icp(x[0], x[1], T_init=x[3], weight=x[2], trim_dist=trim_dist, loss_fn=inp["loss_fn"], dim=dim)["T"]
-    saved = T.grad_fn.saved_tensors                 # weight, src, tgt, idx, T_hist, delta, A, active
-    (T * inp["G"].to(DEV)).sum().backward()
-    torch.cuda.synchronize()
-    grads = {name: (v.grad.cpu() if v.grad is not None else None) for name, v in zip(NAMES, x)}
-    return {"T": T.detach().cpu(), "idx": saved[3].cpu(), "T_hist": saved[4].cpu(), "active": saved[7].cpu(), "grads": grads,
-            "fn": type(T.grad_fn).__name__}
-
-
-_ref_cache = {}
-
-
-def _reference(ci, k, inp, idx_hist):
-    """Autograd through the fp32 restatement replaying ``idx_hist`` (K,B,N,k); computed once per (case, k, neighbours)."""
-    key = (ci, k, idx_hist.numpy().tobytes())
-    if key not in _ref_cache:
-        icp_type, _, dim, _, steep = CASES[ci]
-        leaves = [v.clone().requires_grad_(True) for v in inp["x"]]
-        ref = ICPSoftminRef(icp_type, differentiable=True, max_iterations=K, tolerance=TOL, k=k, tau=TAU, trim_steep=steep)
-        out = ref.icp(leaves[0], leaves[1], T_init=leaves[3], weight=leaves[2], trim_dist=TRIM, loss_fn=inp["loss_fn"], dim=dim,
-                      fixed_idx=[idx_hist[it].long() for it in range(K)])
-        (out["T"] * inp["G"]).sum().backward()
-        _ref_cache[key] = {"T": out["T"].detach(), "hist": out["hist"], "num_iter": out["num_iter"],
-                           "grads": {name: v.grad for name, v in zip(NAMES, leaves)}}
-    return _ref_cache[key]
-
-
-def _free_idx0(ci, k, inp):
-    """Neighbours of the first iteration of the free-running reference."""
-    dim = CASES[ci][2]
-    p = torch.stack(transform_points(inp["x"][0], inp["x"][3], dim), dim=-1)
-    return torch.from_numpy(knn_ref_batch(p.numpy(), inp["x"][1][..., :dim].numpy(), k, dim)[0])
-
-
-def _close(g, ref, name, rel=2e-3):
-    g, ref = g.detach().cpu().double().numpy(), ref.detach().double().numpy()
-    scale = np.abs(ref).max()
-    assert scale > 0, name
-    err = np.abs(g - ref).max()
-    print("GRAD %-7s err/scale = %.3e (scale %.3e)" % (name, err / scale, scale))
-    assert err <= rel * scale, (name, err, scale)
-
-
-def _assert_awake(ci, ref):
-    """Conditions on the reference's own values: no case passes with the soft-min, the gate or the Huber branch asleep."""
-    loss = CASES[ci][1]
-    real = torch.zeros(B, N, dtype=torch.bool)
-    real[:, :N_REAL] = True
-    assert ref["num_iter"] == K and all(bool(a.all()) for a in ref["hist"]["active"])          # no pair froze
-    shared = [float((a[..., 0][real] < 0.9).double().mean()) for a in ref["hist"]["a"]]
-    print("a_0 < 0.9 share per iteration: %s" % ["%.2f" % s for s in shared])
-    assert min(shared) >= 0.30, shared
-    passed = [float((kp[real] > 0.5).double().mean()) for kp in ref["hist"]["keep"]]
-    print("GATE PASSED share per iteration: %s" % ["%.2f" % s for s in passed])
-    assert min(passed) >= 0.30, passed
-    if loss is not None and loss[0] == "huber":
-        hub = [float(h[real].double().mean()) for h in ref["hist"]["huber_out"]]
-        print("HUBER r > k share per iteration: %s" % ["%.2f" % s for s in hub])
-        assert float(torch.stack(ref["hist"]["huber_out"])[:, real].double().mean()) >= 0.3, hub
 
 
 def _knn_search(src, tgt, T, dim, k):
@@ -209,25 +106,25 @@ def test_knn_search_matches_the_numpy_knn(dim, n, m, k):
 def test_softmin_matches_the_restatement(ci, k):
     case = CASES[ci]
     icp_type, _, dim, _, _ = case
-    inp = _inputs(case)
-    run = _gpu(case, inp, configure=_soft(k))
+    inp = inputs(case)
+    run = gpu(case, inp, TRIM, softmin_k=k)
     assert run["fn"].startswith("_IcpSoftFunction") and tuple(run["idx"].shape) == (K, B, N, k)
     assert run["active"][:K].all()
     # forward: the first search is the free-running reference's; the pose is the replay's
-    assert torch.equal(run["idx"][0].long(), _free_idx0(ci, k, inp))
-    ref = _reference(ci, k, inp, run["idx"])
-    _assert_awake(ci, ref)
+    assert torch.equal(run["idx"][0].long(), first_neighbours(case, k))
+    ref = reference(case, TRIM, fixed_idx=run["idx"], soft_k=k)
+    assert_softmin_awake(case, ref)
     err = (run["T"].double() - ref["T"].double()).abs().max().item()
     print("POSE max abs diff = %.3e" % err)
     np.testing.assert_allclose(run["T"].numpy(), ref["T"].numpy(), atol=2e-6, rtol=0)
     # gradients: with the clouds (all four), without them (weight and T_init only)
     for name in NAMES:
-        _close(run["grads"][name], ref["grads"][name], name)
-    two = _gpu(case, inp, need=("weight", "T_init"), configure=_soft(k))
+        close(run["grads"][name], ref["grads"][name], name)
+    two = gpu(case, inp, TRIM, need=("weight", "T_init"), softmin_k=k)
     assert torch.equal(two["T"], run["T"]) and torch.equal(two["idx"], run["idx"])
     assert two["grads"]["source"] is None and two["grads"]["target"] is None
     for name in ("weight", "T_init"):
-        _close(two["grads"][name], ref["grads"][name], name + " (no clouds)")
+        close(two["grads"][name], ref["grads"][name], name + " (no clouds)")
         assert torch.equal(two["grads"][name], run["grads"][name])
     # structural zeros
     gs, gt, gw = run["grads"]["source"], run["grads"]["target"], run["grads"]["weight"]
@@ -244,7 +141,7 @@ def test_softmin_matches_the_restatement(ci, k):
     assert (gs[:, N_REAL:] == 0).all()                                           # zero-weight rows
     assert torch.isfinite(gw).all() and torch.isfinite(gt).all() and torch.isfinite(gs).all()
     # run to run
-    again = _gpu(case, inp, configure=_soft(k))
+    again = gpu(case, inp, TRIM, softmin_k=k)
     assert torch.equal(again["T"], run["T"]) and torch.equal(again["idx"], run["idx"])
     for name in NAMES:
         assert torch.equal(again["grads"][name], run["grads"][name]), name
@@ -256,14 +153,14 @@ def test_softmin_matches_the_restatement(ci, k):
 def test_nearest_limit_is_the_hard_grid_call(ci, k):
     case = CASES[ci]
     dim = case[2]
-    inp = _inputs(case)
+    inp = inputs(case)
     tau = 1e-12
     ICP.NN_SEARCH_OVERRIDE = "grid"
     try:
-        hard = _gpu(case, inp)
+        hard = gpu(case, inp, TRIM)
     finally:
         ICP.NN_SEARCH_OVERRIDE = None
-    soft = _gpu(case, inp, configure=_soft(k, tau))
+    soft = gpu(case, inp, TRIM, softmin_k=k, tau=tau)
     # the premise, on the device's own distances: (d_1 - d_0) / tau >= 120 on every real row of every iteration
     s, t = inp["x"][0].to(DEV), inp["x"][1].to(DEV)
     for it in range(K):
@@ -281,17 +178,10 @@ def test_nearest_limit_is_the_hard_grid_call(ci, k):
 
 
 # ----------------------------------------------------------------------------- 6. correspondence: nearest
-@pytest.fixture(params=["brute", "grid"])
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
-
-
 @pytest.mark.parametrize("ci", [1, 2], ids=[IDS[1], IDS[2]])
 def test_nearest_is_bit_identical_to_a_call_that_never_mentions_it(nn_engine, ci, tmp_path):
     case = CASES[ci]
-    inp = _inputs(case)
+    inp = inputs(case)
 
     def by_attr(icp):
         icp.correspondence, icp.softmin_k, icp.softmin_temp = "nearest", 8, 1.0
@@ -305,23 +195,23 @@ def test_nearest_is_bit_identical_to_a_call_that_never_mentions_it(nn_engine, ci
 
     # the three backward entries: mmk_icp_backward (no clouds), mmk_icp_backward_points, mmk_icp_backward_hp (a tensor trim_dist)
     for need, trim in ((("weight", "T_init"), TRIM), (NAMES, TRIM), (NAMES, torch.tensor(TRIM))):
-        plain = _gpu(case, inp, need=need, trim_dist=trim)
+        plain = gpu(case, inp, trim, need=need)
         assert plain["fn"].startswith("_IcpHpFunction" if torch.is_tensor(trim) else "_IcpFunction")
         for configure in (by_attr, by_yaml):
-            got = _gpu(case, inp, need=need, configure=configure, trim_dist=trim)
+            got = gpu(case, inp, trim, need=need, configure=configure)
             assert got["fn"] == plain["fn"]
             assert torch.equal(got["T"], plain["T"]) and torch.equal(got["idx"], plain["idx"]), configure.__name__
             assert torch.equal(got["active"], plain["active"])
             for name in need:
                 assert torch.equal(got["grads"][name], plain["grads"][name]), (configure.__name__, name)
-    soft = _gpu(case, inp, configure=_soft(4))
+    soft = gpu(case, inp, TRIM, softmin_k=4)
     assert not torch.equal(soft["T"], plain["T"])                       # and the option is not a no-op
     # a call that is not differentiable keeps nearest correspondences, whatever the instance says
     icp = ICP(icp_type=case[0], differentiable=True, max_iterations=K, tolerance=TOL)
     x = [v.to(DEV) for v in inp["x"]]
     with torch.no_grad():
         T_plain = icp.icp(x[0], x[1], T_init=x[3], weight=x[2], trim_dist=TRIM, loss_fn=inp["loss_fn"], dim=case[2])["T"]
-        _soft(4)(icp)
+        icp.correspondence, icp.softmin_k, icp.softmin_temp = "softmin", 4, TAU
         T_soft = icp.icp(x[0], x[1], T_init=x[3], weight=x[2], trim_dist=TRIM, loss_fn=inp["loss_fn"], dim=case[2])["T"]
     assert torch.equal(T_plain, T_soft) and tuple(icp.last_state["idx"].shape) == (1, B, N)
 
@@ -330,11 +220,11 @@ def test_softmin_call_without_a_gradient_input_keeps_the_mode_and_the_pose():
     """differentiable=True with grad enabled but no input that requires grad: still soft correspondences, through the forward
     that saves no state (one (B,N,k) index buffer, the polled early exit), and the pose of the call that saves it."""
     case = CASES[1]
-    inp = _inputs(case)
-    saved = _gpu(case, inp, configure=_soft(4))
+    inp = inputs(case)
+    saved = gpu(case, inp, TRIM, softmin_k=4)
     icp = ICP(icp_type=case[0], differentiable=True, max_iterations=K, tolerance=TOL)
     icp.check_every = 2
-    _soft(4)(icp)
+    icp.correspondence, icp.softmin_k, icp.softmin_temp = "softmin", 4, TAU
     x = [v.to(DEV) for v in inp["x"]]
     T = icp.icp(x[0], x[1], T_init=x[3], weight=x[2], trim_dist=TRIM, loss_fn=inp["loss_fn"], dim=case[2])["T"]
     assert not T.requires_grad and tuple(icp.last_state["idx"].shape) == (1, B, N, 4)

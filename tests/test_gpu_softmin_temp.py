@@ -1,13 +1,13 @@
 """GPU: the soft-min temperature of the HIP dICP on the device, one value for the batch or one per pair, and its gradient
 (mmk_icp_forward_soft_t / mmk_icp_backward_soft_t; DESIGN.md §3 I3⁗, I7⁗) against the restatement
-tests/dicp_softmin_temp_ref.py.
+tests/dicp_restatement.py.
 
-Shapes, cases, inputs and ``_close`` are those of tests/test_gpu_softmin.py (imported from it): B = 2, 300 + 20 source rows (one
+Shapes, cases, inputs and ``close`` are those of tests/dicp_cases.py (its soft-min table): B = 2, 300 + 20 source rows (one
 full and one partial 256-thread block), 700 + 30 target rows, K = 4, its five cases, k in {4, 8}; the reference replays the
 device's idx_hist.  The reference runs once per (case, k, temperatures, correspondences) with tau as a (B,N) leaf: the
 gradient of that leaf is every point's contribution summed over the iterations, its fp64 row sums g_b are the per-pair
 references, and S_b = sum |contributions| makes the awake condition max_b |g_b| / S_b >= 0.03 (tests/test_gpu_icp_hyper.py's
-threshold), asserted on the reference's values and printed next to tests/test_gpu_softmin.py's own conditions.
+threshold), asserted on the reference's values and printed next to tests/test_gpu_softmin.py's conditions (``assert_softmin_awake``).
 
 Tolerances: pose 2e-6 absolute, gradients 2e-3 of the reference's largest magnitude per input (tests/test_gpu_point_grads.py's
 bounds).  Equalities are exact: a tensor holding a number call's fp32 value gives that call's bits (0.25, and 0.3, which fp32
@@ -37,14 +37,13 @@ from mm_masking_amd import _lib
 from mm_masking_amd.dICP.ICP import ICP, check_errors
 
 import icp_freeze_cases as fz
-from dicp_softmin_temp_ref import ICPSoftminTempRef, pair_sums, tau_leaf
-from test_gpu_softmin import B, CASES, DEV, IDS, K, N, NAMES, TOL, TRIM, _assert_awake, _close, _inputs, _soft
-from test_gpu_softmin import _gpu as _gpu_number
+from dicp_cases import (B, K, N, NAMES, PER_PAIR_TAU as PER_PAIR, SOFTMIN_CASES as CASES, SOFTMIN_IDS as IDS, SOFTMIN_TRIM as TRIM, TOL,
+                        assert_softmin_awake, assert_tau_awake, close, gpu, inputs, reference, same)
 
 pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
 
 ALL5 = NAMES + ("tau",)
-PER_PAIR = (0.25, 0.4)
 EQUAL = (0.25, 0.25)
 CASE_K = [(ci, 4) for ci in range(len(CASES))] + [(ci, 8) for ci in range(len(CASES))]
 CASE_K_IDS = ["%s-k%d" % (IDS[ci], k) for ci, k in CASE_K]
@@ -53,62 +52,9 @@ CASE_K_IDS = ["%s-k%d" % (IDS[ci], k) for ci, k in CASE_K]
 POLICY_TAU = 0.25
 
 
-def _gpu(case, inp, k, tau, need=ALL5, K_=K, tol=TOL, trim=TRIM):
-    """One forward + backward with soft correspondences.  ``tau``: a float or a CPU tensor (moved to the device and, if "tau"
-    is in ``need``, requiring grad)."""
-    icp = ICP(icp_type=case[0], differentiable=True, max_iterations=K_, tolerance=tol)
-    if case[4] > 0:
-        icp.trim, icp.tanh_steepness = "tanh", case[4]
-    t = tau.clone().to(DEV).requires_grad_("tau" in need) if isinstance(tau, torch.Tensor) else tau
-    icp.correspondence, icp.softmin_k, icp.softmin_temp = "softmin", k, t
-    x = [v.clone().to(DEV).requires_grad_(name in need) for name, v in zip(NAMES, inp["x"])]
-    T = icp.icp(x[0], x[1], T_init=x[3], weight=x[2], trim_dist=trim, loss_fn=inp["loss_fn"], dim=case[2])["T"]
-    assert T.requires_grad
-    saved = T.grad_fn.saved_tensors                 # weight, src, tgt, idx, T_hist, delta, A, active(, temp)
-    (T * inp["G"].to(DEV)).sum().backward()
-    torch.cuda.synchronize()
-    grads = {name: (v.grad.cpu() if v.grad is not None else None) for name, v in zip(NAMES, x)}
-    grads["tau"] = None
-    if isinstance(t, torch.Tensor) and t.grad is not None:
-        assert t.grad.shape == t.shape and t.grad.dtype == t.dtype and t.grad.device == t.device
-        grads["tau"] = t.grad.cpu()
-    return {"T": T.detach().cpu(), "idx": saved[3].cpu(), "active": saved[7].cpu(), "grads": grads, "fn": type(T.grad_fn).__name__}
-
-
-def _same(a, b, names):
-    assert torch.equal(a["T"], b["T"]) and torch.equal(a["idx"], b["idx"]) and torch.equal(a["active"], b["active"])
-    for name in names:
-        assert torch.equal(a["grads"][name], b["grads"][name]), name
-
-
-_ref_cache = {}
-
-
-def _reference(ci, k, inp, idx_hist, taus):
-    """Autograd through the fp32 restatement replaying ``idx_hist`` (K,B,N,k) with the per-pair temperatures as a (B,N) leaf;
-    computed once per key and left unchanged."""
-    key = (ci, k, tuple(taus), idx_hist.numpy().tobytes())
-    if key not in _ref_cache:
-        case = CASES[ci]
-        leaves = [v.clone().requires_grad_(True) for v in inp["x"]]
-        leaf = tau_leaf(taus, N)
-        ref = ICPSoftminTempRef(case[0], differentiable=True, max_iterations=K, tolerance=TOL, k=k, trim_steep=case[4])
-        out = ref.icp(leaves[0], leaves[1], leaf, T_init=leaves[3], weight=leaves[2], trim_dist=TRIM, loss_fn=inp["loss_fn"],
-                      dim=case[2], fixed_idx=[idx_hist[it].long() for it in range(K)])
-        (out["T"] * inp["G"]).sum().backward()
-        grads = {name: v.grad for name, v in zip(NAMES, leaves)}
-        g, S = pair_sums(leaf.grad)
-        grads["tau"] = g
-        _ref_cache[key] = {"T": out["T"].detach(), "hist": out["hist"], "num_iter": out["num_iter"], "grads": grads, "S": S}
-    return _ref_cache[key]
-
-
-def _assert_tau_is_awake(ref, what):
-    """The tau gradient is not the rounding noise of a cancellation: some pair's |g_b| is at least 0.03 of the sum of the
-    magnitudes of its per-point contributions."""
-    ratios = (ref["grads"]["tau"].abs() / ref["S"]).tolist()
-    print("AWAKE tau %s: |g_b| / S_b per pair %s" % (what, ["%.3f" % r for r in ratios]))
-    assert max(ratios) >= 0.03, ratios
+def _gpu(case, inp, k, tau, need=ALL5, trim=TRIM, **kw):
+    """One forward + backward with soft correspondences.  ``tau``: a float or a CPU tensor."""
+    return gpu(case, inp, trim, need=need, softmin_k=k, tau=tau, **kw)
 
 
 # ----------------------------------------------------------------------------- 1. same value, same bits
@@ -116,16 +62,16 @@ def _assert_tau_is_awake(ref, what):
                          ids=["%s-k4" % i for i in IDS] + ["%s-k8" % IDS[1], "%s-k8" % IDS[3]])
 def test_a_tensor_with_a_number_calls_value_gives_its_bits(ci, k):
     case = CASES[ci]
-    inp = _inputs(case)
+    inp = inputs(case)
     value = 0.3 if ci == 1 else 0.25                             # 0.3 is not representable: the tensor holds its fp32 rounding
     for need in (NAMES, ("weight", "T_init")):                  # both backward shapes
-        plain = _gpu_number(case, inp, need=need, configure=_soft(k, value))
+        plain = gpu(case, inp, TRIM, need=need, softmin_k=k, tau=value)
         assert plain["fn"] == "_IcpSoftFunctionBackward"
         for tau in (torch.tensor(value), torch.tensor([value]), torch.tensor([value] * B), torch.tensor(value, dtype=torch.float64)):
             for with_grad in (need, need + ("tau",)):
                 got = _gpu(case, inp, k, tau, need=with_grad)
                 assert got["fn"] == "_IcpSoftTempFunctionBackward"
-                _same(got, plain, need)
+                same(got, plain, need)
                 assert all(got["grads"][n] is None for n in NAMES if n not in need)
                 assert (got["grads"]["tau"] is not None) == ("tau" in with_grad)
 
@@ -134,21 +80,21 @@ def test_a_tensor_with_a_number_calls_value_gives_its_bits(ci, k):
 @pytest.mark.parametrize("ci,k", CASE_K, ids=CASE_K_IDS)
 def test_per_pair_values_match_the_restatement(ci, k):
     case = CASES[ci]
-    inp = _inputs(case)
+    inp = inputs(case)
     run = _gpu(case, inp, k, torch.tensor(PER_PAIR))
     assert tuple(run["idx"].shape) == (K, B, N, k) and run["active"][:K].all()
-    ref = _reference(ci, k, inp, run["idx"], PER_PAIR)
-    _assert_awake(ci, ref)
-    _assert_tau_is_awake(ref, PER_PAIR)
+    ref = reference(case, TRIM, fixed_idx=run["idx"], soft_k=k, taus=PER_PAIR)
+    assert_softmin_awake(case, ref)
+    assert_tau_awake(ref, PER_PAIR)
     err = (run["T"].double() - ref["T"].double()).abs().max().item()
     print("POSE max abs diff = %.3e" % err)
     np.testing.assert_allclose(run["T"].numpy(), ref["T"].numpy(), atol=2e-6, rtol=0)
     for name in ALL5:
         assert run["grads"][name].shape == ref["grads"][name].shape
-        _close(run["grads"][name], ref["grads"][name], name)
+        close(run["grads"][name], ref["grads"][name], name)
     # the other backward shape (no cloud requires grad): the same temperature gradient, bit for bit
     two = _gpu(case, inp, k, torch.tensor(PER_PAIR), need=("weight", "T_init", "tau"))
-    _same(two, run, ("weight", "T_init", "tau"))
+    same(two, run, ("weight", "T_init", "tau"))
     # per-pair values are not equal values
     assert not torch.equal(run["T"][1], _gpu(case, inp, k, torch.tensor(EQUAL))["T"][1])
 
@@ -157,15 +103,15 @@ def test_per_pair_values_match_the_restatement(ci, k):
 @pytest.mark.parametrize("ci,k", CASE_K, ids=CASE_K_IDS)
 def test_shared_value_gets_the_sum_of_the_pairs(ci, k):
     case = CASES[ci]
-    inp = _inputs(case)
+    inp = inputs(case)
     per = _gpu(case, inp, k, torch.tensor(EQUAL))
-    ref = _reference(ci, k, inp, per["idx"], EQUAL)
-    _assert_tau_is_awake(ref, EQUAL)
-    _close(per["grads"]["tau"], ref["grads"]["tau"], "tau (equal values)")
+    ref = reference(case, TRIM, fixed_idx=per["idx"], soft_k=k, taus=EQUAL)
+    assert_tau_awake(ref, EQUAL)
+    close(per["grads"]["tau"], ref["grads"]["tau"], "tau (equal values)")
     want = per["grads"]["tau"].double().sum().float()
     for shape in ((), (1,)):
         shared = _gpu(case, inp, k, torch.tensor(EQUAL[0]).reshape(shape))
-        _same(shared, per, NAMES)
+        same(shared, per, NAMES)
         assert shared["grads"]["tau"].shape == shape and torch.equal(shared["grads"]["tau"].reshape(()), want)
     half = _gpu(case, inp, k, torch.tensor(EQUAL[0], dtype=torch.float64))           # the gradient in the tensor's own dtype
     assert half["grads"]["tau"].dtype == torch.float64 and half["grads"]["tau"] == per["grads"]["tau"].double().sum()
@@ -175,14 +121,14 @@ def test_shared_value_gets_the_sum_of_the_pairs(ci, k):
 @pytest.mark.parametrize("ci,k", [(0, 4), (3, 8)], ids=["%s-k4" % IDS[0], "%s-k8" % IDS[3]])
 def test_only_tau_requires_grad(ci, k):
     case = CASES[ci]
-    inp = _inputs(case)
+    inp = inputs(case)
     full = _gpu(case, inp, k, torch.tensor(PER_PAIR))
     solo = _gpu(case, inp, k, torch.tensor(PER_PAIR), need=("tau",))             # (_gpu asserts T.requires_grad)
     assert all(solo["grads"][n] is None for n in NAMES)
     assert torch.equal(solo["T"], full["T"]) and torch.equal(solo["idx"], full["idx"])
     assert torch.equal(solo["grads"]["tau"], full["grads"]["tau"]) and solo["grads"]["tau"].abs().min() > 0
     again = _gpu(case, inp, k, torch.tensor(PER_PAIR))
-    _same(again, full, ALL5)
+    same(again, full, ALL5)
     # nothing requires grad: the state-less soft forward with the device tau, and the pose of the call that saves its state
     icp = ICP(icp_type=case[0], differentiable=True, max_iterations=K, tolerance=TOL)
     icp.correspondence, icp.softmin_k, icp.softmin_temp = "softmin", k, torch.tensor(PER_PAIR, device=DEV)
@@ -218,7 +164,7 @@ def test_frozen_iterations_contribute_exactly_zero():
 # ----------------------------------------------------------------------------- 6. the status bit
 def test_bad_value_on_the_device_raises_the_status_bit_and_nothing_else():
     case = CASES[0]
-    inp = _inputs(case)
+    inp = inputs(case)
     check_errors(wait=True)
     icp = ICP(icp_type=case[0], differentiable=True, max_iterations=2, tolerance=TOL)
     icp.correspondence, icp.softmin_k = "softmin", 4

@@ -1,7 +1,7 @@
 """CPU: the dICP's device-resident, learnable robust scale k, trim distance and steepness (DESIGN.md §3 I3'', I7'').  The
-restatement tests/dicp_hyper_ref.py -- bit equality with the soft-trim restatement for plain equal values, the closed forms of
-I7'' against its autograd, fp64 finite differences per pair -- and the host plumbing: the _hp entries of the C ABI and their
-argument checks, dICP.ICP's shape validation, the policy's params["learn_icp"]."""
+restatement tests/dicp_restatement.py -- the same bits for equal values given as numbers or as tensors of any accepted shape,
+the closed forms of I7'' against its autograd, fp64 finite differences per pair -- and the host plumbing: the _hp entries of
+the C ABI and their argument checks, dICP.ICP's shape validation, the policy's params["learn_icp"]."""
 import ctypes
 import importlib
 import os
@@ -16,8 +16,8 @@ from mm_masking_amd.dICP.ICP import ICP
 
 icp_mod = importlib.import_module("mm_masking_amd.dICP.ICP")        # (the package re-exports the class under the module's name)
 
-from dicp_hyper_ref import ICPHyperRef, closed_form_sums
-from dicp_soft_trim_ref import ICPSoftRef
+from dicp_cases import policy_params
+from dicp_restatement import ICPRestatement, closed_form_sums
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B, N, M, K = 2, 70, 160, 3
@@ -48,15 +48,15 @@ def _inputs(case):
 @pytest.mark.parametrize("ci", range(len(CASES)), ids=IDS)
 @pytest.mark.parametrize("soft", [True, False], ids=["soft", "hard"])
 def test_plain_equal_values_are_the_soft_trim_restatement_bit_for_bit(ci, soft):
+    """A number, a 0-d tensor, a (B,) tensor and a (B,N) tensor of equal value give the same bits."""
     icp_type, loss, k, dim, _ = CASES[ci]
     src, tgt, w, T0, G = _inputs(CASES[ci])
-    loss_fn = None if loss is None else {"name": loss, "metric": k}
-    old = ICPSoftRef(icp_type, differentiable=True, max_iterations=K, tolerance=1e-9, trim_steep=STEEP if soft else 0.0)
+    new = ICPRestatement(icp_type, differentiable=True, max_iterations=K, tolerance=1e-9, soft=soft)
     leaves_o = [v.clone().requires_grad_(True) for v in (src, tgt, w, T0)]
-    a = old.icp(leaves_o[0], leaves_o[1], T_init=leaves_o[3], weight=leaves_o[2], trim_dist=TRIM, loss_fn=loss_fn, dim=dim)
+    a = new.icp(leaves_o[0], leaves_o[1], T_init=leaves_o[3], weight=leaves_o[2], k=k, trim_dist=TRIM, trim_steep=STEEP, loss_name=loss,
+                dim=dim)
     (a["T"] * G).sum().backward()
     for shape in ((), (B,), (B, N)):
-        new = ICPHyperRef(icp_type, differentiable=True, max_iterations=K, tolerance=1e-9, soft=soft)
         leaves_n = [v.clone().requires_grad_(True) for v in (src, tgt, w, T0)]
         hy = [torch.full(shape, v, dtype=torch.float32) for v in (k, TRIM, STEEP)]
         b = new.icp(leaves_n[0], leaves_n[1], T_init=leaves_n[3], weight=leaves_n[2], k=hy[0], trim_dist=hy[1], trim_steep=hy[2],
@@ -75,11 +75,11 @@ def _fixed_run(case, soft, hyper_shape, dtype=torch.float64, mult=(1.3, 1.15, 0.
     icp_type, loss, k, dim, _ = case
     src, tgt, w, T0, G = _inputs(case)
     vals = [torch.tensor([v, v * m]) for v, m in zip((k, TRIM, STEEP), mult)]
-    free = ICPHyperRef(icp_type, differentiable=False, max_iterations=K, tolerance=1e-12, soft=soft).icp(
+    free = ICPRestatement(icp_type, differentiable=False, max_iterations=K, tolerance=1e-12, soft=soft).icp(
         src, tgt, T_init=T0, weight=w, k=vals[0], trim_dist=vals[1], trim_steep=vals[2], loss_name=loss, dim=dim)
     fixed = free["hist"]["idx"]
     assert len(fixed) == K
-    ref = ICPHyperRef(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12, soft=soft)
+    ref = ICPRestatement(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12, soft=soft)
 
     def run(kk, cc, ss):
         return ref.icp(src, tgt, T_init=T0, weight=w, k=kk, trim_dist=cc, trim_steep=ss, loss_name=loss, dim=dim, dtype=dtype,
@@ -278,24 +278,15 @@ def test_status_bit_becomes_an_error_that_names_the_parameters():
 
 
 # ----------------------------------------------------------------------------- the policy
-def _policy_params(**kw):
-    p = dict(icp_type="pt2pl", fft_input=True, cfar_input=False, range_input=False, network_input_type="cartesian",
-             network_output_type="cartesian", device="cpu", max_iter=4, loss_icp_rot_weight=1.0, loss_icp_trans_weight=1.0,
-             float_type=torch.float32, leaky=False, dropout=0.0, batch_norm=False, normalize="minmax", log_transform=False,
-             a_thresh=1.0, b_thresh=0.09, gt_eye=True, norm_weights=True, init_weights=True, unet_backend="torch")
-    p.update(kw)
-    return p
-
-
 def test_policy_learn_icp_parameters_and_errors():
     from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-    base = LearnICPWeightPolicy(_policy_params())
+    base = LearnICPWeightPolicy(policy_params())
     keys = list(base.state_dict().keys())
     assert len(list(base.parameters())) == 46 and base.learn_icp == ()
     assert not any(k.startswith("icp_") for k in keys)
-    soft = LearnICPWeightPolicy(_policy_params(icp_trim="tanh"))
+    soft = LearnICPWeightPolicy(policy_params(icp_trim="tanh"))
     assert list(soft.state_dict().keys()) == keys
-    m = LearnICPWeightPolicy(_policy_params(icp_trim="tanh", icp_trim_dist=0.12, icp_tanh_steepness=7.0,
+    m = LearnICPWeightPolicy(policy_params(icp_trim="tanh", icp_trim_dist=0.12, icp_tanh_steepness=7.0,
                                             icp_loss_fn={"name": "huber", "metric": 0.3},
                                             learn_icp=("metric", "trim_dist", "tanh_steepness")))
     new = ["icp_metric", "icp_trim_dist_p", "icp_tanh_steepness_p"]     # (a module's own parameters precede its children's)
@@ -305,7 +296,7 @@ def test_policy_learn_icp_parameters_and_errors():
         q = getattr(m, name)
         assert isinstance(q, torch.nn.Parameter) and q.shape == () and q.dtype == torch.float32 and q.requires_grad
         assert q.item() == np.float32(v)
-    only = LearnICPWeightPolicy(_policy_params(learn_icp=("metric",)))              # the default Cauchy loss, hard gate
+    only = LearnICPWeightPolicy(policy_params(learn_icp=("metric",)))              # the default Cauchy loss, hard gate
     assert list(only.state_dict().keys()) == ["icp_metric"] + keys and only.icp_metric.item() == 1.0
     for bad, msg in ((dict(learn_icp=("trim_dist",)), "icp_trim='tanh'"),
                      (dict(learn_icp=("tanh_steepness",)), "icp_trim='tanh'"),
@@ -313,12 +304,12 @@ def test_policy_learn_icp_parameters_and_errors():
                      (dict(learn_icp=("metric",), icp_loss_fn={"name": "l2"}), "robust loss"),
                      (dict(learn_icp=("tolerance",), icp_trim="tanh"), "unknown name")):
         with pytest.raises(ValueError, match=msg):
-            LearnICPWeightPolicy(_policy_params(**bad))
+            LearnICPWeightPolicy(policy_params(**bad))
 
 
 def test_policy_hands_the_parameters_to_the_right_instance():
     from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-    m = LearnICPWeightPolicy(_policy_params(icp_trim="tanh", learn_icp=("metric", "trim_dist", "tanh_steepness")))
+    m = LearnICPWeightPolicy(policy_params(icp_trim="tanh", learn_icp=("metric", "trim_dist", "tanh_steepness")))
     seen = []
 
     def fake(name):

@@ -1,12 +1,12 @@
 """CPU: the Geman-McClure and Welsch kernels of the dICP (DESIGN.md §3 I3, I7, I7'').  The host plumbing -- the two codes in the
 header, the binding and the C ABI's parameter validation, dICP.ICP's mapping of the names, the policy's ``learn_icp=("metric",)``
--- and the restatement tests/dicp_robust_ref.py: its bits against tests/dicp_hyper_ref.py's for the kernels that existed,
-Geman-McClure as the bit-exact square of Cauchy, the closed forms of the new chains against fp64 autograd, fp64 finite
+-- and the restatement tests/dicp_restatement.py: its bits against oracle.dicp_ref's under the hard gate for the kernels the
+oracle has, Geman-McClure as the bit-exact square of Cauchy, the closed forms of the new chains against fp64 autograd, fp64 finite
 differences, and the awake figures of tests/test_gpu_robust_kernels.py's cases on the restatement's free run, so that a
 drifting input fails here, without a GPU.
 
-Awake figures of a run (that file's ``assert_awake``): no pair froze; in every iteration at least 30 % of the real points pass
-the gate and have 0.05 < rho < 0.95; the scale's gradient max_b |g_b| / S_b >= 0.03.  Free run, all six cases, nearest
+Awake figures of a run (``assert_awake`` of tests/dicp_cases.py): no pair froze; in every iteration at least 30 % of the real
+points pass the gate and have 0.05 < rho < 0.95; the scale's gradient max_b |g_b| / S_b >= 0.03.  Free run, all six cases, nearest
 correspondences with k = (k0, k0) and (k0, 1.3 k0), soft correspondences (4 and 8 rows) with tau = (0.25, 0.25) and (0.25, 0.4):
 band share per iteration 0.32 (pt2pl Welsch dim 2, first iteration) to 0.95, the awake ratio's maximum over the pairs 0.077
 (pt2pt Geman-McClure dim 2, 8 soft rows) to 0.518, the smallest single pair 0.036, the smallest step norm 0.0095 against the
@@ -23,11 +23,12 @@ import torch
 from mm_masking_amd import _lib, synthetic
 from mm_masking_amd.dICP.ICP import ICP
 
-from dicp_hyper_ref import ICPHyperRef
-from dicp_robust_ref import ICPRobustRef, closed_form_kbar, closed_form_r2bar, per_point_terms
-from test_gpu_robust_kernels import CASES as GPU_CASES, IDS as GPU_IDS, PER_PAIR_TAU, assert_awake, k_values, reference
-from test_gpu_softmin import TAU, _inputs as _gpu_inputs
-from test_icp_hyper_cpu import _policy_params
+from oracle.dicp_ref import ICPRef
+
+from dicp_cases import (K_MULT, NAMES, PER_PAIR_TAU, ROBUST_CASES as GPU_CASES, ROBUST_IDS as GPU_IDS, ROBUST_TRIM, TAU, TOL,
+                        assert_awake, inputs, policy_params, reference)
+from dicp_cases import K as GPU_K
+from dicp_restatement import ICPRestatement, closed_form_r2bar, closed_form_sums, per_point_terms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"geman_mcclure": 3, "welsch": 4}
@@ -98,12 +99,12 @@ def test_icp_maps_the_names_and_refuses_the_others():
 def test_policy_learns_the_metric_of_the_new_kernels():
     from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
     for name in NEW:
-        m = LearnICPWeightPolicy(_policy_params(icp_loss_fn={"name": name, "metric": 0.5}, learn_icp=("metric",)))
+        m = LearnICPWeightPolicy(policy_params(icp_loss_fn={"name": name, "metric": 0.5}, learn_icp=("metric",)))
         assert [n for n, _ in m.named_parameters() if n.startswith("icp_")] == ["icp_metric"]
         assert m.icp_metric.item() == 0.5 and m.icp_metric.requires_grad
     for loss_fn in (None, {"name": "l2"}, {"name": "tukey", "metric": 1.0}):
         with pytest.raises(ValueError, match="robust loss.*'cauchy', 'huber', 'geman_mcclure' or 'welsch'"):
-            LearnICPWeightPolicy(_policy_params(icp_loss_fn=loss_fn, learn_icp=("metric",)))
+            LearnICPWeightPolicy(policy_params(icp_loss_fn=loss_fn, learn_icp=("metric",)))
 
 
 # ----------------------------------------------------------------------------- the restatement
@@ -119,35 +120,40 @@ def _inputs(dim, noise):
     return torch.from_numpy(np.stack(S)), torch.from_numpy(np.stack(Tg)), torch.from_numpy(w), T0, G
 
 
-@pytest.mark.parametrize("icp_type,loss,k,dim,noise,soft", [("pt2pt", "cauchy", 0.5, 2, 0.01, True), ("pt2pl", "huber", 0.1, 2, 0.15, False),
-                                                            ("pt2pl", None, 1.0, 3, 0.15, True), ("pt2pt", "cauchy", 0.5, 3, 0.01, False)],
-                         ids=["cauchy-tanh", "huber-hard", "none-tanh", "cauchy-hard"])
-def test_existing_kernels_are_the_hyper_restatement_bit_for_bit(icp_type, loss, k, dim, noise, soft):
-    src, tgt, w, T0, G = _inputs(dim, noise)
-    vals = [torch.tensor([v, v * m], dtype=torch.float32) for v, m in zip((k, TRIM, STEEP), (1.3, 1.15, 0.8))]
-    outs = []
-    for cls in (ICPHyperRef, ICPRobustRef):
-        leaves = [v.clone().requires_grad_(True) for v in (src, tgt, w, T0)]
-        hl = [v.clone().requires_grad_(True) for v in vals]
-        out = cls(icp_type, differentiable=True, max_iterations=K, tolerance=1e-9, soft=soft).icp(
-            leaves[0], leaves[1], T_init=leaves[3], weight=leaves[2], k=hl[0], trim_dist=hl[1], trim_steep=hl[2], loss_name=loss, dim=dim)
-        (out["T"] * G).sum().backward()
-        outs.append((out, leaves + hl))
-    (a, la), (b, lb) = outs
-    assert a["num_iter"] == b["num_iter"] == K and torch.equal(a["T"], b["T"])
-    for name in ("idx", "T", "delta", "keep", "A", "b", "huber_out", "d2"):
-        for x, y in zip(a["hist"][name], b["hist"][name]):
-            assert torch.equal(x, y), name
-    for ta, tb in zip(a["hist"]["terms"], b["hist"]["terms"]):
-        assert torch.equal(ta["w"], tb["w"]) and torch.equal(ta["rho"], tb["rho"]) and torch.equal(ta["w"].grad, tb["w"].grad)
-    for x, y in zip(la, lb):
-        assert (x.grad is None) == (y.grad is None) and (x.grad is None or torch.equal(x.grad, y.grad))
+@pytest.mark.parametrize("loss", [None, ("cauchy", 0.5), ("huber", 0.1)], ids=["none", "cauchy", "huber"])
+@pytest.mark.parametrize("icp_type,dim", [("pt2pt", 2), ("pt2pl", 2), ("pt2pt", 3), ("pt2pl", 3)])
+def test_hard_gate_is_the_oracle_bit_for_bit(icp_type, dim, loss):
+    """On the clouds of tests/dicp_cases.py (B = 2, 320 x 730, K = 4) with trim distances 0.6 and 1.0, the restatement with the
+    hard gate returns what oracle.dicp_ref.ICPRef returns: T, num_iter, the histories of idx, T and delta and the gradients of
+    source, target, weight and T_init, in every bit."""
+    inp = inputs((icp_type, loss, dim, 0.15 if icp_type == "pt2pl" else 0.01, 0.0))
+    for trim in (0.6, 1.0):
+        outs = []
+        for oracle in (True, False):
+            x = [v.clone().requires_grad_(True) for v in inp["x"]]
+            kw = dict(T_init=x[3], weight=x[2], trim_dist=trim, dim=dim)
+            if oracle:
+                out = ICPRef(icp_type, differentiable=True, max_iterations=GPU_K, tolerance=TOL).icp(x[0], x[1], loss_fn=inp["loss_fn"],
+                                                                                                     **kw)
+            else:
+                out = ICPRestatement(icp_type, differentiable=True, max_iterations=GPU_K, tolerance=TOL, soft=False).icp(
+                    x[0], x[1], loss_name=loss and loss[0], k=loss[1] if loss else 1.0, **kw)
+            (out["T"] * inp["G"]).sum().backward()
+            outs.append((out, x))
+        (a, xa), (b, xb) = outs
+        assert a["num_iter"] == b["num_iter"] == GPU_K and torch.equal(a["T"], b["T"])
+        for name in ("idx", "T", "delta"):
+            assert len(a["hist"][name]) == len(b["hist"][name])
+            for p, q in zip(a["hist"][name], b["hist"][name]):
+                assert torch.equal(p, q), (name, trim)
+        for name, p, q in zip(NAMES, xa, xb):
+            assert p.grad is not None and p.grad.abs().max() > 0 and torch.equal(p.grad, q.grad), (name, trim)
 
 
 @pytest.mark.parametrize("icp_type,dim", [("pt2pt", 2), ("pt2pl", 3)])
 def test_geman_mcclure_is_the_bit_exact_square_of_cauchy(icp_type, dim):
     src, tgt, w, T0, _ = _inputs(dim, 0.15)
-    idx = ICPRobustRef(icp_type, differentiable=False, max_iterations=1).icp(src, tgt, T_init=T0, weight=w, k=0.3, trim_dist=TRIM,
+    idx = ICPRestatement(icp_type, differentiable=False, max_iterations=1).icp(src, tgt, T_init=T0, weight=w, k=0.3, trim_dist=TRIM,
                                                                             loss_name="cauchy", dim=dim)["hist"]["idx"][0]
     one = torch.ones(1, 1)
     terms = {name: per_point_terms(src, tgt, T0, idx, w, icp_type, name, one * 0.3, one * TRIM, one * STEEP, dim, True)
@@ -175,11 +181,11 @@ def _fixed_run(case, k_shape, dtype=torch.float64):
     trim = TRIM if soft else 5.0
     src, tgt, w, T0, G = _inputs(dim, noise)
     ks = torch.tensor([k, k * 1.3])
-    free = ICPRobustRef(icp_type, differentiable=False, max_iterations=K, tolerance=1e-12, soft=soft).icp(
+    free = ICPRestatement(icp_type, differentiable=False, max_iterations=K, tolerance=1e-12, soft=soft).icp(
         src, tgt, T_init=T0, weight=w, k=ks, trim_dist=trim, trim_steep=STEEP, loss_name=loss, dim=dim)
     fixed = free["hist"]["idx"]
     assert len(fixed) == K
-    ref = ICPRobustRef(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12, soft=soft)
+    ref = ICPRestatement(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12, soft=soft)
 
     def run(s, t, ww, T, kk):
         return ref.icp(s, t, T_init=T, weight=ww, k=kk, trim_dist=trim, trim_steep=STEEP, loss_name=loss, dim=dim, dtype=dtype,
@@ -201,7 +207,7 @@ def test_closed_forms_match_autograd(case):
     out = run(*leaves)
     (out["T"] * G).sum().backward()
     kv = leaves[4].detach().numpy()
-    got, ref = closed_form_kbar(out["hist"], kv, loss), leaves[4].grad.numpy()
+    got, ref = closed_form_sums(out["hist"], kv, TRIM if soft else 5.0, STEEP, loss, soft)[0], leaves[4].grad.numpy()
     scale = np.abs(ref).max()
     assert scale > 0 and np.abs(got - ref).max() <= 1e-12 * scale, (np.abs(got - ref).max(), scale)
     assert (np.abs(ref) > 1e-3 * scale).sum() >= 20             # and not a handful of points only (the hard gate trims many)
@@ -263,11 +269,9 @@ def test_gpu_cases_are_awake_on_the_free_run(ci):
     """tests/test_gpu_robust_kernels.py's cases on the restatement's free run (its own correspondences): every configuration
     that file replays keeps its conditions -- no pair froze, the band share, the scale's awake ratio."""
     case = GPU_CASES[ci]
-    inp = _gpu_inputs(case)
-    for per_pair in (False, True):
-        assert_awake(reference(case, inp, k_values(case, per_pair), hyper_leaves=per_pair and case[4] > 0),
-                     "%s nearest k %s" % (GPU_IDS[ci], k_values(case, per_pair).tolist()))
+    for mult in (1.0, K_MULT):
+        assert_awake(reference(case, ROBUST_TRIM, mult=(mult, 1.0, 1.0)), "%s nearest k x %s" % (GPU_IDS[ci], (1.0, mult)))
     for soft_k in (4, 8):
         for taus in ((TAU, TAU), PER_PAIR_TAU):
-            assert_awake(reference(case, inp, k_values(case, False), soft_k=soft_k, taus=taus),
+            assert_awake(reference(case, ROBUST_TRIM, soft_k=soft_k, taus=taus),
                          "%s softmin %d tau %s" % (GPU_IDS[ci], soft_k, taus))

@@ -1,4 +1,4 @@
-"""CPU: the soft (tanh) trim gate of the dICP (DESIGN.md §3 I3', I7').  The restatement tests/dicp_soft_trim_ref.py -- known
+"""CPU: the soft (tanh) trim gate of the dICP (DESIGN.md §3 I3', I7').  The restatement tests/dicp_restatement.py -- known
 answers of the gate, its hard limit against oracle.dicp_ref, finite differences of its autograd in fp64 -- and the host
 plumbing of the option: mmk_icp_params.trim_steep / mmk_icp_params_bytes, the argument checks, dICP.ICP's YAML keys and
 attributes, and the policy's params["icp_trim"] / ["icp_tanh_steepness"]."""
@@ -14,7 +14,7 @@ from mm_masking_amd import _lib, synthetic
 from mm_masking_amd.dICP.ICP import ICP
 from oracle import dicp_ref
 
-from dicp_soft_trim_ref import ICPSoftRef, band_share, soft_keep
+from dicp_restatement import ICPRestatement, band_share, soft_keep
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -59,11 +59,14 @@ def test_gate_off_is_the_oracle_and_steep_gate_is_the_hard_gate(icp_type, dim):
     trim_dist: every gate is exactly 0 or 1, so poses and index histories are the hard oracle's, bit for bit."""
     src, tgt, w = _point_grad_inputs(dim)
     loss_fn, K = {"name": "cauchy", "metric": 1.0}, 3
-    kw = dict(T_init=torch.eye(4)[None], weight=w.float(), loss_fn=loss_fn, dim=dim)
+    kw = dict(T_init=torch.eye(4)[None], weight=w.float(), dim=dim)
+    loss = dict(loss_name=loss_fn["name"], k=loss_fn["metric"])
     for trim in (5.0,):               # the inputs' own setting
-        hard = dicp_ref.ICPRef(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12).icp(src, tgt, trim_dist=trim, **kw)
-        off = ICPSoftRef(icp_type, max_iterations=K, tolerance=1e-12, trim_steep=0.0).icp(src, tgt, trim_dist=trim, **kw)
-        steep = ICPSoftRef(icp_type, max_iterations=K, tolerance=1e-12, trim_steep=1e4).icp(src, tgt, trim_dist=trim, **kw)
+        hard = dicp_ref.ICPRef(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12).icp(src, tgt, trim_dist=trim,
+                                                                                                     loss_fn=loss_fn, **kw)
+        off = ICPRestatement(icp_type, max_iterations=K, tolerance=1e-12, soft=False).icp(src, tgt, trim_dist=trim, **loss, **kw)
+        steep = ICPRestatement(icp_type, max_iterations=K, tolerance=1e-12, soft=True).icp(src, tgt, trim_dist=trim, trim_steep=1e4,
+                                                                                           **loss, **kw)
         d = torch.sqrt(torch.stack(steep["hist"]["d2"]))
         assert (d - trim).abs().min() >= 1e-2, float((d - trim).abs().min())
         kept = torch.stack(steep["hist"]["keep"])
@@ -90,13 +93,14 @@ def test_soft_gate_gradients_finite_difference(icp_type, dim):
     w0 = torch.from_numpy(np.random.default_rng(3).uniform(0.2, 1.0, (1, n)))
     G = torch.from_numpy(np.random.default_rng(4).normal(size=(1, 4, 4)))
     loss_fn = {"name": "cauchy", "metric": 1.0}
-    ref = ICPSoftRef(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12, trim_steep=steepness)
-    free = ref.icp(src, tgt, T_init=torch.eye(4)[None], weight=w0.float(), trim_dist=trim, loss_fn=loss_fn, dim=dim)
+    ref = ICPRestatement(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12, soft=True)
+    hyper = dict(k=loss_fn["metric"], trim_dist=trim, trim_steep=steepness, loss_name=loss_fn["name"], dim=dim)
+    free = ref.icp(src, tgt, T_init=torch.eye(4)[None], weight=w0.float(), **hyper)
     fixed = free["hist"]["idx"]
     assert len(fixed) == K and int(fixed[0][0, 5]) == 11 and float(free["hist"]["d2"][0][0, 5]) == 0.0
 
     def run(s, t, w, T0):
-        return ref.icp(s, t, T_init=T0, weight=w, trim_dist=trim, loss_fn=loss_fn, dim=dim, dtype=torch.float64, fixed_idx=fixed)
+        return ref.icp(s, t, T_init=T0, weight=w, dtype=torch.float64, fixed_idx=fixed, **hyper)
 
     def f(s, t, w, T0):
         return (run(s, t, w, T0)["T"] * G).sum()

@@ -1,7 +1,7 @@
 """CPU: soft correspondences of the dICP (DESIGN.md §3 I2', I3''', I7''').  The host plumbing of the option -- the new C
 entries in the header and the binding, the pinned version and struct size, the argument checks, dICP.ICP's YAML keys and
-attributes, the policy's keys, the refused combinations -- and the restatement tests/dicp_softmin_ref.py: its k-NN, its
-nearest limit against tests/dicp_soft_trim_ref.py bit for bit, the closed forms of I7''' against its autograd, and fp64
+attributes, the policy's keys, the refused combinations -- and the restatement tests/dicp_restatement.py: its k-NN, the
+nearest limit of its soft loop against its nearest loop bit for bit, the closed forms of I7''' against its autograd, and fp64
 finite differences of source, target, weight and T_init."""
 import ctypes
 import os
@@ -14,8 +14,7 @@ import torch
 from mm_masking_amd import _lib, synthetic
 from mm_masking_amd.dICP.ICP import ICP
 
-from dicp_soft_trim_ref import ICPSoftRef
-from dicp_softmin_ref import ICPSoftminRef, knn_ref, knn_ref_batch, soft_backward_closed_form, soft_rows
+from dicp_restatement import ICPRestatement, knn_ref, knn_ref_batch, soft_backward_closed_form, soft_rows
 from knn_normals_ref import nn_dist_f32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -202,18 +201,17 @@ def test_knn_ref_is_sorted_exact_and_breaks_ties_to_the_lowest_index():
 @pytest.mark.parametrize("icp_type,dim,loss", [("pt2pt", 2, ("cauchy", 0.5)), ("pt2pl", 3, ("huber", 0.1)), ("pt2pl", 2, None)])
 def test_nearest_limit_of_the_restatement_is_the_hard_restatement_bit_for_bit(icp_type, dim, loss):
     """tau so small that (d_1 - d_0) / tau >= 120 on every real row of every iteration (asserted): every e_j beyond slot 0
-    underflows to exactly 0, the virtual row is the correspondent, and the pose is ICPSoftRef's bit for bit.  (The zero
+    underflows to exactly 0, the virtual row is the correspondent, and the pose is the nearest loop's bit for bit.  (The zero
     source rows share one point and may tie; they carry weight 0.)"""
     src, tgt, w = _clouds(dim)
     n_real = 60
-    loss_fn = None if loss is None else {"name": loss[0], "metric": loss[1]}
     T0 = torch.eye(4).repeat(2, 1, 1)
     T0[:, 0, 3] += 0.1
     K, tau = 3, 1e-9
-    soft = ICPSoftminRef(icp_type, differentiable=False, max_iterations=K, tolerance=1e-9, k=4, tau=tau)
-    hard = ICPSoftRef(icp_type, differentiable=False, max_iterations=K, tolerance=1e-9)
-    a = soft.icp(src, tgt, T_init=T0, weight=w, trim_dist=1.0, loss_fn=loss_fn, dim=dim)
-    b = hard.icp(src, tgt, T_init=T0, weight=w, trim_dist=1.0, loss_fn=loss_fn, dim=dim)
+    ref = ICPRestatement(icp_type, differentiable=False, max_iterations=K, tolerance=1e-9)
+    kw = dict(T_init=T0, weight=w, trim_dist=1.0, loss_name=loss and loss[0], k=loss[1] if loss else 1.0, dim=dim)
+    a = ref.icp_soft(src, tgt, tau, softmin_k=4, **kw)
+    b = ref.icp(src, tgt, **kw)
     assert a["num_iter"] == b["num_iter"] == K
     for it in range(K):
         d = a["hist"]["d"][it][:, :n_real].double()
@@ -223,15 +221,14 @@ def test_nearest_limit_of_the_restatement_is_the_hard_restatement_bit_for_bit(ic
         assert torch.equal(a["hist"]["T"][it + 1], b["hist"]["T"][it + 1])
     assert torch.equal(a["T"], b["T"])
     # and away from the limit the mode is not a no-op
-    c = ICPSoftminRef(icp_type, differentiable=False, max_iterations=K, tolerance=1e-9, k=4, tau=0.25).icp(
-        src, tgt, T_init=T0, weight=w, trim_dist=1.0, loss_fn=loss_fn, dim=dim)
+    c = ref.icp_soft(src, tgt, 0.25, softmin_k=4, **kw)
     assert not torch.equal(c["T"], b["T"])
     assert (c["hist"]["a"][0][:, :n_real, 0] < 0.9).any()          # some points do share their weight among neighbours
 
 
 @pytest.mark.parametrize("dim,with_normals", [(2, False), (2, True), (3, False), (3, True)])
 def test_closed_forms_of_the_backward_against_autograd(dim, with_normals):
-    """I7''' in numpy (tests/dicp_softmin_ref.py::soft_backward_closed_form) against autograd through soft_rows, fp64: both
+    """I7''' in numpy (tests/dicp_restatement.py::soft_backward_closed_form) against autograd through soft_rows, fp64: both
     are exact derivatives of the same expression, so they agree to rounding -- 1e-12 of the largest magnitude."""
     rng = np.random.default_rng(4 + dim)
     N, M, k, tau = 30, 200, 5, 0.25                              # N k < M: some target is nobody's neighbour
@@ -242,8 +239,8 @@ def test_closed_forms_of_the_backward_against_autograd(dim, with_normals):
     assert ((a > 0.01) & (a < 0.99)).double().mean() > 0.5      # the weights are spread: the softmin is awake
     vbar = torch.from_numpy(rng.normal(size=(1, N, 6)))
     (virt * vbar).sum().backward()
-    gt, pbar = soft_backward_closed_form(tgt.detach().numpy()[0], p.detach().numpy()[0], idx.numpy()[0], tau, dim, with_normals,
-                                         vbar.numpy()[0])
+    gt, pbar, _ = soft_backward_closed_form(tgt.detach().numpy()[0], p.detach().numpy()[0], idx.numpy()[0], tau, dim, with_normals,
+                                            vbar.numpy()[0])
     for name, got, ref in (("target", gt, tgt.grad.numpy()[0]), ("p", pbar, p.grad.numpy()[0])):
         scale = np.abs(ref).max()
         assert scale > 0 and np.abs(got - ref).max() <= 1e-12 * scale, (name, np.abs(got - ref).max(), scale)
@@ -264,17 +261,16 @@ def test_fp64_finite_differences(icp_type, dim, loss, steep, tau):
     K, k, trim = 2, 4, 5.0                           # the hard gate (steep 0) keeps every point: no FD across it
     T0 = torch.eye(4, dtype=torch.float64).repeat(1, 1, 1)
     T0[:, 0, 3] += 0.1
-    loss_fn = {"name": loss[0], "metric": loss[1]}
+    hyper = dict(softmin_k=k, trim_dist=trim, trim_steep=steep, loss_name=loss[0], k=loss[1], dim=dim)
     G = torch.from_numpy(np.random.default_rng(3).normal(size=(1, 4, 4)))
-    free = ICPSoftminRef(icp_type, differentiable=False, max_iterations=K, tolerance=1e-12, k=k, tau=tau, trim_steep=steep).icp(
-        src, tgt, T_init=T0, weight=w, trim_dist=trim, loss_fn=loss_fn, dim=dim)
+    free = ICPRestatement(icp_type, differentiable=False, max_iterations=K, tolerance=1e-12, soft=steep > 0).icp_soft(
+        src, tgt, tau, T_init=T0, weight=w, **hyper)
     fixed = [i.clone() for i in free["hist"]["idx"]]
     assert (free["hist"]["a"][0][..., 0] < 0.9).double().mean() >= 0.3
-    ref = ICPSoftminRef(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12, k=k, tau=tau, trim_steep=steep)
+    ref = ICPRestatement(icp_type, differentiable=True, max_iterations=K, tolerance=1e-12, soft=steep > 0)
 
     def L(x):
-        out = ref.icp(x[0], x[1], T_init=x[3], weight=x[2], trim_dist=trim, loss_fn=loss_fn, dim=dim, dtype=torch.float64,
-                      fixed_idx=fixed)
+        out = ref.icp_soft(x[0], x[1], tau, T_init=x[3], weight=x[2], dtype=torch.float64, fixed_idx=fixed, **hyper)
         return (out["T"] * G).sum()
 
     x0 = [src.double(), tgt.double(), w.double(), T0]

@@ -1,13 +1,13 @@
 """CPU: the device-resident, learnable soft-min temperature of the dICP (DESIGN.md §3 I3⁗, I7⁗).  The host plumbing -- the
 three C entries in the header and the binding, their argument checks, the older entries' sizes, dICP.ICP's validation of a
 tensor ``softmin_temp``, the refused combinations, the policy's ``learn_icp=("softmin_temp",)`` -- and the restatement
-tests/dicp_softmin_temp_ref.py: its bits against tests/dicp_softmin_ref.py's for equal values, the closed form of tau-bar
+tests/dicp_restatement.py: the bits of a number temperature for a tensor of equal values, the closed form of tau-bar
 against fp64 autograd, and the awake ratios of the GPU test's cases on the restatement's free run, so that a drifting input
 fails here, without a GPU.
 
 Awake ratio of a run: max_b |g_b| / S_b, g_b the pair's tau gradient and S_b the sum of the magnitudes of its per-point
-contributions; the threshold 0.03 is tests/test_gpu_icp_hyper.py's.  Free-running neighbours, shapes and cases of
-tests/test_gpu_softmin.py, all five cases, k in {4, 8}: with tau = (0.25, 0.4) the smallest max_b ratio is 0.10 and the
+contributions; the threshold 0.03 is tests/test_gpu_icp_hyper.py's.  Free-running neighbours, shapes and soft-min cases of
+tests/dicp_cases.py, all five cases, k in {4, 8}: with tau = (0.25, 0.4) the smallest max_b ratio is 0.10 and the
 smallest single pair 0.055; with (0.25, 0.25) the smallest max_b ratio is 0.055 (pt2pl, Cauchy, dim 3, k = 8).
 """
 import ctypes
@@ -22,9 +22,8 @@ import torch
 from mm_masking_amd import _lib
 from mm_masking_amd.dICP.ICP import ICP
 
-from dicp_softmin_ref import knn_ref_batch, soft_rows
-from dicp_softmin_temp_ref import ICPSoftminTempRef, pair_sums, soft_rows_t, tau_leaf, temp_bar_closed_form
-from test_gpu_softmin import B, CASES, IDS, K, N, TOL, TRIM, _inputs
+from dicp_cases import B, K, SOFTMIN_CASES as CASES, SOFTMIN_IDS as IDS, SOFTMIN_TRIM as TRIM, reference
+from dicp_restatement import knn_ref_batch, soft_backward_closed_form, soft_rows
 
 icp_mod = importlib.import_module("mm_masking_amd.dICP.ICP")        # (the package re-exports the class under the module's name)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -202,14 +201,14 @@ def test_equal_values_give_the_bits_of_the_number_restatement():
         idx = torch.from_numpy(knn_ref_batch(p.numpy(), tgt.numpy(), 5, dim)[0])
         P = [p[..., c] for c in range(dim)]
         want = soft_rows(tgt, P, idx, tau, dim, with_normals)
-        got = soft_rows_t(tgt, P, idx, torch.full((2, 40), tau, dtype=torch.float32), dim, with_normals)
+        got = soft_rows(tgt, P, idx, torch.full((2, 40), tau, dtype=torch.float32), dim, with_normals)
         for a, b in zip(got, want):
             assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("dim,with_normals", [(2, False), (2, True), (3, False), (3, True)])
 def test_closed_form_of_tau_bar_against_autograd(dim, with_normals):
-    """I7⁗ in numpy (temp_bar_closed_form) against autograd through soft_rows_t, fp64, with a temperature of its own per
+    """I7⁗ in numpy (soft_backward_closed_form's tau-bar) against autograd through soft_rows, fp64, with a temperature of its own per
     point: both are exact derivatives of the same expression, so they agree to rounding -- 1e-12 of the largest magnitude."""
     rng = np.random.default_rng(14 + dim)
     N_, M_, k = 30, 200, 5
@@ -217,11 +216,12 @@ def test_closed_form_of_tau_bar_against_autograd(dim, with_normals):
     p = torch.from_numpy(rng.uniform(-2, 2, (1, N_, dim)))
     tau = torch.from_numpy(rng.uniform(0.15, 0.5, (1, N_))).requires_grad_(True)
     idx = torch.from_numpy(knn_ref_batch(p.float().numpy(), tgt.float().numpy(), k, dim)[0])
-    virt, a, d = soft_rows_t(tgt, [p[..., c] for c in range(dim)], idx, tau, dim, with_normals)
+    virt, a, d = soft_rows(tgt, [p[..., c] for c in range(dim)], idx, tau, dim, with_normals)
     assert ((a > 0.01) & (a < 0.99)).double().mean() > 0.5      # the weights are spread: the soft-min is awake
     vbar = torch.from_numpy(rng.normal(size=(1, N_, 6)))
     (virt * vbar).sum().backward()
-    got = temp_bar_closed_form(tgt.numpy()[0], p.numpy()[0], idx.numpy()[0], tau.detach().numpy()[0], dim, with_normals, vbar.numpy()[0])
+    got = soft_backward_closed_form(tgt.numpy()[0], p.numpy()[0], idx.numpy()[0], tau.detach().numpy()[0], dim, with_normals,
+                                    vbar.numpy()[0])[2]
     ref = tau.grad.numpy()[0]
     scale = np.abs(ref).max()
     assert scale > 0 and np.abs(got - ref).max() <= 1e-12 * scale, (np.abs(got - ref).max(), scale)
@@ -234,16 +234,10 @@ def test_tau_gradient_of_the_gpu_cases_is_awake_on_the_free_run(ci, k):
     """The cases of tests/test_gpu_softmin_temp.py on the restatement's free run (its own neighbours): for the per-pair
     temperatures (0.25, 0.4) and the equal ones (0.25, 0.25), some pair's |g_b| is at least 0.03 of the sum of the magnitudes
     of its per-point contributions, and no pair froze."""
-    case = CASES[ci]
-    inp = _inputs(case)
     for taus in ((0.25, 0.4), (0.25, 0.25)):
-        leaf = tau_leaf(taus, N)
-        ref = ICPSoftminTempRef(case[0], differentiable=True, max_iterations=K, tolerance=TOL, k=k, trim_steep=case[4])
-        out = ref.icp(inp["x"][0], inp["x"][1], leaf, T_init=inp["x"][3], weight=inp["x"][2], trim_dist=TRIM, loss_fn=inp["loss_fn"],
-                      dim=case[2])
+        out = reference(CASES[ci], TRIM, soft_k=k, taus=taus)
         assert out["num_iter"] == K and all(bool(a.all()) for a in out["hist"]["active"])
-        (out["T"] * inp["G"]).sum().backward()
-        g, S = pair_sums(leaf.grad)
+        g, S = out["grads"]["tau"], out["S"]
         ratios = (g.abs() / S).tolist()
         print("AWAKE tau %s k %d: |g_b| / S_b per pair %s" % (taus, k, ["%.3f" % r for r in ratios]))
         assert len(ratios) == B and torch.isfinite(g).all() and max(ratios) >= 0.03, ratios
