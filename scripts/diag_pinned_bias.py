@@ -8,13 +8,13 @@ import torch
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 from mm_masking_amd import unet_hip as uh
 import test_gpu_unet_kernels as T
-DEV = torch.device("cuda:0")
+from support import DEV, policy
 B, H, W = 3, 64, 160
 watch = sys.argv[1:] or ["encoder.1.2.bias"]
 
 
 def run(drop, seed):
-    model = T._policy(drop, torch.float32)
+    model = policy(DEV, 11, dropout=drop, amp_dtype=torch.float32, unet_backend="torch")
     model.train()
     g = torch.Generator().manual_seed(1)
     x = torch.rand(B, 1, H, W, generator=g).to(DEV)

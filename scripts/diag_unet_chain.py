@@ -1,13 +1,12 @@
 import os, sys, torch, torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_gpu_unet_kernels as T
+from support import DEV, _Q, policy
 from mm_masking_amd import unet_hip as uh
-DEV = torch.device("cuda:0")
 H = 64
-model = T._policy(0.0, torch.float32); model.train()
+model = policy(DEV, 11, dropout=0.0, amp_dtype=torch.float32, unet_backend="torch"); model.train()
 g = torch.Generator().manual_seed(1)
 x = torch.rand(2, 1, H, H, generator=g).to(DEV); gsel = torch.randn(2, H, H, generator=g).to(DEV)
-q = T._Q.apply
+q = _Q.apply
 keep = {}
 def conv(t, m, name):
     y = q(F.relu(F.conv2d(t, m.weight.to(torch.bfloat16).float(), m.bias, padding=1))); y.retain_grad(); keep[name] = y; return y

@@ -1,10 +1,10 @@
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_gpu_unet_kernels as T
+from support import DEV, policy
 from mm_masking_amd import unet_hip as uh
-DEV = torch.device("cuda:0")
 H = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-model = T._policy(0.0, torch.float32); model.train()
+model = policy(DEV, 11, dropout=0.0, amp_dtype=torch.float32, unet_backend="torch"); model.train()
 g = torch.Generator().manual_seed(1)
 x = torch.rand(2, 1, H, H, generator=g).to(DEV); gsel = torch.randn(2, H, H, generator=g).to(DEV)
 ref = T._emulated_unet(model, x); (ref * gsel).sum().backward()

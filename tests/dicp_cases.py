@@ -14,7 +14,6 @@ with S_b the sum of the magnitudes of pair b's contributions.  Leaves of equal v
 (tests/test_icp_hyper_cpu.py, tests/test_softmin_temp_cpu.py).
 """
 import numpy as np
-import pytest
 import torch
 
 from mm_masking_amd import synthetic
@@ -22,6 +21,7 @@ from mm_masking_amd.dICP.ICP import ICP
 from oracle.dicp_ref import transform_points
 
 from dicp_restatement import ICPRestatement, band_share, knn_ref_batch, pair_sums, tau_leaf
+from support import nn_engine  # noqa: F401  (a fixture, re-exported to the dICP test files)
 
 B, N_REAL, N_ZERO, M_REAL, M_PAD, K, TOL = 2, 300, 20, 700, 30, 4, 1e-9
 N, M = N_REAL + N_ZERO, M_REAL + M_PAD
@@ -63,13 +63,6 @@ ROBUST_TRIM = 1.0
 
 REAL = torch.zeros(B, N, dtype=torch.bool)
 REAL[:, :N_REAL] = True
-
-
-@pytest.fixture(params=["brute", "grid"])
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
 
 
 def inputs(case, coincident=False):

@@ -1,31 +1,25 @@
 """CPU: learnable GO-CFAR thresholds -- the C ABI of mmk_cfar_mask_p / mmk_cfar_mask_bwd_p (declared, exported, host-side
 argument and workspace checks, no launch), the golden fixture tests/golden/cfar_params.npz (the conditions its generator
-asserts, re-asserted on the stored arrays; its fp64 threshold gradients against an fp64 numpy restatement that lives here),
-``radar_utils.cfar_mask``'s shape check, and the policy switch params["learn_cfar"].
-
-The restatement (``threshold_grads_f64``; tests/test_gpu_cfar_params.py uses it for shapes that have no golden value):
-    ga = - sum over the kept cells c of [mincol, maxcol) of k_c stat_c,      gb = - sum of k_c,
-    k_c = G_c 0.5 steep (1 - t_c^2),  t_c = tanh(steep (x_c - a stat_c - b) + 2.5),  stat_c = max(left_c, right_c) / w2,
-with kept_c = (0.5 t_c + 0.5 > 0.99), as autograd takes them through radar_utils.py:56-65 of the reference.  Its scale is the
-same sum with |G|: every term then has one sign.
+asserts, re-asserted on the stored arrays; its fp64 threshold gradients against an fp64 numpy restatement),
+``radar_utils.cfar_mask``'s shape check, and the policy switch params["learn_cfar"].  Cases, fixture loader and restatement
+(``threshold_grads_f64``) are in tests/radar_cases.py.
 """
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from mm_masking_amd import _lib
+from radar_cases import CASES, RES, geom_of, load_fixture, per_scan_values, threshold_grads_f64
+from support import ROOT, policy_params
+from make_golden_radar_grads import cfar_terms, cfar_violations  # (radar_cases puts tests/golden on the path)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-from make_golden_radar_grads import cfar_terms, cfar_violations  # noqa: E402
-
+CPU = torch.device("cpu")
+POLICY = {"dropout": 0.0, "amp_dtype": torch.float32, "unet_backend": "torch"}
 NEW = ("mmk_cfar_mask_p", "mmk_cfar_mask_bwd_p_ws_bytes", "mmk_cfar_mask_bwd_p")
-RES = 0.0596
 
 
 @pytest.fixture(scope="module")
@@ -34,62 +28,9 @@ def L():
     return _lib.lib()
 
 
-def load_fixture(golden_dir):
-    """cfar_params.npz plus the inputs it shares with radar_grads.npz (the scans with the fixture's own changes applied)."""
-    g = dict(np.load(os.path.join(golden_dir, "cfar_params.npz")))
-    base = dict(np.load(os.path.join(golden_dir, "radar_grads.npz")))
-    for pre, src in (("cp", "ca_raw"), ("cc", "ch_raw")):
-        raw = base[src].copy()
-        raw.reshape(-1)[g[pre + "_fix_idx"]] = g[pre + "_fix_val"]
-        g[pre + "_raw"] = raw
-    g["cp_G"] = base["ca_G"]
-    for k in ("ch_az", "ch_map", "ch_mu", "ch_mv", "ch_G", "ch_npad", "ch_iters", "ca_grad0", "ca_grad1"):
-        g[k] = base[k]
-    return g
-
-
 @pytest.fixture(scope="module")
 def gold(golden_dir):
     return load_fixture(golden_dir)
-
-
-CASES = ["0s", "0p", "1s", "1p"]
-
-
-def geom_of(gold, key):
-    """Window geometry and steepness of a case's parameter set, as cfar_mask keywords."""
-    if key[0] == "0":
-        return {}
-    w, g, s = gold["cp_geom1"]
-    return {"width": int(w), "guard": int(g), "steep_fact": float(s)}
-
-
-def per_scan_values(gold, key, B):
-    """The thresholds of a case as (B,) fp64 arrays holding the stored fp32 numbers."""
-    a, b = gold["cp_a" + key], gold["cp_b" + key]
-    return np.broadcast_to(a.astype(np.float64), (B,)), np.broadcast_to(b.astype(np.float64), (B,))
-
-
-def threshold_grads_f64(raw, G, a, b, res=RES, **geom):
-    """(ga, gb) per scan in fp64 for the scans ``raw`` (B,A,R) with per-scan thresholds ``a``, ``b`` (B,).  m_raw, the column
-    range and the gate come from the generator's cfar_terms; the window statistic is formed here in fp64."""
-    B = raw.shape[0]
-    ga, gb = np.zeros(B), np.zeros(B)
-    G = np.asarray(G, dtype=np.float64)
-    steep = float(geom.get("steep_fact", 10.0))
-    for i in range(B):
-        m_raw, _, _, (w2, guard, mincol, maxcol) = cfar_terms(raw[i], res=res, a_thresh=float(a[i]), b_thresh=float(b[i]), **geom)
-        x = raw[i].astype(np.float64)
-        R = x.shape[-1]
-        cs = np.concatenate([np.zeros(x.shape[:-1] + (1,)), np.cumsum(x, axis=-1)], axis=-1)
-        c = np.arange(mincol, maxcol)
-        left = cs[..., c - guard] - cs[..., c - w2 - guard]
-        right = cs[..., np.minimum(R, c + w2 + guard + 1)] - cs[..., np.minimum(R, c + guard + 1)]
-        stat = np.maximum(left, right) / w2
-        t = 2.0 * m_raw[..., c] - 1.0
-        k = np.where(m_raw[..., c] > 0.99, G[i][..., c] * 0.5 * steep * (1.0 - t * t), 0.0)
-        ga[i], gb[i] = -(k * stat).sum(), -k.sum()
-    return ga, gb
 
 
 # ----------------------------------------------------------------------------- the C ABI
@@ -192,24 +133,16 @@ def test_bad_threshold_shape_raises_before_any_device_use():
 
 
 # ----------------------------------------------------------------------------- the policy
-def _params(**over):
-    from mm_masking_amd import train_icp_weights as trn
-    p = trn.default_params(torch.device("cpu"))
-    p.update({"dropout": 0.0, "amp_dtype": torch.float32, "unet_backend": "torch"})
-    p.update(over)
-    return p
-
-
 def test_policy_learn_cfar_switch(golden_dir, tmp_path):
     from mm_masking_amd import ddp
     from mm_masking_amd import train_icp_weights as trn
     from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
     today = [str(n) for n in np.load(os.path.join(golden_dir, "unet.npz"), allow_pickle=False)["names_a"]]
     for kw in ({}, {"mask_target": "scan"}, {"mask_target": "scan", "learn_cfar": False}):
-        plain = LearnICPWeightPolicy(_params(**kw))
+        plain = LearnICPWeightPolicy(policy_params(CPU, **POLICY, **kw))
         assert list(plain.state_dict().keys()) == today and len(list(plain.parameters())) == 46
         assert not hasattr(plain, "cfar_a") and not plain.learn_cfar
-    model = LearnICPWeightPolicy(_params(mask_target="scan", learn_cfar=True, a_thresh=1.1, b_thresh=0.08))
+    model = LearnICPWeightPolicy(policy_params(CPU, **POLICY, mask_target="scan", learn_cfar=True, a_thresh=1.1, b_thresh=0.08))
     keys = list(model.state_dict().keys())
     assert sorted(set(keys) - set(today)) == ["cfar_a", "cfar_b"] and len(keys) == len(today) + 2
     assert [k for k in keys if k in today] == today
@@ -220,14 +153,14 @@ def test_policy_learn_cfar_switch(golden_dir, tmp_path):
     assert (model.a_thres, model.b_thres) == (1.1, 0.08)        # the fixed values of the CFAR input channel stay
     for kw in ({}, {"mask_target": "weights"}):
         with pytest.raises(ValueError, match="learn_cfar"):
-            LearnICPWeightPolicy(_params(learn_cfar=True, **kw))
+            LearnICPWeightPolicy(policy_params(CPU, **POLICY, learn_cfar=True, **kw))
     # the gradient bucket: the 46-parameter layout has the U-Net's buckets, anything else is one
     assert len(ddp.FlatGradSync(plain).bucket_ranges()) > 1
     sync = ddp.FlatGradSync(model)
     assert len(sync.params) == 48 and sync.bucket_ranges() == [(0, sync.flat.numel())]
     assert sync.flat.numel() == sum(q.numel() for q in plain.parameters()) + 2
     # optimizer and checkpoint pick the two up
-    p = _params(mask_target="scan", learn_cfar=True)
+    p = policy_params(CPU, **POLICY, mask_target="scan", learn_cfar=True)
     opt = trn.make_optimizer(model, p)
     assert sum(len(g["params"]) for g in opt.param_groups) == 48
     for q in model.parameters():

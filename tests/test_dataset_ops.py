@@ -1,20 +1,15 @@
 """Dataset-side tensor ops against golden vectors captured from the reference's
 ICPWeightDataset methods (tests/golden/make_golden.py); CPU only."""
-import os
-
 import numpy as np
 import torch
 
 from mm_masking_amd import icp_weight_dataset as ds
 from mm_masking_amd import synthetic
-
-
-def _g(golden_dir):
-    return np.load(os.path.join(golden_dir, "dataset_ops.npz"), allow_pickle=False)
+from support import load_golden
 
 
 def test_augment_data(golden_dir):
-    g = _g(golden_dir)
+    g = load_golden(golden_dir, "dataset_ops.npz")
     t = lambda k: torch.from_numpy(g[k])
     out = ds.augment_data(t("scan_raw"), t("scan_filt"), t("map6"), t("az"), t("fft"), t("cfar"), angle=float(g["angle"]))
     for got, key in zip(out, ("aug_raw", "aug_filt", "aug_map", "aug_az", "aug_fft", "aug_cfar")):
@@ -25,7 +20,7 @@ def test_augment_data(golden_dir):
 
 
 def test_filter_map(golden_dir):
-    g = _g(golden_dir)
+    g = load_golden(golden_dir, "dataset_ops.npz")
     pts, nrm, T = torch.from_numpy(g["pts"]), torch.from_numpy(g["nrm"]), torch.from_numpy(g["T_gt"])
     pa, na = ds.filter_map(pts, nrm, T, return_aligned=True)
     pb, nb = ds.filter_map(pts, nrm, T, return_aligned=False)

@@ -5,21 +5,16 @@ tree with its twice-applied decoder blocks, the batch-global min-max normalisati
 amax-normalised mask, `FlatGradSync`, Adam), which on the CPU runs through the nn.Module mirror of the U-Net;
 the dICP / radar kernels have no CPU path, so the real-kernel variant of this test is tests/test_gpu_ddp.py."""
 import os
-import socket
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from mm_masking_amd import ddp
+from support import free_port, policy, policy_params
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+CPU = torch.device("cpu")
+POLICY = {"dropout": 0.0, "unet_backend": "torch"}
 
 
 def _model(seed):
@@ -57,7 +52,7 @@ def _worker(rank, world, port, out):
 
 def test_two_rank_allreduce_equals_single_process_global_batch():
     world = 2
-    port = _free_port()
+    port = free_port()
     mgr = mp.Manager()
     out = mgr.dict()
     mp.spawn(_worker, args=(world, port, out), nprocs=world, join=True)
@@ -83,15 +78,6 @@ def test_shard_indices_cover_global_batch():
 
 # ------------------------------------------------------------------------------------------------------------------
 # the policy's real host logic
-def _policy(seed):
-    from mm_masking_amd import train_icp_weights as trn
-    from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-    p = trn.default_params(torch.device("cpu"))
-    p.update({"dropout": 0.0, "unet_backend": "torch"})
-    torch.manual_seed(seed)
-    return LearnICPWeightPolicy(p), p
-
-
 def _scan(idx, hw=64):
     """Pair `idx`: an image whose value range depends on the pair (a per-rank min-max normalisation would show)."""
     g = torch.Generator().manual_seed(2000 + idx)
@@ -126,7 +112,7 @@ def _policy_worker(rank, world, port, out):
         from mm_masking_amd import train_icp_weights as trn
         res = {}
         for overlap in (False, True):             # one all-reduce of the block / the three buckets of the native backward
-            model, p = _policy(seed=10 + rank)    # different init per rank on purpose: rank 0's is broadcast
+            model, p = policy(CPU, 10 + rank, **POLICY), policy_params(CPU, **POLICY)    # init differs per rank: rank 0's is broadcast
             assert model.global_minmax            # the default inside a multi-rank job
             model.train()
             sync = ddp.FlatGradSync(model, overlap=overlap)
@@ -150,7 +136,7 @@ def test_policy_host_logic_two_ranks_equal_one_process():
     multi-rank job: the shards' value ranges differ), the decoder's shared weights to accumulate both applications on
     every rank, and the flat bucket to average the 46 gradients."""
     world = 2
-    port = _free_port()
+    port = free_port()
     mgr = mp.Manager()
     out = mgr.dict()
     mp.spawn(_policy_worker, args=(world, port, out), nprocs=world, join=True)
@@ -167,7 +153,7 @@ def test_policy_host_logic_two_ranks_equal_one_process():
         assert ranges[2][0] == 0 and ranges[2][1] == ranges[1][0] and ranges[1][1] == ranges[0][0] and ranges[0][1] == 1769905
         assert ranges[2][1] - ranges[2][0] < 20000 < ranges[0][1] - ranges[0][0] < ranges[1][1] - ranges[1][0]
     from mm_masking_amd import train_icp_weights as trn
-    model, p = _policy(seed=10)
+    model, p = policy(CPU, 10, **POLICY), policy_params(CPU, **POLICY)
     assert not model.global_minmax               # single process: nothing to reduce over
     model.train()
     opt = trn.make_optimizer(model, p)
@@ -211,7 +197,7 @@ def _fit_worker(rank, world, port, out, ckpt_dir):
     from mm_masking_amd import icp_weight_policy as pol
     from mm_masking_amd import train_icp_weights as trn
     # the model exists BEFORE the process group does: the global min-max default must still resolve to "on"
-    model, p = _policy(seed=20 + rank)
+    model, p = policy(CPU, 20 + rank, **POLICY), policy_params(CPU, **POLICY)
     p.update({"num_epochs": 2, "loss_cfar_mask_weight": 1.0, "loss_map_pts_mask_weight": 0.0})
     # one predicate says whether this process is a rank of a multi-rank job, before and after the group exists
     from mm_masking_amd import unet_hip
@@ -251,7 +237,7 @@ def test_fit_two_ranks_final_validation_on_all_ranks(tmp_path):
     both run the same number of forwards incl. the final validation, both end with the best policy's parameters, and
     only the main rank wrote files."""
     world = 2
-    port = _free_port()
+    port = free_port()
     mgr = mp.Manager()
     out = mgr.dict()
     mp.spawn(_fit_worker, args=(world, port, out, str(tmp_path)), nprocs=world, join=True)

@@ -1,7 +1,7 @@
 """GPU: the GO-CFAR thresholds as tensors -- radar_utils.cfar_mask with a_thresh / b_thresh on the device (mmk_cfar_mask_p)
 and their gradients (mmk_cfar_mask_bwd_p) against the reference's own autograd through ``thres = a_thresh * stat + b_thresh``
 (tests/golden/cfar_params.npz, written by tests/golden/make_golden_cfar_params.py), against the fp64 restatement of
-tests/test_cfar_params_cpu.py where there is no golden value, and the policy switch params["learn_cfar"].
+tests/radar_cases.py where there is no golden value, and the policy switch params["learn_cfar"].
 
 Bit equalities: the tensor path hands the same two floats to the same expression as the number path, so masks and scan
 gradients are torch.equal; the threshold sums are fp64 in a fixed order, so they are equal from run to run, with and without the
@@ -26,12 +26,10 @@ import torch
 
 from mm_masking_amd import radar_utils as ru
 from mm_masking_amd.dICP.ICP import ICP
-from test_cfar_params_cpu import CASES, geom_of, load_fixture, threshold_grads_f64
-from test_gpu_mask_scan import _policy, scene64  # noqa: F401  (scene64: the 64 x 64 scan-mode batch, a module fixture)
+from radar_cases import CASES, RES, geom_of, load_fixture, scene64, threshold_grads_f64  # noqa: F401  (scene64: a module fixture)
+from support import DEV, dev, nn_engine, policy, policy_params  # noqa: F401  (nn_engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-RES = 0.0596
 CFAR_REL = 1.6e-5
 CHAIN_REL = 1.6e-5
 
@@ -41,23 +39,12 @@ def gold(golden_dir):
     return load_fixture(golden_dir)
 
 
-@pytest.fixture(params=["brute", "grid"])
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
-
-
-def _g(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 def _thresholds(gold, key, grad=True):
     """The case's thresholds as device tensors: 0-dim when shared; a as (B,) and b as (B,1,1) per scan."""
     if key[1] == "s":
         a, b = (torch.tensor(float(gold[k + key]), dtype=torch.float32, device=DEV) for k in ("cp_a", "cp_b"))
     else:
-        a, b = _g(gold["cp_a" + key]), _g(gold["cp_b" + key]).reshape(-1, 1, 1)
+        a, b = dev(gold["cp_a" + key]), dev(gold["cp_b" + key]).reshape(-1, 1, 1)
     return a.requires_grad_(grad), b.requires_grad_(grad)
 
 
@@ -87,7 +74,7 @@ def _ratios(got, ref64, scale, name):
 def runs(gold):
     """One forward and backward per case with scan and thresholds requiring grad; shared by the tests below."""
     out = {}
-    raw, G = _g(gold["cp_raw"]), _g(gold["cp_G"])
+    raw, G = dev(gold["cp_raw"]), dev(gold["cp_G"])
     for key in CASES:
         x = raw.clone().requires_grad_(True)
         a, b = _thresholds(gold, key)
@@ -101,7 +88,7 @@ def runs(gold):
 @pytest.mark.parametrize("key", CASES)
 @pytest.mark.parametrize("diff", [True, False])
 def test_forward_bits_equal_the_number_path(gold, key, diff):
-    raw = _g(gold["cp_raw"])
+    raw = dev(gold["cp_raw"])
     want, _ = _number_path(gold, key, raw, diff=diff)
     assert want.abs().max() > 0
     a, b = _thresholds(gold, key, grad=False)
@@ -136,19 +123,19 @@ def test_threshold_gradients_match_reference(gold, runs, key):
     print("      the reference's own fp32 rounding e32: a %s  b %s" % (gold["cp_ea32_" + key], gold["cp_eb32_" + key]))
     assert (ra <= CFAR_REL).all() and (rb <= CFAR_REL).all(), (key, ra, rb)
     # the scan's gradient and the mask are the number path's, bit for bit
-    want_mask, want_grad = _number_path(gold, key, _g(gold["cp_raw"]), G=_g(gold["cp_G"]))
+    want_mask, want_grad = _number_path(gold, key, dev(gold["cp_raw"]), G=dev(gold["cp_G"]))
     assert torch.equal(r["mask"], want_mask) and torch.equal(x.grad, want_grad) and x.grad.abs().max() > 0
 
 
 def test_gradients_come_back_in_the_thresholds_form(gold, runs):
     """Host fp64 thresholds get host fp64 gradients; a single value used with per-scan values gets the sum over the scans."""
-    raw, G = _g(gold["cp_raw"]), _g(gold["cp_G"])
+    raw, G = dev(gold["cp_raw"]), dev(gold["cp_G"])
     a = torch.from_numpy(gold["cp_a0p"]).double().requires_grad_(True)
     b = torch.tensor(float(gold["cp_b0s"]), device=DEV, requires_grad=True)
     ru.cfar_mask(raw, RES, a_thresh=a, b_thresh=b, diff=True).backward(G)
     assert a.grad.shape == (3,) and a.grad.dtype == torch.float64 and a.grad.device.type == "cpu"
     assert b.grad.shape == () and b.grad.is_cuda
-    a2 = _g(gold["cp_a0p"]).requires_grad_(True)
+    a2 = dev(gold["cp_a0p"]).requires_grad_(True)
     b2 = b.detach().expand(3).clone().requires_grad_(True)
     ru.cfar_mask(raw, RES, a_thresh=a2, b_thresh=b2, diff=True).backward(G)
     assert torch.equal(a.grad, a2.grad.cpu().double()) and torch.equal(b.grad, b2.grad.sum())
@@ -157,29 +144,29 @@ def test_gradients_come_back_in_the_thresholds_form(gold, runs):
 # ----------------------------------------------------------------------------- 3. thresholds only
 @pytest.mark.parametrize("key", CASES)
 def test_thresholds_only_skip_the_scan_gradient(gold, runs, key):
-    raw = _g(gold["cp_raw"])
+    raw = dev(gold["cp_raw"])
     a, b = _thresholds(gold, key)
     m = ru.cfar_mask(raw, RES, a_thresh=a, b_thresh=b, diff=True, **geom_of(gold, key))
     assert m.requires_grad and torch.equal(m.detach(), runs[key]["mask"])
-    m.backward(_g(gold["cp_G"]))
+    m.backward(dev(gold["cp_G"]))
     assert torch.equal(a.grad, runs[key]["a"].grad) and torch.equal(b.grad, runs[key]["b"].grad)
     assert a.grad.abs().min() > 0 and b.grad.abs().min() > 0
     # one threshold alone
     a1, _ = _thresholds(gold, key)
-    ru.cfar_mask(raw, RES, a_thresh=a1, b_thresh=b.detach(), diff=True, **geom_of(gold, key)).backward(_g(gold["cp_G"]))
+    ru.cfar_mask(raw, RES, a_thresh=a1, b_thresh=b.detach(), diff=True, **geom_of(gold, key)).backward(dev(gold["cp_G"]))
     assert torch.equal(a1.grad, a.grad)
 
 
 # ----------------------------------------------------------------------------- 4. structure
 @pytest.mark.parametrize("key", ["0p", "1p"])
 def test_structure_zero_scan_batch_independence_and_reproducibility(gold, runs, key):
-    raw, G = _g(gold["cp_raw"]), _g(gold["cp_G"])
+    raw, G = dev(gold["cp_raw"]), dev(gold["cp_G"])
     kw = geom_of(gold, key)
 
     def grads(x, sel, with_scan=True):
         x = x.clone().requires_grad_(with_scan)
-        a = _g(np.atleast_1d(gold["cp_a" + key])[sel]).requires_grad_(True)
-        b = _g(np.atleast_1d(gold["cp_b" + key])[sel]).requires_grad_(True)
+        a = dev(np.atleast_1d(gold["cp_a" + key])[sel]).requires_grad_(True)
+        b = dev(np.atleast_1d(gold["cp_b" + key])[sel]).requires_grad_(True)
         ru.cfar_mask(x, RES, a_thresh=a, b_thresh=b, diff=True, **kw).backward(G[sel].contiguous())
         return a.grad, b.grad, x.grad
 
@@ -215,10 +202,10 @@ def _conditioned_scan(seed, shape, last_return):
 def _against_restatement(raw, G, name, per_scan):
     B = raw.shape[0]
     av, bv = np.full(B, 1.0), np.full(B, np.float32(0.09), dtype=np.float64)
-    a = _g(av.astype(np.float32) if per_scan else np.float32(1.0)).requires_grad_(True)
-    b = _g(bv.astype(np.float32) if per_scan else np.float32(0.09)).requires_grad_(True)
-    x = _g(raw).requires_grad_(True)
-    ru.cfar_mask(x, RES, a_thresh=a, b_thresh=b, diff=True).backward(_g(G))
+    a = dev(av.astype(np.float32) if per_scan else np.float32(1.0)).requires_grad_(True)
+    b = dev(bv.astype(np.float32) if per_scan else np.float32(0.09)).requires_grad_(True)
+    x = dev(raw).requires_grad_(True)
+    ru.cfar_mask(x, RES, a_thresh=a, b_thresh=b, diff=True).backward(dev(G))
     ga, gb = threshold_grads_f64(raw, G, av, bv)
     sa, sb = threshold_grads_f64(raw, np.abs(G), av, bv)
     if not per_scan:
@@ -228,8 +215,8 @@ def _against_restatement(raw, G, name, per_scan):
     rb = _ratios(b.grad, gb, np.abs(sb), name + " b_thresh")
     assert (ra <= CFAR_REL).all() and (rb <= CFAR_REL).all(), (name, ra, rb)
     # the scan gradient is the number path's here too
-    x2 = _g(raw).requires_grad_(True)
-    ru.cfar_mask(x2, RES, diff=True).backward(_g(G))
+    x2 = dev(raw).requires_grad_(True)
+    ru.cfar_mask(x2, RES, diff=True).backward(dev(G))
     assert torch.equal(x.grad, x2.grad)
 
 
@@ -249,30 +236,30 @@ def test_full_size_shared_thresholds_against_restatement():
 
 # ----------------------------------------------------------------------------- 6. the chain
 def test_chain_pose_to_thresholds(gold, nn_engine):
-    az = _g(gold["ch_az"])
+    az = dev(gold["ch_az"])
     npad, K = int(gold["ch_npad"]), int(gold["ch_iters"])
-    a = _g(gold["cc_a"]).reshape(-1, 1, 1).requires_grad_(True)
-    b = _g(gold["cc_b"]).reshape(-1, 1, 1).requires_grad_(True)
-    m = ru.cfar_mask(_g(gold["cc_raw"]), RES, a_thresh=a, b_thresh=b, diff=True)
+    a = dev(gold["cc_a"]).reshape(-1, 1, 1).requires_grad_(True)
+    b = dev(gold["cc_b"]).reshape(-1, 1, 1).requires_grad_(True)
+    m = ru.cfar_mask(dev(gold["cc_raw"]), RES, a_thresh=a, b_thresh=b, diff=True)
     cloud, cnt = ru.extract_pc_padded(m, RES, az, torch.zeros_like(az), npad, diff=True)
-    wmask = _g(gold["ch_mu"])[:, :, None] * _g(gold["ch_mv"])[:, None, :]
+    wmask = dev(gold["ch_mu"])[:, :, None] * dev(gold["ch_mv"])[:, None, :]
     w = ru.extract_weights(wmask, cloud)[0]
     icp = ICP(icp_type="pt2pl", differentiable=True, max_iterations=K, tolerance=1e-9)
-    T = icp.icp(cloud, _g(gold["ch_map"]), weight=w, trim_dist=5.0, loss_fn={"name": "huber", "metric": 1.0}, dim=2)["T"]
+    T = icp.icp(cloud, dev(gold["ch_map"]), weight=w, trim_dist=5.0, loss_fn={"name": "huber", "metric": 1.0}, dim=2)["T"]
     assert cnt.cpu().tolist() == gold["cc_n"].tolist()
     np.testing.assert_allclose(cloud.detach().cpu().numpy(), gold["cc_cloud"], atol=2e-5)
     np.testing.assert_allclose(T.detach().cpu().numpy(), gold["cc_T"], atol=2e-6)
-    (T * _g(gold["ch_G"])).sum().backward()
+    (T * dev(gold["ch_G"])).sum().backward()
     ra = _ratios(a.grad, gold["cc_ga"].astype(np.float64), gold["cc_sa"], "chain %s a_thresh" % nn_engine)
     rb = _ratios(b.grad, gold["cc_gb"].astype(np.float64), gold["cc_sb"], "chain %s b_thresh" % nn_engine)
     assert a.grad.shape == a.shape and (ra <= CHAIN_REL).all() and (rb <= CHAIN_REL).all(), (nn_engine, ra, rb)
 
 
 # ----------------------------------------------------------------------------- 7. the policy
-def test_policy_learns_the_thresholds(scene64, tmp_path):  # noqa: F811
+def test_policy_learns_the_thresholds(scene64, tmp_path):
     from mm_masking_amd import train_icp_weights as trn
     scan, mp, T0, G = scene64
-    model = _policy(mask_target="scan", learn_cfar=True)
+    model = policy(DEV, 3, dropout=0.0, mask_target="scan", learn_cfar=True)
     assert len(list(model.parameters())) == 48 and model.cfar_a.is_cuda
     model.train()
     T, mask, _ = model(scan, mp, T0)
@@ -291,7 +278,7 @@ def test_policy_learns_the_thresholds(scene64, tmp_path):  # noqa: F811
     (T2 * G).sum().backward()
     assert torch.equal(T2.detach(), T.detach()) and torch.equal(a.grad, ga) and torch.equal(b.grad, gb)
     # the U-Net's 46 gradients and the pose are those of a policy with the same values as numbers
-    plain = _policy(mask_target="scan")
+    plain = policy(DEV, 3, dropout=0.0, mask_target="scan")
     assert (np.float32(plain.a_thres), np.float32(plain.b_thres)) == (model.cfar_a.item(), model.cfar_b.item())
     plain.train()
     Tp = plain(scan, mp, T0)[0]
@@ -303,14 +290,13 @@ def test_policy_learns_the_thresholds(scene64, tmp_path):  # noqa: F811
         assert torch.equal(mine[k].grad, q.grad), k
     assert any(q.grad.abs().max() > 0 for q in theirs.values())
     # one Adam step moves both; a checkpoint restores them
-    params = trn.default_params(DEV)
-    params.update({"dropout": 0.0, "mask_target": "scan", "learn_cfar": True})
+    params = policy_params(DEV, dropout=0.0, mask_target="scan", learn_cfar=True)
     opt = trn.make_optimizer(model, params)
     before = (model.cfar_a.item(), model.cfar_b.item())
     opt.step()
     assert model.cfar_a.item() != before[0] and model.cfar_b.item() != before[1]
     trn.save_checkpoint(str(tmp_path / "ck.pt"), model, opt, epoch=0, best_norm=1.0)
-    other = _policy(seed=5, mask_target="scan", learn_cfar=True)
+    other = policy(DEV, 5, dropout=0.0, mask_target="scan", learn_cfar=True)
     assert other.cfar_a.item() == before[0]
     trn.load_checkpoint(str(tmp_path / "ck.pt"), other, trn.make_optimizer(other, params))
     assert torch.equal(other.cfar_a, model.cfar_a) and torch.equal(other.cfar_b, model.cfar_b)

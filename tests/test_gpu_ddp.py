@@ -3,7 +3,6 @@
 step on its shard of the pairs -- 2 ranks x 4 pairs must give the averaged flat gradient (and the same loss) as
 1 rank x 8 pairs, including the batch-global min-max normalisation (2-float MAX all-reduce)."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -11,15 +10,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from support import free_port
+
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def _step(rank, world, global_batch, global_minmax, overlap=False):
@@ -69,7 +62,7 @@ def _worker(rank, world, port, global_batch, out):
 
 def test_two_ranks_on_one_gpu_equal_one_rank_global_batch():
     world, gb = 2, 8
-    port = _free_port()
+    port = free_port()
     ctx = mp.get_context("spawn")
     mgr = ctx.Manager()
     out = mgr.dict()

@@ -40,9 +40,9 @@ import torch
 import dropout_ref as dr
 from mm_masking_amd import _lib
 from mm_masking_amd import unet_hip as uh
+from support import DEV, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 P = 0.05                   # the benchmarked probability (thr = 3277)
 SEED = 0x5EED5
 
@@ -365,16 +365,6 @@ def test_edge_probabilities(name, cin, cout):
     assert np.array_equal(_bits(_edge_run(name, cin, cout, 1e-6, seed)), _bits(y0)), name + " thr = 0"
 
 
-def _policy(dropout, **over):
-    from mm_masking_amd import train_icp_weights as trn
-    from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-    p = trn.default_params(DEV)
-    p.update({"dropout": dropout})
-    p.update(over)
-    torch.manual_seed(11)
-    return LearnICPWeightPolicy(p).to(DEV)
-
-
 def test_probability_that_quantises_to_everything_dropped_is_refused():
     """p = 1 - 1e-6 passes p < 1 but rounds to thr = 65536 (nothing kept, 1 / keep infinite): the three entries that take a
     dropout probability name it in an argument error before anything is launched."""
@@ -389,7 +379,7 @@ def test_probability_that_quantises_to_everything_dropped_is_refused():
         _bn_apply(x, torch.tensor([[1.0, 0.0]] * 16, device=DEV), p, 1, y=y)
     torch.cuda.synchronize()
     assert (_bits(y) == _bf16_bits(7.0)).all()
-    model = _policy(0.05)
+    model = policy(DEV, 11, dropout=0.05)
     model.dropout = p
     model.train()
     with pytest.raises(_lib.MmkError, match="mmk_unet_forward: dropout probability"):
@@ -426,7 +416,7 @@ def _check_schedule(tensors, step_seed, exact, p=P):
 @pytest.mark.parametrize("driver", ["python", "native"])
 @pytest.mark.parametrize("B,H,W", [(2, 64, 64), (1, 50, 84)])
 def test_network_seed_schedule(B, H, W, driver, slope):
-    model = _policy(P)
+    model = policy(DEV, 11, dropout=P)
     model.train()
     x = torch.rand(B, 1, H, W, generator=torch.Generator().manual_seed(3)).to(DEV)
     uh.DEBUG = {}
@@ -440,7 +430,7 @@ def test_network_seed_schedule(B, H, W, driver, slope):
 
 def test_policy_advances_the_step_seed():
     """Two consecutive training forwards of the policy draw with _step and _step + 1 (first layer's mask of both)."""
-    model = _policy(P)
+    model = policy(DEV, 11, dropout=P)
     assert model.unet_backend == "hip"
     model.train()
     g = torch.Generator().manual_seed(4)
@@ -467,7 +457,7 @@ def test_batch_norm_network_seed_schedule(slope):
     """The BatchNorm network draws in bn_apply behind each block's second BatchNorm, same schedule; it stores a kept zero as
     -0.0 whatever the activation, so the zero pattern is the mask exactly."""
     from mm_masking_amd import unet_hip_bn as ub
-    model = _policy(P, batch_norm=True, leaky=slope > 0, norm_weights=False)
+    model = policy(DEV, 11, dropout=P, batch_norm=True, leaky=slope > 0, norm_weights=False)
     model.train()
     x = torch.rand(2, 1, 64, 64, generator=torch.Generator().manual_seed(3)).to(DEV)
     uh.DEBUG = {}

@@ -11,18 +11,15 @@ import torch
 from mm_masking_amd import _lib, synthetic
 from mm_masking_amd.dICP.ICP import ICP
 from oracle import _clib, dicp_ref
+from support import DEV, nn_engine, pair_batch  # noqa: F401  (nn_engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
-@pytest.fixture(params=["brute", "grid"], autouse=True)
-def nn_engine(request):
+@pytest.fixture(autouse=True)
+def _both_engines(nn_engine):  # noqa: F811
     """Every ICP test runs with both nearest-neighbour engines: the exhaustive scan and the exact
     uniform-grid search must produce identical correspondences."""
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
 
 
 def _nn_gpu(src, tgt, T, dim):
@@ -91,15 +88,6 @@ def test_nn_padded_targets_and_sources():
     assert idx.max() < 1200
 
 
-def _pair_batch(B, n, m, dim, pad_n=0, pad_m=0, seed=0, with_normals=True):
-    S, Tg, Tt = [], [], []
-    for b in range(B):
-        s, t, T = synthetic.simple_cloud_pair(seed + b, n, m, dim=dim, pad_n=pad_n, pad_m=pad_m,
-                                              with_normals=with_normals, yaw=0.02 + 0.01 * b, trans=(0.6, -0.4 + 0.1 * b, 0.1))
-        S.append(s), Tg.append(t), Tt.append(T)
-    return np.stack(S), np.stack(Tg), np.stack(Tt)
-
-
 CASES = [("pt2pt", "cauchy", 2), ("pt2pl", "huber", 2), ("pt2pt", "huber", 3), ("pt2pl", "cauchy", 3),
          ("pt2pl", None, 2)]
 
@@ -107,7 +95,7 @@ CASES = [("pt2pt", "cauchy", 2), ("pt2pl", "huber", 2), ("pt2pt", "huber", 3), (
 @pytest.mark.parametrize("icp_type,loss,dim", CASES)
 def test_icp_forward_matches_oracle(icp_type, loss, dim):
     B, n, m = 3, 1500, 4000
-    src, tgt, T_true = _pair_batch(B, n, m, dim, pad_n=100, pad_m=96, seed=10 * dim)
+    src, tgt, T_true = pair_batch(B, n, m, dim, pad_n=100, pad_m=96, seed=10 * dim)
     rng = np.random.default_rng(1)
     w = rng.uniform(0.1, 1.0, (B, n + 100)).astype(np.float32)
     w[:, n:] = 0.0
@@ -144,7 +132,7 @@ def test_icp_zero_rows_anywhere_match_oracle():
     not be trailing padding: a whole 512-row block of zeros in the middle of a scan, zero rows at the front, a scan of
     nothing but zeros and one without any -- correspondences of every row and every iteration equal the oracle's."""
     B, n, m, dim = 4, 2048, 3000, 2
-    src, tgt, _ = _pair_batch(B, n, m, dim, pad_n=0, pad_m=40, seed=91)
+    src, tgt, _ = pair_batch(B, n, m, dim, pad_n=0, pad_m=40, seed=91)
     src[0, 512:1024] = 0.0                 # a zero block in the middle, real rows behind it
     src[0, 100:110] = 0.0                  # ... and the first zero row in an earlier, mixed block
     src[1, :600] = 0.0                     # zeros at the front (the first block is all zero and holds the representative)
@@ -171,7 +159,7 @@ def test_icp_zero_rows_anywhere_match_oracle():
 @pytest.mark.parametrize("icp_type,loss,dim", CASES)
 def test_icp_backward_matches_autograd(icp_type, loss, dim):
     B, n, m = 2, 900, 2500
-    src, tgt, _ = _pair_batch(B, n, m, dim, pad_n=60, seed=77 + dim)
+    src, tgt, _ = pair_batch(B, n, m, dim, pad_n=60, seed=77 + dim)
     rng = np.random.default_rng(2)
     w0 = rng.uniform(0.2, 1.0, (B, n + 60)).astype(np.float32)
     w0[:, n:] = 0.0
@@ -205,7 +193,7 @@ def test_icp_backward_matches_autograd(icp_type, loss, dim):
 
 def test_icp_invariances():
     B, n, m = 2, 800, 2000
-    src, tgt, _ = _pair_batch(B, n, m, 2, seed=31)
+    src, tgt, _ = pair_batch(B, n, m, 2, seed=31)
     s, t = torch.from_numpy(src).to(DEV), torch.from_numpy(tgt).to(DEV)
     w = torch.rand(B, n, device=DEV) + 0.1
     icp = ICP("pt2pl", differentiable=False, max_iterations=6, tolerance=1e-9)
@@ -230,7 +218,7 @@ def test_icp_invariances():
 
 def test_icp_tolerance_freezes_pairs_and_early_exit():
     B, n, m = 2, 600, 1500
-    src, tgt, T_true = _pair_batch(B, n, m, 2, seed=3)
+    src, tgt, T_true = pair_batch(B, n, m, 2, seed=3)
     src[1] = tgt[1, :n, :3]              # pair 1 starts converged (exact copy)
     s, t = torch.from_numpy(src).to(DEV), torch.from_numpy(tgt).to(DEV)
     icp = ICP("pt2pt", differentiable=False, max_iterations=50, tolerance=1e-5)

@@ -11,33 +11,23 @@ error shows in the second pair.  No tolerance anywhere: every comparison is torc
 import ctypes
 import functools
 
-import numpy as np
 import pytest
 import torch
 
-from mm_masking_amd import _lib, synthetic
+from mm_masking_amd import _lib
+from support import DEV, icp_params, pair_batch
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device("cuda:0")
 B, N, M, K = 2, 300, 700, 3
 METRIC, TRIM = 1.0, 5.0
 STATE = ("idx_hist", "T_hist", "delta_hist", "A_hist", "active_hist")
 CASES = [(t, d, nn) for t, d in (("pt2pt", 2), ("pt2pl", 2), ("pt2pt", 3), ("pt2pl", 3)) for nn in ("brute", "grid")]
 
 
-def _pair_batch(dim, seed):
-    S, Tg = [], []
-    for b in range(B):
-        s, t, _ = synthetic.simple_cloud_pair(seed + b, N, M, dim=dim, yaw=0.02 + 0.01 * b, trans=(0.6, -0.4 + 0.1 * b, 0.1))
-        S.append(s), Tg.append(t)
-    return np.stack(S), np.stack(Tg)
-
-
 @functools.lru_cache(maxsize=None)
 def _inputs(dim):
     """Seeded clouds, weights, start poses and the upstream gradient of a dim: made once, never written."""
-    src, tgt = _pair_batch(dim, seed=31 + dim)
+    src, tgt, _ = pair_batch(B, N, M, dim, seed=31 + dim)
     g = torch.Generator().manual_seed(7 + dim)
     T0 = torch.eye(4).repeat(B, 1, 1)
     T0[:, 0, 3] += 0.2
@@ -47,9 +37,8 @@ def _inputs(dim):
 
 
 def _params(icp_type, dim, nn):
-    return _lib.IcpParams(B=B, N=N, M=M, tgt_cols=6, dim=dim, icp_type=_lib.ICP_TYPES[icp_type], loss=_lib.LOSSES["huber"],
-                          loss_k=METRIC, trim_dist=TRIM, tolerance=1e-9, max_iter=K, save_state=1, check_every=0,
-                          nn_method=_lib.NN_METHODS[nn], trim_steep=0.0)
+    return icp_params(B=B, N=N, M=M, dim=dim, icp_type=_lib.ICP_TYPES[icp_type], loss=_lib.LOSSES["huber"], loss_k=METRIC,
+                      trim_dist=TRIM, tolerance=1e-9, max_iter=K, nn_method=_lib.NN_METHODS[nn], trim_steep=0.0)
 
 
 def _forward(p, x, hyper):

@@ -14,16 +14,14 @@ import torch
 import icp_freeze_cases as fc
 from mm_masking_amd import _lib
 from mm_masking_amd.dICP.ICP import ICP
+from support import DEV, nn_engine  # noqa: F401  (nn_engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
-@pytest.fixture(params=["brute", "grid"], autouse=True)
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
+@pytest.fixture(autouse=True)
+def _both_engines(nn_engine):  # noqa: F811
+    """Every test of this file runs with both nearest-neighbour engines."""
 
 
 def _leaves(arrays, need, with_weight=True, pairs=slice(None)):

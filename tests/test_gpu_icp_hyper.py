@@ -31,9 +31,10 @@ from mm_masking_amd.dICP.ICP import ICP, check_errors
 import icp_freeze_cases as fz
 from dicp_cases import (B, GATE_CASES as CASES, GATE_IDS as IDS, GATE_TRIM as TRIM, HNAMES, K, MULT, NAMES, TOL, assert_gate_awake,
                         assert_hyper_awake, close, gpu, inputs, nn_engine, reference, same)  # noqa: F401
+from radar_cases import scene64  # noqa: F401  (the smallest scan-mode batch of the suite, a module fixture)
+from support import DEV, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 ALL7 = NAMES + HNAMES
 
@@ -179,14 +180,11 @@ def test_bad_value_on_the_device_raises_the_status_bit_and_nothing_else():
 
 
 # ----------------------------------------------------------------------------- 7. the policy
-from test_gpu_mask_scan import scene64, _policy  # noqa: E402,F401
-
-
 def test_policy_learns_the_three_values(scene64):
     scan, mp, T0, G = scene64
-    kw = dict(mask_target="scan", icp_trim="tanh", icp_trim_dist=0.12)
+    kw = dict(dropout=0.0, mask_target="scan", icp_trim="tanh", icp_trim_dist=0.12)
     names = ("icp_metric", "icp_trim_dist_p", "icp_tanh_steepness_p")
-    model, plain = _policy(learn_icp=("metric", "trim_dist", "tanh_steepness"), **kw), _policy(**kw)
+    model, plain = policy(DEV, 3, learn_icp=("metric", "trim_dist", "tanh_steepness"), **kw), policy(DEV, 3, **kw)
     assert [n for n, _ in model.named_parameters() if n.startswith("icp_")] == list(names)
     assert not any(n.startswith("icp_") for n, _ in plain.named_parameters())
     model.train(), plain.train()
@@ -212,8 +210,8 @@ def test_policy_learns_the_three_values(scene64):
     with torch.no_grad():
         Te = model(scan, mp, T0)[0]
     net = {k: v for k, v in model.state_dict().items() if not k.startswith("icp_")}           # the stepped U-Net
-    stepped = _policy(icp_loss_fn={"name": "cauchy", "metric": model.icp_metric.item()}, **dict(kw, icp_trim_dist=model.icp_trim_dist_p.item()))
-    unstepped = _policy(**kw)
+    stepped = policy(DEV, 3, icp_loss_fn={"name": "cauchy", "metric": model.icp_metric.item()}, **dict(kw, icp_trim_dist=model.icp_trim_dist_p.item()))
+    unstepped = policy(DEV, 3, **kw)
     for m in (stepped, unstepped):
         m.load_state_dict(net)
         m.eval()

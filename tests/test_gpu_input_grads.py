@@ -13,9 +13,9 @@ from mm_masking_amd import unet_hip_bn as ub
 from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
 
 import input_grad_cases as igc
+from support import DEV, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 BF16 = torch.bfloat16
 
 # fp32 sums of at most 288 products (8 output channels x 9 taps x 4 input channels) in a fixed order, one more rounding for the
@@ -34,14 +34,8 @@ def _rand_case(B, cin, H, W, seed):
 
 
 def _model(cin=1, dropout=0.0, leaky=False, bn=False, normalize="minmax", norm_weights=True, seed=17, **extra):
-    p = trn.default_params(DEV)
-    p.update({"dropout": dropout, "leaky": leaky, "cfar_input": cin >= 2, "range_input": cin >= 3, "batch_norm": bn,
-              "normalize": [normalize], "norm_weights": norm_weights})
-    p.update(extra)
-    torch.manual_seed(seed)
-    m = LearnICPWeightPolicy(p).to(DEV)
-    m.train()
-    return m
+    return policy(DEV, seed, train=True, dropout=dropout, leaky=leaky, cfar_input=cin >= 2, range_input=cin >= 3, batch_norm=bn,
+                  normalize=[normalize], norm_weights=norm_weights, **extra)
 
 
 def _pre(x, mode):

@@ -6,7 +6,6 @@ import os
 import numpy as np
 import pytest
 import torch
-import yaml
 
 from mm_masking_amd import dICP, synthetic
 from mm_masking_amd import icp_weight_dataset as ds
@@ -14,10 +13,12 @@ from mm_masking_amd.dICP.ICP import ICP
 import dicp_kat as kat
 from export_util import assert_same, dataset_params, write_fixture_export
 from knn_normals_ref import knn_normals_ref_batch, lattice_line, lattice_plane
+from support import icp_yaml
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 PAD = 1000.0
+ESTIMATE = dict(target_normals="estimate", normals_k=16)
 WALL_SEED = 11            # simple_cloud_pair seeds WALL_SEED, WALL_SEED + 1: every k / k+1 gap > 1e-6 (asserted below)
 KS = (5, 16, 32)
 
@@ -215,13 +216,6 @@ def test_reproducible_and_independent_of_the_batch(walls, dim):
     assert torch.equal(dICP.estimate_normals(t, k=16, dim=dim, pad_val=PAD), dICP.estimate_normals(t, k=16, dim=dim, pad_val=PAD))
 
 
-def _estimate_yaml(tmp_path):
-    path = os.path.join(str(tmp_path), "estimate.yaml")
-    with open(path, "w") as f:
-        yaml.safe_dump({"dICP": {"target_pad_val": PAD, "parameters": {"target_normals": "estimate", "normals_k": 16}}}, f)
-    return path
-
-
 @pytest.mark.parametrize("dim", [2, 3])
 def test_icp_estimates_the_normals_of_an_xyz_target(tmp_path, dim):
     """`target_normals: estimate` == with_normals() + the default instance, bit for bit, and the pose meets the project's
@@ -235,7 +229,7 @@ def test_icp_estimates_the_normals_of_an_xyz_target(tmp_path, dim):
     src, tgt = torch.from_numpy(np.stack(S)).to(DEV), torch.from_numpy(np.stack(Tg)).to(DEV)
     w = torch.ones(2, 320, device=DEV)
     w[:, 300:] = 0
-    est = ICP("pt2pl", config_path=_estimate_yaml(tmp_path), differentiable=False, max_iterations=50, tolerance=1e-9)
+    est = ICP("pt2pl", config_path=icp_yaml(tmp_path, **ESTIMATE), differentiable=False, max_iterations=50, tolerance=1e-9)
     dfl = ICP("pt2pl", differentiable=False, max_iterations=50, tolerance=1e-9)
     assert est.target_normals == "estimate" and dfl.target_normals == "given" and dfl.target_pad_val == PAD
     with pytest.raises(ValueError, match="pt2pl needs target normals"):
@@ -253,7 +247,7 @@ def test_icp_estimates_the_normals_of_an_xyz_target(tmp_path, dim):
         assert dt <= 1e-3 and da <= 1e-4, (dim, b, dt, da)
     # the target's gradient flows through xyz only
     if dim == 2:
-        g_icp = ICP("pt2pl", config_path=_estimate_yaml(tmp_path), differentiable=True, max_iterations=3, tolerance=1e-9)
+        g_icp = ICP("pt2pl", config_path=icp_yaml(tmp_path, **ESTIMATE), differentiable=True, max_iterations=3, tolerance=1e-9)
         tg = tgt.clone().requires_grad_(True)
         g_icp.icp(src, tg, weight=w, trim_dist=5.0, dim=dim)["T"][:, :2, 3].sum().backward()
         assert tuple(tg.grad.shape) == (2, 960, 3) and torch.isfinite(tg.grad).all() and tg.grad.abs().sum() > 0

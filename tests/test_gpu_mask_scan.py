@@ -22,61 +22,41 @@ Tolerances.
                             project's ceiling for anything behind the dICP backward is 2e-3.
 """
 import importlib
-import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from mm_masking_amd import radar_utils as ru
-from mm_masking_amd.dICP.ICP import ICP
+from radar_cases import B64, H64, NP64, RES, chain_inputs, scene64, wobbly_azimuths  # noqa: F401  (scene64: a module fixture)
+from support import DEV, dev, load_golden, nn_engine, policy  # noqa: F401  (nn_engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-RES = 0.0596
 ULP = 2.0 ** -23
 CHAIN_MASK_REL = 1.04e-5
 
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, "mask_scan.npz")))
+    return load_golden(golden_dir, "mask_scan.npz")
 
 
 @pytest.fixture(scope="module")
 def chain_in(golden_dir):
-    base = dict(np.load(os.path.join(golden_dir, "radar_grads.npz")))
-    rg = dict(np.load(os.path.join(golden_dir, "resample_grads.npz")))
-    raw = base["ch_raw"].copy()
-    raw.reshape(-1)[rg["ch_fix_idx"]] = rg["ch_fix_val"]
-    return {"raw": raw, "az": base["ch_az"], "map": base["ch_map"], "G": base["ch_G"], "npad": int(base["ch_npad"]),
-            "iters": int(base["ch_iters"]), "cu": rg["ch_cu"], "cv": rg["ch_cv"]}
-
-
-@pytest.fixture(params=["brute", "grid"])
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
-
-
-def _g(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return chain_inputs(golden_dir)
 
 
 def _case(gold, key):
     rres, cres = (float(v) for v in gold[key + "_res"])
-    return _g(gold[key + "_scan"]), _g(gold[key + "_mask"]), torch.from_numpy(gold[key + "_az"]), _g(gold[key + "_G"]), rres, cres
+    return dev(gold[key + "_scan"]), dev(gold[key + "_mask"]), torch.from_numpy(gold[key + "_az"]), dev(gold[key + "_G"]), rres, cres
 
 
 def _full_size_case():
-    from test_gpu_resample_grads import _wobbly_azimuths
     g = torch.Generator().manual_seed(91)
     scan = torch.rand(2, 400, 3360, generator=g).to(DEV)
     mask = torch.rand(2, 640, 640, generator=g).to(DEV)
     G = torch.randn(2, 400, 3360, generator=g).to(DEV)
-    az = torch.cat([_wobbly_azimuths(5), _wobbly_azimuths(6)])
+    az = torch.cat([wobbly_azimuths(5), wobbly_azimuths(6)])
     return scan, mask, az, G, RES, 0.2384
 
 
@@ -152,10 +132,10 @@ def test_one_sided_gradients_at_full_size(full_size, which):
 def test_structural_zeros(gold):
     for key in ("ms_a", "ms_b"):
         y, gs, gm = _fused(*_case(gold, key))
-        notap = _g(gold[key + "_notap"])
+        notap = dev(gold[key + "_notap"])
         assert notap.float().mean() > 0.1
         assert (y[notap] == 0).all() and (gs[notap] == 0).all() and (y[~notap] != 0).float().mean() > 0.99
-        untouched = _g(gold[key + "_grad_mask"] == 0)
+        untouched = dev(gold[key + "_grad_mask"] == 0)
         assert untouched.float().mean() > 0.4
         assert (gm[untouched] == 0).all() and (gm[~untouched] != 0).float().mean() > 0.99
 
@@ -192,8 +172,8 @@ def test_dtype_device_and_no_grad_paths(gold):
     y.backward(torch.from_numpy(gold["ms_a_G"]))
     yd, gs, gm = _fused(scan, mask, az, G, rres, cres)
     assert torch.equal(y.detach(), yd.cpu())
-    for got, dev in ((s.grad, gs), (m.grad, gm)):
-        assert got.device.type == "cpu" and got.dtype == torch.float64 and torch.equal(got, dev.cpu().double())
+    for got, on_dev in ((s.grad, gs), (m.grad, gm)):
+        assert got.device.type == "cpu" and got.dtype == torch.float64 and torch.equal(got, on_dev.cpu().double())
     # requires_grad=False and no_grad(): a single launch, no graph
     assert ru.mask_polar_scan(scan, mask, az, rres, cart_resolution=cres).grad_fn is None
     with torch.no_grad():
@@ -204,47 +184,6 @@ def test_dtype_device_and_no_grad_paths(gold):
 
 
 # ----------------------------------------------------------------------------- 6. + 9. the policy at 64 x 64
-B64, H64, A64, R64, NP64 = 2, 64, 32, 200, 128
-
-
-@pytest.fixture(scope="module")
-def scene64():
-    """A 32 x 200 polar scan whose only detections lie between GO-CFAR's first column (89) and the edge of a 64 x 64 Cartesian
-    image (range cell 128 on the axes, 181 in the corners): one three-cell blob per azimuth at cells 95..122, the map = the
-    blob centres moved by a small rigid offset, with radial normals."""
-    g = torch.Generator().manual_seed(11)
-    az = ((torch.arange(A64, dtype=torch.float64) + 0.5) * (2 * math.pi / A64))[None].repeat(B64, 1)
-    az = az + 0.02 * (torch.rand(B64, A64, generator=g, dtype=torch.float64) - 0.5)
-    polar = 0.02 * torch.rand(B64, A64, R64, generator=g)
-    col = torch.zeros(B64, A64, dtype=torch.long)
-    for b in range(B64):
-        for a in range(A64):
-            c = 95 + (7 * a + 13 * b) % 28
-            col[b, a] = c
-            polar[b, a, c - 1:c + 2] = torch.tensor([0.55, 0.7, 0.55])
-    rho = (col.double() * RES).float()
-    x, y = rho * torch.cos(az.float()), rho * torch.sin(az.float())
-    nrm = torch.stack((torch.cos(az.float()), torch.sin(az.float()), torch.zeros(B64, A64)), dim=2)
-    pts = torch.stack((x + 0.10, y - 0.06, torch.zeros(B64, A64)), dim=2)
-    map_pc = torch.cat((torch.cat((pts, nrm), dim=2), torch.cat((pts + 0.03 * nrm, nrm), dim=2)), dim=1)
-    polar, azd = polar.to(DEV), az.float().to(DEV)
-    raw_pc, cnt = ru.extract_pc_padded(ru.cfar_mask(polar, RES, diff=False), RES, azd, torch.zeros_like(azd), NP64, diff=False)
-    assert cnt.min() >= 8 and cnt.max() <= NP64
-    scan = {"fft_data": ru.radar_polar_to_cartesian_diff(polar, azd, RES, cart_pixel_width=H64), "fft_cfar": torch.zeros(B64, H64, H64, device=DEV),
-            "raw_pc": raw_pc, "filtered_pc": raw_pc, "fft_polar": polar, "azimuths": az}          # azimuths on the host: no sync
-    return scan, {"pc": map_pc.to(DEV)}, torch.eye(4, device=DEV).repeat(B64, 1, 1), torch.randn(B64, 4, 4, generator=g).to(DEV)
-
-
-def _policy(seed=3, **kw):
-    from mm_masking_amd import train_icp_weights as trn
-    from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-    params = trn.default_params(DEV)
-    params.update({"dropout": 0.0})
-    params.update(kw)
-    torch.manual_seed(seed)
-    return LearnICPWeightPolicy(params).to(DEV)
-
-
 def _front_end(model, scan, mask):
     masked = ru.mask_polar_scan(scan["fft_polar"], mask, scan["azimuths"], model.res)
     m = ru.cfar_mask(masked, model.res, a_thresh=model.a_thres, b_thresh=model.b_thres, diff=True)
@@ -254,7 +193,7 @@ def _front_end(model, scan, mask):
 
 def test_policy_scan_mode_equals_manual_composition(scene64):
     scan, mp, T0, G = scene64
-    model = _policy(mask_target="scan")
+    model = policy(DEV, 3, dropout=0.0, mask_target="scan")
     model.train()
     T, mask, _ = model(scan, mp, T0)
     assert mask.shape == (B64, H64, H64) and T.requires_grad
@@ -292,7 +231,7 @@ def test_policy_scan_mode_equals_manual_composition(scene64):
 
 def test_policy_scan_mode_needs_the_polar_scan(scene64):
     scan, mp, T0, _ = scene64
-    model = _policy(mask_target="scan")
+    model = policy(DEV, 3, dropout=0.0, mask_target="scan")
     for key in ("fft_polar", "azimuths"):
         with pytest.raises(KeyError, match=key):
             model({k: v for k, v in scan.items() if k != key}, mp, T0)
@@ -302,7 +241,7 @@ def test_default_mode_is_untouched(scene64):
     scan, mp, T0, G = scene64
     outs = []
     for kw in ({}, {"mask_target": "weights"}):
-        model = _policy(**kw)
+        model = policy(DEV, 3, dropout=0.0, **kw)
         model.train()
         T, mask, num = model(scan, mp, T0)
         ((T * G).sum() + num).backward()
@@ -315,15 +254,15 @@ def test_default_mode_is_untouched(scene64):
 # ----------------------------------------------------------------------------- 7. the policy on the golden chain
 def test_policy_override_mask_matches_reference_chain(gold, chain_in, nn_engine):
     K, npad = chain_in["iters"], chain_in["npad"]
-    model = _policy(mask_target="scan", icp_type="pt2pl", icp_loss_fn={"name": "huber", "metric": 1.0}, max_iter=K,
-                    norm_weights=False)
+    model = policy(DEV, 3, dropout=0.0, mask_target="scan", icp_type="pt2pl", icp_loss_fn={"name": "huber", "metric": 1.0},
+                   max_iter=K, norm_weights=False)
     model.ICP_alg.tolerance = 1e-9                              # the chain's: all K iterations run
     model.train()
     B = chain_in["raw"].shape[0]
-    c = (_g(chain_in["cu"])[:, :, None] * _g(chain_in["cv"])[:, None, :]).contiguous().requires_grad_(True)
+    c = (dev(chain_in["cu"])[:, :, None] * dev(chain_in["cv"])[:, None, :]).contiguous().requires_grad_(True)
     scan = {"fft_data": torch.zeros(B, 64, 64, device=DEV), "fft_cfar": torch.zeros(B, 64, 64, device=DEV),
-            "raw_pc": torch.zeros(B, npad, 3, device=DEV), "fft_polar": _g(chain_in["raw"]), "azimuths": torch.from_numpy(chain_in["az"])}
-    T, mask, _ = model(scan, {"pc": _g(chain_in["map"])}, torch.eye(4, device=DEV).repeat(B, 1, 1), override_mask=c)
+            "raw_pc": torch.zeros(B, npad, 3, device=DEV), "fft_polar": dev(chain_in["raw"]), "azimuths": torch.from_numpy(chain_in["az"])}
+    T, mask, _ = model(scan, {"pc": dev(chain_in["map"])}, torch.eye(4, device=DEV).repeat(B, 1, 1), override_mask=c)
     assert mask is c
     cloud, cnt = _front_end(model, scan, c.detach())
     assert cnt.cpu().tolist() == gold["ms_ch_n"].tolist()
@@ -331,7 +270,7 @@ def test_policy_override_mask_matches_reference_chain(gold, chain_in, nn_engine)
     np.testing.assert_allclose(cloud.cpu().numpy(), gold["ms_ch_cloud"], atol=2e-5)
     print("RATIO policy chain %s T max abs diff = %.3e" % (nn_engine, np.abs(T.detach().cpu().numpy() - gold["ms_ch_T"]).max()))
     np.testing.assert_allclose(T.detach().cpu().numpy(), gold["ms_ch_T"], atol=2e-6)
-    (T * _g(chain_in["G"])).sum().backward()
+    (T * dev(chain_in["G"])).sum().backward()
     assert c.grad.dtype == torch.float32
     for b in range(B):
         want = gold["ms_ch_grad_mask"][b].astype(np.float64)

@@ -13,25 +13,9 @@ from mm_masking_amd import _lib, synthetic
 from mm_masking_amd import radar_utils as ru
 from mm_masking_amd.dICP.ICP import ICP
 from oracle import dicp_ref
+from support import DEV, nn_engine, pair_batch  # noqa: F401  (nn_engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-@pytest.fixture(params=["brute", "grid"])
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
-
-
-def _pair_batch(B, n, m, dim, pad_n=0, pad_m=0, seed=0):
-    S, Tg = [], []
-    for b in range(B):
-        s, t, _ = synthetic.simple_cloud_pair(seed + b, n, m, dim=dim, pad_n=pad_n, pad_m=pad_m,
-                                              yaw=0.02 + 0.01 * b, trans=(0.6, -0.4 + 0.1 * b, 0.1))
-        S.append(s), Tg.append(t)
-    return np.stack(S), np.stack(Tg)
 
 
 def _close(g, ref, name, rel=2e-3):
@@ -50,7 +34,7 @@ def test_cloud_gradients_match_autograd(nn_engine, icp_type, loss, dim):
     """All four inputs require grad: source, target (xyz + normals), weight and T_init gradients against autograd through
     the CPU restatement; zero-padded source rows and target_pad_val target rows included."""
     B, n, m, K = 2, 900, 2500, 5
-    src, tgt = _pair_batch(B, n, m, dim, pad_n=60, pad_m=40, seed=77 + dim)
+    src, tgt, _ = pair_batch(B, n, m, dim, pad_n=60, pad_m=40, seed=77 + dim)
     rng = np.random.default_rng(2)
     w0 = rng.uniform(0.2, 1.0, (B, n + 60)).astype(np.float32)
     w0[:, n:] = 0.0
@@ -76,7 +60,7 @@ def test_cloud_gradients_match_autograd(nn_engine, icp_type, loss, dim):
 @pytest.mark.parametrize("which", [("source",), ("target",), ("source", "target"), ("source", "target", "weight", "T_init")])
 def test_gradients_go_exactly_to_the_inputs_that_require_them(nn_engine, which):
     B, n, m = 2, 600, 1500
-    src, tgt = _pair_batch(B, n, m, 2, seed=5)
+    src, tgt, _ = pair_batch(B, n, m, 2, seed=5)
     x = {"source": torch.from_numpy(src).to(DEV), "target": torch.from_numpy(tgt).to(DEV),
          "weight": torch.rand(B, n, device=DEV) + 0.1, "T_init": torch.eye(4, device=DEV).repeat(B, 1, 1)}
     for k in which:
@@ -96,7 +80,7 @@ def test_gradients_go_exactly_to_the_inputs_that_require_them(nn_engine, which):
 def test_cloud_gradients_in_the_callers_dtype_and_device(nn_engine):
     """CPU fp64 clouds: the gradients come back as CPU fp64 -- the device fp32 gradients, converted."""
     B, n, m = 2, 500, 1200
-    src, tgt = _pair_batch(B, n, m, 2, seed=9)
+    src, tgt, _ = pair_batch(B, n, m, 2, seed=9)
     w = torch.rand(B, n, generator=torch.Generator().manual_seed(1)) + 0.1
     loss_fn = {"name": "cauchy", "metric": 1.0}
     grads = []
@@ -115,7 +99,7 @@ def test_cloud_gradients_in_the_callers_dtype_and_device(nn_engine):
 @pytest.mark.parametrize("icp_type,dim", [("pt2pt", 2), ("pt2pl", 2), ("pt2pt", 3), ("pt2pl", 3)])
 def test_structural_zeros(nn_engine, icp_type, dim):
     B, n, m, K = 2, 700, 1800, 4
-    src, tgt = _pair_batch(B, n, m, dim, pad_n=20, pad_m=50, seed=21)
+    src, tgt, _ = pair_batch(B, n, m, dim, pad_n=20, pad_m=50, seed=21)
     s = torch.from_numpy(src).to(DEV).requires_grad_(True)
     t = torch.from_numpy(tgt).to(DEV).requires_grad_(True)
     icp = ICP(icp_type, differentiable=True, max_iterations=K, tolerance=1e-9)
@@ -181,7 +165,7 @@ def test_hot_target_matches_oracle_and_backward_is_reproducible(nn_engine):
 
 def test_backward_is_bit_reproducible(nn_engine):
     B, n, m = 3, 1200, 3000
-    src, tgt = _pair_batch(B, n, m, 2, pad_n=200, seed=33)
+    src, tgt, _ = pair_batch(B, n, m, 2, pad_n=200, seed=33)
     w = torch.rand(B, n + 200, generator=torch.Generator().manual_seed(2)).to(DEV)
     runs = []
     for rep in range(2):
@@ -200,7 +184,7 @@ def test_weight_and_pose_gradients_untouched_by_cloud_gradients(nn_engine):
     """weight.grad and T_init.grad are the same bits whether or not the clouds also require grad, and the new entry with
     NULL point outputs is bit-identical to mmk_icp_backward."""
     B, n, m, dim = 2, 800, 2000, 2
-    src, tgt = _pair_batch(B, n, m, dim, pad_n=40, seed=51)
+    src, tgt, _ = pair_batch(B, n, m, dim, pad_n=40, seed=51)
     w = torch.rand(B, n + 40, generator=torch.Generator().manual_seed(5)).to(DEV)
     loss_fn = {"name": "huber", "metric": 1.0}
     grads = []

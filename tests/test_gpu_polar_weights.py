@@ -11,6 +11,7 @@ covers the range's ulp (R 2^-23 cells).  A weight is Lipschitz in the position w
 grad_pc: the bilinear slopes are Lipschitz with constant 2 max|mask| per cell and are multiplied by du/drng = 1 / res and by
 dv/dang / rng, on top of the project's 1e-5 max|ref| for the Cartesian kernel (test_gpu_point_grads.py):
     |grad_pc - ref| <= 1e-5 max|ref| + 2 max|mask| max|gw| delta (1 / res + dv / rng)   per point."""
+import functools
 import os
 
 import numpy as np
@@ -22,10 +23,10 @@ from mm_masking_amd import radar_utils as ru
 from mm_masking_amd import train_icp_weights as trn
 from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
 from polar_weights_ref import azimuth_tables, polar_weights_ref, position_error, tap_counts
+from radar_cases import RES
+from support import DEV, policy_params
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-RES = 0.0596
 N = 300
 FLAGS = [(0, 0), (0, 1), (1, 0), (1, 1)]
 FAKE_ROWS = (100, 255, 256, 299)            # both sides of the 256-thread block's edge, and the last row
@@ -245,12 +246,8 @@ def test_known_answer_and_what_the_cartesian_sampler_reads():
     assert (wc[:, :n] - 1.0).abs().max() > 0.5
 
 
-def _policy_params(**over):
-    p = trn.default_params(DEV)
-    p.update({"dropout": 0.0, "network_input_type": "polar", "network_output_type": "polar", "icp_type": "pt2pl",
-              "icp_loss_fn": {"name": "huber", "metric": 1.0}, "max_iter": 5})
-    p.update(over)
-    return p
+_policy_params = functools.partial(policy_params, DEV, dropout=0.0, network_input_type="polar", network_output_type="polar",
+                                   icp_type="pt2pl", icp_loss_fn={"name": "huber", "metric": 1.0}, max_iter=5)
 
 
 def test_policy_switch():

@@ -1,6 +1,7 @@
 """The policy module and the training step on the GPU: U-Net parity with the golden
 vectors of the reference module (fp32) and with the bf16 MFMA path within bf16
 tolerance; reference call signatures; one full train step against the CPU port."""
+import functools
 import os
 
 import numpy as np
@@ -11,16 +12,10 @@ from mm_masking_amd import _lib, synthetic
 from mm_masking_amd import radar_utils as ru
 from mm_masking_amd import train_icp_weights as trn
 from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
+from support import DEV, policy_params
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def _params(**over):
-    p = trn.default_params(DEV)
-    p.update({"dropout": 0.0})
-    p.update(over)
-    return p
+_params = functools.partial(policy_params, DEV, dropout=0.0)
 
 
 def _grad_vectors(g, tag, names):

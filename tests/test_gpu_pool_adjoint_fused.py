@@ -6,9 +6,9 @@ import pytest
 import torch
 
 from mm_masking_amd import unet_hip as uh
+from support import DEV, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 BF16 = torch.bfloat16
 SCALES = [1.0, 1.0 / 0.95]
 
@@ -138,21 +138,12 @@ def test_pooled_input_refused_where_no_kernel_stages_it():
         uh.conv3x3_wgrad_partial(x8, gy, 16, uh.partial_buffer(uh.wgrad_slices(16, 8, 8, 1, 16, 32), 16, 8, DEV), g_pool_arg=arg)
 
 
-def _policy(dropout):
-    from mm_masking_amd import train_icp_weights as trn
-    from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-    p = trn.default_params(DEV)
-    p.update({"dropout": dropout, "amp_dtype": torch.float32, "unet_backend": "torch"})
-    torch.manual_seed(11)
-    return LearnICPWeightPolicy(p).to(DEV)
-
-
 @pytest.mark.parametrize("drop", [0.0, 0.05])
 @pytest.mark.parametrize("B,H,W", [(3, 64, 160), (1, 50, 210)])
 def test_unet_backward_pooled_adjoint_bit_identical(B, H, W, drop, monkeypatch):
     """mmk_unet_backward: all 46 gradients with the adjoint inside the consumers == with the standalone launch on every level
     (MMK_UNET_POOL_ADJOINT=0), and == a second run.  (1, 50, 210) reaches odd sizes: 25 x 105 at level 1, 3 x 13 at level 4."""
-    model = _policy(drop)
+    model = policy(DEV, 11, dropout=drop, amp_dtype=torch.float32, unet_backend="torch")
     model.train()
     g = torch.Generator().manual_seed(1)
     x = torch.rand(B, 1, H, W, generator=g).to(DEV)

@@ -4,8 +4,8 @@ written by tests/golden/make_golden_radar_grads.py), the chain scan -> CFAR -> p
 structural zeros, run-to-run bit equality, full-size scans and long rows, dtype / device of the gradients.
 
 Tolerances: the only rounding difference between the kernels and the reference's autograd is the device tanhf /
-sinf / cosf against the host's; every comparison is against each gradient's own scale, max |ref| (the convention of _close in
-test_gpu_point_grads.py), and every bound is 4 x the worst ratio measured on an MI355X:
+sinf / cosf against the host's; every comparison is against each gradient's own scale, max |ref| (support.close), and every
+bound is 4 x the worst ratio measured on an MI355X:
 
     test                                    worst measured    bound
     cfar, default parameters                3.9e-6            CFAR_REL  = 1.6e-5
@@ -20,10 +20,10 @@ import torch
 from mm_masking_amd import synthetic
 from mm_masking_amd import radar_utils as ru
 from mm_masking_amd.dICP.ICP import ICP
+from radar_cases import RES, cfar_kw
+from support import DEV, close, dev, load_golden, nn_engine  # noqa: F401  (nn_engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-RES = 0.0596
 CFAR_REL = 1.6e-5
 PEAKS_REL = 1.0e-6
 CHAIN_REL = 1.6e-5
@@ -31,40 +31,7 @@ CHAIN_REL = 1.6e-5
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
-    import os
-    return dict(np.load(os.path.join(golden_dir, "radar_grads.npz")))
-
-
-@pytest.fixture(params=["brute", "grid"])
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
-
-
-def _g(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _ratio(g, ref, name):
-    g, ref = g.detach().cpu().double().numpy(), np.asarray(ref, dtype=np.float64)
-    scale = np.abs(ref).max()
-    assert scale > 0, name
-    r = np.abs(g - ref).max() / scale
-    print("RATIO %-40s err/scale = %.3e   (scale %.3e)" % (name, r, scale))
-    return r
-
-
-def _close(g, ref, name, rel):
-    r = _ratio(g, ref, name)
-    assert r <= rel, (name, r, rel)
-
-
-def _cfar_kw(gold, tag):
-    if tag == 0:
-        return {}
-    w, g, s, a, b = gold["ca_params1"]
-    return {"width": int(w), "guard": int(g), "steep_fact": float(s), "a_thresh": float(a), "b_thresh": float(b)}
+    return load_golden(golden_dir, "radar_grads.npz")
 
 
 # ----------------------------------------------------------------------------- 1. cfar_mask
@@ -72,20 +39,20 @@ def _cfar_kw(gold, tag):
 def test_cfar_gradient_matches_reference(gold, tag):
     """raw.grad of cfar_mask(diff=True) for the three fixture items (the third: an empty field with isolated returns,
     exact ties of the two window sums), each against its own scale."""
-    kw = _cfar_kw(gold, tag)
-    raw = _g(gold["ca_raw"]).requires_grad_(True)
+    kw = cfar_kw(gold, tag)
+    raw = dev(gold["ca_raw"]).requires_grad_(True)
     m = ru.cfar_mask(raw, RES, diff=True, **kw)
     assert m.requires_grad and m.grad_fn is not None
-    m.backward(_g(gold["ca_G"]))
+    m.backward(dev(gold["ca_G"]))
     assert raw.grad is not None and raw.grad.shape == raw.shape and raw.grad.dtype == torch.float32 and raw.grad.is_cuda
     want = gold["ca_grad%d" % tag]
     for item in range(want.shape[0]):
-        _close(raw.grad[item], want[item], "cfar set %d item %d" % (tag, item), CFAR_REL)
+        close(raw.grad[item], want[item], "cfar set %d item %d" % (tag, item), CFAR_REL)
     assert ((raw.grad.cpu().numpy() == 0) == (want == 0)).mean() > 0.999
 
 
 def test_cfar_without_grad_is_todays_path(gold):
-    raw = _g(gold["ca_raw"])
+    raw = dev(gold["ca_raw"])
     plain = ru.cfar_mask(raw, RES, diff=True)
     assert not plain.requires_grad
     with_grad = ru.cfar_mask(raw.clone().requires_grad_(True), RES, diff=True)
@@ -102,8 +69,8 @@ PEAK_CASES = [(True, False), (True, True), (False, False), (False, True)]
 
 
 def _peaks_inputs(gold, use_T):
-    az = _g(gold["pk_az"])
-    return az, torch.zeros_like(az), (_g(gold["pk_T_ab"]) if use_T else None)
+    az = dev(gold["pk_az"])
+    return az, torch.zeros_like(az), (dev(gold["pk_T_ab"]) if use_T else None)
 
 
 @pytest.mark.parametrize("diff,use_T", PEAK_CASES)
@@ -112,24 +79,24 @@ def test_peaks_gradient_matches_reference(gold, diff, use_T):
     az, tm, T_ab = _peaks_inputs(gold, use_T)
     n, G, want = gold["pk_n" + tag], gold["pk_G" + tag], gold["pk_grad" + tag]
     # padded form
-    mask = _g(gold["pk_mask"]).requires_grad_(True)
+    mask = dev(gold["pk_mask"]).requires_grad_(True)
     pc, cnt = ru.extract_pc_padded(mask, RES, az, tm, int(n.max()), T_ab=T_ab, diff=diff)
     assert pc.requires_grad and not cnt.requires_grad and cnt.dtype == torch.int32
     assert cnt.cpu().tolist() == n.tolist()
     np.testing.assert_allclose(pc.detach().cpu().numpy(), gold["pk_pc" + tag], atol=2e-5)
-    pc.backward(_g(G))
-    _close(mask.grad, want, "peaks padded diff=%d T=%d" % (diff, use_T), PEAKS_REL)
+    pc.backward(dev(G))
+    close(mask.grad, want, "peaks padded diff=%d T=%d" % (diff, use_T), PEAKS_REL)
     assert (mask.grad[:, 5] == 0).all()                                  # an all-zero row
     # ragged list form: a loss on the list elements reaches the mask
-    mask2 = _g(gold["pk_mask"]).requires_grad_(True)
+    mask2 = dev(gold["pk_mask"]).requires_grad_(True)
     pcs = ru.extract_pc(mask2, RES, az, tm, T_ab=T_ab, diff=diff)
     assert [p.shape[0] for p in pcs] == n.tolist() and all(p.requires_grad for p in pcs)
-    sum((p * _g(G[b, :n[b]])).sum() for b, p in enumerate(pcs)).backward()
-    _close(mask2.grad, want, "peaks list diff=%d T=%d" % (diff, use_T), PEAKS_REL)
+    sum((p * dev(G[b, :n[b]])).sum() for b, p in enumerate(pcs)).backward()
+    close(mask2.grad, want, "peaks list diff=%d T=%d" % (diff, use_T), PEAKS_REL)
     # a loss on one element only: the other item's cells get exactly 0
-    mask3 = _g(gold["pk_mask"]).requires_grad_(True)
+    mask3 = dev(gold["pk_mask"]).requires_grad_(True)
     pcs = ru.extract_pc(mask3, RES, az, tm, T_ab=T_ab, diff=diff)
-    (pcs[1] * _g(G[1, :n[1]])).sum().backward()
+    (pcs[1] * dev(G[1, :n[1]])).sum().backward()
     assert (mask3.grad[0] == 0).all() and torch.equal(mask3.grad[1], mask2.grad[1])
 
 
@@ -149,9 +116,9 @@ def test_peaks_structural_zeros(gold, diff):
     B, A, R = base.shape
 
     def grad_of(mask_np, max_pts, Gp):
-        m = _g(mask_np).requires_grad_(True)
+        m = dev(mask_np).requires_grad_(True)
         pc, cnt = ru.extract_pc_padded(m, RES, az, tm, max_pts, diff=diff)
-        pc.backward(_g(Gp))
+        pc.backward(dev(Gp))
         return m.grad, cnt.cpu().numpy()
 
     full, _ = grad_of(base, int(n.max()), G)
@@ -189,49 +156,49 @@ def test_peaks_structural_zeros(gold, diff):
 
 # ----------------------------------------------------------------------------- 3. the chain
 def _chain(gold, raw):
-    az = _g(gold["ch_az"])
+    az = dev(gold["ch_az"])
     npad, K = int(gold["ch_npad"]), int(gold["ch_iters"])
     m = ru.cfar_mask(raw, RES, diff=True)
     cloud, cnt = ru.extract_pc_padded(m, RES, az, torch.zeros_like(az), npad, diff=True)
-    wmask = _g(gold["ch_mu"])[:, :, None] * _g(gold["ch_mv"])[:, None, :]
+    wmask = dev(gold["ch_mu"])[:, :, None] * dev(gold["ch_mv"])[:, None, :]
     w = ru.extract_weights(wmask, cloud)[0]
     icp = ICP(icp_type="pt2pl", differentiable=True, max_iterations=K, tolerance=1e-9)
-    T = icp.icp(cloud, _g(gold["ch_map"]), weight=w, trim_dist=5.0, loss_fn={"name": "huber", "metric": 1.0}, dim=2)["T"]
+    T = icp.icp(cloud, dev(gold["ch_map"]), weight=w, trim_dist=5.0, loss_fn={"name": "huber", "metric": 1.0}, dim=2)["T"]
     return T, cloud, cnt, w
 
 
 def test_chain_pose_to_scan(gold, nn_engine):
     """pose functional -> T -> source cloud and extract_weights' scan_pc -> peak markers -> CFAR mask -> polar scan, against
     the reference's front end composed with the CPU restatement of dICP."""
-    raw = _g(gold["ch_raw"]).requires_grad_(True)
+    raw = dev(gold["ch_raw"]).requires_grad_(True)
     T, cloud, cnt, w = _chain(gold, raw)
     assert cnt.cpu().tolist() == gold["ch_n"].tolist()
     np.testing.assert_allclose(cloud.detach().cpu().numpy(), gold["ch_cloud"], atol=2e-5)
     np.testing.assert_allclose(w.detach().cpu().numpy(), gold["ch_w"], atol=2e-6)
     print("RATIO chain T max abs diff = %.3e" % np.abs(T.detach().cpu().numpy() - gold["ch_T"]).max())
-    (T * _g(gold["ch_G"])).sum().backward()
+    (T * dev(gold["ch_G"])).sum().backward()
     np.testing.assert_allclose(T.detach().cpu().numpy(), gold["ch_T"], atol=2e-6)
     for b in range(raw.shape[0]):
-        _close(raw.grad[b], gold["ch_grad"][b], "chain %s item %d" % (nn_engine, b), CHAIN_REL)
+        close(raw.grad[b], gold["ch_grad"][b], "chain %s item %d" % (nn_engine, b), CHAIN_REL)
 
 
 # ----------------------------------------------------------------------------- 4. reproducibility
 def test_gradients_are_bit_reproducible(gold):
     def cfar():
-        raw = _g(gold["ca_raw"]).requires_grad_(True)
-        ru.cfar_mask(raw, RES, diff=True).backward(_g(gold["ca_G"]))
+        raw = dev(gold["ca_raw"]).requires_grad_(True)
+        ru.cfar_mask(raw, RES, diff=True).backward(dev(gold["ca_G"]))
         return raw.grad
 
     def peaks(diff):
         az, tm, T_ab = _peaks_inputs(gold, True)
         tag = "%d1" % int(diff)
-        m = _g(gold["pk_mask"]).requires_grad_(True)
-        ru.extract_pc_padded(m, RES, az, tm, int(gold["pk_n" + tag].max()), T_ab=T_ab, diff=diff)[0].backward(_g(gold["pk_G" + tag]))
+        m = dev(gold["pk_mask"]).requires_grad_(True)
+        ru.extract_pc_padded(m, RES, az, tm, int(gold["pk_n" + tag].max()), T_ab=T_ab, diff=diff)[0].backward(dev(gold["pk_G" + tag]))
         return m.grad
 
     def chain():
-        raw = _g(gold["ch_raw"]).requires_grad_(True)
-        (_chain(gold, raw)[0] * _g(gold["ch_G"])).sum().backward()
+        raw = dev(gold["ch_raw"]).requires_grad_(True)
+        (_chain(gold, raw)[0] * dev(gold["ch_G"])).sum().backward()
         return raw.grad
 
     for name, f in (("cfar", cfar), ("peaks diff", lambda: peaks(True)), ("peaks hard", lambda: peaks(False)), ("chain", chain)):
@@ -278,15 +245,15 @@ def test_cfar_gradient_long_rows(R):
     for c in range(150, 1250, 37):
         raw[:, :, c:c + 3] += rng.uniform(0.1, 0.4, (2, 5, 3)).astype(np.float32)
     G = rng.normal(size=raw.shape).astype(np.float32)
-    x = _g(raw).requires_grad_(True)
+    x = dev(raw).requires_grad_(True)
     m = ru.cfar_mask(x, RES, diff=True)
-    m.backward(_g(G))
+    m.backward(dev(G))
     assert torch.isfinite(x.grad).all() and x.grad.abs().max() > 0
-    x2 = _g(raw[:, :, :3360]).requires_grad_(True)
+    x2 = dev(raw[:, :, :3360]).requires_grad_(True)
     m2 = ru.cfar_mask(x2, RES, diff=True)
-    m2.backward(_g(G[:, :, :3360]))
+    m2.backward(dev(G[:, :, :3360]))
     assert (x.grad[:, :, 3360:] == 0).all()
-    _close(x.grad[:, :, :3360], x2.grad.cpu().numpy(), "cfar long rows R=%d vs 3360" % R, 1e-6)
+    close(x.grad[:, :, :3360], x2.grad.cpu().numpy(), "cfar long rows R=%d vs 3360" % R, 1e-6)
     # and the peaks backward on a long row
     az = torch.linspace(0.1, 6.0, 5, device=DEV).repeat(2, 1)
     mm = m.detach().clone().requires_grad_(True)
@@ -302,9 +269,9 @@ def test_cpu_tensors_in_cpu_gradients_out(gold):
     assert m.device.type == "cpu" and m.requires_grad
     m.backward(torch.from_numpy(gold["ca_G"]))
     assert raw.grad.device.type == "cpu" and raw.grad.dtype == torch.float64
-    dev = _g(gold["ca_raw"]).requires_grad_(True)
-    ru.cfar_mask(dev, RES, diff=True).backward(_g(gold["ca_G"]))
-    assert torch.equal(raw.grad, dev.grad.cpu().double())
+    on_dev = dev(gold["ca_raw"]).requires_grad_(True)
+    ru.cfar_mask(on_dev, RES, diff=True).backward(dev(gold["ca_G"]))
+    assert torch.equal(raw.grad, on_dev.grad.cpu().double())
 
     az, tm, _ = _peaks_inputs(gold, False)
     mask = torch.from_numpy(gold["pk_mask"]).double().requires_grad_(True)

@@ -4,8 +4,7 @@ autograd (tests/golden/resample_grads.npz, written by tests/golden/make_golden_r
 structural zeros, the adjoint identity at full size, run-to-run bit equality, the chain through both links into dICP,
 the U-Net's parameters behind the Cartesian -> polar link, dtype / device of the gradients.
 
-Tolerances.  Against the golden gradients every comparison is max |got - ref| over max |ref| (_ratio, as in
-test_gpu_radar_grads.py), no cell excluded, and every bound is 4 x the worst ratio measured on an MI355X:
+Tolerances.  Against the golden gradients every comparison is max |got - ref| over max |ref| (support.ratio), no cell excluded, and every bound is 4 x the worst ratio measured on an MI355X:
 
     test                                          worst measured    bound
     polar -> Cartesian, pc_a (three variants)     8.7e-6            PC_A_REL  = 1.6e-5  (the front end's ceiling; 4 x = 3.5e-5)
@@ -33,7 +32,6 @@ additions, shared tap weights, and one rounding of each gradient cell)  +  n_tap
 (every tap rounded to the nearest fixed-point step).  Measured: 5.7e-11 (fp32) and 2.0e-17 (fp64) of sum|G| F(|X|).
 """
 import math
-import os
 
 import numpy as np
 import pytest
@@ -41,10 +39,10 @@ import torch
 
 from mm_masking_amd import radar_utils as ru
 from mm_masking_amd.dICP.ICP import ICP
+from radar_cases import RES, wobbly_azimuths
+from support import DEV, close, dev, load_golden, nn_engine, policy  # noqa: F401  (nn_engine: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-RES = 0.0596
 PC_A_REL = 1.6e-5
 PC_B_REL = 5.0e-6
 CP_REL = 9.4e-16
@@ -55,42 +53,17 @@ PC_VARIANTS = ({}, {"fix_wobble": False}, {"interpolate_crossover": False})
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, "resample_grads.npz")))
+    return load_golden(golden_dir, "resample_grads.npz")
 
 
 @pytest.fixture(scope="module")
 def base(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, "radar_grads.npz")))
-
-
-@pytest.fixture(params=["brute", "grid"])
-def nn_engine(request):
-    ICP.NN_SEARCH_OVERRIDE = request.param
-    yield request.param
-    ICP.NN_SEARCH_OVERRIDE = None
-
-
-def _g(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _ratio(g, ref, name):
-    g, ref = g.detach().cpu().double().numpy(), np.asarray(ref, dtype=np.float64)
-    scale = np.abs(ref).max()
-    assert scale > 0, name
-    r = np.abs(g - ref).max() / scale
-    print("RATIO %-40s err/scale = %.3e   (scale %.3e)" % (name, r, scale))
-    return r
-
-
-def _close(g, ref, name, rel):
-    r = _ratio(g, ref, name)
-    assert r <= rel, (name, r, rel)
+    return load_golden(golden_dir, "radar_grads.npz")
 
 
 def _pc_args(gold, key):
     R, W = (int(v) for v in gold[key + "_shape"])
-    return _g(gold[key + "_az"]), float(gold[key + "_res"]), W
+    return dev(gold[key + "_az"]), float(gold[key + "_res"]), W
 
 
 # ----------------------------------------------------------------------------- 1. against the golden gradients
@@ -99,30 +72,30 @@ def _pc_args(gold, key):
 def test_polar_to_cart_gradient_matches_reference(gold, key, tag):
     az, res, W = _pc_args(gold, key)
     kw = PC_VARIANTS[tag]
-    x = _g(gold[key + "_x"]).requires_grad_(True)
+    x = dev(gold[key + "_x"]).requires_grad_(True)
     y = ru.radar_polar_to_cartesian_diff(x, az, res, cart_pixel_width=W, **kw)
     assert y.requires_grad and y.grad_fn is not None
     plain = ru.radar_polar_to_cartesian_diff(x.detach(), az, res, cart_pixel_width=W, **kw)
     assert not plain.requires_grad and torch.equal(y.detach(), plain)
-    y.backward(_g(gold[key + "_G"]))
+    y.backward(dev(gold[key + "_G"]))
     assert x.grad.shape == x.shape and x.grad.dtype == torch.float32 and x.grad.is_cuda
     want = gold["%s_grad%d" % (key, tag)]
     for item in range(want.shape[0]):
-        _close(x.grad[item], want[item], "%s variant %d item %d" % (key, tag, item), PC_A_REL if key == "pc_a" else PC_B_REL)
+        close(x.grad[item], want[item], "%s variant %d item %d" % (key, tag, item), PC_A_REL if key == "pc_a" else PC_B_REL)
 
 
 def test_cart_to_polar_gradient_matches_reference(gold):
     A, R = (int(v) for v in gold["cp_a_shape"])
-    az = _g(gold["cp_a_az"])
-    x = _g(gold["cp_a_x"]).requires_grad_(True)
+    az = dev(gold["cp_a_az"])
+    x = dev(gold["cp_a_x"]).requires_grad_(True)
     y = ru.radar_cartesian_to_polar(x, az, 0.1, cart_resolution=0.3, polar_pixel_shape=(A, R))
     assert y.requires_grad and y.grad_fn is not None and y.dtype == torch.float64
     plain = ru.radar_cartesian_to_polar(x.detach(), az, 0.1, cart_resolution=0.3, polar_pixel_shape=(A, R))
     assert not plain.requires_grad and torch.equal(y.detach(), plain)
-    y.backward(_g(gold["cp_a_G"]))
+    y.backward(dev(gold["cp_a_G"]))
     assert x.grad.shape == x.shape and x.grad.dtype == torch.float64 and x.grad.is_cuda
     for item in range(x.shape[0]):
-        _close(x.grad[item], gold["cp_a_grad"][item], "cp_a item %d" % item, CP_REL)
+        close(x.grad[item], gold["cp_a_grad"][item], "cp_a item %d" % item, CP_REL)
 
 
 # ----------------------------------------------------------------------------- 2. structural zeros
@@ -132,8 +105,8 @@ def test_polar_cells_no_pixel_samples_get_exact_zero(gold):
     for key, cols in (("pc_a", slice(0, 1)), ("pc_b", slice(28, None))):
         az, res, W = _pc_args(gold, key)
         for tag, kw in enumerate(PC_VARIANTS):
-            x = _g(gold[key + "_x"]).requires_grad_(True)
-            ru.radar_polar_to_cartesian_diff(x, az, res, cart_pixel_width=W, **kw).backward(_g(gold[key + "_G"]))
+            x = dev(gold[key + "_x"]).requires_grad_(True)
+            ru.radar_polar_to_cartesian_diff(x, az, res, cart_pixel_width=W, **kw).backward(dev(gold[key + "_G"]))
             assert (x.grad[:, :, cols] == 0).all(), (key, tag)
             assert (gold["%s_grad%d" % (key, tag)][:, :, cols] == 0).all()
             assert x.grad.abs().max() > 0
@@ -145,13 +118,13 @@ def test_rows_cut_off_without_crossover_get_exact_zero(gold):
     az, res, W = _pc_args(gold, "pc_a")
     A = az.shape[1]
     ang = ru.form_cart_range_angle_grid(cart_pixel_width=W, dtype=torch.float32)[1].to(DEV)
-    G = _g(gold["pc_a_G"]).clone()
+    G = dev(gold["pc_a_G"]).clone()
     for b in range(G.shape[0]):
         G[b][~(ang > az[b, -1] + 0.02)] = 0.0
         assert (G[b] != 0).sum() > 20
     grads = {}
     for cross in (False, True):
-        x = _g(gold["pc_a_x"]).requires_grad_(True)
+        x = dev(gold["pc_a_x"]).requires_grad_(True)
         ru.radar_polar_to_cartesian_diff(x, az, res, cart_pixel_width=W, interpolate_crossover=cross,
                                          fix_wobble=False).backward(G)
         grads[cross] = x.grad
@@ -162,27 +135,19 @@ def test_rows_cut_off_without_crossover_get_exact_zero(gold):
 
 def test_cartesian_pixels_no_ray_touches_get_exact_zero(gold):
     A, R = (int(v) for v in gold["cp_a_shape"])
-    x = _g(gold["cp_a_x"]).requires_grad_(True)
-    ru.radar_cartesian_to_polar(x, _g(gold["cp_a_az"]), 0.1, cart_resolution=0.3, polar_pixel_shape=(A, R)).backward(_g(gold["cp_a_G"]))
-    untouched = _g(gold["cp_a_grad"] == 0)
+    x = dev(gold["cp_a_x"]).requires_grad_(True)
+    ru.radar_cartesian_to_polar(x, dev(gold["cp_a_az"]), 0.1, cart_resolution=0.3, polar_pixel_shape=(A, R)).backward(dev(gold["cp_a_G"]))
+    untouched = dev(gold["cp_a_grad"] == 0)
     assert untouched.float().mean() > 0.4
     assert (x.grad[untouched] == 0).all() and (x.grad[~untouched] != 0).float().mean() > 0.99
 
 
 # ----------------------------------------------------------------------------- 3. + 4. full size
-def _wobbly_azimuths(seed):
-    """One ascending table of 400 azimuths that is far from uniform: steps between 0.2 and 1.8 of the mean step."""
-    g = torch.Generator().manual_seed(seed)
-    steps = (0.2 + 1.6 * torch.rand(400, generator=g, dtype=torch.float64)) * (2 * math.pi / 400)
-    az = 0.004 + torch.cumsum(steps, 0) * (2 * math.pi - 0.02) / steps.sum()
-    return az[None]
-
-
 @pytest.fixture(scope="module")
 def full_size():
     """Inputs and both adjoints at 400 x 3360 <-> 640 x 640, B = 1, default parameters; computed once."""
     g = torch.Generator().manual_seed(77)
-    az = _wobbly_azimuths(5)
+    az = wobbly_azimuths(5)
     out = {"az": az}
     # polar -> Cartesian, fp32
     X = torch.randn(1, 400, 3360, generator=g).to(DEV)
@@ -246,24 +211,24 @@ def test_full_size_adjoints_are_bit_reproducible(full_size, op):
 
 # ----------------------------------------------------------------------------- 5. the chain
 def _chain(gold, base, c, p):
-    az = _g(base["ch_az"])
+    az = dev(base["ch_az"])
     npad, K = int(base["ch_npad"]), int(base["ch_iters"])
     B, A, R = base["ch_raw"].shape
     raw = base["ch_raw"].copy()
     raw.reshape(-1)[gold["ch_fix_idx"]] = gold["ch_fix_val"]
     polar_mask = ru.radar_cartesian_to_polar(c.double(), az.double(), RES, polar_pixel_shape=(A, R)).float()
-    m = ru.cfar_mask(polar_mask * _g(raw), RES, diff=True)
+    m = ru.cfar_mask(polar_mask * dev(raw), RES, diff=True)
     cloud, cnt = ru.extract_pc_padded(m, RES, az, torch.zeros_like(az), npad, diff=True)
     wmask = ru.radar_polar_to_cartesian_diff(p, az, float(gold["ch_p_res"]), cart_pixel_width=640)
     w = ru.extract_weights(wmask, cloud)[0]
     icp = ICP(icp_type="pt2pl", differentiable=True, max_iterations=K, tolerance=1e-9)
-    T = icp.icp(cloud, _g(base["ch_map"]), weight=w, trim_dist=5.0, loss_fn={"name": "huber", "metric": 1.0}, dim=2)["T"]
+    T = icp.icp(cloud, dev(base["ch_map"]), weight=w, trim_dist=5.0, loss_fn={"name": "huber", "metric": 1.0}, dim=2)["T"]
     return T, cloud, cnt, w
 
 
 def _chain_leaves(gold):
-    c = (_g(gold["ch_cu"])[:, :, None] * _g(gold["ch_cv"])[:, None, :]).contiguous().requires_grad_(True)
-    p = _g(gold["ch_p"]).requires_grad_(True)
+    c = (dev(gold["ch_cu"])[:, :, None] * dev(gold["ch_cv"])[:, None, :]).contiguous().requires_grad_(True)
+    p = dev(gold["ch_p"]).requires_grad_(True)
     return c, p
 
 
@@ -277,18 +242,18 @@ def test_chain_pose_to_both_images(gold, base, nn_engine):
     np.testing.assert_allclose(cloud.detach().cpu().numpy(), gold["ch_cloud"], atol=2e-5)
     np.testing.assert_allclose(w.detach().cpu().numpy(), gold["ch_w"], atol=2e-6)
     print("RATIO chain T max abs diff = %.3e" % np.abs(T.detach().cpu().numpy() - gold["ch_T"]).max())
-    (T * _g(base["ch_G"])).sum().backward()
+    (T * dev(base["ch_G"])).sum().backward()
     np.testing.assert_allclose(T.detach().cpu().numpy(), gold["ch_T"], atol=2e-6)
     assert c.grad.dtype == torch.float32 and p.grad.dtype == torch.float32
     for b in range(c.shape[0]):
-        _close(c.grad[b], gold["ch_grad_c"][b], "chain %s grad c item %d" % (nn_engine, b), CHAIN_C_REL)
-        _close(p.grad[b], gold["ch_grad_p"][b], "chain %s grad p item %d" % (nn_engine, b), CHAIN_P_REL)
+        close(c.grad[b], gold["ch_grad_c"][b], "chain %s grad c item %d" % (nn_engine, b), CHAIN_C_REL)
+        close(p.grad[b], gold["ch_grad_p"][b], "chain %s grad p item %d" % (nn_engine, b), CHAIN_P_REL)
 
 
 def test_chain_is_bit_reproducible(gold, base):
     def run():
         c, p = _chain_leaves(gold)
-        (_chain(gold, base, c, p)[0] * _g(base["ch_G"])).sum().backward()
+        (_chain(gold, base, c, p)[0] * dev(base["ch_G"])).sum().backward()
         return c.grad, p.grad
     (c1, p1), (c2, p2) = run(), run()
     assert torch.equal(c1, c2) and torch.equal(p1, p2)
@@ -298,13 +263,7 @@ def test_chain_is_bit_reproducible(gold, base):
 def test_gradient_reaches_the_unet_parameters():
     """A 64 x 64 mask of the U-Net through radar_cartesian_to_polar: every parameter gradient equals, bit for bit, the one
     obtained by feeding the standalone adjoint's mask gradient into mask.backward()."""
-    from mm_masking_amd import train_icp_weights as trn
-    from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-    params = trn.default_params(DEV)
-    params.update({"dropout": 0.0})
-    torch.manual_seed(3)
-    model = LearnICPWeightPolicy(params).to(DEV)
-    model.train()
+    model = policy(DEV, 3, train=True, dropout=0.0)
     g = torch.Generator().manual_seed(4)
     B, H, A, R = 2, 64, 32, 200
     scan = {"fft_data": (torch.rand(B, H, H, generator=g) ** 4).to(DEV), "fft_cfar": torch.zeros(B, H, H, device=DEV),
@@ -340,8 +299,8 @@ def test_dtype_device_and_no_grad_paths(gold):
     assert y.device.type == "cpu" and y.requires_grad
     y.backward(torch.from_numpy(gold["pc_a_G"]))
     assert x.grad.device.type == "cpu" and x.grad.dtype == torch.float64
-    d = _g(gold["pc_a_x"]).requires_grad_(True)
-    ru.radar_polar_to_cartesian_diff(d, az, res, cart_pixel_width=W).backward(_g(gold["pc_a_G"]))
+    d = dev(gold["pc_a_x"]).requires_grad_(True)
+    ru.radar_polar_to_cartesian_diff(d, az, res, cart_pixel_width=W).backward(dev(gold["pc_a_G"]))
     assert torch.equal(x.grad, d.grad.cpu().double())
     # requires_grad=False and no_grad(): today's path
     assert ru.radar_polar_to_cartesian_diff(d.detach(), az, res, cart_pixel_width=W).grad_fn is None

@@ -49,9 +49,10 @@ from dicp_cases import (B, HARD_STEEP, K, M, M_REAL, N, N_REAL, NAMES, PER_PAIR_
                         ROBUST_TRIM as TRIM, K_MULT, TAU, TOL, assert_awake, close, first_neighbours, gpu, inputs, nn_engine,
                         reference, same)  # noqa: F401
 from dicp_restatement import per_point_terms
+from radar_cases import scene64  # noqa: F401  (the smallest scan-mode batch of the suite, a module fixture)
+from support import DEV, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def _pose(run, ref):
@@ -284,16 +285,13 @@ def test_bad_scale_on_the_device_raises_the_status_bit_and_nothing_else(name):
 
 
 # ----------------------------------------------------------------------------- 7. the policy
-from test_gpu_mask_scan import scene64, _policy  # noqa: E402,F401
-
-
 def test_policy_learns_the_welsch_scale(scene64):
     """One training step with icp_loss_fn = Welsch at 0.5 and learn_icp=("metric",): a finite, non-zero gradient of
     icp_metric (printed; 4.2714e-17 on an MI355X); the inference instance runs with the same kernel and nearest
     correspondences."""
     scan, mp, T0, G = scene64
-    kw = dict(mask_target="scan", icp_loss_fn={"name": "welsch", "metric": 0.5})
-    model, plain = _policy(learn_icp=("metric",), **kw), _policy(**kw)
+    kw = dict(dropout=0.0, mask_target="scan", icp_loss_fn={"name": "welsch", "metric": 0.5})
+    model, plain = policy(DEV, 3, learn_icp=("metric",), **kw), policy(DEV, 3, **kw)
     assert [n for n, _ in model.named_parameters() if n.startswith("icp_")] == ["icp_metric"]
     model.train(), plain.train()
     T, _, _ = model(scan, mp, T0)

@@ -33,9 +33,10 @@ from mm_masking_amd.dICP.ICP import ICP
 from dicp_cases import (B, GATE_CASES as CASES, GATE_IDS as IDS, GATE_TRIM as TRIM, K, M, M_REAL, N, N_REAL, NAMES, REAL, TOL,
                         assert_gate_awake, close, gpu, inputs, nn_engine, reference)  # noqa: F401
 from dicp_restatement import as_bn, band_share, per_point_terms
+from radar_cases import scene64  # noqa: F401  (the smallest scan-mode batch of the suite, a module fixture)
+from support import DEV, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 # ----------------------------------------------------------------------------- 1. - 4. forward, gradients, zeros, run-to-run
@@ -205,14 +206,11 @@ def test_coincident_point_keeps_every_gradient_finite(nn_engine, ci):
 
 
 # ----------------------------------------------------------------------------- 8. the policy
-from test_gpu_mask_scan import scene64, _policy  # noqa: E402,F401  (the smallest scan-mode batch of the suite, as a fixture)
-
-
 def test_policy_soft_gate_trains_and_inference_stays_hard(scene64):
     """mask_target="scan": one training step with params["icp_trim"] = "tanh".  The points of this scene lie 0.09 .. 0.15 m
     from their correspondents, so a trim distance of 0.12 m puts them inside the gate's band (steepness 10: |argument| < 0.4)."""
     scan, mp, T0, G = scene64
-    kw = dict(mask_target="scan", icp_trim_dist=0.12)
+    kw = dict(dropout=0.0, mask_target="scan", icp_trim_dist=0.12)
 
     def step(model):
         model.train()
@@ -220,7 +218,7 @@ def test_policy_soft_gate_trains_and_inference_stays_hard(scene64):
         (T * G).sum().backward()
         return T.detach(), [q.grad.detach().clone() for q in model.parameters()]
 
-    soft_model, hard_model = _policy(icp_trim="tanh", **kw), _policy(**kw)
+    soft_model, hard_model = policy(DEV, 3, icp_trim="tanh", **kw), policy(DEV, 3, **kw)
     assert soft_model.ICP_alg.trim == "tanh" and soft_model.ICP_alg_inference.trim == "hard"
     T_soft, g_soft = step(soft_model)
     T_hard, g_hard = step(hard_model)

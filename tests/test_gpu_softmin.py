@@ -35,9 +35,10 @@ from oracle.dicp_ref import transform_points
 from dicp_cases import (B, K, M, M_REAL, N, N_REAL, NAMES, SOFTMIN_CASES as CASES, SOFTMIN_IDS as IDS, SOFTMIN_TRIM as TRIM, TAU, TOL,
                         assert_softmin_awake, close, first_neighbours, gpu, inputs, nn_engine, reference)  # noqa: F401
 from dicp_restatement import knn_ref_batch
+from radar_cases import scene64  # noqa: F401  (the smallest scan-mode batch of the suite, a module fixture)
+from support import DEV, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def _knn_search(src, tgt, T, dim, k):
@@ -233,12 +234,9 @@ def test_softmin_call_without_a_gradient_input_keeps_the_mode_and_the_pose():
 
 
 # ----------------------------------------------------------------------------- 7. the policy
-from test_gpu_mask_scan import scene64, _policy  # noqa: E402,F401  (the smallest scan-mode batch of the suite, as a fixture)
-
-
 def test_policy_softmin_trains_and_inference_stays_nearest(scene64):
     scan, mp, T0, G = scene64
-    kw = dict(mask_target="scan")
+    kw = dict(dropout=0.0, mask_target="scan")
 
     def step(model):
         model.train()
@@ -246,7 +244,7 @@ def test_policy_softmin_trains_and_inference_stays_nearest(scene64):
         (T * G).sum().backward()
         return T.detach(), [q.grad.detach().clone() if q.grad is not None else None for q in model.parameters()]
 
-    soft_model, hard_model = _policy(icp_correspondence="softmin", **kw), _policy(**kw)
+    soft_model, hard_model = policy(DEV, 3, icp_correspondence="softmin", **kw), policy(DEV, 3, **kw)
     assert soft_model.ICP_alg.correspondence == "softmin" and soft_model.ICP_alg_inference.correspondence == "nearest"
     T_soft, g_soft = step(soft_model)
     T_hard, g_hard = step(hard_model)

@@ -18,7 +18,7 @@ Frozen iterations: the pt2pl, Huber, dim 2 batch of tests/icp_freeze_cases.py wi
 k = 4, tau = (0.25, 0.275, 0.225), tolerance 3e-5 -- on the CPU restatement the pairs stay active for 4, 3 and 2 iterations
 and every step norm of an active pair is at least 14x away from the tolerance.
 
-The policy: scene64 of tests/test_gpu_mask_scan.py, icp_softmin_temp = POLICY_TAU (see there).
+The policy: scene64 of tests/radar_cases.py, icp_softmin_temp = POLICY_TAU (see there).
 
 Measured on an MI355X (all cases, k = 4 and 8): pose within 6.8e-7 of the replay; gradients within 4.0e-5 of the reference's
 largest magnitude for the four inputs (weight, pt2pt Huber dim 3; source 1.3e-5, target 1.8e-5, T_init 6.6e-6 at most) and
@@ -39,9 +39,10 @@ from mm_masking_amd.dICP.ICP import ICP, check_errors
 import icp_freeze_cases as fz
 from dicp_cases import (B, K, N, NAMES, PER_PAIR_TAU as PER_PAIR, SOFTMIN_CASES as CASES, SOFTMIN_IDS as IDS, SOFTMIN_TRIM as TRIM, TOL,
                         assert_softmin_awake, assert_tau_awake, close, gpu, inputs, reference, same)
+from radar_cases import scene64  # noqa: F401  (the smallest scan-mode batch of the suite, a module fixture)
+from support import DEV, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 ALL5 = NAMES + ("tau",)
 EQUAL = (0.25, 0.25)
@@ -189,13 +190,10 @@ def test_bad_value_on_the_device_raises_the_status_bit_and_nothing_else():
 
 
 # ----------------------------------------------------------------------------- 7. the policy
-from test_gpu_mask_scan import scene64, _policy  # noqa: E402,F401
-
-
 def test_policy_learns_the_temperature(scene64):
     scan, mp, T0, G = scene64
-    kw = dict(mask_target="scan", icp_correspondence="softmin", icp_softmin_temp=POLICY_TAU)
-    model, plain, hard = _policy(learn_icp=("softmin_temp",), **kw), _policy(**kw), _policy(mask_target="scan")
+    kw = dict(dropout=0.0, mask_target="scan", icp_correspondence="softmin", icp_softmin_temp=POLICY_TAU)
+    model, plain, hard = policy(DEV, 3, learn_icp=("softmin_temp",), **kw), policy(DEV, 3, **kw), policy(DEV, 3, dropout=0.0, mask_target="scan")
     assert [n for n, _ in model.named_parameters() if n.startswith("icp_")] == ["icp_softmin_temp_p"]
     assert not any(n.startswith("icp_") for n, _ in plain.named_parameters())
     model.train(), plain.train()

@@ -11,10 +11,9 @@ import torch.nn.functional as F
 from mm_masking_amd import train_icp_weights as trn
 from mm_masking_amd import unet_hip_bn as ub
 from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-
+from support import DEV, _Q, nchw
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 @pytest.mark.parametrize("B,H,W,C,drop", [(2, 24, 40, 8, 0.0), (3, 17, 23, 32, 0.2), (2, 9, 11, 256, 0.0)])
@@ -63,17 +62,12 @@ def _bn_train(a, bn_w, bn_b, eps=1e-5):
     return (a - mean) / torch.sqrt(var + eps) * bn_w.view(1, -1, 1, 1) + bn_b.view(1, -1, 1, 1)
 
 
-def _nchw(t):
-    return t.float().permute(0, 3, 1, 2)
-
-
 @pytest.mark.parametrize("B,H,W,drop,leaky", [(2, 64, 64, 0.0, False), (3, 96, 64, 0.1, False), (2, 64, 96, 0.05, True)])
 def test_batch_norm_network_on_pinned_activations(B, H, W, drop, leaky):
     """The whole batch-norm network, layer by layer on the tensors the HIP path itself stored (so that bf16
     differences do not compound through 22 BatchNorms over a handful of pixels), then every parameter gradient
     against autograd through an fp32 graph whose forward values are pinned to the HIP activations (the technique
     of test_gpu_unet_kernels.py::test_unet_hip_backward_exact_on_pinned_activations)."""
-    from test_gpu_unet_kernels import _Q
     p = trn.default_params(DEV)
     p.update({"dropout": drop, "batch_norm": True, "leaky": leaky, "norm_weights": False})
     torch.manual_seed(5)
@@ -103,7 +97,7 @@ def test_batch_norm_network_on_pinned_activations(B, H, W, drop, leaky):
     q = _Q.apply
 
     def pin(ref, mine_nhwc):
-        mine = _nchw(mine_nhwc)
+        mine = nchw(mine_nhwc)
         return q(ref + (mine - ref).detach())
 
     def conv(t, m):
@@ -114,22 +108,22 @@ def test_batch_norm_network_on_pinned_activations(B, H, W, drop, leaky):
         blk = blocks[k]
         zA = conv(xin, blk[0])
         aA_ref = act(zA)
-        assert (aA_ref - _nchw(aA)).abs().max().item() < 0.03 + 0.01 * aA_ref.abs().max().item(), (key, "conv A")
+        assert (aA_ref - nchw(aA)).abs().max().item() < 0.03 + 0.01 * aA_ref.abs().max().item(), (key, "conv A")
         # activation factor taken from the stored tensor, as the HIP adjoint does
-        fA = torch.where(_nchw(aA) > 0, 1.0, slope) if leaky else (_nchw(aA) > 0).float()
-        aA_p = q(zA * fA + (_nchw(aA) - zA * fA).detach())
+        fA = torch.where(nchw(aA) > 0, 1.0, slope) if leaky else (nchw(aA) > 0).float()
+        aA_p = q(zA * fA + (nchw(aA) - zA * fA).detach())
         yA_ref = _bn_train(aA_p, blk[2].weight, blk[2].bias)
-        assert (yA_ref - _nchw(yA)).abs().max().item() < 0.04 + 0.01 * yA_ref.abs().max().item(), (key, "BN A")
+        assert (yA_ref - nchw(yA)).abs().max().item() < 0.04 + 0.01 * yA_ref.abs().max().item(), (key, "BN A")
         yA_p = pin(yA_ref, yA)
         zB = conv(yA_p, blk[3])
         aB_ref = act(zB)
-        assert (aB_ref - _nchw(aB)).abs().max().item() < 0.03 + 0.01 * aB_ref.abs().max().item(), (key, "conv B")
-        fB = torch.where(_nchw(aB) > 0, 1.0, slope) if leaky else (_nchw(aB) > 0).float()
-        aB_p = q(zB * fB + (_nchw(aB) - zB * fB).detach())
+        assert (aB_ref - nchw(aB)).abs().max().item() < 0.03 + 0.01 * aB_ref.abs().max().item(), (key, "conv B")
+        fB = torch.where(nchw(aB) > 0, 1.0, slope) if leaky else (nchw(aB) > 0).float()
+        aB_p = q(zB * fB + (nchw(aB) - zB * fB).detach())
         yB_ref = _bn_train(aB_p, blk[5].weight, blk[5].bias)
-        keep = ((_nchw(d) != 0) | torch.signbit(_nchw(d))).float()
+        keep = ((nchw(d) != 0) | torch.signbit(nchw(d))).float()
         d_ref = yB_ref * keep * sd_scale
-        assert ((d_ref - _nchw(d)).abs() * keep).max().item() < 0.05 + 0.01 * d_ref.abs().max().item(), (key, "BN B")
+        assert ((d_ref - nchw(d)).abs() * keep).max().item() < 0.05 + 0.01 * d_ref.abs().max().item(), (key, "BN B")
         return pin(d_ref, d)
 
     xb = x.to(torch.bfloat16).float()

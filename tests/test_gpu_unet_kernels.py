@@ -6,9 +6,9 @@ import torch
 import torch.nn.functional as F
 
 from mm_masking_amd import unet_hip as uh
+from support import DEV, _Q, _QB, nchw, nhwc, policy
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def _rand_nhwc(B, H, W, C, seed):
@@ -241,10 +241,6 @@ def test_conv3x3_wgrad_concat_deep():
         assert (dW - w.grad).abs().max().item() < 2e-3 * w.grad.abs().max().item() + 1e-3
 
 
-def _nhwc(x_nchw):
-    return x_nchw.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
-
-
 def test_aux_kernels_vs_torch():
     g = torch.Generator().manual_seed(0)
     # first layer
@@ -296,27 +292,27 @@ def test_aux_kernels_vs_torch():
         assert torch.equal(prm[:, 0], mn) and torch.equal(prm[:, 1], 1.0 / (mx - mn))
     # max pool fwd / bwd (with the fused relu+dropout factor)
     d = F.relu(torch.randn(2, 16, 12, 20, generator=g)).to(DEV)
-    dn = _nhwc(d)
+    dn = nhwc(d)
     p = uh.maxpool2(dn)
     dref = dn.float().permute(0, 3, 1, 2).requires_grad_(True)
     pref = F.max_pool2d(dref, 2, 2)
     assert torch.equal(p.float(), pref.permute(0, 2, 3, 1))
     gy = torch.randn(2, 16, 6, 10, generator=g).to(DEV)
     pref.backward(gy.to(torch.bfloat16).float())
-    gz = uh.maxpool2_bwd(dn, _nhwc(gy), 1.25)
+    gz = uh.maxpool2_bwd(dn, nhwc(gy), 1.25)
     want = (dref.grad * (dref > 0) * 1.25).permute(0, 2, 3, 1)
     assert (gz.float() - want).abs().max().item() < 0.02
     # odd sizes: floor-rounded output, the last row / column gets a zero gradient
     for (hh, ww) in [(13, 20), (12, 21), (25, 105), (3, 5)]:
         d = F.relu(torch.randn(2, 16, hh, ww, generator=g)).to(DEV)
-        dn = _nhwc(d)
+        dn = nhwc(d)
         p = uh.maxpool2(dn)
         dref = dn.float().permute(0, 3, 1, 2).requires_grad_(True)
         pref = F.max_pool2d(dref, 2, 2)
         assert p.shape == (2, hh // 2, ww // 2, 16) and torch.equal(p.float(), pref.permute(0, 2, 3, 1))
         gy = torch.randn(2, 16, hh // 2, ww // 2, generator=g).to(DEV)
         pref.backward(gy.to(torch.bfloat16).float())
-        gz = uh.maxpool2_bwd(dn, _nhwc(gy), 1.25)
+        gz = uh.maxpool2_bwd(dn, nhwc(gy), 1.25)
         want = (dref.grad * (dref > 0) * 1.25).permute(0, 2, 3, 1)
         assert (gz.float() - want).abs().max().item() < 0.02
     # bilinear upsample (align_corners) fwd / bwd
@@ -325,44 +321,23 @@ def test_aux_kernels_vs_torch():
         xs = torch.randn(2, ch, hs, ws, generator=g).to(DEV)
         xr = xs.to(torch.bfloat16).float().requires_grad_(True)
         ur = F.interpolate(xr, size=(ho, wo), mode="bilinear", align_corners=True)
-        u = uh.upsample(_nhwc(xs), ho, wo)
+        u = uh.upsample(nhwc(xs), ho, wo)
         assert (u.float() - ur.permute(0, 2, 3, 1)).abs().max().item() < 0.02
         gu = torch.randn(2, ch, ho, wo, generator=g).to(DEV)
         ur.backward(gu.to(torch.bfloat16).float())
-        gx = uh.upsample_bwd(_nhwc(gu), hs, ws)
+        gx = uh.upsample_bwd(nhwc(gu), hs, ws)
         assert (gx.float() - xr.grad.permute(0, 2, 3, 1)).abs().max().item() < 0.05 + 0.008 * xr.grad.abs().max().item()   # bf16 output
         src = torch.randn(2, ch, hs, ws, generator=g).to(DEV)
-        gx2 = uh.upsample_bwd(_nhwc(gu), hs, ws, relu_src=_nhwc(src), scale=2.0)
+        gx2 = uh.upsample_bwd(nhwc(gu), hs, ws, relu_src=nhwc(src), scale=2.0)
         want = (xr.grad * (src.to(torch.bfloat16).float() > 0) * 2.0).permute(0, 2, 3, 1)
         assert (gx2.float() - want).abs().max().item() < 0.1 + 0.008 * want.abs().max().item()
     # final layer
     xf = F.relu(torch.randn(2, 8, 10, 12, generator=g)).to(DEV)
     wf = torch.randn(8, generator=g).to(DEV)
     bf = torch.randn(1, generator=g).to(DEV)
-    m = uh.final_fwd(_nhwc(xf), wf, bf)
+    m = uh.final_fwd(nhwc(xf), wf, bf)
     mref = torch.sigmoid((xf.to(torch.bfloat16).float() * wf.to(torch.bfloat16).float().view(1, 8, 1, 1)).sum(1) + bf)
     assert (m - mref).abs().max().item() < 1e-4
-
-
-def _policy(dropout, amp):
-    from mm_masking_amd import train_icp_weights as trn
-    from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
-    p = trn.default_params(DEV)
-    p.update({"dropout": dropout, "amp_dtype": amp, "unet_backend": "torch"})
-    torch.manual_seed(11)
-    return LearnICPWeightPolicy(p).to(DEV)
-
-
-class _Q(torch.autograd.Function):
-    """bf16 storage point: rounds the tensor in forward and its gradient in backward."""
-
-    @staticmethod
-    def forward(ctx, x):
-        return x.to(torch.bfloat16).float()
-
-    @staticmethod
-    def backward(ctx, g):
-        return g.to(torch.bfloat16).float()
 
 
 def _emulated_unet(model, x):
@@ -390,22 +365,6 @@ def _emulated_unet(model, x):
     return torch.sigmoid(F.conv2d(cur, fl.weight.to(torch.bfloat16).float(), fl.bias)).squeeze(1)
 
 
-def _nchw(t):
-    return t.float().permute(0, 3, 1, 2)
-
-
-class _QB(torch.autograd.Function):
-    """bf16 storage point of a gradient tensor only: identity in forward, rounds the gradient in backward."""
-
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g.to(torch.bfloat16).float()
-
-
 def _forced(z_or_y, mine_nhwc, relu, scale=1.0):
     """Forward value := the HIP path's stored tensor; backward := the reference operator's
     (ReLU mask taken from the stored tensor, as the HIP epilogues do), rounded to bf16 where the HIP path
@@ -413,7 +372,7 @@ def _forced(z_or_y, mine_nhwc, relu, scale=1.0):
     kept elements, so the gradient is scaled first and rounded then (rounding g and scaling afterwards is the
     same tensor only for scale = 1, and made this reference differ from the kernels by one bf16 rounding per
     element at every dropout layer: DESIGN.md 6b)."""
-    mine = _nchw(mine_nhwc)
+    mine = nchw(mine_nhwc)
     if not relu:
         return _Q.apply(z_or_y + (mine - z_or_y).detach())
     y = _QB.apply(z_or_y * (mine > 0)) * scale
@@ -453,7 +412,7 @@ def test_unet_hip_backward_exact_on_pinned_activations(B, H, W, drop):
     """Whole network, forward + all 46 parameter gradients, against autograd on the activations the HIP
     path produced (square and non-square images, batch sizes that are not multiples of the XCD count, sizes
     that go odd under the floor-rounding poolings as the polar 400 x 3360 input does)."""
-    model = _policy(drop, torch.float32)
+    model = policy(DEV, 11, dropout=drop, amp_dtype=torch.float32, unet_backend="torch")
     model.train()
     g = torch.Generator().manual_seed(1)
     x = torch.rand(B, 1, H, W, generator=g).to(DEV)
@@ -509,7 +468,7 @@ def test_unet_hip_close_to_fp32_module():
     network's gradients by tens of percent per tensor (PyTorch's own bf16 autocast path
     deviates more: scripts/diag_unet_grads.py), so only direction and global error are bounded."""
     H = 64
-    model = _policy(0.0, torch.float32)
+    model = policy(DEV, 11, dropout=0.0, amp_dtype=torch.float32, unet_backend="torch")
     model.train()
     g = torch.Generator().manual_seed(1)
     x = torch.rand(2, 1, H, H, generator=g).to(DEV)
@@ -534,7 +493,7 @@ def test_unet_hip_fused_mask_normalisation(B, H, W):
     """norm=True (mask / amax per image inside the network's autograd node: mmk_mask_normalize,
     mmk_final_bwd_normalized) against the same network followed by the tensor expression of
     icp_weight_policy.py:192-193 under autograd."""
-    model = _policy(0.0, torch.float32)
+    model = policy(DEV, 11, dropout=0.0, amp_dtype=torch.float32, unet_backend="torch")
     model.train()
     g = torch.Generator().manual_seed(2)
     x = torch.rand(B, 1, H, W, generator=g).to(DEV)
@@ -588,23 +547,23 @@ def test_elementwise_kernels_random_shapes():
         xs = torch.randn(B, C, hs, ws, generator=g).to(DEV)
         xr = xs.to(torch.bfloat16).float().requires_grad_(True)
         ur = F.interpolate(xr, size=(ho, wo), mode="bilinear", align_corners=True)
-        u = uh.upsample(_nhwc(xs), ho, wo)
+        u = uh.upsample(nhwc(xs), ho, wo)
         assert (u.float() - ur.permute(0, 2, 3, 1)).abs().max().item() < 0.03, (B, C, hs, ws, ho, wo)
         gu = torch.randn(B, C, ho, wo, generator=g).to(DEV)
         ur.backward(gu.to(torch.bfloat16).float())
-        gx = uh.upsample_bwd(_nhwc(gu), hs, ws)
+        gx = uh.upsample_bwd(nhwc(gu), hs, ws)
         assert (gx.float() - xr.grad.permute(0, 2, 3, 1)).abs().max().item() < 0.05 + 0.008 * xr.grad.abs().max().item(), (B, C, hs, ws)
         # pooling forward / backward on the up-sampled size
         if ho >= 2 and wo >= 2:
             d = F.relu(torch.randn(B, C, ho, wo, generator=g)).to(DEV)
-            dn = _nhwc(d)
+            dn = nhwc(d)
             p = uh.maxpool2(dn)
             dref = dn.float().permute(0, 3, 1, 2).requires_grad_(True)
             pref = F.max_pool2d(dref, 2, 2)
             assert torch.equal(p.float(), pref.permute(0, 2, 3, 1))
             gy = torch.randn(B, C, ho // 2, wo // 2, generator=g).to(DEV)
             pref.backward(gy.to(torch.bfloat16).float())
-            gz = uh.maxpool2_bwd(dn, _nhwc(gy), 1.0)
+            gz = uh.maxpool2_bwd(dn, nhwc(gy), 1.0)
             assert (gz.float() - (dref.grad * (dref > 0)).permute(0, 2, 3, 1)).abs().max().item() < 0.02
     # fused pool in the convolution epilogue, random sizes
     for _ in range(6):

@@ -18,8 +18,7 @@ icp_mod = importlib.import_module("mm_masking_amd.dICP.ICP")        # (the packa
 
 from dicp_cases import policy_params
 from dicp_restatement import ICPRestatement, closed_form_sums
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, icp_params, n_args
 B, N, M, K = 2, 70, 160, 3
 TRIM, STEEP = 0.6, 4.0
 #        type     loss      k    dim noise
@@ -165,28 +164,17 @@ def L():
     return _lib.lib()
 
 
-def _params(**kw):
-    d = dict(B=2, N=100, M=300, tgt_cols=6, dim=2, icp_type=1, loss=2, loss_k=1.0, trim_dist=5.0, tolerance=1e-5,
-             max_iter=10, save_state=1, check_every=0, nn_method=0)
-    d.update(kw)
-    return _lib.IcpParams(**d)
-
-
-def _n_args(hdr, name):
-    return len(re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, hdr).group(1).split(","))
-
-
 def test_hp_entries_exist_and_older_sizes_are_unchanged(L):
     raw = open(os.path.join(ROOT, "include", "mmk.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     for name in ("mmk_icp_forward_hp", "mmk_icp_backward_hp_workspace_bytes", "mmk_icp_backward_hp"):
         assert hasattr(L, name) and name in _lib.EXPORTED, name
-        assert _n_args(hdr, name) == len(_lib.EXPORTED[name][1]), name
-    assert _n_args(hdr, "mmk_icp_forward_hp") == _n_args(hdr, "mmk_icp_forward") + 2
-    assert _n_args(hdr, "mmk_icp_backward_hp") == _n_args(hdr, "mmk_icp_backward_points") + 3
+        assert n_args(hdr, name) == len(_lib.EXPORTED[name][1]), name
+    assert n_args(hdr, "mmk_icp_forward_hp") == n_args(hdr, "mmk_icp_forward") + 2
+    assert n_args(hdr, "mmk_icp_backward_hp") == n_args(hdr, "mmk_icp_backward_points") + 3
     assert int(re.search(r"#define\s+MMK_ICP_STATUS_BAD_HYPER\s+(\d+)", raw).group(1)) == icp_mod.ICP_STATUS_BAD_HYPER == 2
     assert ctypes.sizeof(_lib.IcpParams) == L.mmk_icp_params_bytes() == 60          # the struct did not grow
-    for p in (_params(), _params(trim_steep=4.0), _params(N=1000, dim=3, nn_method=1)):
+    for p in (icp_params(), icp_params(trim_steep=4.0), icp_params(N=1000, dim=3, nn_method=1)):
         r = ctypes.byref(p)
         base = L.mmk_icp_backward_points_workspace_bytes(r, 0)
         assert base == L.mmk_icp_workspace_bytes(r) > 0
@@ -202,7 +190,7 @@ def test_hp_entries_exist_and_older_sizes_are_unchanged(L):
 def test_hp_argument_errors(L):
     null, fake = ctypes.c_void_p(0), ctypes.c_void_p(4096)       # never dereferenced: every call fails before any launch
     iters = ctypes.c_int(0)
-    p = _params()
+    p = icp_params()
     for per_pair in (2, -1):
         assert L.mmk_icp_forward_hp(ctypes.byref(p), *([fake] * 10), fake, per_pair, fake, 1 << 30, ctypes.byref(iters), null) == -1
         assert b"per_pair" in L.mmk_last_error()
@@ -212,9 +200,9 @@ def test_hp_argument_errors(L):
     assert b"grad_hyper needs hyper" in L.mmk_last_error()
     assert L.mmk_icp_backward_hp(ctypes.byref(p), *([fake] * 13), fake, 0, fake, fake, 64, null) == -1
     assert b"workspace too small" in L.mmk_last_error()
-    assert L.mmk_icp_backward_hp(ctypes.byref(_params(save_state=0)), *([fake] * 13), fake, 0, fake, fake, 1 << 30, null) == -1
+    assert L.mmk_icp_backward_hp(ctypes.byref(icp_params(save_state=0)), *([fake] * 13), fake, 0, fake, fake, 1 << 30, null) == -1
     assert b"save_state" in L.mmk_last_error()
-    bad = _params(trim_steep=-1.0)
+    bad = icp_params(trim_steep=-1.0)
     assert L.mmk_icp_backward_hp_workspace_bytes(ctypes.byref(bad), 1, 1) == 0 and b"trim_steep" in L.mmk_last_error()
     assert L.mmk_icp_forward_hp(ctypes.byref(bad), *([fake] * 10), fake, 0, fake, 1 << 30, ctypes.byref(iters), null) == -1
 

@@ -2,7 +2,6 @@
 exported, host-side argument checks (no launch) -- and the CPU mirror of the policy against the reference's golden input
 gradients (tests/golden/input_grads.npz)."""
 import ctypes
-import os
 import re
 
 import pytest
@@ -11,8 +10,8 @@ import torch
 from mm_masking_amd import _lib
 
 import input_grad_cases as igc
+from support import header, n_args
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmk_conv_first_dgrad_ws_bytes", "mmk_conv_first_dgrad", "mmk_input_norm_bwd", "mmk_unet_backward_input")
 NULL = ctypes.c_void_p(0)
 FAKE = ctypes.c_void_p(4096)          # never dereferenced: every call below fails on the host before any launch
@@ -25,21 +24,11 @@ def L():
     return _lib.lib()
 
 
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mmk.h")).read(), flags=re.S)
-
-
-def _n_args(hdr, name):
-    m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, hdr, flags=re.S)
-    assert m, name
-    return len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
-
-
 def test_new_entries_declared_and_exported(L):
-    hdr = _header()
+    hdr = header()
     for name in NEW:
         assert hasattr(L, name) and name in _lib.EXPORTED, name
-        assert _n_args(hdr, name) == len(_lib.EXPORTED[name][1]), name         # the binding has the header's arity
+        assert n_args(hdr, name) == len(_lib.EXPORTED[name][1]), name         # the binding has the header's arity
     assert L.mmk_version() == int(re.search(r"#define\s+MMK_VERSION\s+(\d+)", hdr).group(1))
     for mode, val in (("NONE", None), ("MINMAX", "minmax"), ("STANDARDIZE", "standardize")):
         assert int(re.search(r"#define\s+MMK_NORM_%s\s+(\d+)" % mode, hdr).group(1)) == _lib.NORM_MODES[val]

@@ -8,12 +8,12 @@ import re
 import numpy as np
 import pytest
 import torch
-import yaml
 
 from mm_masking_amd import _lib
 from mm_masking_amd import dICP
 from mm_masking_amd.dICP.ICP import ICP
 from knn_normals_ref import knn_normals_ref, lattice_line, lattice_plane, nn_dist_f32
+from support import icp_yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmk_knn_normals_workspace_bytes", "mmk_knn_normals")
@@ -86,23 +86,16 @@ def test_no_device_is_an_error_not_a_fallback():
         dICP.with_normals(torch.zeros(1, 10, 3), k=5, dim=2)
 
 
-def _yaml(tmp_path, **params):
-    path = os.path.join(str(tmp_path), "cfg.yaml")
-    with open(path, "w") as f:
-        yaml.safe_dump({"dICP": {"target_pad_val": 1000.0, "parameters": params}}, f)
-    return path
-
-
 def test_config_key(tmp_path):
     d = ICP("pt2pl")
     assert d.target_normals == "given" and d.normals_k == 16               # the built-in YAML keeps `given`
-    e = ICP("pt2pl", config_path=_yaml(tmp_path, target_normals="estimate", normals_k=9))
+    e = ICP("pt2pl", config_path=icp_yaml(tmp_path, target_normals="estimate", normals_k=9))
     assert e.target_normals == "estimate" and e.normals_k == 9
-    assert ICP("pt2pl", config_path=_yaml(tmp_path, target_normals="estimate")).normals_k == 16
+    assert ICP("pt2pl", config_path=icp_yaml(tmp_path, target_normals="estimate")).normals_k == 16
     with pytest.raises(ValueError, match="target_normals"):
-        ICP("pt2pl", config_path=_yaml(tmp_path, target_normals="pca"))
+        ICP("pt2pl", config_path=icp_yaml(tmp_path, target_normals="pca"))
     with pytest.raises(ValueError, match="normals_k"):
-        ICP("pt2pl", config_path=_yaml(tmp_path, target_normals="estimate", normals_k=40))
+        ICP("pt2pl", config_path=icp_yaml(tmp_path, target_normals="estimate", normals_k=40))
     src, tgt = torch.zeros(1, 8, 3), torch.zeros(1, 12, 3)
     with pytest.raises(ValueError, match=re.escape("pt2pl needs target normals: target must be (B,M,6)")):
         d.icp(src, tgt, dim=2)

@@ -8,6 +8,7 @@ the output is below 1; the fixture may come from a host whose sin / cos differ i
 fp32 rounding of the polar mask by an ulp (at most 2^-24 below 1) before the product with a scan value below 1.
 """
 import ctypes
+import functools
 import os
 import re
 
@@ -17,8 +18,8 @@ import torch
 
 from mm_masking_amd import _lib
 from oracle import radar_ref
+from support import ROOT, load_golden, policy_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmk_mask_polar_scan", "mmk_mask_polar_scan_bwd", "mmk_mask_polar_scan_bwd_ws_bytes")
 FWD_ABS = 2.0 ** -23
 
@@ -31,7 +32,7 @@ def L():
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, "mask_scan.npz")))
+    return load_golden(golden_dir, "mask_scan.npz")
 
 
 def test_new_entries_declared_and_exported(L):
@@ -156,11 +157,7 @@ def test_chain_fixture_is_consistent(gold, golden_dir):
 
 
 # ----------------------------------------------------------------------------- the policy's key
-def _params(**kw):
-    from mm_masking_amd import train_icp_weights as trn
-    p = trn.default_params(torch.device("cpu"))
-    p.update(kw)
-    return p
+_params = functools.partial(policy_params, torch.device("cpu"))
 
 
 def _cpu_batch(B=1, H=32, A=8, R=40, polar=True):

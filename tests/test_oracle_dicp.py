@@ -6,15 +6,7 @@ import torch
 
 from mm_masking_amd import synthetic
 from oracle import _clib, dicp_ref
-
-
-def _pair_batch(B, n, m, dim, pad_n=0, pad_m=0, seed=0):
-    S, Tg, Tt = [], [], []
-    for b in range(B):
-        s, t, T = synthetic.simple_cloud_pair(seed + b, n, m, dim=dim, pad_n=pad_n, pad_m=pad_m,
-                                              yaw=0.02 + 0.01 * b, trans=(0.6, -0.4 + 0.1 * b, 0.1))
-        S.append(s), Tg.append(t), Tt.append(T)
-    return np.stack(S), np.stack(Tg), np.stack(Tt)
+from support import pair_batch
 
 
 def test_config1_plumbing_pt2pt_5_iters():
@@ -73,7 +65,7 @@ def test_se_exp_properties():
 
 def test_invariances_and_padding():
     B, n, m = 2, 500, 1200
-    src, tgt, T_true = _pair_batch(B, n, m, 2, seed=31)
+    src, tgt, T_true = pair_batch(B, n, m, 2, seed=31)
     s, t = torch.from_numpy(src), torch.from_numpy(tgt)
     w = torch.rand(B, n) + 0.1
     icp = dicp_ref.ICPRef("pt2pl", differentiable=False, max_iterations=8, tolerance=1e-9)
@@ -89,7 +81,7 @@ def test_invariances_and_padding():
     assert np.abs(T1.numpy()[:, :2, 3] - T_true[:, :2, 3]).max() < 0.05
     assert np.abs(T1.numpy()[:, 1, 0] - T_true[:, 1, 0]).max() < 5e-3
     # dim 3, point-to-plane recovers the full SE(3) offset
-    src3, tgt3, T3true = _pair_batch(1, 1500, 3000, 3, seed=8)
+    src3, tgt3, T3true = pair_batch(1, 1500, 3000, 3, seed=8)
     icp3 = dicp_ref.ICPRef("pt2pl", differentiable=False, max_iterations=15, tolerance=1e-9)
     T3d = icp3.icp(torch.from_numpy(src3), torch.from_numpy(tgt3), trim_dist=5.0, loss_fn={"name": "cauchy", "metric": 1.0},
                    dim=3)["T"].numpy()
@@ -99,7 +91,7 @@ def test_invariances_and_padding():
 def test_oracle_gradient_finite_difference():
     """Pins the oracle's own gradient (fp64 restatement, fixed correspondences)."""
     B, n, m = 1, 120, 400
-    src, tgt, _ = _pair_batch(B, n, m, 2, seed=5)
+    src, tgt, _ = pair_batch(B, n, m, 2, seed=5)
     K = 3
     ref32 = dicp_ref.ICPRef("pt2pl", differentiable=True, max_iterations=K, tolerance=1e-12)
     base = ref32.icp(torch.from_numpy(src), torch.from_numpy(tgt), T_init=torch.eye(4).repeat(B, 1, 1),

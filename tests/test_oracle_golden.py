@@ -1,34 +1,20 @@
 """The oracle (oracle/) against the golden vectors generated from the reference's
 own modules (tests/golden/make_golden.py).  CPU only."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import radar_ref as R
 from oracle import train_ref, unet_ref
-
-
-def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
-
-
-def _assert_mask_close(raw, got, want, thres, band=1e-6):
-    """Masks may differ only where the cell sits within `band` of its threshold
-    (window-sum rounding order)."""
-    bad = got != want
-    if bad.any():
-        assert np.all(np.abs(raw[bad] - thres[bad]) < band), "CFAR mask differs away from the threshold"
-    assert bad.mean() < 1e-4
+from support import load_golden, mask_close
 
 
 def test_cfar_hard_and_soft(golden_dir):
-    g = _load(golden_dir, "radar_cfar.npz")
+    g = load_golden(golden_dir, "radar_cfar.npz")
     raw = g["raw"]
     th = R.cfar_threshold(raw, 0.0596)
     hard = R.cfar_mask(raw, 0.0596, diff=False)
-    _assert_mask_close(raw, hard, g["hard"].astype(np.float32), th)
+    mask_close(raw, hard, g["hard"].astype(np.float32), th)
     soft = R.cfar_mask(raw, 0.0596, diff=True)
     d = np.abs(soft - g["soft"])
     # soft mask jumps 0 <-> >0.99 at the hardshrink edge; elsewhere smooth
@@ -39,14 +25,14 @@ def test_cfar_hard_and_soft(golden_dir):
         kw[k] = int(kw[k])
     raw2 = g["raw2"]
     th2 = R.cfar_threshold(raw2, 0.2, **kw)
-    _assert_mask_close(raw2, R.cfar_mask(raw2, 0.2, diff=False, **kw), g["hard2"].astype(np.float32), th2)
+    mask_close(raw2, R.cfar_mask(raw2, 0.2, diff=False, **kw), g["hard2"].astype(np.float32), th2)
     d2 = np.abs(R.cfar_mask(raw2, 0.2, diff=True, steep_fact=7.0, **kw) - g["soft2"])
     assert (d2 > 0.5).mean() < 1e-3 and d2[d2 <= 0.5].max() < 2e-5
     assert R.cfar_cols(3360, 0.0596)[1:] == (89, 1287)
 
 
 def test_peaks_and_extract_pc(golden_dir):
-    g = _load(golden_dir, "radar_peaks.npz")
+    g = load_golden(golden_dir, "radar_peaks.npz")
     mask = g["mask"].astype(np.float32)
     rng = (np.float32(0.0596) * np.arange(mask.shape[2]).astype(np.float32))
     np.testing.assert_array_equal(R.mean_peaks_parallel_fast(mask * rng, False, 10.0), g["peaks_hard"])
@@ -71,7 +57,7 @@ def test_peaks_and_extract_pc(golden_dir):
 def test_grids(golden_dir):
     # torch.linspace's vectorised fp32 evaluation is reproduced to ~1 ulp of the
     # 76 m half-width (7.6e-6 m), hence the absolute tolerances below.
-    g = _load(golden_dir, "radar_grids.npz")
+    g = load_golden(golden_dir, "radar_grids.npz")
     rg, ag = R.form_cart_range_angle_grid()
     np.testing.assert_allclose(rg[::16, ::16], g["range_sub"], rtol=2e-6, atol=1e-5)
     np.testing.assert_allclose(ag[::16, ::16], g["angle_sub"], rtol=0, atol=5e-5)
@@ -89,7 +75,7 @@ def test_grids(golden_dir):
 
 
 def test_polar_to_cart(golden_dir):
-    g = _load(golden_dir, "radar_polar2cart.npz")
+    g = load_golden(golden_dir, "radar_polar2cart.npz")
     pol = (g["pol"] / np.float32(255.0)).astype(np.float32)
     kw = dict(cart_resolution=0.9536, cart_pixel_width=160)
     np.testing.assert_allclose(R.radar_polar_to_cartesian_diff(pol, g["az"], 0.5, **kw), g["cart"], atol=2e-5)
@@ -108,7 +94,7 @@ def test_polar_to_cart(golden_dir):
 
 
 def test_points_pixels_weights_bev(golden_dir):
-    g = _load(golden_dir, "radar_points.npz")
+    g = load_golden(golden_dir, "radar_points.npz")
     pts = g["pts"]
     np.testing.assert_allclose(R.point_to_cart_idx(pts), g["idx_plain"], rtol=1e-6, atol=1e-5)
     np.testing.assert_allclose(R.point_to_cart_idx(pts, min_to_plus_1=True), g["idx_norm"], rtol=1e-6, atol=1e-7)
@@ -130,7 +116,7 @@ def test_points_pixels_weights_bev(golden_dir):
 
 
 def test_load_radar(golden_dir):
-    g = _load(golden_dir, "radar_load.npz")
+    g = load_golden(golden_dir, "radar_load.npz")
     fft, az, ts = R.load_radar(g["png"])
     np.testing.assert_array_equal(fft, g["fft"])
     np.testing.assert_array_equal(az, g["az"])
@@ -139,7 +125,7 @@ def test_load_radar(golden_dir):
 
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_unet_forward_backward(golden_dir, tag):
-    g = _load(golden_dir, "unet.npz")
+    g = load_golden(golden_dir, "unet.npz")
     in_ch = 1 if tag == "a" else 3
     sd = unet_ref.init_state_dict(in_ch, 1234)
     names = [str(n) for n in g["names_" + tag]]
@@ -166,7 +152,7 @@ def test_unet_forward_backward(golden_dir, tag):
 
 
 def test_losses(golden_dir):
-    g = _load(golden_dir, "losses.npz")
+    g = load_golden(golden_dir, "losses.npz")
     Tp, Tg = torch.from_numpy(g["T_pred"]), torch.from_numpy(g["T_gt"])
     np.testing.assert_allclose(train_ref.eval_validation_loss(Tp, Tg, True).numpy(), g["val_eye"], rtol=1e-6)
     np.testing.assert_allclose(train_ref.eval_validation_loss(Tp, Tg, False).numpy(), g["val_gt"], rtol=1e-5)
@@ -194,7 +180,7 @@ def test_losses(golden_dir):
 def test_unet_polar_sizes(golden_dir, tag):
     """network_input_type='polar': non-square input whose sizes go odd under the poolings
     (50 x 84 -> ... -> 1 x 2); fixtures from tests/golden/make_golden_polar.py."""
-    g = _load(golden_dir, "polar_net.npz")
+    g = load_golden(golden_dir, "polar_net.npz")
     in_ch = 1 if tag == "p" else 2
     sd = unet_ref.init_state_dict(in_ch, 1234)
     names = [str(n) for n in g["names_" + tag]]
@@ -218,7 +204,7 @@ def test_unet_polar_sizes(golden_dir, tag):
 def test_extract_weights_non_square_mask(golden_dir, tag):
     """The reference normalises points by the 640-pixel Cartesian width and lets grid_sample stretch
     [-1,1] over whatever mask it is given: (40,96) and the polar (400,3360)."""
-    g = _load(golden_dir, "polar_net.npz")
+    g = load_golden(golden_dir, "polar_net.npz")
     B, H, W = (int(v) for v in g["ew_shape_" + tag])
     mask = np.random.default_rng(int(g["ew_seed_" + tag])).uniform(0, 1, size=(B, H, W)).astype(np.float32)
     pts = g["ew_pts_" + tag]

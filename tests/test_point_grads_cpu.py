@@ -11,8 +11,7 @@ import torch
 
 from mm_masking_amd import _lib, synthetic
 from oracle import dicp_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, icp_params
 NEW = ("mmk_icp_backward_points", "mmk_icp_backward_points_workspace_bytes", "mmk_sample_weights_bwd_pc")
 
 
@@ -30,21 +29,14 @@ def test_new_entries_declared_and_exported(L):
     assert L.mmk_version() == 502
 
 
-def _params(**kw):
-    d = dict(B=2, N=100, M=300, tgt_cols=6, dim=2, icp_type=1, loss=2, loss_k=1.0, trim_dist=5.0, tolerance=1e-5,
-             max_iter=10, save_state=1, check_every=0, nn_method=0)
-    d.update(kw)
-    return _lib.IcpParams(**d)
-
-
 def test_icp_backward_points_workspace_and_argument_checks(L):
-    p = _params()
+    p = icp_params()
     base = L.mmk_icp_workspace_bytes(ctypes.byref(p))
     assert L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(p), 0) == base
     need = L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(p), 1)
     # per-iteration rows (K,B,N,2 dim) fp32 + (B,M,4) int64 sums
     assert need >= base + 10 * 2 * 100 * 4 * 4 + 2 * 300 * 4 * 8
-    assert L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(_params(tgt_cols=3)), 1) == 0
+    assert L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(icp_params(tgt_cols=3)), 1) == 0
     assert b"normals" in L.mmk_last_error()
 
     null = ctypes.c_void_p(0)
@@ -56,8 +48,8 @@ def test_icp_backward_points_workspace_and_argument_checks(L):
 
     assert call(p, src=null) == -1 and b"NULL" in L.mmk_last_error()
     assert call(p, gw=null) == -1 and b"NULL" in L.mmk_last_error()
-    assert call(_params(dim=4)) == -1 and b"dim" in L.mmk_last_error()
-    assert call(_params(save_state=0)) == -1 and b"save_state" in L.mmk_last_error()
+    assert call(icp_params(dim=4)) == -1 and b"dim" in L.mmk_last_error()
+    assert call(icp_params(save_state=0)) == -1 and b"save_state" in L.mmk_last_error()
     assert call(p, nbytes=need - 1) == -1 and b"workspace" in L.mmk_last_error()
     assert call(p, ws=null) == -1 and b"workspace" in L.mmk_last_error()
 

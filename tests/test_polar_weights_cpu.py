@@ -2,6 +2,7 @@
 (no launch) -- the policy's constructor checks for params["polar_sampling"], and the test-side restatement against the golden
 images of the reference's radar_polar_to_cartesian_diff at the pixel centres."""
 import ctypes
+import functools
 import os
 import re
 
@@ -14,6 +15,7 @@ from mm_masking_amd import radar_utils as ru
 from mm_masking_amd import train_icp_weights as trn
 from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
 from polar_weights_ref import azimuth_tables, polar_weights_ref, position_error
+from support import policy_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmk_sample_weights_polar_fwd", "mmk_sample_weights_polar_bwd_ws_bytes", "mmk_sample_weights_polar_bwd",
@@ -80,11 +82,7 @@ def test_workspace_too_small(L):
     assert _bwd(L, nbytes=0) == -1 and b"workspace" in L.mmk_last_error()
 
 
-def _policy_params(**over):
-    p = trn.default_params(torch.device("cpu"))
-    p.update({"unet_backend": "torch"})
-    p.update(over)
-    return p
+_policy_params = functools.partial(policy_params, torch.device("cpu"), unet_backend="torch")
 
 
 def test_policy_constructor_checks():

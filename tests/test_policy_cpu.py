@@ -2,6 +2,7 @@
 ``LearnICPWeightPolicy`` (input assembly, normalisation, encoder / twice-applied decoder, amax
 normalisation, ``mask_only``) against the golden vectors of the reference module, and the checkpoint
 helpers of the trainer.  CPU only."""
+import functools
 import os
 
 import numpy as np
@@ -10,13 +11,10 @@ import torch
 
 from mm_masking_amd import train_icp_weights as trn
 from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
+from support import policy_params
 
 
-def _params(**over):
-    p = trn.default_params(torch.device("cpu"))
-    p.update({"dropout": 0.0, "amp_dtype": torch.float32, "unet_backend": "torch"})
-    p.update(over)
-    return p
+_params = functools.partial(policy_params, torch.device("cpu"), dropout=0.0, amp_dtype=torch.float32, unet_backend="torch")
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])

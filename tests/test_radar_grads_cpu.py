@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 from mm_masking_amd import _lib
+from radar_cases import RES
+from support import ROOT, load_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmk_cfar_mask_bwd", "mmk_extract_peaks_bwd", "mmk_extract_peaks_bwd_workspace_bytes")
-RES = 0.0596
 
 
 @pytest.fixture(scope="module")
@@ -24,7 +24,7 @@ def L():
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, "radar_grads.npz")))
+    return load_golden(golden_dir, "radar_grads.npz")
 
 
 def test_new_entries_declared_and_exported(L):

@@ -18,8 +18,8 @@ import pytest
 
 from mm_masking_amd import _lib
 from oracle import radar_ref
+from support import ROOT, load_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmk_polar_to_cart_bwd", "mmk_polar_to_cart_bwd_ws_bytes", "mmk_cart_to_polar_bwd", "mmk_cart_to_polar_bwd_ws_bytes")
 PC_VARIANTS = ({}, {"fix_wobble": False}, {"interpolate_crossover": False})
 PC_ADJOINT_REL = 8.8e-8
@@ -34,7 +34,7 @@ def L():
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, "resample_grads.npz")))
+    return load_golden(golden_dir, "resample_grads.npz")
 
 
 def test_new_entries_declared_and_exported(L):
@@ -131,7 +131,7 @@ def test_cart_to_polar_golden_gradient_is_the_adjoint(gold):
 
 
 def test_chain_fixture_is_consistent(gold, golden_dir):
-    base = np.load(os.path.join(golden_dir, "radar_grads.npz"))
+    base = load_golden(golden_dir, "radar_grads.npz")
     B, A, R = base["ch_raw"].shape
     assert gold["ch_fix_idx"].max() < B * A * R and len(gold["ch_fix_idx"]) == len(gold["ch_fix_val"])
     assert gold["ch_grad_c"].shape == (B, 640, 640) and gold["ch_grad_p"].shape == gold["ch_p"].shape == (B, A, 160)

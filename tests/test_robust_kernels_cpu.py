@@ -29,8 +29,7 @@ from dicp_cases import (K_MULT, NAMES, PER_PAIR_TAU, ROBUST_CASES as GPU_CASES, 
                         assert_awake, inputs, policy_params, reference)
 from dicp_cases import K as GPU_K
 from dicp_restatement import ICPRestatement, closed_form_r2bar, closed_form_sums, per_point_terms
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, icp_params
 NEW = {"geman_mcclure": 3, "welsch": 4}
 B, N, M, K = 2, 70, 160, 3
 TRIM, STEEP = 0.6, 4.0
@@ -41,13 +40,6 @@ TRIM, STEEP = 0.6, 4.0
 def L():
     _lib.build()
     return _lib.lib()
-
-
-def _params(**kw):
-    d = dict(B=2, N=100, M=300, tgt_cols=6, dim=2, icp_type=1, loss=3, loss_k=1.0, trim_dist=5.0, tolerance=1e-5,
-             max_iter=10, save_state=1, check_every=0, nn_method=0)
-    d.update(kw)
-    return _lib.IcpParams(**d)
 
 
 def test_header_and_binding_name_the_two_codes(L):
@@ -67,17 +59,17 @@ def test_parameter_validation_accepts_the_new_codes_and_nothing_beyond(L):
 
     for code in NEW.values():
         for kw in ({}, {"trim_steep": 4.0}, {"dim": 3, "loss_k": 0.2}):
-            p = _params(loss=code, **kw)
+            p = icp_params(loss=code, **kw)
             r = ctypes.byref(p)
             assert L.mmk_icp_workspace_bytes(r) > 0 and L.mmk_icp_backward_points_workspace_bytes(r, 1) > 0
             assert L.mmk_icp_backward_hp_workspace_bytes(r, 1, 1) > 0 and L.mmk_icp_partials_count(r) > 0
-            assert L.mmk_icp_workspace_bytes(r) == L.mmk_icp_workspace_bytes(ctypes.byref(_params(loss=1, **kw)))     # Cauchy's sizes
+            assert L.mmk_icp_workspace_bytes(r) == L.mmk_icp_workspace_bytes(ctypes.byref(icp_params(loss=1, **kw)))     # Cauchy's sizes
         for bad_k in (0.0, -0.5, float("nan")):
-            p = _params(loss=code, loss_k=bad_k)
+            p = icp_params(loss=code, loss_k=bad_k)
             assert L.mmk_icp_workspace_bytes(ctypes.byref(p)) == 0 and b"metric" in L.mmk_last_error()
             assert forward(p) == -1 and b"metric" in L.mmk_last_error()                                     # MMK_ERR_ARG
     for code in (5, -1):
-        p = _params(loss=code)
+        p = icp_params(loss=code)
         assert L.mmk_icp_workspace_bytes(ctypes.byref(p)) == 0 and b"bad loss" in L.mmk_last_error()
         assert forward(p) == -1 and ("bad loss %d" % code).encode() in L.mmk_last_error()
     assert int(re.search(r"#define\s+MMK_ERR_ARG\s+\((-?\d+)\)", open(os.path.join(ROOT, "include", "mmk.h")).read()).group(1)) == -1

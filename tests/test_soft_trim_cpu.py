@@ -3,6 +3,7 @@ answers of the gate, its hard limit against oracle.dicp_ref, finite differences 
 plumbing of the option: mmk_icp_params.trim_steep / mmk_icp_params_bytes, the argument checks, dICP.ICP's YAML keys and
 attributes, and the policy's params["icp_trim"] / ["icp_tanh_steepness"]."""
 import ctypes
+import functools
 import os
 import re
 
@@ -15,8 +16,7 @@ from mm_masking_amd.dICP.ICP import ICP
 from oracle import dicp_ref
 
 from dicp_restatement import ICPRestatement, band_share, soft_keep
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, icp_params, icp_yaml, policy_params
 
 
 # ----------------------------------------------------------------------------- the gate itself
@@ -155,16 +155,9 @@ def L():
     return _lib.lib()
 
 
-def _params(**kw):
-    d = dict(B=2, N=100, M=300, tgt_cols=6, dim=2, icp_type=1, loss=2, loss_k=1.0, trim_dist=5.0, tolerance=1e-5,
-             max_iter=10, save_state=1, check_every=0, nn_method=0)
-    d.update(kw)
-    return _lib.IcpParams(**d)
-
-
 def test_params_struct_and_new_symbol(L):
-    assert _params().trim_steep == 0.0                       # keyword constructions that never mention it: the hard gate
-    assert _params(trim_steep=4.0).trim_steep == 4.0
+    assert icp_params().trim_steep == 0.0                       # keyword constructions that never mention it: the hard gate
+    assert icp_params(trim_steep=4.0).trim_steep == 4.0
     assert _lib.IcpParams._fields_[-1][0] == "trim_steep"    # appended: every earlier field keeps its offset
     assert _lib.IcpParams.nn_method.offset + 4 == _lib.IcpParams.trim_steep.offset
     assert ctypes.sizeof(_lib.IcpParams) == L.mmk_icp_params_bytes()
@@ -180,7 +173,7 @@ def test_params_struct_and_new_symbol(L):
 
 @pytest.mark.parametrize("bad", [-1.0, float("nan"), float("inf"), -0.5])
 def test_bad_trim_steep_is_an_argument_error(L, bad):
-    p = _params(trim_steep=bad)
+    p = icp_params(trim_steep=bad)
     null, fake = ctypes.c_void_p(0), ctypes.c_void_p(4096)       # never dereferenced: every call fails before any launch
     assert L.mmk_icp_workspace_bytes(ctypes.byref(p)) == 0 and b"trim_steep" in L.mmk_last_error()
     assert L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(p), 1) == 0 and b"trim_steep" in L.mmk_last_error()
@@ -195,18 +188,12 @@ def test_bad_trim_steep_is_an_argument_error(L, bad):
         lambda: L.mmk_icp_status(ctypes.byref(p), fake, 1 << 30, fake, null),
     ]
     for call in calls:
-        L.mmk_icp_workspace_bytes(ctypes.byref(_params()))         # (a good call in between: the message below is the new one)
+        L.mmk_icp_workspace_bytes(ctypes.byref(icp_params()))         # (a good call in between: the message below is the new one)
         assert call() == -1 and b"trim_steep" in L.mmk_last_error()
-    good = _params(trim_steep=4.0)
-    assert L.mmk_icp_workspace_bytes(ctypes.byref(good)) == L.mmk_icp_workspace_bytes(ctypes.byref(_params())) > 0
+    good = icp_params(trim_steep=4.0)
+    assert L.mmk_icp_workspace_bytes(ctypes.byref(good)) == L.mmk_icp_workspace_bytes(ctypes.byref(icp_params())) > 0
     assert (L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(good), 1)
-            == L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(_params()), 1) > 0)
-
-
-def _yaml(tmp_path, text):
-    path = tmp_path / "dICP_config.yaml"
-    path.write_text(text)
-    return str(path)
+            == L.mmk_icp_backward_points_workspace_bytes(ctypes.byref(icp_params()), 1) > 0)
 
 
 def test_icp_yaml_keys_and_attributes(tmp_path):
@@ -220,16 +207,16 @@ def test_icp_yaml_keys_and_attributes(tmp_path):
         assert icp._params(1, 8, 8, 3, 2, None, 5.0, save_state=diff).trim_steep == 2.5
         icp.trim = "hard"
         assert icp._params(1, 8, 8, 3, 2, None, 5.0, save_state=diff).trim_steep == 0.0
-        cfg = _yaml(tmp_path, "dICP:\n  target_pad_val: 1000.0\n  parameters:\n    trim: tanh\n    tanh_steepness: 4\n")
+        cfg = icp_yaml(tmp_path, "dICP:\n  target_pad_val: 1000.0\n  parameters:\n    trim: tanh\n    tanh_steepness: 4\n")
         icp = ICP("pt2pl", config_path=cfg, differentiable=diff)
         assert icp.trim == "tanh" and icp.tanh_steepness == 4.0
         assert icp._params(1, 8, 8, 6, 2, None, 5.0, save_state=diff).trim_steep == 4.0
-    icp = ICP("pt2pt", config_path=_yaml(tmp_path, "dICP:\n  parameters:\n    trim: tanh\n"))
+    icp = ICP("pt2pt", config_path=icp_yaml(tmp_path, "dICP:\n  parameters:\n    trim: tanh\n"))
     assert icp.trim == "tanh" and icp.tanh_steepness == 10.0
     for text in ("    trim: soft\n", "    trim: tanh\n    tanh_steepness: 0\n", "    trim: tanh\n    tanh_steepness: -3.0\n",
                  "    tanh_steepness: 0.0\n", "    trim: tanh\n    tanh_steepness: .nan\n"):
         with pytest.raises(ValueError, match="trim|tanh_steepness"):
-            ICP("pt2pt", config_path=_yaml(tmp_path, "dICP:\n  parameters:\n" + text))
+            ICP("pt2pt", config_path=icp_yaml(tmp_path, "dICP:\n  parameters:\n" + text))
     icp = ICP("pt2pt")
     icp.trim = "sigmoid"
     with pytest.raises(ValueError, match="trim"):
@@ -240,14 +227,9 @@ def test_icp_yaml_keys_and_attributes(tmp_path):
 
 
 def test_policy_parameters_switch_the_training_instance_only():
-    from mm_masking_amd import train_icp_weights as trn
     from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
 
-    def params(**over):
-        p = trn.default_params(torch.device("cpu"))
-        p.update({"dropout": 0.0, "amp_dtype": torch.float32, "unet_backend": "torch"})
-        p.update(over)
-        return p
+    params = functools.partial(policy_params, torch.device("cpu"), dropout=0.0, amp_dtype=torch.float32, unet_backend="torch")
 
     assert "icp_trim" not in params() and "icp_tanh_steepness" not in params()      # default_params stays as it is
     model = LearnICPWeightPolicy(params())

@@ -4,7 +4,7 @@ attributes, the policy's keys, the refused combinations -- and the restatement t
 nearest limit of its soft loop against its nearest loop bit for bit, the closed forms of I7''' against its autograd, and fp64
 finite differences of source, target, weight and T_init."""
 import ctypes
-import os
+import functools
 import re
 
 import numpy as np
@@ -16,8 +16,8 @@ from mm_masking_amd.dICP.ICP import ICP
 
 from dicp_restatement import ICPRestatement, knn_ref, knn_ref_batch, soft_backward_closed_form, soft_rows
 from knn_normals_ref import nn_dist_f32
+from support import header, icp_params, n_args, policy_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmk_icp_soft_workspace_bytes", "mmk_icp_forward_soft", "mmk_icp_backward_soft_workspace_bytes", "mmk_icp_backward_soft",
        "mmk_knn_search_workspace_bytes", "mmk_knn_search")
 
@@ -27,21 +27,14 @@ def L():
     return _lib.lib()
 
 
-def _params(M=16, **kw):
-    d = dict(B=1, N=8, M=M, tgt_cols=6, dim=2, icp_type=0, loss=0, loss_k=1.0, trim_dist=5.0, tolerance=1e-9, max_iter=2,
-             save_state=1, check_every=0, nn_method=0, trim_steep=0.0)
-    d.update(kw)
-    return _lib.IcpParams(**d)
+_params = functools.partial(icp_params, B=1, N=8, M=16, icp_type=0, loss=0, tolerance=1e-9, max_iter=2, trim_steep=0.0)
 
 
 # ----------------------------------------------------------------------------- the C ABI
 def test_header_and_binding_carry_the_new_entries(L):
-    hdr = open(os.path.join(ROOT, "include", "mmk.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = header()
     for name in NEW:
-        m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, hdr, flags=re.S)
-        assert m, name + " is not declared in include/mmk.h"
-        arity = len([a for a in m.group(1).split(",") if a.strip()])
+        arity = n_args(hdr, name)
         assert name in _lib.EXPORTED, name
         assert arity == len(_lib.EXPORTED[name][1]), (name, arity, len(_lib.EXPORTED[name][1]))
         assert hasattr(L, name)
@@ -139,14 +132,9 @@ def test_refused_combinations_raise_before_the_device_is_touched():
 
 
 def test_policy_keys():
-    from mm_masking_amd import train_icp_weights as trn
     from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
 
-    def params(**over):
-        p = trn.default_params(torch.device("cpu"))
-        p.update({"dropout": 0.0, "amp_dtype": torch.float32, "unet_backend": "torch"})
-        p.update(over)
-        return p
+    params = functools.partial(policy_params, torch.device("cpu"), dropout=0.0, amp_dtype=torch.float32, unet_backend="torch")
 
     assert not any(k in params() for k in ("icp_correspondence", "icp_softmin_k", "icp_softmin_temp"))
     model = LearnICPWeightPolicy(params())

@@ -11,9 +11,8 @@ tests/dicp_cases.py, all five cases, k in {4, 8}: with tau = (0.25, 0.4) the sma
 smallest single pair 0.055; with (0.25, 0.25) the smallest max_b ratio is 0.055 (pt2pl, Cauchy, dim 3, k = 8).
 """
 import ctypes
+import functools
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
@@ -24,9 +23,9 @@ from mm_masking_amd.dICP.ICP import ICP
 
 from dicp_cases import B, K, SOFTMIN_CASES as CASES, SOFTMIN_IDS as IDS, SOFTMIN_TRIM as TRIM, reference
 from dicp_restatement import knn_ref_batch, soft_backward_closed_form, soft_rows
+from support import header, icp_params, n_args, policy_params
 
 icp_mod = importlib.import_module("mm_masking_amd.dICP.ICP")        # (the package re-exports the class under the module's name)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mmk_icp_forward_soft_t", "mmk_icp_backward_soft_t_workspace_bytes", "mmk_icp_backward_soft_t")
 
 
@@ -35,25 +34,17 @@ def L():
     return _lib.lib()
 
 
-def _params(**kw):
-    d = dict(B=2, N=300, M=64, tgt_cols=6, dim=2, icp_type=0, loss=0, loss_k=1.0, trim_dist=5.0, tolerance=1e-9, max_iter=3,
-             save_state=1, check_every=0, nn_method=0, trim_steep=0.0)
-    d.update(kw)
-    return _lib.IcpParams(**d)
-
-
-def _n_args(hdr, name):
-    return len([a for a in re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, hdr, flags=re.S).group(1).split(",") if a.strip()])
+_params = functools.partial(icp_params, N=300, M=64, icp_type=0, loss=0, tolerance=1e-9, max_iter=3, trim_steep=0.0)
 
 
 # ----------------------------------------------------------------------------- the C ABI
 def test_entries_exist_and_older_sizes_are_unchanged(L):
-    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "mmk.h")).read(), flags=re.S)
+    hdr = header()
     for name in NEW:
         assert hasattr(L, name) and name in _lib.EXPORTED, name
-        assert _n_args(hdr, name) == len(_lib.EXPORTED[name][1]), name
-    assert _n_args(hdr, "mmk_icp_forward_soft_t") == _n_args(hdr, "mmk_icp_forward_soft") + 2          # temp, per_pair
-    assert _n_args(hdr, "mmk_icp_backward_soft_t") == _n_args(hdr, "mmk_icp_backward_soft") + 3       # + grad_temp
+        assert n_args(hdr, name) == len(_lib.EXPORTED[name][1]), name
+    assert n_args(hdr, "mmk_icp_forward_soft_t") == n_args(hdr, "mmk_icp_forward_soft") + 2          # temp, per_pair
+    assert n_args(hdr, "mmk_icp_backward_soft_t") == n_args(hdr, "mmk_icp_backward_soft") + 3       # + grad_temp
     assert L.mmk_version() == 502 and ctypes.sizeof(_lib.IcpParams) == L.mmk_icp_params_bytes() == 60
     assert ctypes.sizeof(_lib.IcpSoft) == 8
     for p in (_params(), _params(N=1000, dim=3, icp_type=1, max_iter=5)):
@@ -163,14 +154,9 @@ def test_status_message_names_the_temperature():
 
 # ----------------------------------------------------------------------------- the policy
 def test_policy_keys():
-    from mm_masking_amd import train_icp_weights as trn
     from mm_masking_amd.icp_weight_policy import LearnICPWeightPolicy
 
-    def params(**over):
-        p = trn.default_params(torch.device("cpu"))
-        p.update({"dropout": 0.0, "amp_dtype": torch.float32, "unet_backend": "torch"})
-        p.update(over)
-        return p
+    params = functools.partial(policy_params, torch.device("cpu"), dropout=0.0, amp_dtype=torch.float32, unet_backend="torch")
 
     for over in ({"learn_icp": ("softmin_temp",)}, {"learn_icp": "softmin_temp"},
                  {"learn_icp": ("softmin_temp",), "icp_correspondence": "nearest"}):
