@@ -5,12 +5,17 @@ reference has no FFI of its own, so every entry point replaces a *Python* call
 site of mm_masking (cited in include/mmk.h).  PyTorch is only the owner of the
 device buffers and of the HIP stream the kernels are enqueued on.
 
+Signatures, struct layouts and constants are not written down here: they are
+read from include/mmk.h when this module is imported (``read_header``), so the
+binding cannot disagree with the declaration.
+
 The library is mandatory: there is NO CPU or PyTorch fallback.  ``lib()`` raises
 if the shared object is missing or fails to load, and every wrapper raises if a
 tensor is not a contiguous tensor of the expected dtype on a HIP device.
 """
 import ctypes
 import os
+import re
 import sys
 import subprocess
 
@@ -23,63 +28,103 @@ SOURCES = ["mmk_api.hip", "mmk_icp.hip", "mmk_radar.hip", "mmk_unet.hip", "mmk_u
 
 _lib = None
 
-c_f32p = ctypes.c_void_p
-c_vp = ctypes.c_void_p
-
 
 class MmkError(RuntimeError):
     pass
 
 
-class ReadJob(ctypes.Structure):
-    """mmk_read_job of include/mmk.h (one row-copy of the batched loader)."""
-    _fields_ = [("path", ctypes.c_char_p), ("header_bytes", ctypes.c_int64), ("rows", ctypes.c_int32),
-                ("row_bytes", ctypes.c_int32), ("col0", ctypes.c_int32), ("ncols", ctypes.c_int32), ("roll", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("dst", ctypes.c_void_p)]
+# ------------------------------------------------------------------------------------------------ include/mmk.h -> ctypes
+_SCALARS = {"void": None, "char": ctypes.c_char, "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+            "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+_DECLARATION = re.compile(r"typedef\s+struct\s*\w*\s*\{(?P<fields>[^{}]*)\}\s*(?P<struct>\w+)\s*;"
+                          r"|(?P<ret>[^;{}()]+?)\((?P<args>[^;{}]*)\)\s*;")
 
 
-class IcpParams(ctypes.Structure):
-    """mmk_icp_params of include/mmk.h."""
-    _fields_ = [("B", ctypes.c_int32), ("N", ctypes.c_int32), ("M", ctypes.c_int32),
-                ("tgt_cols", ctypes.c_int32), ("dim", ctypes.c_int32), ("icp_type", ctypes.c_int32),
-                ("loss", ctypes.c_int32), ("loss_k", ctypes.c_float), ("trim_dist", ctypes.c_float),
-                ("tolerance", ctypes.c_float), ("max_iter", ctypes.c_int32), ("save_state", ctypes.c_int32),
-                ("check_every", ctypes.c_int32), ("nn_method", ctypes.c_int32),
-                ("trim_steep", ctypes.c_float)]        # 0 (the default of a keyword construction): the hard trim gate
+def _ctype(decl, structs, where):
+    """(ctypes type, name) of one C declarator such as ``const float *const *params``; a plain ``void`` gives type None.
+    ``char *`` is c_char_p, a pointer to a typedef'd struct POINTER(its class), a pointer to a pointer POINTER(c_void_p)
+    (it takes a ``(c_void_p * n)`` array both as an argument and as a struct field), every other pointer c_void_p."""
+    m = re.fullmatch(r"\s*(\w+)\s*((?:\*\s*)*)(\w*)\s*", re.sub(r"\bconst\b", " ", decl))
+    if not m:              # arrays, function pointers, '...', bit-fields, 'unsigned int', 'struct tag': nothing mmk.h uses
+        raise MmkError("mmk.h, %s: cannot read the declarator '%s'" % (where, " ".join(decl.split())))
+    base, stars, name = m.group(1), m.group(2).count("*"), m.group(3)
+    if base not in _SCALARS and base not in structs:
+        raise MmkError("mmk.h, %s: unknown type '%s' in '%s' (a struct must be typedef'd above its first use)"
+                       % (where, base, " ".join(decl.split())))
+    if stars >= 2:
+        return ctypes.POINTER(ctypes.c_void_p), name
+    if stars == 1:
+        return (ctypes.c_char_p if base == "char" else ctypes.POINTER(structs[base]) if base in structs else ctypes.c_void_p), name
+    if base in structs:
+        raise MmkError("mmk.h, %s: struct '%s' by value in '%s'" % (where, base, " ".join(decl.split())))
+    return _SCALARS[base], name
 
 
-class IcpSoft(ctypes.Structure):
-    """mmk_icp_soft of include/mmk.h: the soft correspondences' k (2..8) and temperature (m^2)."""
-    _fields_ = [("k", ctypes.c_int32), ("temp", ctypes.c_float)]
+def read_header(text):
+    """The C ABI that the header ``text`` declares, as ctypes: ({function: (restype, [argtypes])}, {typedef name:
+    Structure class}, {MMK_* define: int}).  It understands the subset of C that include/mmk.h is written in and raises
+    MmkError, naming the declaration, for anything else: a header edit in a new style stops the import instead of
+    producing a wrong signature."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"#\s*ifdef\s+__cplusplus.*?#\s*endif", " ", text, flags=re.S)          # the extern "C" brackets
+    protos, structs, consts, code = {}, {}, {}, []
+    for line in text.splitlines():
+        if not line.lstrip().startswith("#"):
+            code.append(line)
+            continue
+        m = re.match(r"\s*#\s*define\s+(MMK_\w+)[ \t]+(\S.*?)\s*$", line)
+        if m:
+            value = re.fullmatch(r"\(?\s*(-?\d+)\s*\)?", m.group(2))
+            if not value:
+                raise MmkError("mmk.h, %s: '%s' is not an integer" % (m.group(1), m.group(2)))
+            consts[m.group(1)] = int(value.group(1))
+
+    def declare(m):
+        if m.group("struct"):
+            where, fields = "struct " + m.group("struct"), []
+            for member in filter(str.strip, m.group("fields").split(";")):
+                first, *more = member.split(",")                      # 'int32_t rows, row_bytes': the type word is shared
+                base = re.match(r"(?:\s|\bconst\b)*(\w*)", first).group(1)
+                for decl in [first] + [base + " " + d for d in more]:
+                    t, field = _ctype(decl, structs, where)
+                    if t is None or not field:
+                        raise MmkError("mmk.h, %s: cannot read the member '%s'" % (where, " ".join(decl.split())))
+                    fields.append((field, t))
+            structs[m.group("struct")] = type(m.group("struct"), (ctypes.Structure,),
+                                              {"_fields_": fields, "__doc__": "%s of include/mmk.h." % m.group("struct")})
+            return " "
+        res, name = _ctype(m.group("ret"), structs, "'%s'" % " ".join(m.group("ret").split()))
+        args = [] if m.group("args").strip() == "void" else m.group("args").split(",")
+        protos[name] = (res, [])
+        for decl in args:
+            t, arg = _ctype(decl, structs, name)
+            if t is None or not arg:
+                raise MmkError("mmk.h, %s: parameter '%s' has no %s" % (name, " ".join(decl.split()), "name" if t else "type"))
+            protos[name][1].append(t)
+        return " "
+    rest = _DECLARATION.sub(declare, "\n".join(code)).split()
+    if rest:
+        raise MmkError("mmk.h: cannot read '%s'" % " ".join(rest[:12]))
+    return protos, structs, consts
 
 
-class ConvDesc(ctypes.Structure):
-    """mmk_conv_desc of include/mmk.h."""
-    _fields_ = [("x1", ctypes.c_void_p), ("x2", ctypes.c_void_p), ("C1", ctypes.c_int32), ("C2", ctypes.c_int32),
-                ("wpack", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("y1", ctypes.c_void_p), ("relu_src1", ctypes.c_void_p), ("O1", ctypes.c_int32),
-                ("accumulate1", ctypes.c_int32), ("scale1", ctypes.c_float),
-                ("y2", ctypes.c_void_p), ("relu_src2", ctypes.c_void_p), ("O2", ctypes.c_int32),
-                ("accumulate2", ctypes.c_int32), ("scale2", ctypes.c_float),
-                ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("relu", ctypes.c_int32),
-                ("leaky_slope", ctypes.c_float), ("drop_p", ctypes.c_float), ("seed", ctypes.c_uint32), ("pool_y", ctypes.c_void_p),
-                ("pool_arg", ctypes.c_void_p), ("x1_pool_arg", ctypes.c_void_p), ("x1_pool_scale", ctypes.c_float)]
+with open(os.path.join(_ROOT, "include", "mmk.h")) as _f:
+    EXPORTED, STRUCTS, CONSTANTS = read_header(_f.read())
+IcpParams, IcpSoft, ReadJob, ConvDesc, UNetDesc = (STRUCTS["mmk_" + n] for n in
+                                                   ("icp_params", "icp_soft", "read_job", "conv_desc", "unet_desc"))
 
 
-class UNetDesc(ctypes.Structure):
-    """mmk_unet_desc of include/mmk.h."""
-    _fields_ = [("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("cin", ctypes.c_int32),
-                ("x", ctypes.c_void_p), ("pre", ctypes.c_void_p), ("params", ctypes.POINTER(ctypes.c_void_p)),
-                ("drop_p", ctypes.c_float), ("seed", ctypes.c_uint32), ("leaky_slope", ctypes.c_float), ("norm", ctypes.c_int32),
-                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("mask", ctypes.c_void_p),
-                ("keep_full_res", ctypes.c_int32)]
+def _codes(prefix, keys):
+    return {k: CONSTANTS[prefix + v] for k, v in keys.items()}
 
 
-FINAL_BWD_WS_FLOATS = 16384        # MMK_FINAL_BWD_WS_FLOATS of include/mmk.h
-NORM_MODES = {None: 0, "none": 0, "minmax": 1, "standardize": 2}      # MMK_NORM_* of include/mmk.h
-ICP_TYPES = {"pt2pt": 0, "pt2pl": 1}
-LOSSES = {None: 0, "none": 0, "l2": 0, "cauchy": 1, "huber": 2, "geman_mcclure": 3, "welsch": 4}
-NN_METHODS = {"brute": 0, "grid": 1}
+FINAL_BWD_WS_FLOATS = CONSTANTS["MMK_FINAL_BWD_WS_FLOATS"]
+NORM_MODES = _codes("MMK_NORM_", {None: "NONE", "none": "NONE", "minmax": "MINMAX", "standardize": "STANDARDIZE"})
+ICP_TYPES = _codes("MMK_ICP_", {"pt2pt": "PT2PT", "pt2pl": "PT2PL"})
+LOSSES = _codes("MMK_LOSS_", {None: "NONE", "none": "NONE", "l2": "NONE", "cauchy": "CAUCHY", "huber": "HUBER",
+                              "geman_mcclure": "GEMAN_MCCLURE", "welsch": "WELSCH"})
+NN_METHODS = _codes("MMK_NN_", {"brute": "BRUTE", "grid": "GRID"})
 
 
 def build(verbose=False):
@@ -129,155 +174,15 @@ def build(verbose=False):
 
 
 def _declare(lib):
-    i32, f32, sz = ctypes.c_int32, ctypes.c_float, ctypes.c_size_t
-    P = ctypes.POINTER(IcpParams)
-    S = ctypes.POINTER(IcpSoft)
-    sig = {
-        "mmk_version": (ctypes.c_int, []),
-        "mmk_last_error": (ctypes.c_char_p, []),
-        "mmk_icp_params_bytes": (sz, []),
-        "mmk_icp_workspace_bytes": (sz, [P]),
-        "mmk_icp_forward": (ctypes.c_int, [P] + [c_vp] * 10 + [c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
-        "mmk_icp_backward": (ctypes.c_int, [P] + [c_vp] * 11 + [c_vp, sz, c_vp]),
-        "mmk_icp_backward_points_workspace_bytes": (sz, [P, i32]),
-        "mmk_icp_backward_points": (ctypes.c_int, [P] + [c_vp] * 13 + [c_vp, sz, c_vp]),
-        "mmk_icp_status": (ctypes.c_int, [P, c_vp, sz, c_vp, c_vp]),
-        "mmk_icp_forward_hp": (ctypes.c_int, [P] + [c_vp] * 10 + [c_vp, i32, c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
-        "mmk_icp_backward_hp_workspace_bytes": (sz, [P, i32, i32]),
-        "mmk_icp_backward_hp": (ctypes.c_int, [P] + [c_vp] * 13 + [c_vp, i32, c_vp, c_vp, sz, c_vp]),
-        "mmk_icp_soft_workspace_bytes": (sz, [P, S]),
-        "mmk_icp_forward_soft": (ctypes.c_int, [P] + [c_vp] * 10 + [S, c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
-        "mmk_icp_backward_soft_workspace_bytes": (sz, [P, S, i32]),
-        "mmk_icp_backward_soft": (ctypes.c_int, [P] + [c_vp] * 13 + [S, c_vp, sz, c_vp]),
-        "mmk_icp_forward_soft_t": (ctypes.c_int, [P] + [c_vp] * 10 + [S, c_vp, i32, c_vp, sz, ctypes.POINTER(ctypes.c_int), c_vp]),
-        "mmk_icp_backward_soft_t_workspace_bytes": (sz, [P, S, i32, i32]),
-        "mmk_icp_backward_soft_t": (ctypes.c_int, [P] + [c_vp] * 13 + [S, c_vp, i32, c_vp, c_vp, sz, c_vp]),
-        "mmk_knn_search_workspace_bytes": (sz, [i32, i32, i32, i32]),
-        "mmk_knn_search": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, i32, c_vp, c_vp, c_vp, sz, c_vp]),
-        "mmk_pose_loss_fwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp]),
-        "mmk_pose_loss_bwd": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_bce_ws_bytes": (sz, []),
-        "mmk_bce_mean_fwd": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, sz, c_vp, c_vp]),
-        "mmk_bce_mean_bwd": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
-        "mmk_pose_loss_gt_fwd": (ctypes.c_int, [c_vp, c_vp, i32, c_vp, c_vp]),
-        "mmk_pose_loss_gt_bwd": (ctypes.c_int, [c_vp, c_vp, i32, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_val_metric": (ctypes.c_int, [c_vp, c_vp, i32, c_vp, c_vp]),
-        "mmk_fft_threshold_ws_bytes": (sz, [i32]),
-        "mmk_fft_threshold_mask": (ctypes.c_int, [c_vp, i32, ctypes.c_int64, c_vp, sz, c_vp, c_vp]),
-        "mmk_bce_fft_threshold_fwd": (ctypes.c_int, [c_vp, c_vp, i32, ctypes.c_int64, c_vp, sz, c_vp, c_vp, c_vp]),
-        "mmk_bce_fft_threshold_bwd": (ctypes.c_int, [c_vp, c_vp, i32, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_icp_partials_count": (sz, [P]),
-        "mmk_icp_accumulate": (ctypes.c_int, [P] + [c_vp] * 8 + [c_vp]),
-        "mmk_icp_solve_update": (ctypes.c_int, [P] + [c_vp] * 7 + [c_vp]),
-        "mmk_nn_padded_m": (i32, [i32]),
-        "mmk_pack_target": (ctypes.c_int, [c_vp, i32, i32, i32, i32, c_vp, c_vp]),
-        "mmk_nn_workspace_bytes": (sz, [i32, i32, i32, i32]),
-        "mmk_nn_search": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, c_vp, c_vp, c_vp, sz, c_vp]),
-        "mmk_knn_normals_workspace_bytes": (sz, [i32, i32]),
-        "mmk_knn_normals": (ctypes.c_int, [c_vp, i32, i32, i32, i32, i32, f32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, sz, c_vp]),
-        "mmk_nn_profile_begin": (ctypes.c_int, [i32]),
-        "mmk_nn_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), i32, ctypes.POINTER(ctypes.c_int32)]),
-        "mmk_conv3x3_packed_elems": (sz, [i32, i32, i32]),
-        "mmk_conv3x3_pack_weights": (ctypes.c_int, [c_vp, i32, i32, i32, c_vp, c_vp]),
-        "mmk_conv3x3_pack_weights_batch": (ctypes.c_int, [i32, c_vp, c_vp, c_vp, i32, c_vp, c_vp]),
-        "mmk_conv3x3": (ctypes.c_int, [ctypes.POINTER(ConvDesc), c_vp]),
-        "mmk_conv3x3_wgrad_unpack_batch": (ctypes.c_int, [i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_conv3x3_wgrad_slices": (i32, [i32, i32, i32, i32, i32, i32]),
-        "mmk_conv3x3_wgrad_partial": (ctypes.c_int, [c_vp, c_vp, i32, i32, c_vp, i32, i32, i32, i32, c_vp, i32, c_vp]),
-        "mmk_conv_bwd_fused": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_float, i32, i32, i32, i32, c_vp, c_vp, i32, c_vp]),
-        "mmk_conv_bwd_fused_pooled": (ctypes.c_int, [c_vp, c_vp, c_vp, f32, c_vp, f32, i32, i32, i32, i32, c_vp, c_vp, i32, c_vp]),
-        "mmk_conv3x3_wgrad_partial_pooled": (ctypes.c_int, [c_vp, c_vp, i32, i32, c_vp, c_vp, f32, i32, i32, i32, i32, c_vp, i32, c_vp]),
-        "mmk_conv8x16_bwd_fused": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_float, i32, i32, i32, c_vp, c_vp, i32, c_vp]),
-        "mmk_conv16x8_bwd_fused": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_float, i32, i32, i32, c_vp, c_vp, c_vp, i32, c_vp]),
-        "mmk_conv_desc_bytes": (sz, []),
-        "mmk_conv3x3_pool_fusable": (ctypes.c_int32, [i32, i32, i32, i32, i32]),
-        "mmk_channel_minmax": (ctypes.c_int, [c_vp, i32, i32, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_channel_meanstd": (ctypes.c_int, [c_vp, i32, i32, ctypes.c_int64, c_vp, c_vp, c_vp]),
-        "mmk_conv_first": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, i32, i32, i32, f32, c_vp, c_vp]),
-        "mmk_conv_first_wgrad_ws_bytes": (sz, [i32]),
-        "mmk_conv_first_wgrad": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, i32, i32, i32, c_vp, c_vp, c_vp, sz, c_vp]),
-        "mmk_conv_first_dgrad_ws_bytes": (sz, [i32]),
-        "mmk_conv_first_dgrad": (ctypes.c_int, [c_vp, i32, c_vp, c_vp, c_vp, c_vp, i32, i32, i32, c_vp, c_vp, sz, c_vp]),
-        "mmk_input_norm_bwd": (ctypes.c_int, [c_vp, c_vp, i32, c_vp, c_vp, i32, i32, i32, i32, c_vp, sz, c_vp]),
-        "mmk_maxpool2_fwd": (ctypes.c_int, [c_vp, i32, i32, i32, i32, c_vp, c_vp]),
-        "mmk_maxpool2_bwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, f32, f32, c_vp, c_vp]),
-        "mmk_maxpool2_fwd_arg": (ctypes.c_int, [c_vp, i32, i32, i32, i32, c_vp, c_vp, c_vp]),
-        "mmk_maxpool2_bwd_arg": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, f32, c_vp, c_vp]),
-        "mmk_upsample_fwd": (ctypes.c_int, [c_vp, i32, i32, i32, i32, i32, i32, c_vp, c_vp]),
-        "mmk_upsample_bwd": (ctypes.c_int, [c_vp, i32, i32, i32, i32, i32, i32, c_vp, f32, f32, c_vp, c_vp]),
-        "mmk_final_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
-        "mmk_final_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, f32, f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_mask_normalize": (ctypes.c_int, [c_vp, i32, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_final_bwd_normalized": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, i32, ctypes.c_int64, f32, f32, c_vp, c_vp,
-                                                    c_vp, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_bn_forward_stats": (ctypes.c_int, [c_vp, ctypes.c_int64, i32, c_vp, c_vp, f32, f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-        "mmk_bn_apply": (ctypes.c_int, [c_vp, ctypes.c_int64, i32, c_vp, f32, ctypes.c_uint32, c_vp, c_vp]),
-        "mmk_bn_backward": (ctypes.c_int, [c_vp, c_vp, f32, c_vp, ctypes.c_int64, i32, c_vp, c_vp, c_vp, f32, i32, c_vp, c_vp, c_vp,
-                                           c_vp, c_vp, c_vp]),
-        "mmk_unet_workspace_bytes": (sz, [i32, i32, i32, i32]),
-        "mmk_unet_scratch_bytes": (sz, [i32, i32, i32, i32]),
-        "mmk_unet_forward": (ctypes.c_int, [ctypes.POINTER(UNetDesc), c_vp]),
-        "mmk_unet_backward": (ctypes.c_int, [ctypes.POINTER(UNetDesc), c_vp, ctypes.POINTER(ctypes.c_void_p), c_vp, sz, c_vp]),
-        "mmk_unet_backward_buckets": (ctypes.c_int, [ctypes.POINTER(UNetDesc), c_vp, ctypes.POINTER(ctypes.c_void_p), c_vp, sz,
-                                                     ctypes.POINTER(ctypes.c_void_p), c_vp]),
-        "mmk_unet_backward_input": (ctypes.c_int, [ctypes.POINTER(UNetDesc), c_vp, ctypes.POINTER(ctypes.c_void_p), c_vp, i32, c_vp,
-                                                   c_vp, sz, ctypes.POINTER(ctypes.c_void_p), c_vp]),
-        "mmk_unet_grad_bucket": (i32, [i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
-        "mmk_unet_tensor": (ctypes.c_int, [i32, i32, i32, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(i32), ctypes.POINTER(i32),
-                                           ctypes.POINTER(i32)]),
-        "mmk_cfar_mask": (ctypes.c_int, [c_vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, c_vp, c_vp]),
-        "mmk_cfar_mask_bwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, c_vp, c_vp]),
-        "mmk_cfar_mask_p": (ctypes.c_int, [c_vp, i32, i32, i32, i32, i32, i32, i32, c_vp, c_vp, i32, i32, f32, c_vp, c_vp]),
-        "mmk_cfar_mask_bwd_p_ws_bytes": (sz, [i32, i32]),
-        "mmk_cfar_mask_bwd_p": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, i32, c_vp, c_vp, i32, f32, c_vp, c_vp, c_vp,
-                                               c_vp, sz, c_vp]),
-        "mmk_extract_peaks_workspace_bytes": (sz, [i32, i32, i32, i32]),
-        "mmk_extract_peaks_bwd_workspace_bytes": (sz, [i32, i32, i32, i32]),
-        "mmk_extract_peaks_bwd": (ctypes.c_int, [c_vp, i32, i32, i32, f32, c_vp, c_vp, i32, f32, i32, c_vp, c_vp, c_vp, sz, c_vp]),
-        "mmk_extract_peaks": (ctypes.c_int, [c_vp, i32, i32, i32, f32, c_vp, c_vp, c_vp, i32, f32, i32, c_vp, c_vp,
-                                             c_vp, sz, c_vp]),
-        "mmk_polar_to_cart": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, f32, i32, i32, c_vp, c_vp]),
-        "mmk_polar_to_cart_pair": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, f32, i32, i32, c_vp, c_vp,
-                                                  c_vp]),
-        "mmk_cart_to_polar": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, ctypes.c_double, c_vp, c_vp]),
-        "mmk_polar_to_cart_bwd_ws_bytes": (sz, [i32, i32, i32, i32]),
-        "mmk_polar_to_cart_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, f32, i32, i32, c_vp, c_vp, sz, c_vp]),
-        "mmk_cart_to_polar_bwd_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
-        "mmk_cart_to_polar_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, ctypes.c_double, ctypes.c_double,
-                                                 c_vp, c_vp, sz, c_vp]),
-        "mmk_mask_polar_scan": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, ctypes.c_double, c_vp, c_vp]),
-        "mmk_mask_polar_scan_bwd_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
-        "mmk_mask_polar_scan_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, ctypes.c_double,
-                                                   ctypes.c_double, c_vp, c_vp, c_vp, sz, c_vp]),
-        "mmk_sample_weights_fwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, f32, c_vp, c_vp]),
-        "mmk_host_read_rows": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64, i32, i32, i32, i32, i32, c_vp]),
-        "mmk_host_read_rows_batch": (ctypes.c_int, [ctypes.POINTER(ReadJob), i32, i32]),
-        "mmk_u8_to_float": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
-        "mmk_sample_weights_bwd_ws_bytes": (sz, [i32, i32]),
-        "mmk_sample_weights_bwd": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, i32, i32, i32, f32, c_vp, c_vp, sz, c_vp]),
-        "mmk_sample_weights_bwd_pc": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, i32, f32, c_vp, c_vp]),
-        "mmk_sample_weights_polar_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, f32, i32, i32, c_vp, c_vp]),
-        "mmk_sample_weights_polar_bwd_ws_bytes": (sz, [i32, i32]),
-        "mmk_sample_weights_polar_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, f32, i32, i32, c_vp, c_vp, sz,
-                                                        c_vp]),
-        "mmk_sample_weights_polar_bwd_pc": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, i32, i32, i32, i32, i32, f32, i32, i32, c_vp,
-                                                           c_vp]),
-        "mmk_weight_stats": (ctypes.c_int, [c_vp, c_vp, i32, i32, i32, c_vp, c_vp, c_vp]),
-        "mmk_bev_raster": (ctypes.c_int, [c_vp, i32, i32, i32, i32, f32, c_vp, c_vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in EXPORTED.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    return sig
-
-
-EXPORTED = None
 
 
 def lib():
     """The loaded C-ABI library; raises MmkError when it is absent (no fallback)."""
-    global _lib, EXPORTED
+    global _lib
     if _lib is None:
         if not os.path.exists(SO_PATH):
             raise MmkError("libmmk_hip.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -286,11 +191,11 @@ def lib():
             loaded = ctypes.CDLL(SO_PATH)
         except OSError as e:
             raise MmkError("cannot load %s: %s" % (SO_PATH, e)) from e
-        EXPORTED = _declare(loaded)
+        _declare(loaded)
         if loaded.mmk_conv_desc_bytes() != ctypes.sizeof(ConvDesc):
-            raise MmkError("%s: mmk_conv_desc is %d bytes, the ctypes mirror %d" % (SO_PATH, loaded.mmk_conv_desc_bytes(), ctypes.sizeof(ConvDesc)))
+            raise MmkError("%s: mmk_conv_desc is %d bytes, the ctypes class %d" % (SO_PATH, loaded.mmk_conv_desc_bytes(), ctypes.sizeof(ConvDesc)))
         if loaded.mmk_icp_params_bytes() != ctypes.sizeof(IcpParams):
-            raise MmkError("%s: mmk_icp_params is %d bytes, the ctypes mirror %d" % (SO_PATH, loaded.mmk_icp_params_bytes(), ctypes.sizeof(IcpParams)))
+            raise MmkError("%s: mmk_icp_params is %d bytes, the ctypes class %d" % (SO_PATH, loaded.mmk_icp_params_bytes(), ctypes.sizeof(IcpParams)))
         _lib = loaded
     return _lib
 

@@ -110,8 +110,8 @@ def _state_buffers(p, device, soft=None):
     }
 
 
-ICP_STATUS_UNARMED_KEY = 1          # include/mmk.h: MMK_ICP_STATUS_UNARMED_KEY
-ICP_STATUS_BAD_HYPER = 2            # include/mmk.h: MMK_ICP_STATUS_BAD_HYPER
+ICP_STATUS_UNARMED_KEY = _lib.CONSTANTS["MMK_ICP_STATUS_UNARMED_KEY"]
+ICP_STATUS_BAD_HYPER = _lib.CONSTANTS["MMK_ICP_STATUS_BAD_HYPER"]
 
 
 class _StatusWatch:
