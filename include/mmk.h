@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 502 /* 0.5.2: mmk_icp_soft, mmk_icp_forward_soft, mmk_icp_backward_soft (+ _workspace_bytes), mmk_knn_search (+ _workspace_bytes) (soft correspondences of the dICP; the option travels in a struct of its own, so mmk_icp_params keeps its size: additions only, the number stays), mmk_icp_params.trim_steep appended and mmk_icp_params_bytes (the soft tanh trim gate of the dICP; the struct grows at its end and 0 keeps the hard gate: additions only, the number stays), mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 502 /* 0.5.2: mmk_pose_loss_se3_fwd / _bwd, mmk_val_metric_se3 (the SE(3) pose terms: additions only, the number stays), mmk_icp_soft, mmk_icp_forward_soft, mmk_icp_backward_soft (+ _workspace_bytes), mmk_knn_search (+ _workspace_bytes) (soft correspondences of the dICP; the option travels in a struct of its own, so mmk_icp_params keeps its size: additions only, the number stays), mmk_icp_params.trim_steep appended and mmk_icp_params_bytes (the soft tanh trim gate of the dICP; the struct grows at its end and 0 keeps the hard gate: additions only, the number stays), mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -333,6 +333,23 @@ int mmk_pose_loss_gt_fwd(const float *T_pred /*B,16*/, const float *T_gt /*B,16*
 int mmk_pose_loss_gt_bwd(const float *T_pred, const float *T_gt, int32_t B, const float *g_rot, const float *g_trans,
                          float *grad_T /*B,16*/, void *stream);
 int mmk_val_metric(const float *T_pred /*B,16*/, const float *T_gt /*B,16 or NULL*/, int32_t B, float *out3, void *stream);
+/* SE(3) pose terms (pose_loss="se3"; the planar terms above read xi[1,0], xi[0,3], xi[1,3] only).  xi = T_pred T_gt^-1 - I as
+ * above: T_pred - I with T_gt NULL, (T_pred - T_gt) T_gt^-1 with the fp64 Gauss-Jordan inverse otherwise, so T_pred = T_gt gives
+ * xi = 0 exactly.  Per pair, in fp64 from the fp32 inputs, in both forms:
+ *   v = 1/2 (xi[2,1] - xi[1,2], xi[0,2] - xi[2,0], xi[1,0] - xi[0,1]),  s = ||v||,  c = 1 + 1/2 (xi[0,0] + xi[1,1] + xi[2,2]),
+ *   theta = atan2(s, c) in [0, pi] (the geodesic rotation angle),  r = ||(xi[0,3], xi[1,3], xi[2,3])||.
+ * mmk_pose_loss_se3_fwd: out2 = (mean_b theta_b, mean_b r_b).  mmk_val_metric_se3: out3 = (mean_b sqrt(theta_b^2 + r_b^2),
+ *   mean_b theta_b, mean_b r_b).  Means as above: one wave, lane l sums pairs l, l + 64, ... in index order, a fixed shuffle tree
+ *   in fp64, rounded once to fp32.
+ * mmk_pose_loss_se3_bwd: grad_T (B,16) = G with T_gt NULL, G T_gt^-T otherwise, G = d(g_rot mean theta + g_trans mean r) / dxi;
+ *   g_rot / g_trans DEVICE scalars (NULL = 0).  With d = s^2 + c^2: d theta / dv = c v / (s d) (0 at s = 0, the subgradient of
+ *   torch.norm's backward) spread with +-1/2 onto the six off-diagonal entries, d theta / dc = -s / d (0 at d = 0) spread with 1/2
+ *   onto the diagonal, d r / dxi[i,3] = xi[i,3] / r (0 at r = 0).  Row 3 of G is zero; T_gt gets no gradient.
+ * One launch each, deterministic, no float atomics.  B < 1, a NULL T_pred or a NULL output: MMK_ERR_ARG.                        */
+int mmk_pose_loss_se3_fwd(const float *T_pred /*B,16*/, const float *T_gt /*B,16 or NULL = identity*/, int32_t B, float *out2, void *stream);
+int mmk_pose_loss_se3_bwd(const float *T_pred, const float *T_gt /*or NULL*/, int32_t B, const float *g_rot, const float *g_trans,
+                          float *grad_T /*B,16*/, void *stream);
+int mmk_val_metric_se3(const float *T_pred, const float *T_gt /*or NULL*/, int32_t B, float *out3, void *stream);
 size_t mmk_fft_threshold_ws_bytes(int32_t B);
 int mmk_fft_threshold_mask(const float *fft, int32_t B, int64_t hw, void *ws, size_t ws_bytes, float *mask_out,
                            void *stream);

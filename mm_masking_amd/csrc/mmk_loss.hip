@@ -11,6 +11,9 @@
 //                                   Gauss-Jordan inverse (partial pivoting): poses read from data are not exactly orthonormal,
 //                                   and T_pred = T_gt gives xi = 0 exactly (a zero gradient, as torch.norm's backward at zero)
 //   validation metric (:255-273):   mean_b ||(xi[1,0], xi[0,3], xi[1,3])||, mean_b |xi[1,0]|, mean_b ||(xi[0,3], xi[1,3])||
+//   SE(3) pose terms (pose_loss="se3"): v = half the skew part of xi's rotation block, s = ||v||, c = 1 + trace / 2,
+//                                   theta = atan2(s, c) (the geodesic angle), r = ||xi[0:3,3]||, all in fp64, both forms of xi;
+//                                   rot = mean_b theta, trans = mean_b r, metric = (mean_b sqrt(theta^2 + r^2), rot, trans)
 //   fft mask term (:204-207):       target = fft > 3 * mean_{H,W}(fft) per image, computed on the fly inside the BCE passes (no
 //                                   target tensor); the per-image mean is an ordered fp64 reduction rounded to fp32
 #include <math.h>
@@ -241,6 +244,110 @@ __global__ void pose_loss_gt_bwd_kernel(const float *__restrict__ T, const float
     }
 }
 
+// ----------------------------------------------------------------------------- SE(3) pose terms
+// The 3x4 block X of xi = T_pred T_gt^-1 - I.  Tg == NULL: X = T - I.  Otherwise X = (T - Tg) Tg^-1 with Tg^-1 returned in R (the
+// backward needs it): T = Tg gives X = 0 exactly.  The differences are exact in fp64, the products are summed as pose_residual's.
+__device__ __forceinline__ void pose_residual_se3(const float *__restrict__ t, const float *__restrict__ tg, double (&R)[4][4],
+                                                  double (&X)[3][4])
+{
+    if (tg == nullptr) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) X[i][j] = (double)t[i * 4 + j] - (i == j ? 1.0 : 0.0);
+        return;
+    }
+    inverse4(tg, R);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double d[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) d[j] = (double)t[i * 4 + j] - (double)tg[i * 4 + j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) X[i][j] = (d[0] * R[0][j] + d[1] * R[1][j]) + (d[2] * R[2][j] + d[3] * R[3][j]);
+    }
+}
+
+// Rotation part of X: v = the axis times sin(theta) (half the skew part), s = ||v||, c = cos(theta) (from the trace) for a
+// rotation; theta = atan2(s, c) in [0, pi] is taken from them as they are for a block that is not orthonormal.
+struct Se3Terms {
+    double v[3], s, c, r;
+};
+
+__device__ __forceinline__ Se3Terms se3_terms(const double (&X)[3][4])
+{
+    Se3Terms q;
+    q.v[0] = 0.5 * (X[2][1] - X[1][2]);
+    q.v[1] = 0.5 * (X[0][2] - X[2][0]);
+    q.v[2] = 0.5 * (X[1][0] - X[0][1]);
+    q.s = sqrt(q.v[0] * q.v[0] + q.v[1] * q.v[1] + q.v[2] * q.v[2]);
+    q.c = 1.0 + 0.5 * (X[0][0] + X[1][1] + X[2][2]);
+    q.r = sqrt(X[0][3] * X[0][3] + X[1][3] * X[1][3] + X[2][3] * X[2][3]);
+    return q;
+}
+
+// one wave; lane l takes pairs l, l + 64, ... in index order, then a fixed shuffle tree (as pose_metric_kernel).
+// NOUT = 2: (mean theta, mean r); NOUT = 3: (mean sqrt(theta^2 + r^2), mean theta, mean r).
+template <int NOUT>
+__global__ __launch_bounds__(64) void pose_se3_metric_kernel(const float *__restrict__ T, const float *__restrict__ Tg, int B,
+                                                             float *__restrict__ out)
+{
+    double full = 0.0, rot = 0.0, trans = 0.0;
+    for (int b = threadIdx.x; b < B; b += 64) {
+        double R[4][4], X[3][4];
+        pose_residual_se3(T + (size_t)b * 16, Tg ? Tg + (size_t)b * 16 : nullptr, R, X);
+        const Se3Terms q = se3_terms(X);
+        const double th = atan2(q.s, q.c);
+        rot += th;
+        trans += q.r;
+        if (NOUT == 3) full += sqrt(th * th + q.r * q.r);
+    }
+    rot = wave_sum(rot);
+    trans = wave_sum(trans);
+    if (NOUT == 3) full = wave_sum(full);
+    if (threadIdx.x == 0) {
+        if (NOUT == 3) {
+            out[0] = (float)(full / B);
+            out[1] = (float)(rot / B);
+            out[2] = (float)(trans / B);
+        } else {
+            out[0] = (float)(rot / B);
+            out[1] = (float)(trans / B);
+        }
+    }
+}
+
+// d/dT_pred of (g_rot mean theta + g_trans mean r) = G (Tg == NULL) or G Tg^-T, G = dL/dxi: with d = s^2 + c^2,
+// d theta / dv = c v / (s d) (zero at s = 0, as torch.norm's backward) spread with +-1/2 onto the off-diagonal entries,
+// d theta / dc = -s / d spread with 1/2 onto the diagonal, d r / dxi[i,3] = xi[i,3] / r (zero at r = 0).  Row 3 is zero.
+__global__ void pose_se3_bwd_kernel(const float *__restrict__ T, const float *__restrict__ Tg, int B, const float *__restrict__ g_rot,
+                                    const float *__restrict__ g_trans, float *__restrict__ gT)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double gr = g_rot ? (double)g_rot[0] / B : 0.0, gt = g_trans ? (double)g_trans[0] / B : 0.0;
+    double R[4][4], X[3][4];
+    pose_residual_se3(T + (size_t)b * 16, Tg ? Tg + (size_t)b * 16 : nullptr, R, X);
+    const Se3Terms q = se3_terms(X);
+    const double d = q.s * q.s + q.c * q.c;
+    const double kv = q.s > 0.0 ? q.c / (q.s * d) * gr : 0.0;      // d theta / dv = kv v
+    const double gc = d > 0.0 ? -q.s / d * gr : 0.0;
+    const double kr = q.r > 0.0 ? gt / q.r : 0.0;
+    const double h0 = 0.5 * (kv * q.v[0]), h1 = 0.5 * (kv * q.v[1]), h2 = 0.5 * (kv * q.v[2]);
+    const double G[3][4] = {{0.5 * gc, -h2, h1, kr * X[0][3]}, {h2, 0.5 * gc, -h0, kr * X[1][3]}, {-h1, h0, 0.5 * gc, kr * X[2][3]}};
+    float *g = gT + (size_t)b * 16;
+    // (+ 0.0: a zero gradient is stored as +0 whatever the signs of the zeros it came from, so T = Tg gives all-zero bits)
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double v = Tg ? (G[i][0] * R[j][0] + G[i][1] * R[j][1]) + (G[i][2] * R[j][2] + G[i][3] * R[j][3]) : G[i][j];
+            g[i * 4 + j] = (float)(v + 0.0);
+        }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) g[12 + j] = 0.f;
+}
+
 // ----------------------------------------------------------------------------- fft-threshold target
 // Per-image sums of the fft over (H,W): block (k, b) sums its grid-stride share of image b in fp64 -> part[b * FFT_MEAN_BLOCKS + k]
 __global__ __launch_bounds__(256) void image_sum_partial_kernel(const float *__restrict__ x, size_t hw, double *__restrict__ part)
@@ -404,6 +511,38 @@ extern "C" int mmk_val_metric(const float *T_pred, const float *T_gt, int32_t B,
 {
     MMK_REQUIRE(T_pred && out3 && B >= 1, "mmk_val_metric: bad argument");
     hipLaunchKernelGGL(pose_metric_kernel<3>, dim3(1), dim3(64), 0, (hipStream_t)stream, T_pred, T_gt, B, out3);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_pose_loss_se3_fwd(const float *T_pred, const float *T_gt, int32_t B, float *out2, void *stream)
+{
+    MMK_REQUIRE(T_pred, "mmk_pose_loss_se3_fwd: T_pred is NULL");
+    MMK_REQUIRE(out2, "mmk_pose_loss_se3_fwd: out2 is NULL");
+    MMK_REQUIRE(B >= 1, "mmk_pose_loss_se3_fwd: B = %d < 1", (int)B);
+    hipLaunchKernelGGL(pose_se3_metric_kernel<2>, dim3(1), dim3(64), 0, (hipStream_t)stream, T_pred, T_gt, B, out2);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_pose_loss_se3_bwd(const float *T_pred, const float *T_gt, int32_t B, const float *g_rot, const float *g_trans,
+                                     float *grad_T, void *stream)
+{
+    MMK_REQUIRE(T_pred, "mmk_pose_loss_se3_bwd: T_pred is NULL");
+    MMK_REQUIRE(grad_T, "mmk_pose_loss_se3_bwd: grad_T is NULL");
+    MMK_REQUIRE(B >= 1, "mmk_pose_loss_se3_bwd: B = %d < 1", (int)B);
+    hipLaunchKernelGGL(pose_se3_bwd_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, T_pred, T_gt, B, g_rot, g_trans,
+                       grad_T);
+    MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" int mmk_val_metric_se3(const float *T_pred, const float *T_gt, int32_t B, float *out3, void *stream)
+{
+    MMK_REQUIRE(T_pred, "mmk_val_metric_se3: T_pred is NULL");
+    MMK_REQUIRE(out3, "mmk_val_metric_se3: out3 is NULL");
+    MMK_REQUIRE(B >= 1, "mmk_val_metric_se3: B = %d < 1", (int)B);
+    hipLaunchKernelGGL(pose_se3_metric_kernel<3>, dim3(1), dim3(64), 0, (hipStream_t)stream, T_pred, T_gt, B, out3);
     MMK_LAUNCH_CHECK();
     return MMK_OK;
 }

@@ -47,21 +47,30 @@ def pad_map(map_pts, map_norms, max_map_pts, target_pad_val, float_type=torch.fl
 
 
 def sample_T_init(dataset_type="train", pos_std=2.0, rot_std=0.6, float_type=torch.float32, generator=None,
-                  np_rng=None):
+                  np_rng=None, z_std=0.0, tilt_std=0.0):
     """icp_weight_dataset.py:260-280: T_init = Exp(xi), xi = (x, y, 0, 0, 0, yaw); uniform in
-    [-std, std] for training, normal(0, std) otherwise."""
+    [-std, std] for training, normal(0, std) otherwise.  ``z_std`` / ``tilt_std`` > 0 (absent upstream) also perturb z and
+    (roll, pitch), for the SE(3) solve of params["icp_dim"] = 3: the training branch scales the uniforms it already draws for
+    them, the other branch draws them after phi, x, y, so x, y and yaw are those of the planar call in both."""
     if dataset_type == "train":
         xi = 2 * torch.rand((6, 1), dtype=float_type, generator=generator) - 1
         xi[0:2] = pos_std * xi[0:2]
         xi[5] = rot_std * xi[5]
-        xi[2:5] = 0.0
+        if z_std > 0 or tilt_std > 0:
+            xi[2] = z_std * xi[2]
+            xi[3:5] = tilt_std * xi[3:5]
+        else:
+            xi[2:5] = 0.0
         xi = xi.reshape(6).double().numpy()
     else:
         rng = np_rng if np_rng is not None else np.random
         phi = rng.normal(0.0, rot_std)
         x = rng.normal(0.0, pos_std)
         y = rng.normal(0.0, pos_std)
-        xi = np.array([x, y, 0.0, 0.0, 0.0, phi])
+        z = rng.normal(0.0, z_std) if z_std > 0 else 0.0
+        roll = rng.normal(0.0, tilt_std) if tilt_std > 0 else 0.0
+        pitch = rng.normal(0.0, tilt_std) if tilt_std > 0 else 0.0
+        xi = np.array([x, y, z, roll, pitch, phi])
     return torch.tensor(se3_exp(xi), dtype=float_type)
 
 
@@ -219,7 +228,8 @@ class ICPWeightDataset(torch.utils.data.Dataset):
                 if params["use_gt"]:                                               # :248-252
                     T_init_idx = torch.eye(4, dtype=self.float_type) if self.gt_eye else T_gt_idx.clone()
                 else:
-                    T_rand = sample_T_init(dataset_type, params["pos_std"], params["rot_std"], self.float_type)
+                    T_rand = sample_T_init(dataset_type, params["pos_std"], params["rot_std"], self.float_type,
+                                           z_std=params.get("z_std", 0.0), tilt_std=params.get("tilt_std", 0.0))
                     T_init_idx = T_rand if self.gt_eye else (T_rand.double() @ T_gt_idx.double()).type(self.float_type)
                 self.samples.append((pair_idx, loc_stamp, map_stamp))
                 T_gt.append(T_gt_idx)

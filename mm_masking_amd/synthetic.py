@@ -160,11 +160,13 @@ def _radar(rng, segs, poles, wobble=True, hits=13):
 
 
 def make_pair(index, m_valid=20000, m_pad=20480, pad_val=1000.0, dataset_type="train", pos_std=2.0, rot_std=0.6,
-              wobble=True, density="survey", dim=2):
+              wobble=True, density="survey", dim=2, z_std=0.0, tilt_std=0.0):
     """One synthetic scan pair (numpy).  ``dim=3`` (the SE(3) / 6x6 variant of SURVEY.md §8d config 3): the map points get
     a height z ~ U(-1.5, 1.5) m and 40 % of the normals are tilted out of the plane -- drawn from a stream of their own,
     so that everything else equals the dim-2 pair of the same index -- which makes z, roll and pitch observable for the
-    planar radar scan (z = 0) under the point-to-plane residual."""
+    planar radar scan (z = 0) under the point-to-plane residual.  ``z_std`` / ``tilt_std`` > 0: T_init is also off in z and in
+    (roll, pitch), uniform in [-std, std] for training pairs and normal(0, std) otherwise, again from a stream of their own:
+    every other array of the pair, and the x, y and yaw components of T_init's xi, stay what they are without them."""
     rng = np.random.default_rng(BASE_SEED + int(index))
     dens = DENSITY[density]
     segs = _walls(rng, count=dens["walls"])
@@ -183,6 +185,10 @@ def make_pair(index, m_valid=20000, m_pad=20480, pad_val=1000.0, dataset_type="t
         xi[5] = rot_std * rng.uniform(-1, 1)
     else:
         xi = np.array([rng.normal(0, pos_std), rng.normal(0, pos_std), 0, 0, 0, rng.normal(0, rot_std)])
+    if z_std > 0 or tilt_std > 0:
+        r6 = np.random.default_rng([BASE_SEED + int(index), 6])
+        extra = r6.uniform(-1, 1, 3) if dataset_type == "train" else r6.normal(0, 1, 3)
+        xi[2:5] = extra * np.array([z_std, tilt_std, tilt_std])
     return {"fft_polar": fft, "azimuths": az, "az_times": times, "map_pc": map_pc,
             "T_init": se3_exp(xi).astype(np.float32), "T_gt": np.eye(4, dtype=np.float32)}
 

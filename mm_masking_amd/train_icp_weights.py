@@ -32,6 +32,7 @@ def default_params(device=None):
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     return {
         "device": device, "float_type": torch.float32, "gt_eye": True, "pos_std": 2.0, "rot_std": 0.6,
+        "z_std": 0.0, "tilt_std": 0.0, "pose_loss": "se2",
         "log_transform": False, "normalize": ["minmax"], "batch_size_train": 16, "batch_size_test": 32,
         "icp_type": "pt2pt", "learning_rate": 1e-4, "leaky": False, "dropout": 0.05, "batch_norm": False,
         "init_weights": True, "a_thresh": 1.0, "b_thresh": 0.09, "loss_icp_rot_weight": 1.0,
@@ -128,6 +129,33 @@ class _PoseLossFn(torch.autograd.Function):
 
 
 _PoseLossGtFn = _PoseLossFn         # (T_pred, T_gt): the name its tests call
+
+
+class _PoseLossSe3Fn(torch.autograd.Function):
+    """(loss_rot, loss_trans) of pose_loss="se3" -- the batch means of the geodesic rotation angle and of the 3-D translation
+    norm of xi = T_pred T_gt^-1 - I (_se3_terms) -- in one launch, their gradient w.r.t. T_pred in another (csrc/mmk_loss.hip).
+    ``T_gt=None`` is the gt_eye form; T_gt gets no gradient.  A None incoming gradient is a NULL pointer (a zero weight)."""
+
+    @staticmethod
+    def forward(ctx, T_pred, T_gt=None):
+        T = T_pred.contiguous().float()
+        Tg = None if T_gt is None else _lib.dev_f32(T_gt, T.device)
+        if Tg is not None and Tg.shape != T.shape:
+            raise ValueError("T_gt %s does not match T_pred %s" % (tuple(Tg.shape), tuple(T.shape)))
+        out = torch.empty(2, dtype=torch.float32, device=T.device)
+        _lib.check(_lib.lib().mmk_pose_loss_se3_fwd(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], _lib.ptr(out), _lib.stream_ptr(T.device)))
+        ctx.save_for_backward(T, Tg)
+        ctx.set_materialize_grads(False)            # a term that is not used arrives as None, not as a tensor of zeros
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_rot, g_trans):
+        T, Tg = ctx.saved_tensors
+        gT = torch.empty_like(T)
+        grads = [None if g is None else g.contiguous().float() for g in (g_rot, g_trans)]
+        _lib.check(_lib.lib().mmk_pose_loss_se3_bwd(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], *map(_lib.ptr, grads), _lib.ptr(gT),
+                                                    _lib.stream_ptr(T.device)))
+        return gT, None
 
 
 def _shape_mismatch(x, t):
@@ -234,11 +262,44 @@ def _xi_wedge(T_pred, T_gt, gt_eye):
     return torch.matmul(T_pred, torch.inverse(T_gt)) - eye
 
 
-def _pose_terms(T_pred, T_gt, gt_eye):
+POSE_LOSSES = ("se2", "se3")
+
+
+def _check_pose_loss(pose_loss):
+    if pose_loss not in POSE_LOSSES:
+        raise ValueError("pose_loss must be one of %s, got %r" % (", ".join(map(repr, POSE_LOSSES)), pose_loss))
+
+
+def _xi_wedge_se3(T_pred, T_gt, gt_eye):
+    """xi = T_pred T_gt^-1 - I as the kernels form it, (T_pred - T_gt) T_gt^-1: exactly zero for T_pred = T_gt, where _xi_wedge's
+    product leaves rounding noise -- harmless to the planar terms' values, but theta and r are norms, and the gradient of a norm
+    at rounding noise is a unit vector of noise instead of the zero it has at zero."""
+    if gt_eye:
+        return T_pred - _const("eye", T_pred.device, T_pred.dtype)
+    return torch.matmul(T_pred - T_gt, torch.inverse(T_gt))
+
+
+def _se3_terms(xi):
+    """(theta, r) per pair of pose_loss="se3" from xi (B,4,4): v = half the skew part of the rotation block (the axis times
+    sin(theta) of a rotation), c = 1 + trace / 2 (its cos(theta)), theta = atan2(||v||, c) in [0, pi], the geodesic angle, and
+    r = ||xi[0:3,3]||.  A yaw-only pose has theta = asin|T[1,0]|, so small planar errors keep the scale of the "se2" terms."""
+    v = 0.5 * torch.stack((xi[:, 2, 1] - xi[:, 1, 2], xi[:, 0, 2] - xi[:, 2, 0], xi[:, 1, 0] - xi[:, 0, 1]), dim=1)
+    s = torch.linalg.vector_norm(v, dim=1)
+    c = 1 + 0.5 * (xi[:, 0, 0] + xi[:, 1, 1] + xi[:, 2, 2])
+    return torch.atan2(s, c), torch.linalg.vector_norm(xi[:, 0:3, 3], dim=1)
+
+
+def _pose_terms(T_pred, T_gt, gt_eye, pose_loss="se2"):
     """(loss_rot, loss_trans): one launch each way for fp32 HIP tensors (csrc/mmk_loss.hip; against T_gt without torch.inverse,
-    so without a host synchronisation), the reference's expression otherwise."""
+    so without a host synchronisation), the reference's expression otherwise.  ``pose_loss="se3"``: the batch means of
+    _se3_terms, which see all six components of the error, instead of the reference's planar |xi[1,0]| and ||xi[0:2,3]||."""
+    _check_pose_loss(pose_loss)
     if _on_hip_f32(T_pred) and (gt_eye or T_gt.dtype == torch.float32):
-        return _PoseLossFn.apply(T_pred) if gt_eye else _PoseLossFn.apply(T_pred, T_gt)
+        fn = _PoseLossFn if pose_loss == "se2" else _PoseLossSe3Fn
+        return fn.apply(T_pred) if gt_eye else fn.apply(T_pred, T_gt)
+    if pose_loss == "se3":
+        theta, r = _se3_terms(_xi_wedge_se3(T_pred, T_gt, gt_eye))
+        return theta.mean(), r.mean()
     xi_wedge = _xi_wedge(T_pred, T_gt, gt_eye)
     xi_r = xi_wedge[:, 0:2, 3]
     xi_theta = xi_wedge[:, 1, 0].unsqueeze(-1)
@@ -251,17 +312,18 @@ _LOSS_TERMS = (("rot", "icp_rot"), ("trans", "icp_trans"), ("fft", "fft"), ("mas
 
 
 def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map, model, loss_weights=[],
-                       icp_loss_only_iter=0, gt_eye=True, epoch=0):
+                       icp_loss_only_iter=0, gt_eye=True, epoch=0, pose_loss="se2"):
     """train_icp_weights.py:179-253.  Same values and shapes as the reference's expression
     ``w_rot * loss_rot + ... + w_num * loss_num_pts`` (a term that is switched off is a (1,) zero there, so the sum has
     shape (1,) whenever one is); the switched-off terms are not multiplied and added on the GPU, though: they are a
     shared constant zero (x + 0 = x bit for bit), which takes ~20 two-microsecond launches out of a training step."""
+    _check_pose_loss(pose_loss)
     mask_criterion = _bce_mean
     zero = _const("zero", T_pred.device, T_pred.dtype)
     terms = {}
     want_pose = loss_weights["icp_rot"] > 0.0 or loss_weights["icp_trans"] > 0.0
     if want_pose:
-        terms["rot"], terms["trans"] = _pose_terms(T_pred, batch_T_gt, gt_eye)
+        terms["rot"], terms["trans"] = _pose_terms(T_pred, batch_T_gt, gt_eye, pose_loss)
     if icp_loss_only_iter <= 0 or (icp_loss_only_iter > 0 and epoch < icp_loss_only_iter) or \
             (loss_weights["icp_rot"] <= 0 and loss_weights["icp_trans"] <= 0):
         if loss_weights["fft"] > 0.0:
@@ -297,10 +359,23 @@ def eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map
     return loss, loss_components
 
 
-def eval_validation_loss(T_pred, batch_T_gt, gt_eye=True):
+def eval_validation_loss(T_pred, batch_T_gt, gt_eye=True, pose_loss="se2"):
     """train_icp_weights.py:255-273 -> [||(theta,x,y)||, |theta|, ||(x,y)||] batch means.  gt_eye=False on a HIP device:
     one launch (csrc/mmk_loss.hip) instead of torch.inverse, which synchronises with the host; the result carries no gradient,
-    so a T_pred that needs one (the reference only calls this under no_grad) keeps the PyTorch expression."""
+    so a T_pred that needs one (the reference only calls this under no_grad) keeps the PyTorch expression.
+    ``pose_loss="se3"``: [sqrt(theta^2 + r^2), theta, r] batch means of _se3_terms, one launch on a HIP device in both forms."""
+    _check_pose_loss(pose_loss)
+    if pose_loss == "se3":
+        if _on_hip_f32(T_pred) and (gt_eye or batch_T_gt.dtype == torch.float32) and \
+                not (torch.is_grad_enabled() and T_pred.requires_grad):
+            T = T_pred.detach().contiguous()
+            Tg = None if gt_eye else _lib.dev_f32(batch_T_gt, T.device)
+            out = torch.empty(3, dtype=torch.float32, device=T.device)
+            _lib.check(_lib.lib().mmk_val_metric_se3(_lib.ptr(T), _lib.ptr(Tg), T.shape[0], _lib.ptr(out), _lib.stream_ptr(T.device)))
+            return out
+        theta, r = _se3_terms(_xi_wedge_se3(T_pred, batch_T_gt, gt_eye))
+        full = torch.linalg.vector_norm(torch.stack((theta, r), dim=1), dim=1)     # (a zero subgradient at theta = r = 0)
+        return torch.hstack((full.mean(), theta.mean(), r.mean()))
     if not gt_eye and _on_hip_f32(T_pred) and batch_T_gt.dtype == torch.float32 and \
             not (torch.is_grad_enabled() and T_pred.requires_grad):
         T = T_pred.detach().contiguous()
@@ -324,9 +399,10 @@ def _unpack(batch, device):
 
 
 def train_step(model, batch, opt, loss_weights, device, gt_eye=True, epoch=None, icp_loss_only_iter=0,
-               grad_sync=None):
+               grad_sync=None, pose_loss="se2"):
     """Body of the reference's batch loop (train_icp_weights.py:31-58).  ``grad_sync``
     (optional callable) is where a data-parallel job all-reduces the gradients."""
+    _check_pose_loss(pose_loss)
     # (not _unpack: the ground-truth pose of a host-resident batch is copied after the forward, as it always was)
     batch_scan, batch_map, batch_T = batch["loc_data"], batch["map_data"], batch["transforms"]
     batch_T_init = batch_T["T_ml_init"].to(device)
@@ -338,7 +414,7 @@ def train_step(model, batch, opt, loss_weights, device, gt_eye=True, epoch=None,
     batch_T_gt = batch_T["T_ml_gt"].to(device)
     loss, loss_comp = eval_training_loss(T_pred, mask, num_non0, batch_T_gt, batch_scan, batch_map, model,
                                          loss_weights=loss_weights, icp_loss_only_iter=icp_loss_only_iter,
-                                         gt_eye=gt_eye, epoch=epoch)
+                                         gt_eye=gt_eye, epoch=epoch, pose_loss=pose_loss)
     loss.backward()
     if grad_sync is not None:
         grad_sync()
@@ -347,15 +423,16 @@ def train_step(model, batch, opt, loss_weights, device, gt_eye=True, epoch=None,
 
 
 def train_policy(model, iterator, opt, loss_weights=[], device="cpu", epoch=None, icp_loss_only_iter=0, gt_eye=True,
-                 grad_sync=None):
+                 grad_sync=None, pose_loss="se2"):
     """train_icp_weights.py:22-69."""
+    _check_pose_loss(pose_loss)
     model.train()
     loss_hist = 0.0
     loss_comp_hist = []
     n = 0
     for batch in iterator:
         loss, loss_comp = train_step(model, batch, opt, loss_weights, device, gt_eye=gt_eye, epoch=epoch,
-                                     icp_loss_only_iter=icp_loss_only_iter, grad_sync=grad_sync)
+                                     icp_loss_only_iter=icp_loss_only_iter, grad_sync=grad_sync, pose_loss=pose_loss)
         loss_hist += loss
         loss_comp_hist.append(loss_comp)
         n += 1
@@ -375,8 +452,9 @@ def _check_device_errors(device):
         icp_mod.check_errors(wait=True)
 
 
-def validate_policy(model, iterator, gt_eye=True, device="cpu", binary=False, neptune_run=None, epoch=None):
+def validate_policy(model, iterator, gt_eye=True, device="cpu", binary=False, neptune_run=None, epoch=None, pose_loss="se2"):
     """train_icp_weights.py:71-177 (without the Neptune figures)."""
+    _check_pose_loss(pose_loss)
     model.eval()
     val_acc = torch.zeros((1, 3), device=device)
     mean_num_pc, mean_w, max_w, min_w = 0.0, 0.0, 0.0, 1000.0
@@ -389,15 +467,17 @@ def validate_policy(model, iterator, gt_eye=True, device="cpu", binary=False, ne
             max_w = model.max_w if model.max_w > max_w else max_w
             min_w = model.min_w if model.min_w < min_w else min_w
             mean_w += model.mean_w
-            val_acc += eval_validation_loss(T_pred, batch_T_gt, gt_eye=gt_eye)
+            val_acc += eval_validation_loss(T_pred, batch_T_gt, gt_eye=gt_eye, pose_loss=pose_loss)
             n += 1
     _check_device_errors(device)
     return val_acc / n, mean_num_pc / n, mean_w / n, max_w, min_w
 
 
 def generate_baseline(model, iterator, baseline_type="train", device="cpu",
-                      loss_weights={"icp": 1.0, "fft": 0.0, "mask_pts": 0.0, "cfar": 0.0}, binary=False, gt_eye=True):
+                      loss_weights={"icp": 1.0, "fft": 0.0, "mask_pts": 0.0, "cfar": 0.0}, binary=False, gt_eye=True,
+                      pose_loss="se2"):
     """train_icp_weights.py:275-344: ICP with a fixed (non-learned) mask."""
+    _check_pose_loss(pose_loss)
     model.train() if baseline_type == "train" else model.eval()
     loss_init_hist, loss_ones_hist = [], []
     with torch.no_grad():
@@ -416,12 +496,12 @@ def generate_baseline(model, iterator, baseline_type="train", device="cpu",
                                                      override_mask=ones_mask)
             if baseline_type == "train":
                 li, _ = eval_training_loss(batch_T_init, mask_ones, num_non0, batch_T_gt, batch_scan, batch_map, model,
-                                           loss_weights=loss_weights, gt_eye=gt_eye)
+                                           loss_weights=loss_weights, gt_eye=gt_eye, pose_loss=pose_loss)
                 lo, _ = eval_training_loss(T_pred_ones, mask_ones, num_non0, batch_T_gt, batch_scan, batch_map, model,
-                                           loss_weights=loss_weights, gt_eye=gt_eye)
+                                           loss_weights=loss_weights, gt_eye=gt_eye, pose_loss=pose_loss)
             else:
-                li = eval_validation_loss(batch_T_init, batch_T_gt, gt_eye=gt_eye)[0]
-                lo = eval_validation_loss(T_pred_ones, batch_T_gt, gt_eye=gt_eye)[0]
+                li = eval_validation_loss(batch_T_init, batch_T_gt, gt_eye=gt_eye, pose_loss=pose_loss)[0]
+                lo = eval_validation_loss(T_pred_ones, batch_T_gt, gt_eye=gt_eye, pose_loss=pose_loss)[0]
             loss_init_hist.append(float(li))
             loss_ones_hist.append(float(lo))
     _check_device_errors(device)
@@ -475,6 +555,8 @@ def fit(policy, training_iterator, validation_iterator, opt, params, checkpoint_
     import os
     dev = params["device"]
     lw = loss_weights if loss_weights is not None else loss_weights_from(params)
+    pose_loss = params.get("pose_loss", "se2")
+    _check_pose_loss(pose_loss)
     if is_main:
         os.makedirs(checkpoint_dir, exist_ok=True)
     best_path = os.path.join(checkpoint_dir, "best_policy.pt")
@@ -482,12 +564,13 @@ def fit(policy, training_iterator, validation_iterator, opt, params, checkpoint_
 
     def validate(epoch=None):
         return _rank_mean(validate_policy(policy, validation_iterator, epoch=epoch, device=dev, binary=params["binary_inference"],
-                                          gt_eye=params["gt_eye"])[0])
+                                          gt_eye=params["gt_eye"], pose_loss=pose_loss)[0])
     if start_epoch == 0:
         hist["train_baseline"] = generate_baseline(policy, training_iterator, baseline_type="train", device=dev, binary=False,
-                                                   loss_weights=lw, gt_eye=params["gt_eye"])
+                                                   loss_weights=lw, gt_eye=params["gt_eye"], pose_loss=pose_loss)
         hist["val_baseline"] = generate_baseline(policy, validation_iterator, baseline_type="val", device=dev,
-                                                 binary=params["binary_inference"], gt_eye=params["gt_eye"])
+                                                 binary=params["binary_inference"], gt_eye=params["gt_eye"],
+                                                 pose_loss=pose_loss)
         avg_norm = validate(epoch=-1)
         best_norm = float(avg_norm[0, 0])
         log("Norm before training: %.6f" % best_norm)
@@ -495,7 +578,7 @@ def fit(policy, training_iterator, validation_iterator, opt, params, checkpoint_
         tic = time.time()
         mean_loss, mean_loss_comp = train_policy(policy, training_iterator, opt, lw, device=dev, epoch=epoch,
                                                  icp_loss_only_iter=params["icp_loss_only_iter"], gt_eye=params["gt_eye"],
-                                                 grad_sync=grad_sync)
+                                                 grad_sync=grad_sync, pose_loss=pose_loss)
         mean_loss = float(mean_loss)
         t_train = time.time() - tic
         tic = time.time()
@@ -578,7 +661,8 @@ class SyntheticIterator:
         idx = [first + self.rank + j * self.ws for j in range(self.bs)]
         return synthetic.make_batch(idx, device=self.params["device"], m_valid=self.m_valid, m_pad=self.m_pad,
                                     dataset_type=self.kind, pos_std=self.params["pos_std"],
-                                    rot_std=self.params["rot_std"], density=self.density)
+                                    rot_std=self.params["rot_std"], density=self.density,
+                                    z_std=self.params.get("z_std", 0.0), tilt_std=self.params.get("tilt_std", 0.0))
 
     def __iter__(self):
         for i in range(self.nb):
