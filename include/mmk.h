@@ -362,6 +362,9 @@ int mmk_bce_fft_threshold_bwd(const float *x, const float *fft, int32_t B, int64
  * mmk_cfar_mask        <- cfar_mask                      radar_utils.py:29-69
  * mmk_extract_peaks    <- extract_pc (+mean_peaks_parallel_fast, pol_2_cart)
  *                                                        radar_utils.py:71-106,167-195
+ * mmk_extract_peaks_t  <- the same, keeping the third (time) column of its pair mean       radar_utils.py:97
+ * mmk_deskew_points, mmk_deskew_points_bwd <- the motion compensation that produced the reference's filtered_pc
+ *                        (icp_weight_dataset.py:331-332), as a constant-twist operator with its gradients
  * mmk_cfar_mask_bwd, mmk_extract_peaks_bwd <- what autograd does for the two above when
  *                        the scan / the mask requires grad (both default to diff=True upstream)
  * mmk_cfar_mask_p, mmk_cfar_mask_bwd_p <- the same with a_thresh / b_thresh as tensors   radar_utils.py:56
@@ -426,6 +429,16 @@ int mmk_extract_peaks(const float *mask, int32_t B, int32_t A, int32_t R, float 
                       const float *T_ab, int32_t diff, float steep_fact, int32_t max_pts,
                       float *out_pc, int32_t *out_count, void *workspace,
                       size_t workspace_bytes, void *stream);
+/* mmk_extract_peaks plus the measurement time of every point: out_time (B,max_pts) holds
+ * t_k = (times[b, row of marker 2k+1] + times[b, row of marker 2k]) / 2 (one fp32 add and an exact halving: the pair mean
+ * of radar_utils.py:97 applied to the time column) for the rows that hold a point and 0 for the padding rows.  T_ab does not
+ * enter the times.  times must not be NULL here.  out_pc and out_count are mmk_extract_peaks's, bit for bit; the workspace
+ * is mmk_extract_peaks_workspace_bytes(B, A, R, max_pts). */
+int mmk_extract_peaks_t(const float *mask, int32_t B, int32_t A, int32_t R, float res,
+                        const float *azimuths /*B,A*/, const float *times /*B,A*/,
+                        const float *T_ab, int32_t diff, float steep_fact, int32_t max_pts,
+                        float *out_pc, int32_t *out_count, void *workspace,
+                        size_t workspace_bytes, float *out_time /*B,max_pts*/, void *stream);
 /* grad_mask (B,A,R) = dL/dmask of mmk_extract_peaks given grad_pc (B,max_pts,3) <- autograd through radar_utils.py:74
  * (res * j * mask), mean_peaks_parallel_fast (:167-185; diff=1: through both factors of each product, z = 1 - tanh;
  * diff=0: z is the bool (arr == 0), a constant, and the gradient flows through the arr factors), the pair mean (:95),
@@ -439,6 +452,27 @@ int mmk_extract_peaks_bwd(const float *mask, int32_t B, int32_t A, int32_t R, fl
                           const float *T_ab, int32_t diff, float steep_fact, int32_t max_pts,
                           const float *grad_pc /*B,max_pts,3*/, float *grad_mask /*B,A,R*/, void *workspace,
                           size_t workspace_bytes, void *stream);
+
+/* Constant-twist motion compensation of a scan cloud (absent upstream, whose filtered_pc arrives
+ * compensated).  twist (B,6) = (v; omega), the sensor's body-frame velocity in m/s and rad/s, translation first, constant
+ * over the scan; t (B,N) the measurement time of every point in seconds relative to the scan's reference time.  Point i
+ * moves to p' = Exp(t_i twist) p, evaluated per point in fp64 from the fp32 inputs with one rounding per output:
+ *   w = t omega, u = t v, th2 = w.w, A = sin th / th, B = (1 - cos th) / th2, C = (th - sin th) / th^3 (Taylor series to
+ *   th^6 for th2 < 1e-4), p' = p + A (w x p) + B w x (w x p) + u + B (w x u) + C w x (w x u).
+ * A row of pc whose three coordinates are exactly 0 is padding: its output and both of its gradients are 0.  twist = 0 and
+ * t_i = 0 return the input bits; a planar twist (vx, vy, 0, 0, 0, wz) keeps z = 0 exactly.
+ * mmk_deskew_points_bwd: grad_pc (B,N,3) = R^T grad_out and grad_twist (B,6) = sum_i t_i (u_bar_i; w_bar_i), the
+ * hand-derived reverse of the expression above; either may be NULL.  t gets no gradient.  grad_twist is summed in fp64
+ * without atomics (thread -> wave -> block partial -> one wave per item in index order) and rounded once: two runs agree
+ * in every bit.  The workspace (mmk_deskew_points_bwd_workspace_bytes(B, N) bytes) is read only when grad_twist is asked
+ * for; with grad_twist NULL it may be NULL. */
+int mmk_deskew_points(const float *pc /*B,N,3*/, const float *t /*B,N*/, const float *twist /*B,6*/,
+                      int32_t B, int32_t N, float *out /*B,N,3*/, void *stream);
+size_t mmk_deskew_points_bwd_workspace_bytes(int32_t B, int32_t N);
+int mmk_deskew_points_bwd(const float *pc /*B,N,3*/, const float *t /*B,N*/, const float *twist /*B,6*/,
+                          int32_t B, int32_t N, const float *grad_out /*B,N,3*/,
+                          float *grad_pc /*B,N,3 or NULL*/, float *grad_twist /*B,6 or NULL*/,
+                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* Polar (B,A,R) -> Cartesian (B,W,W) bilinear resample.  range_grid/angle_grid (W,W)
  * are form_cart_range_angle_grid's outputs (radar_utils.py:399-419), built by the host. */

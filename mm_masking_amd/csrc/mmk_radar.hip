@@ -340,6 +340,169 @@ __global__ void peaks_pair_kernel(const float *__restrict__ mval, const int32_t 
     o[0] = x; o[1] = y; o[2] = z;
 }
 
+// The third column of the pair mean (radar_utils.py:97): the time of point k is the mean of its two markers' azimuth times, one
+// fp32 add and an exact halving; padding rows get 0.  peaks_pair_kernel's grid and its rule for which rows hold a point.
+__global__ void peaks_time_kernel(const int32_t *__restrict__ mrow, int cap, const int32_t *__restrict__ total,
+                                  const float *__restrict__ times, int A, int max_pts, float *__restrict__ out_time)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (k >= max_pts) return;
+    const int npts = total[b] / 2;
+    float tv = 0.f;
+    if (k < npts && 2 * k + 1 < cap) {
+        const size_t m = (size_t)b * cap + 2 * k;
+        tv = (times[b * A + mrow[m + 1]] + times[b * A + mrow[m]]) / 2.0f;
+    }
+    out_time[(size_t)b * max_pts + k] = tv;
+}
+
+// ------------------------------------------------------------------------------------------
+// D1: constant-twist motion compensation, p' = Exp(s (v; omega)) p per point in fp64, one rounding per output.
+//   w = s omega, u = s v, th2 = w.w,  a1 = w x p, a2 = w x a1, b1 = w x u, b2 = w x b1
+//   p' = p + A a1 + B a2 + u + B b1 + C b2
+// and its reverse, written out by hand (c = x cross y: x_bar += y cross c_bar, y_bar += c_bar cross x).
+struct D3 {
+    double x, y, z;
+};
+__device__ __forceinline__ D3 cross3(const D3 &a, const D3 &b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ double dot3(const D3 &a, const D3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ D3 scale3(double s, const D3 &a) { return {s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ D3 add3(const D3 &a, const D3 &b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+
+constexpr double DESKEW_SERIES_CUT = 1e-4;   // th2 below it: the Taylor series to th^6
+constexpr int DESKEW_T = 256;
+
+// A = sin th / th, B = (1 - cos th) / th2, C = (th - sin th) / th^3 and, when WITH_D, their derivatives in th2.
+template <bool WITH_D>
+__device__ __forceinline__ void deskew_coef(double th2, double &A, double &B, double &C, double &dA, double &dB, double &dC)
+{
+    if (th2 < DESKEW_SERIES_CUT) {
+        const double th4 = th2 * th2, th6 = th4 * th2;
+        A = ((1.0 - th2 / 6.0) + th4 / 120.0) - th6 / 5040.0;
+        B = ((0.5 - th2 / 24.0) + th4 / 720.0) - th6 / 40320.0;
+        C = ((1.0 / 6.0 - th2 / 120.0) + th4 / 5040.0) - th6 / 362880.0;
+        if (WITH_D) {
+            dA = (-1.0 / 6.0 + th2 / 60.0) - th4 / 1680.0;
+            dB = (-1.0 / 24.0 + th2 / 360.0) - th4 / 13440.0;
+            dC = (-1.0 / 120.0 + th2 / 2520.0) - th4 / 120960.0;
+        }
+    } else {
+        const double th = sqrt(th2), s = sin(th), c = cos(th);
+        A = s / th;
+        B = (1.0 - c) / th2;
+        C = (th - s) / (th2 * th);
+        if (WITH_D) {
+            dA = (C - B) * 0.5;                  // (th cos th - sin th) / (2 th^3)
+            dB = (A - 2.0 * B) / (2.0 * th2);
+            dC = (B - 3.0 * C) / (2.0 * th2);
+        }
+    }
+}
+
+__global__ __launch_bounds__(DESKEW_T) void deskew_points_kernel(const float *__restrict__ pc, const float *__restrict__ t,
+                                                                 const float *__restrict__ twist, int N,
+                                                                 float *__restrict__ out)
+{
+    const int i = blockIdx.x * DESKEW_T + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= N) return;
+    const float *tw = twist + (size_t)b * 6;                        // a block-uniform address
+    const size_t r = (size_t)b * N + i;
+    const float fx = pc[r * 3], fy = pc[r * 3 + 1], fz = pc[r * 3 + 2];
+    float *o = out + r * 3;
+    if (fx == 0.f && fy == 0.f && fz == 0.f) {                      // a padding row stays one
+        o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
+        return;
+    }
+    const double s = (double)t[r];
+    const D3 p = {(double)fx, (double)fy, (double)fz};
+    const D3 u = {s * (double)tw[0], s * (double)tw[1], s * (double)tw[2]};
+    const D3 w = {s * (double)tw[3], s * (double)tw[4], s * (double)tw[5]};
+    double A, B, C, d0, d1, d2;
+    deskew_coef<false>(dot3(w, w), A, B, C, d0, d1, d2);
+    const D3 a1 = cross3(w, p), a2 = cross3(w, a1), b1 = cross3(w, u), b2 = cross3(w, b1);
+    o[0] = (float)(((((p.x + A * a1.x) + B * a2.x) + u.x) + B * b1.x) + C * b2.x);
+    o[1] = (float)(((((p.y + A * a1.y) + B * a2.y) + u.y) + B * b1.y) + C * b2.y);
+    o[2] = (float)(((((p.z + A * a1.z) + B * a2.z) + u.z) + B * b1.z) + C * b2.z);
+}
+
+// One point per thread; gpc (may be NULL) = R^T g, and the point's share s (u_bar; w_bar) of the twist's gradient goes
+// thread -> wave64 shuffle -> LDS -> one fp64 partial per block (part (B,nblk,6), every entry written; NULL: not asked for).
+__global__ __launch_bounds__(DESKEW_T) void deskew_points_bwd_kernel(const float *__restrict__ pc, const float *__restrict__ t,
+                                                                     const float *__restrict__ twist, int N,
+                                                                     const float *__restrict__ gout, float *__restrict__ gpc,
+                                                                     double *__restrict__ part)
+{
+    __shared__ double sm[DESKEW_T / 64][6];
+    const int i = blockIdx.x * DESKEW_T + threadIdx.x;
+    const int b = blockIdx.y;
+    double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0, c4 = 0.0, c5 = 0.0;
+    if (i < N) {
+        const float *tw = twist + (size_t)b * 6;
+        const size_t r = (size_t)b * N + i;
+        const float fx = pc[r * 3], fy = pc[r * 3 + 1], fz = pc[r * 3 + 2];
+        D3 pb = {0.0, 0.0, 0.0};
+        if (!(fx == 0.f && fy == 0.f && fz == 0.f)) {
+            const double s = (double)t[r];
+            const D3 p = {(double)fx, (double)fy, (double)fz};
+            const D3 g = {(double)gout[r * 3], (double)gout[r * 3 + 1], (double)gout[r * 3 + 2]};
+            const D3 u = {s * (double)tw[0], s * (double)tw[1], s * (double)tw[2]};
+            const D3 w = {s * (double)tw[3], s * (double)tw[4], s * (double)tw[5]};
+            double A, B, C, dA, dB, dC;
+            deskew_coef<true>(dot3(w, w), A, B, C, dA, dB, dC);
+            const D3 a1 = cross3(w, p), a2 = cross3(w, a1), b1 = cross3(w, u), b2 = cross3(w, b1);
+            const double Ab = dot3(g, a1), Bb = dot3(g, a2) + dot3(g, b1), Cb = dot3(g, b2);
+            const D3 b2b = scale3(C, g);
+            const D3 b1b = add3(scale3(B, g), cross3(b2b, w));
+            const D3 ub = add3(g, cross3(b1b, w));
+            const D3 a2b = scale3(B, g);
+            const D3 a1b = add3(scale3(A, g), cross3(a2b, w));
+            D3 wb = add3(cross3(b1, b2b), cross3(u, b1b));
+            wb = add3(wb, add3(cross3(a1, a2b), cross3(p, a1b)));
+            wb = add3(wb, scale3(2.0 * ((dA * Ab + dB * Bb) + dC * Cb), w));
+            pb = add3(g, cross3(a1b, w));
+            c0 = s * ub.x; c1 = s * ub.y; c2 = s * ub.z;
+            c3 = s * wb.x; c4 = s * wb.y; c5 = s * wb.z;
+        }
+        if (gpc) {
+            gpc[r * 3] = (float)pb.x; gpc[r * 3 + 1] = (float)pb.y; gpc[r * 3 + 2] = (float)pb.z;
+        }
+    }
+    if (part == nullptr) return;                                    // (the same for every thread of the launch)
+    c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2);
+    c3 = wave_sum(c3); c4 = wave_sum(c4); c5 = wave_sum(c5);
+    if ((threadIdx.x & 63) == 0) {
+        double *row = sm[threadIdx.x >> 6];
+        row[0] = c0; row[1] = c1; row[2] = c2; row[3] = c3; row[4] = c4; row[5] = c5;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double acc = sm[0][threadIdx.x];
+        for (int wv = 1; wv < DESKEW_T / 64; ++wv) acc += sm[wv][threadIdx.x];
+        part[((size_t)b * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = acc;
+    }
+}
+
+// One wave per item: lane l adds the partials of blocks l, l + 64, ... in index order, the fixed shuffle tree adds the
+// lanes, and the sum is rounded once to fp32.
+__global__ __launch_bounds__(64) void deskew_twist_sum_kernel(const double *__restrict__ part, int nblk,
+                                                              float *__restrict__ grad_twist)
+{
+    const int b = blockIdx.x;
+    double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0, c4 = 0.0, c5 = 0.0;
+    for (int r = threadIdx.x; r < nblk; r += 64) {
+        const double *row = part + ((size_t)b * nblk + r) * 6;
+        c0 += row[0]; c1 += row[1]; c2 += row[2]; c3 += row[3]; c4 += row[4]; c5 += row[5];
+    }
+    c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2);
+    c3 = wave_sum(c3); c4 = wave_sum(c4); c5 = wave_sum(c5);
+    if (threadIdx.x == 0) {
+        float *o = grad_twist + (size_t)b * 6;
+        o[0] = (float)c0; o[1] = (float)c1; o[2] = (float)c2; o[3] = (float)c3; o[4] = (float)c4; o[5] = (float)c5;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Bilinear tap fetch with zero padding; `rows` > H means the image is wrap-padded by one
 // row at both ends (interpolate_crossover, radar_utils.py:317-319) without materialising it.
@@ -1639,21 +1802,94 @@ extern "C" size_t mmk_extract_peaks_workspace_bytes(int32_t B, int32_t A, int32_
     return carve_peaks(B, A, max_pts, nullptr, 0).bytes;
 }
 
+// Both extractor entries.  out_time NULL: the reference's own result, which averages the azimuth times too but drops them in
+// pol_2_cart (radar_utils.py:99,187-195), and `times` is not read; otherwise peaks_time_kernel keeps them.
+static int run_extract_peaks(const char *who, const float *mask, int32_t B, int32_t A, int32_t R, float res, const float *azimuths,
+                             const float *times, const float *T_ab, int32_t diff, float steep_fact, int32_t max_pts,
+                             float *out_pc, int32_t *out_count, void *workspace, size_t workspace_bytes, float *out_time,
+                             void *stream)
+{
+    MMK_REQUIRE(mask && azimuths && out_pc && out_count, "%s: NULL pointer", who);
+    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 2 && max_pts >= 1, "%s: bad shape", who);
+    const PeakWs w = carve_peaks(B, A, max_pts, workspace, workspace_bytes);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, w.bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = launch_peaks_placement(who, mask, B, A, R, res, diff, steep_fact, w, st)) return rc;
+    hipLaunchKernelGGL(peaks_pair_kernel, dim3((max_pts + 255) / 256, B), dim3(256), 0, st, w.mval, w.mrow, w.cap,
+                       w.total, azimuths, T_ab, A, max_pts, out_pc, out_count);
+    MMK_LAUNCH_CHECK();
+    if (out_time) {
+        hipLaunchKernelGGL(peaks_time_kernel, dim3((max_pts + 255) / 256, B), dim3(256), 0, st, w.mrow, w.cap, w.total, times, A,
+                           max_pts, out_time);
+        MMK_LAUNCH_CHECK();
+    }
+    return MMK_OK;
+}
+
 extern "C" int mmk_extract_peaks(const float *mask, int32_t B, int32_t A, int32_t R, float res, const float *azimuths,
                                  const float *times, const float *T_ab, int32_t diff, float steep_fact,
                                  int32_t max_pts, float *out_pc, int32_t *out_count, void *workspace,
                                  size_t workspace_bytes, void *stream)
 {
-    (void)times;  // the reference averages the azimuth times too but drops them in pol_2_cart (radar_utils.py:99,187-195)
-    MMK_REQUIRE(mask && azimuths && out_pc && out_count, "mmk_extract_peaks: NULL pointer");
-    MMK_REQUIRE(B >= 1 && A >= 1 && R >= 2 && max_pts >= 1, "mmk_extract_peaks: bad shape");
-    const PeakWs w = carve_peaks(B, A, max_pts, workspace, workspace_bytes);
-    if (int rc = check_workspace("mmk_extract_peaks", workspace, workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = launch_peaks_placement("mmk_extract_peaks", mask, B, A, R, res, diff, steep_fact, w, st)) return rc;
-    hipLaunchKernelGGL(peaks_pair_kernel, dim3((max_pts + 255) / 256, B), dim3(256), 0, st, w.mval, w.mrow, w.cap,
-                       w.total, azimuths, T_ab, A, max_pts, out_pc, out_count);
+    return run_extract_peaks("mmk_extract_peaks", mask, B, A, R, res, azimuths, times, T_ab, diff, steep_fact, max_pts, out_pc,
+                             out_count, workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int mmk_extract_peaks_t(const float *mask, int32_t B, int32_t A, int32_t R, float res, const float *azimuths,
+                                   const float *times, const float *T_ab, int32_t diff, float steep_fact,
+                                   int32_t max_pts, float *out_pc, int32_t *out_count, void *workspace,
+                                   size_t workspace_bytes, float *out_time, void *stream)
+{
+    MMK_REQUIRE(times && out_time, "mmk_extract_peaks_t: NULL times or out_time");
+    return run_extract_peaks("mmk_extract_peaks_t", mask, B, A, R, res, azimuths, times, T_ab, diff, steep_fact, max_pts, out_pc,
+                             out_count, workspace, workspace_bytes, out_time, stream);
+}
+
+static int deskew_args(const char *who, const float *pc, const float *t, const float *twist, int32_t B, int32_t N)
+{
+    MMK_REQUIRE(pc && t && twist, "%s: NULL pointer", who);
+    MMK_REQUIRE(B >= 1 && B <= 65535 && N >= 1, "%s: bad shape (B=%d in 1..65535, N=%d >= 1)", who, B, N);
+    return MMK_OK;
+}
+
+extern "C" int mmk_deskew_points(const float *pc, const float *t, const float *twist, int32_t B, int32_t N, float *out,
+                                 void *stream)
+{
+    if (int rc = deskew_args("mmk_deskew_points", pc, t, twist, B, N)) return rc;
+    MMK_REQUIRE(out, "mmk_deskew_points: NULL pointer");
+    hipLaunchKernelGGL(deskew_points_kernel, dim3((N + DESKEW_T - 1) / DESKEW_T, B), dim3(DESKEW_T), 0, (hipStream_t)stream, pc, t,
+                       twist, N, out);
     MMK_LAUNCH_CHECK();
+    return MMK_OK;
+}
+
+extern "C" size_t mmk_deskew_points_bwd_workspace_bytes(int32_t B, int32_t N)
+{
+    if (B < 1 || N < 1) return 0;
+    return mmk::align_up((size_t)B * ((N + DESKEW_T - 1) / DESKEW_T) * 6 * sizeof(double), 256);    // one partial per block
+}
+
+extern "C" int mmk_deskew_points_bwd(const float *pc, const float *t, const float *twist, int32_t B, int32_t N,
+                                     const float *grad_out, float *grad_pc, float *grad_twist, void *workspace,
+                                     size_t workspace_bytes, void *stream)
+{
+    if (int rc = deskew_args("mmk_deskew_points_bwd", pc, t, twist, B, N)) return rc;
+    MMK_REQUIRE(grad_out, "mmk_deskew_points_bwd: NULL pointer");
+    MMK_REQUIRE(grad_pc || grad_twist, "mmk_deskew_points_bwd: neither gradient is asked for");
+    double *part = nullptr;
+    if (grad_twist) {
+        if (int rc = check_workspace("mmk_deskew_points_bwd", workspace, workspace_bytes, mmk_deskew_points_bwd_workspace_bytes(B, N)))
+            return rc;
+        part = static_cast<double *>(workspace);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (N + DESKEW_T - 1) / DESKEW_T;
+    hipLaunchKernelGGL(deskew_points_bwd_kernel, dim3(nblk, B), dim3(DESKEW_T), 0, st, pc, t, twist, N, grad_out, grad_pc, part);
+    MMK_LAUNCH_CHECK();
+    if (grad_twist) {
+        hipLaunchKernelGGL(deskew_twist_sum_kernel, dim3(B), dim3(64), 0, st, part, nblk, grad_twist);
+        MMK_LAUNCH_CHECK();
+    }
     return MMK_OK;
 }
 

@@ -25,8 +25,8 @@ from torch.nn import ModuleList
 
 from . import _lib
 from .dICP.ICP import ICP
-from .radar_utils import (_extract_weights_polar_stats, _extract_weights_stats, cfar_mask, extract_pc_padded, extract_weights, form_cart_range_angle_grid,
-                          form_polar_range_grid, mask_polar_scan)
+from .radar_utils import (_extract_weights_polar_stats, _extract_weights_stats, cfar_mask, deskew_pc, extract_pc_padded, extract_weights,
+                          form_cart_range_angle_grid, form_polar_range_grid, mask_polar_scan, scan_times)
 
 
 def weights_init(m):
@@ -174,6 +174,16 @@ class LearnICPWeightPolicy(nn.Module):
         # time (the ``global_minmax`` property), so a model built before init_process_group normalises globally too.
         # The reduction is a COLLECTIVE: every rank must run the same number of forwards (training and validation
         # alike) -- train_icp_weights.fit() validates on all ranks for this reason.
+        # params["motion_comp"] (absent upstream, whose filtered_pc arrives motion-compensated): in the scan mode the cloud that
+        # is extracted from the masked scan is de-skewed with the constant twist batch_scan["velocity"] (B,6) = (v; omega) in
+        # m/s and rad/s before ICP (radar_utils.deskew_pc).  batch_scan["az_times"] holds the azimuth stamps
+        # in multiples of params["motion_time_unit"] seconds (1e-6: synthetic's stamps); params["motion_ref"] names the time
+        # the pose refers to ("mid", "first" or "last", radar_utils.scan_times).
+        self.motion_comp = bool(params.get("motion_comp", False))
+        self.motion_time_unit = float(params.get("motion_time_unit", 1e-6))
+        self.motion_ref = params.get("motion_ref", "mid")
+        if self.motion_ref not in ("mid", "first", "last"):
+            raise ValueError("motion_ref must be 'mid', 'first' or 'last' (got %r)" % (self.motion_ref,))
         gm = params.get("global_minmax", None)
         self._global_minmax = None if gm is None else bool(gm)
         self._step = 0
@@ -355,6 +365,11 @@ class LearnICPWeightPolicy(nn.Module):
 
     def forward(self, batch_scan, batch_map, T_init, binary=False, override_mask=None, neptune_run=None, epoch=0,
                 batch_idx=0, mask_only=False):
+        if self.motion_comp and self.mask_target == "scan" and not mask_only:      # (before anything touches the device)
+            for key in ("velocity", "az_times"):
+                if batch_scan.get(key) is None:
+                    raise ValueError("motion_comp needs batch_scan[%r] (prepare_batch with params['motion_comp'] = True on "
+                                     "pairs that carry a velocity)" % key)
         fft_data = batch_scan["fft_data"].to(self.device)
         fft_cfar = batch_scan["fft_cfar"].to(self.device)
         scan_pc_raw = batch_scan["raw_pc"].to(self.device)
@@ -431,7 +446,14 @@ class LearnICPWeightPolicy(nn.Module):
         az = azimuths.to(self.device)
         az_times = batch_scan.get("az_times")
         az_times = torch.zeros_like(az) if az_times is None else az_times.to(self.device)
-        cloud, cnt = extract_pc_padded(m, self.res, az, az_times, max_pts=max_pts, diff=True)
+        if self.motion_comp:
+            # (forward has checked the two keys)  The extracted cloud lies where the image shows it; ICP gets it de-skewed.
+            # batch_scan["velocity"] may require grad: it receives the ICP's source-cloud gradient through deskew_pc.
+            seconds = scan_times(az_times, self.motion_time_unit, self.motion_ref)
+            cloud, cnt, t = extract_pc_padded(m, self.res, az, seconds, max_pts=max_pts, diff=True, return_times=True)
+            cloud = deskew_pc(cloud, t, batch_scan["velocity"].to(self.device))
+        else:
+            cloud, cnt = extract_pc_padded(m, self.res, az, az_times, max_pts=max_pts, diff=True)
         self.mean_scan_pts = cnt.float().mean()
         if self.training and not self.use_ICP_4_train:
             return T_init

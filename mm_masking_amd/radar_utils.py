@@ -21,7 +21,7 @@ from . import _lib
 __all__ = ["load_pc_from_file", "load_radar", "cfar_mask", "extract_pc", "extract_pc_padded", "extract_weights",
            "extract_weights_polar", "polar_target_from_pts", "extract_bev_from_pts", "mean_peaks_parallel_fast", "pol_2_cart", "radar_polar_to_cartesian",
            "radar_polar_to_cartesian_diff", "radar_cartesian_to_polar", "mask_polar_scan", "point_to_cart_idx",
-           "form_cart_range_angle_grid", "form_polar_range_grid"]
+           "form_cart_range_angle_grid", "form_polar_range_grid", "scan_times", "deskew_pc"]
 
 
 def _hip_device(t):
@@ -408,34 +408,40 @@ def cfar_mask(raw_scans, res, width=101, minr=2.0, maxr=80.0, guard=5,
 
 
 # ----------------------------------------------------------------------------- R3 + R4
-def _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts):
+def _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts, with_times=False):
+    """(pc, cnt) from mmk_extract_peaks or, ``with_times``, (pc, cnt, t) from mmk_extract_peaks_t."""
     B, A, R = m.shape
     dev = m.device
     L = _lib.lib()
     ws = _sized_workspace(L.mmk_extract_peaks_workspace_bytes, dev, B, A, R, int(max_pts))
     pc = torch.empty(B, int(max_pts), 3, dtype=torch.float32, device=dev)
     cnt = torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.check(L.mmk_extract_peaks(_lib.ptr(m), B, A, R, float(res), _lib.ptr(az), _lib.ptr(tm), _lib.ptr(Tab),
-                                   1 if diff else 0, float(steep_fact), int(max_pts), _lib.ptr(pc), _lib.ptr(cnt),
-                                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-    return pc, cnt
+    args = (_lib.ptr(m), B, A, R, float(res), _lib.ptr(az), _lib.ptr(tm), _lib.ptr(Tab), 1 if diff else 0, float(steep_fact),
+            int(max_pts), _lib.ptr(pc), _lib.ptr(cnt), _lib.ptr(ws), ws.numel())
+    if not with_times:
+        _lib.check(L.mmk_extract_peaks(*args, _lib.stream_ptr(dev)))
+        return pc, cnt
+    t = torch.empty(B, int(max_pts), dtype=torch.float32, device=dev)
+    _lib.check(L.mmk_extract_peaks_t(*args, _lib.ptr(t), _lib.stream_ptr(dev)))
+    return pc, cnt, t
 
 
 class _ExtractPeaks(torch.autograd.Function):
     """extract_pc_padded with the gradient autograd takes through radar_utils.py:71-106 / :167-185 with respect to the
-    mask (mmk_extract_peaks_bwd).  The marker set, its order and its pairing are constants; so are the azimuths and T_ab."""
+    mask (mmk_extract_peaks_bwd).  The marker set, its order and its pairing are constants; so are the azimuths and T_ab,
+    and the per-point times (``with_times``) are a non-differentiable output."""
 
     @staticmethod
-    def forward(ctx, thres_mask, m, res, az, tm, Tab, diff, steep_fact, max_pts):
-        pc, cnt = _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts)
+    def forward(ctx, thres_mask, m, res, az, tm, Tab, diff, steep_fact, max_pts, with_times=False):
+        out = _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts, with_times)
         ctx.save_for_backward(m, az, Tab)
         ctx.args = (float(res), 1 if diff else 0, float(steep_fact), int(max_pts))
         _remember(ctx, thres_mask)
-        ctx.mark_non_differentiable(cnt)
-        return pc, cnt
+        ctx.mark_non_differentiable(*out[1:])
+        return out
 
     @staticmethod
-    def backward(ctx, gpc, _gcnt):
+    def backward(ctx, gpc, *_rest):
         m, az, Tab = ctx.saved_tensors
         res, diff, steep_fact, max_pts = ctx.args
         B, A, R = m.shape
@@ -446,26 +452,111 @@ class _ExtractPeaks(torch.autograd.Function):
         gm = torch.empty_like(m)
         _lib.check(L.mmk_extract_peaks_bwd(_lib.ptr(m), B, A, R, res, _lib.ptr(az), _lib.ptr(Tab), diff, steep_fact, max_pts,
                                            _lib.ptr(gpc), _lib.ptr(gm), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        return _grads_back(ctx, (gm,), 8)
+        return _grads_back(ctx, (gm,), 9)
 
 
 def extract_pc_padded(thres_mask, res, azimuth_angles, azimuth_times, max_pts, T_ab=None, diff=True,
-                      steep_fact=10.0):
+                      steep_fact=10.0, return_times=False):
     """Batched form of ``extract_pc``: zero-padded (B,max_pts,3) cloud in the
     reference's azimuth-major order plus the per-item point count (int32 (B,)),
     with no host synchronisation.  This is the layout the dataset hands to the
     policy (icp_weight_dataset.py:379-381).  The cloud is differentiable in
     ``thres_mask`` for both values of ``diff`` (the gradient comes back in the mask's
     dtype and on its device); ``azimuth_angles``, ``azimuth_times`` and ``T_ab`` are
-    constants, and the count is a non-differentiable int32 tensor."""
+    constants, and the count is a non-differentiable int32 tensor.
+
+    ``return_times=True`` returns ``(pc, cnt, t)``: ``t`` (B,max_pts) fp32 is the time of every point, the mean of its two
+    markers' ``azimuth_times`` (the column the reference's pair mean forms at :97 and pol_2_cart drops), 0 in the padding
+    rows, in the unit of ``azimuth_times`` (``scan_times`` gives seconds relative to the scan's reference time).  It is a
+    constant, never differentiated; ``T_ab`` does not enter it.  ``azimuth_times=None`` is then a ``ValueError``."""
+    if return_times and azimuth_times is None:
+        raise ValueError("extract_pc_padded: return_times=True needs azimuth_times")
     dev = _hip_device(thres_mask)
     m = _lib.dev_f32(thres_mask, dev)
     az = _lib.dev_f32(azimuth_angles, dev)
     tm = _lib.dev_f32(azimuth_times, dev) if azimuth_times is not None else None
     Tab = _lib.dev_f32(T_ab, dev).reshape(-1, 16) if T_ab is not None else None
     if torch.is_grad_enabled() and thres_mask.requires_grad:
-        return _ExtractPeaks.apply(thres_mask, m, res, az, tm, Tab, diff, steep_fact, max_pts)
-    return _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts)
+        return _ExtractPeaks.apply(thres_mask, m, res, az, tm, Tab, diff, steep_fact, max_pts, bool(return_times))
+    return _peaks_forward(m, res, az, tm, Tab, diff, steep_fact, max_pts, bool(return_times))
+
+
+def scan_times(az_times, unit=1e-6, ref="mid"):
+    """The azimuth stamps of a scan as (B,A) fp32 seconds relative to the scan's reference time: what ``deskew_pc`` reads
+    through ``extract_pc_padded(..., return_times=True)``.  ``az_times`` (B,A) holds stamps in multiples of ``unit``
+    seconds, integers or floats of any size (epoch stamps included: the subtraction runs in fp64 before the cast).  ``ref``
+    names the reference time of each row: "mid" = (min + max) / 2 of its stamps, "first" = min, "last" = max -- min and max,
+    so that a row rolled by the augmentation keeps its reference.  Stays on the device of ``az_times``."""
+    if ref not in ("mid", "first", "last"):
+        raise ValueError("scan_times: ref must be 'mid', 'first' or 'last' (got %r)" % (ref,))
+    if az_times.ndim != 2:
+        raise ValueError("scan_times: az_times must be (B, A) (got %s)" % (tuple(az_times.shape),))
+    t = az_times.detach().to(torch.float64)
+    lo, hi = t.amin(dim=1, keepdim=True), t.amax(dim=1, keepdim=True)
+    t0 = lo if ref == "first" else hi if ref == "last" else lo + (hi - lo) / 2
+    return ((t - t0) * float(unit)).to(torch.float32)
+
+
+# ----------------------------------------------------------------------------- D1
+class _DeskewPoints(torch.autograd.Function):
+    """deskew_pc with its hand-derived gradients (mmk_deskew_points_bwd): grad_pc = R^T g per point, grad_twist the ordered
+    fp64 sum of the points' shares.  Only the halves that are needed are computed; the times are constants."""
+
+    @staticmethod
+    def forward(ctx, pc, twist, dev, t):
+        p, w = _lib.dev_f32(pc, dev), _lib.dev_f32(twist, dev)
+        out = _deskew_forward(p, t, w)
+        ctx.save_for_backward(p, t, w)
+        _remember(ctx, pc, twist)
+        return _back(out, pc)
+
+    @staticmethod
+    def backward(ctx, g):
+        p, t, w = ctx.saved_tensors
+        B, N = t.shape
+        dev = p.device
+        g = _lib.dev_f32(g, dev)
+        want_pc, want_twist = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        L = _lib.lib()
+        ws = _sized_workspace(L.mmk_deskew_points_bwd_workspace_bytes, dev, B, N) if want_twist else None
+        gp = torch.empty_like(p) if want_pc else None
+        gw = torch.empty_like(w) if want_twist else None
+        _lib.check(L.mmk_deskew_points_bwd(_lib.ptr(p), _lib.ptr(t), _lib.ptr(w), B, N, _lib.ptr(g), _lib.ptr(gp), _lib.ptr(gw),
+                                           _lib.ptr(ws), ws.numel() if want_twist else 0, _lib.stream_ptr(dev)))
+        return _grads_back(ctx, (gp, gw), 2)
+
+
+def _deskew_forward(p, t, w):
+    B, N = t.shape
+    out = torch.empty_like(p)
+    _lib.check(_lib.lib().mmk_deskew_points(_lib.ptr(p), _lib.ptr(t), _lib.ptr(w), B, N, _lib.ptr(out), _lib.stream_ptr(p.device)))
+    return out
+
+
+def deskew_pc(pc, t, twist):
+    """Constant-twist motion compensation of a scan cloud (absent upstream, whose ``filtered_pc`` arrives
+    compensated, icp_weight_dataset.py:331-332).  ``pc`` (B,N,3), ``t`` (B,N) the points' times in seconds relative to the
+    scan's reference time (``extract_pc_padded(..., return_times=True)`` of ``scan_times``), ``twist`` (B,6) = (v; omega), the
+    sensor's body-frame velocity in m/s and rad/s, translation first, constant over the scan.  Point i moves to
+    ``Exp(t_i twist) p_i``, where it would have been measured from the sensor's pose at the reference time; evaluated per
+    point in fp64 with one rounding per output.  A row of ``pc`` that is exactly (0, 0, 0) is padding and stays 0.  A zero
+    twist and a zero time return the input bits; a planar twist keeps z = 0.  Differentiable in ``pc`` and ``twist`` (each
+    gradient comes back in its input's dtype and on its device; the twist's is an ordered fp64 sum, equal bits in every
+    run); ``t`` is a constant."""
+    if pc.ndim != 3 or pc.shape[2] != 3:
+        raise ValueError("deskew_pc: pc must be (B, N, 3) (got %s)" % (tuple(pc.shape),))
+    B, N = pc.shape[0], pc.shape[1]
+    if tuple(t.shape) != (B, N):
+        raise ValueError("deskew_pc: t must be (%d, %d) (got %s)" % (B, N, tuple(t.shape)))
+    if tuple(twist.shape) != (B, 6):
+        raise ValueError("deskew_pc: twist must be (%d, 6) (got %s)" % (B, tuple(twist.shape)))
+    if B < 1 or N < 1:
+        raise ValueError("deskew_pc: empty cloud %s" % (tuple(pc.shape),))
+    dev = _hip_device(pc)
+    tt = _lib.dev_f32(t, dev)
+    if torch.is_grad_enabled() and (pc.requires_grad or twist.requires_grad):
+        return _DeskewPoints.apply(pc, twist, dev, tt)
+    return _back(_deskew_forward(_lib.dev_f32(pc, dev), tt, _lib.dev_f32(twist, dev)), pc)
 
 
 def extract_pc(thres_mask, res, azimuth_angles, azimuth_times, T_ab=None, diff=True, steep_fact=10.0):

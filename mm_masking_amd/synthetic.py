@@ -15,6 +15,8 @@ counterpart (what the mask network should learn to down-weight).  Pure
 numpy on the host; seed = 1234 + global pair index so that every rank of a
 data-parallel job draws its own pairs of the same stream.
 """
+import copy
+
 import numpy as np
 import torch
 
@@ -111,18 +113,35 @@ def _lidar(rng, segs, poles, m_valid, m_pad, pad_val):
     return pc
 
 
-def _radar(rng, segs, poles, wobble=True, hits=13):
+def scan_seconds(times, unit=1e-6):
+    """Azimuth stamps (A,) in multiples of ``unit`` seconds -> fp64 seconds relative to mid-scan, (min + max) / 2: the
+    "mid" rule of radar_utils.scan_times."""
+    t = np.asarray(times, dtype=np.float64)
+    return (t - (t.min() + (t.max() - t.min()) / 2)) * unit
+
+
+def _radar(rng, segs, poles, wobble=True, hits=13, varpi=None):
+    """``varpi`` (6,) = (v; omega), m/s and rad/s: the sensor moves with this constant body-frame twist while the scan is
+    formed, and T_gt = I refers to its pose at mid-scan.  The ray of azimuth a then starts at o_a = trans(Exp(s_a varpi))
+    with direction R(s_a varpi) d_a, s_a = scan_seconds(times)[a] (the world is planar: the x, y part).  None: it stands still."""
     counts = np.round(np.arange(N_AZ) * (ENCODER / N_AZ)).astype(np.int64)
     if wobble:
         counts = np.sort(np.clip(counts + rng.integers(-1, 2, N_AZ), 0, ENCODER - 1))
         az = (counts * (2 * np.pi / ENCODER)).astype(np.float32)
     d = np.stack([np.cos(az), np.sin(az)], axis=1).astype(np.float64)          # (A,2)
+    times = (np.arange(N_AZ, dtype=np.float32) * 625.0).astype(np.float32)
     p0, e = segs[:, :2], segs[:, 2:] - segs[:, :2]                               # (S,2)
-    # ray o + t d hits p0 + s e :  t = cross(p0, e) / cross(d, e), s = cross(p0, d) / cross(d, e)
+    p0 = p0[None]                                                                # (1,S,2): the wall's start seen from the ray's
+    if varpi is not None:
+        poses = np.stack([se3_exp(s_a * np.asarray(varpi, dtype=np.float64)) for s_a in scan_seconds(times)])   # (A,4,4)
+        org, rot = poses[:, :2, 3], poses[:, :2, :2]
+        d = np.einsum("aij,aj->ai", rot, d)
+        p0 = p0 - org[:, None, :]                                                # (A,S,2)
+    # ray o + t d hits p0 + s e :  t = cross(p0 - o, e) / cross(d, e), s = cross(p0 - o, d) / cross(d, e)
     den = d[:, None, 0] * e[None, :, 1] - d[:, None, 1] * e[None, :, 0]
     den = np.where(np.abs(den) < 1e-9, np.nan, den)
-    t = (p0[None, :, 0] * e[None, :, 1] - p0[None, :, 1] * e[None, :, 0]) / den
-    s = (p0[None, :, 0] * d[:, None, 1] - p0[None, :, 1] * d[:, None, 0]) / den
+    t = (p0[:, :, 0] * e[None, :, 1] - p0[:, :, 1] * e[None, :, 0]) / den
+    s = (p0[:, :, 0] * d[:, None, 1] - p0[:, :, 1] * d[:, None, 0]) / den
     hit = (t > 3.0) & (s >= 0) & (s <= 1) & (t < (N_RANGE - 40) * POLAR_RES)
     t = np.where(hit, t, np.inf)
     t.sort(axis=1)
@@ -142,37 +161,61 @@ def _radar(rng, segs, poles, wobble=True, hits=13):
                 break
             blob(a, t[a, h], rng.uniform(0.4, 0.9) * amp)
             amp *= 0.9
-    pr = np.linalg.norm(poles, axis=1)
-    pa = np.mod(np.arctan2(poles[:, 1], poles[:, 0]), 2 * np.pi)
-    pk = np.searchsorted(az, pa.astype(np.float32)) % N_AZ
+    if varpi is None:
+        pr = np.linalg.norm(poles, axis=1)
+        pa = np.mod(np.arctan2(poles[:, 1], poles[:, 0]), 2 * np.pi)
+        pk = np.searchsorted(az, pa.astype(np.float32)) % N_AZ
+        pr2 = pr
+    else:
+        # a pole in every azimuth's own frame, R_a^T (pole - o_a): it lights the azimuth whose bearing is nearest there, at
+        # that frame's range (and the next azimuth at its own frame's)
+        q = np.einsum("aji,akj->aki", rot, poles[None] - org[:, None, :])       # (A,K,2)
+        off = np.mod(np.arctan2(q[:, :, 1], q[:, :, 0]) - az[:, None].astype(np.float64) + np.pi, 2 * np.pi) - np.pi
+        pk = np.argmin(np.abs(off), axis=0)
+        rng_frame = np.linalg.norm(q, axis=2)
+        kk = np.arange(len(poles))
+        pr, pr2 = rng_frame[pk, kk], rng_frame[(pk + 1) % N_AZ, kk]
     for k in range(len(poles)):                # a pole lights up one or two neighbouring azimuths
         if pr[k] < (N_RANGE - 40) * POLAR_RES:
             blob(int(pk[k]), pr[k], rng.uniform(0.4, 0.9))
             if rng.uniform() < 0.5:
-                blob(int((pk[k] + 1) % N_AZ), pr[k], rng.uniform(0.3, 0.7))
+                blob(int((pk[k] + 1) % N_AZ), pr2[k], rng.uniform(0.3, 0.7))
     for _ in range(rng.integers(3, 9)):        # ghosts / multipath: no lidar counterpart
         a0 = rng.integers(0, N_AZ)
         r = rng.uniform(8.0, 70.0)
         for da in range(rng.integers(3, 7)):
             blob((a0 + da) % N_AZ, r + rng.normal(0, 0.05), rng.uniform(0.5, 0.9))
-    times = (np.arange(N_AZ, dtype=np.float32) * 625.0).astype(np.float32)
     return np.clip(img, 0.0, 1.0).astype(np.float32), az, times
 
 
 def make_pair(index, m_valid=20000, m_pad=20480, pad_val=1000.0, dataset_type="train", pos_std=2.0, rot_std=0.6,
-              wobble=True, density="survey", dim=2, z_std=0.0, tilt_std=0.0):
+              wobble=True, density="survey", dim=2, z_std=0.0, tilt_std=0.0, vel_std=0.0, yawrate_std=0.0, velocity=None):
     """One synthetic scan pair (numpy).  ``dim=3`` (the SE(3) / 6x6 variant of SURVEY.md §8d config 3): the map points get
     a height z ~ U(-1.5, 1.5) m and 40 % of the normals are tilted out of the plane -- drawn from a stream of their own,
     so that everything else equals the dim-2 pair of the same index -- which makes z, roll and pitch observable for the
     planar radar scan (z = 0) under the point-to-plane residual.  ``z_std`` / ``tilt_std`` > 0: T_init is also off in z and in
     (roll, pitch), uniform in [-std, std] for training pairs and normal(0, std) otherwise, again from a stream of their own:
-    every other array of the pair, and the x, y and yaw components of T_init's xi, stay what they are without them."""
+    every other array of the pair, and the x, y and yaw components of T_init's xi, stay what they are without them.
+    ``vel_std`` (m/s) / ``yawrate_std`` (rad/s) > 0: the sensor moves while the scan is formed, with a planar twist
+    (vx, vy, 0, 0, 0, wz) drawn like them from a stream of its own (or given as ``velocity`` (6,)); the pair then carries it
+    as "velocity", T_gt = I refers to mid-scan, and only the scan differs from the pair without: the map, the azimuths, the
+    stamps and T_init keep their bits (the moving scan draws from a copy of the stream, which starts with the same speckle)."""
     rng = np.random.default_rng(BASE_SEED + int(index))
     dens = DENSITY[density]
     segs = _walls(rng, count=dens["walls"])
     poles = _poles(rng, count=dens["poles"])
     map_pc = _lidar(rng, segs, poles, m_valid, m_pad, pad_val)
-    fft, az, times = _radar(rng, segs, poles, wobble=wobble, hits=dens["hits"])
+    twist = None
+    if velocity is not None:
+        twist = np.asarray(velocity, dtype=np.float64).reshape(6)
+    elif vel_std > 0 or yawrate_std > 0:
+        r7 = np.random.default_rng([BASE_SEED + int(index), 7])
+        draw = r7.uniform(-1, 1, 3) if dataset_type == "train" else r7.normal(0, 1, 3)
+        twist = np.array([vel_std * draw[0], vel_std * draw[1], 0.0, 0.0, 0.0, yawrate_std * draw[2]])
+    moving_rng = None if twist is None else copy.deepcopy(rng)
+    fft, az, times = _radar(rng, segs, poles, wobble=wobble, hits=dens["hits"])    # (moving too: it advances the pair's stream)
+    if twist is not None:
+        fft, az, times = _radar(moving_rng, segs, poles, wobble=wobble, hits=dens["hits"], varpi=twist)
     if dim == 3:
         r3 = np.random.default_rng([BASE_SEED + int(index), 3])
         map_pc[:m_valid, 2] = r3.uniform(-1.5, 1.5, m_valid)
@@ -189,8 +232,11 @@ def make_pair(index, m_valid=20000, m_pad=20480, pad_val=1000.0, dataset_type="t
         r6 = np.random.default_rng([BASE_SEED + int(index), 6])
         extra = r6.uniform(-1, 1, 3) if dataset_type == "train" else r6.normal(0, 1, 3)
         xi[2:5] = extra * np.array([z_std, tilt_std, tilt_std])
-    return {"fft_polar": fft, "azimuths": az, "az_times": times, "map_pc": map_pc,
+    pair = {"fft_polar": fft, "azimuths": az, "az_times": times, "map_pc": map_pc,
             "T_init": se3_exp(xi).astype(np.float32), "T_gt": np.eye(4, dtype=np.float32)}
+    if twist is not None:
+        pair["velocity"] = twist.astype(np.float32)
+    return pair
 
 
 def make_batch(indices, device="cpu", **kw):

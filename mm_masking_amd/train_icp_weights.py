@@ -58,16 +58,32 @@ def prepare_batch(raw, params, max_loc_pts=5120, polar_res=0.0596):
     fft_polar (B,400,3360), azimuths (B,400), az_times (B,400), map_pc (B,M,6),
     T_init, T_gt.  Returns the reference's dict-of-dicts batch; with params["mask_target"] == "scan" its ``loc_data`` also
     carries fft_polar, azimuths and az_times (what the policy's scan mode reads), with params["polar_sampling"] the azimuths
-    (what the polar sampler and the polar map-point target read)."""
+    (what the polar sampler and the polar map-point target read).  With params["motion_comp"] ``raw`` also holds velocity
+    (B,6): raw_pc stays the image-frame cloud, filtered_pc is that cloud de-skewed with the twist (radar_utils.deskew_pc), and
+    loc_data carries velocity."""
+    motion = bool(params.get("motion_comp", False))
+    if motion and (raw.get("velocity") is None or raw.get("az_times") is None):
+        raise ValueError("motion_comp needs raw['velocity'] (B,6) and raw['az_times'] (synthetic.make_pair with vel_std or "
+                         "yawrate_std > 0)")
     fft = raw["fft_polar"]
     az = raw["azimuths"]
     cfar = ru.cfar_mask(fft, polar_res, a_thresh=params["a_thresh"], b_thresh=params["b_thresh"], diff=False)
-    pc, _ = ru.extract_pc_padded(cfar, polar_res, az, raw["az_times"], max_loc_pts, diff=False)
+    if motion:
+        # the reference's split (icp_weight_dataset.py:331-332,377-381): raw_pc lies where the image shows it and samples the
+        # mask, which is distorted like the image; filtered_pc is the motion-compensated cloud that goes to ICP
+        seconds = ru.scan_times(raw["az_times"], params.get("motion_time_unit", 1e-6), params.get("motion_ref", "mid"))
+        pc, _, t = ru.extract_pc_padded(cfar, polar_res, az, seconds, max_loc_pts, diff=False, return_times=True)
+        filtered = ru.deskew_pc(pc, t, raw["velocity"])
+    else:
+        pc, _ = ru.extract_pc_padded(cfar, polar_res, az, raw["az_times"], max_loc_pts, diff=False)
+        filtered = pc
     if params.get("network_input_type", "cartesian") == "cartesian":    # icp_weight_dataset.py:350-352
         fft_img, cfar_img = ru._polar_to_cart_pair(fft, cfar, az, polar_res)     # one pass, shared coordinates
     else:                                                               # polar network: images stay (400,3360)
         fft_img, cfar_img = fft, cfar
-    loc_data = {"raw_pc": pc, "filtered_pc": pc, "fft_data": fft_img, "fft_cfar": cfar_img, "timestamp": 0}
+    loc_data = {"raw_pc": pc, "filtered_pc": filtered, "fft_data": fft_img, "fft_cfar": cfar_img, "timestamp": 0}
+    if motion:
+        loc_data["velocity"] = raw["velocity"]
     if params.get("mask_target") == "scan":
         loc_data.update({"fft_polar": fft, "azimuths": az, "az_times": raw["az_times"]})
     if params.get("polar_sampling"):

@@ -5,6 +5,7 @@ repeated calls after a warm-up; the two variants alternate within one run and th
 the spread.  Bytes are the algorithm's, computed from the shapes.  Development tool (GPU box); prints one JSON line.
 
     python scripts/bench_mask_scan.py [--batch 32] [--rounds 7] [--reps 10] [--out FILE]
+    python scripts/bench_mask_scan.py --motion [...]      the motion compensation: deskew_pc's launches and the scan-mode step
 """
 import argparse
 import json
@@ -45,17 +46,60 @@ def alternate(variants, rounds, reps):
     return {k: (statistics.median(v), min(v), max(v)) for k, v in times.items()}
 
 
+def motion(args, dev):
+    """--motion: the scan-mode train_step with and without params["motion_comp"] on the same moving pairs, and deskew_pc's two
+    launches (forward; forward + backward with both gradients) at N = 5 120 points x ``--batch`` items."""
+    B, N = args.batch, 5120
+    g = torch.Generator().manual_seed(2)
+    pc = ((torch.rand(B, N, 3, generator=g) - 0.5) * 140.0).to(dev)
+    t = ((torch.rand(B, N, generator=g) - 0.5) * 0.25).to(dev)
+    tw = (torch.tensor([12.0, 0.5, 0.0, 0.0, 0.0, 0.3]).repeat(B, 1) * (0.5 + torch.rand(B, 1, generator=g))).to(dev)
+    G = torch.randn(B, N, 3, generator=g).to(dev)
+    pg, wg = pc.clone().requires_grad_(True), tw.clone().requires_grad_(True)
+
+    def forward_backward():
+        pg.grad = wg.grad = None
+        ru.deskew_pc(pg, t, wg).backward(G)
+
+    res = {"shape": {"B": B, "N": N}, "algorithmic_bytes": {"forward": 28 * B * N, "backward": 52 * B * N},
+           "deskew_ms": alternate({"forward": lambda: ru.deskew_pc(pc, t, tw), "forward_backward": forward_backward},
+                                  args.rounds, args.reps)}
+    Bs = args.step_batch
+    raw = synthetic.make_batch(list(range(Bs)), device=dev, vel_std=12.0, yawrate_std=0.3)
+    steps = {}
+    for name, flag in (("scan", False), ("scan_motion_comp", True)):
+        params = trn.default_params(dev)
+        params.update({"mask_target": "scan", "motion_comp": flag})
+        batch = trn.prepare_batch(raw, params)
+        torch.manual_seed(0)
+        model = LearnICPWeightPolicy(params).to(dev)
+        opt = trn.make_optimizer(model, params)
+        model.train()
+        steps[name] = (lambda model=model, batch=batch, opt=opt, params=params:
+                       trn.train_step(model, batch, opt, trn.loss_weights_from(params), dev))
+    res["train_step_ms"] = {"B": Bs, **alternate(steps, args.rounds, max(1, args.reps // 3))}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--step-batch", type=int, default=8)
+    ap.add_argument("--motion", action="store_true", help="time the motion compensation instead (deskew_pc and the scan-mode step)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mask_scan needs a HIP device: a CPU run cannot give a time")
     dev = torch.device("cuda:0")
+    if args.motion:
+        line = json.dumps(motion(args, dev))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     B, A, R, H = args.batch, 400, 3360, 640
     g = torch.Generator().manual_seed(1)
     scan, mask = torch.rand(B, A, R, generator=g).to(dev), torch.rand(B, H, H, generator=g).to(dev)
