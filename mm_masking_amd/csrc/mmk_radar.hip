@@ -1165,7 +1165,7 @@ PeakWs carve_peaks(int B, int A, int max_pts, void *ws, size_t cap_bytes)
 // With TH::params (device thresholds) the same step 1 also gives the gradients of the two thresholds (th_c = a_th stat_c + b_th, radar_utils.py:56):
 //   ga = - sum of k_c stat_c,  gb = - sum of k_c   over the cells c in [mincol, maxcol) (outside, th is the constant 1000).
 // Each thread adds its cells in fp64 in ascending i, the block adds the 512 pairs in a fixed order (a shuffle tree per
-// wave, then the eight wave totals through 16 doubles of LDS) and writes one pair of doubles per row to `part`;
+// wave, then the eight wave totals of each sum through the scan's eight doubles of LDS) and writes one pair of doubles per row to `part`;
 // cfar_param_sum_kernel finishes the sum.  No atomics.  graw == nullptr (only the thresholds require grad): the block stops
 // after step 1.
 template <int NPRE, class TH>
@@ -1235,24 +1235,26 @@ __global__ __launch_bounds__(CFAR_T) void cfar_mask_bwd_kernel(const float *__re
         }
     }
     if constexpr (PARAMS) {
-        __shared__ double psum[2 * (CFAR_T / 64)];
+        // (the two sums go through wsum one after the other: an array of their own would be static LDS beyond the 64 bytes
+        // cfar_args leaves beside the longest row, and the launch of R = 13 637 .. 13 647 would be refused)
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
             pa += __shfl_down(pa, off, 64);
             pb += __shfl_down(pb, off, 64);
         }
-        if ((threadIdx.x & 63) == 0) {
-            psum[2 * (threadIdx.x >> 6)] = pa;
-            psum[2 * (threadIdx.x >> 6) + 1] = pb;
-        }
+        double ta = 0.0, tb = 0.0;
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = pa;
         __syncthreads();
         if (threadIdx.x == 0) {
-            double ta = 0.0, tb = 0.0;
 #pragma unroll
-            for (int w = 0; w < CFAR_T / 64; ++w) {
-                ta += psum[2 * w];
-                tb += psum[2 * w + 1];
-            }
+            for (int w = 0; w < CFAR_T / 64; ++w) ta += wsum[w];
+        }
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = pb;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int w = 0; w < CFAR_T / 64; ++w) tb += wsum[w];
             const size_t rowid = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
             thr.part[2 * rowid] = ta;
             thr.part[2 * rowid + 1] = tb;
@@ -1686,6 +1688,7 @@ static int cfar_args(const char *who, CfarCall &c)
     MMK_REQUIRE(c.w2 >= 1 && c.guard >= 0, "%s: bad window (w2=%d guard=%d)", who, c.w2, c.guard);
     MMK_REQUIRE(c.mincol >= c.w2 + c.guard && c.maxcol <= c.R, "%s: column range [%d,%d) outside the row", who, c.mincol, c.maxcol);
     c.smem = (size_t)(c.R + 1) * sizeof(double) + (size_t)c.R * sizeof(float);
+    // (the 64 bytes are the static LDS of every CFAR kernel, the scan's eight wave totals: none of them may declare more)
     MMK_REQUIRE(c.smem <= 160 * 1024 - 64, "%s: R=%d does not fit the 160 KB LDS row buffer", who, c.R);
     return MMK_OK;
 }
