@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MMK_VERSION 502 /* 0.5.2: mmk_pose_loss_se3_fwd / _bwd, mmk_val_metric_se3 (the SE(3) pose terms: additions only, the number stays), mmk_icp_soft, mmk_icp_forward_soft, mmk_icp_backward_soft (+ _workspace_bytes), mmk_knn_search (+ _workspace_bytes) (soft correspondences of the dICP; the option travels in a struct of its own, so mmk_icp_params keeps its size: additions only, the number stays), mmk_icp_params.trim_steep appended and mmk_icp_params_bytes (the soft tanh trim gate of the dICP; the struct grows at its end and 0 keeps the hard gate: additions only, the number stays), mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
+#define MMK_VERSION 502 /* 0.5.2: mmk_voxel_downsample (+ _workspace_bytes) (the voxel filter of clouds: additions only, the number stays), mmk_pose_loss_se3_fwd / _bwd, mmk_val_metric_se3 (the SE(3) pose terms: additions only, the number stays), mmk_icp_soft, mmk_icp_forward_soft, mmk_icp_backward_soft (+ _workspace_bytes), mmk_knn_search (+ _workspace_bytes) (soft correspondences of the dICP; the option travels in a struct of its own, so mmk_icp_params keeps its size: additions only, the number stays), mmk_icp_params.trim_steep appended and mmk_icp_params_bytes (the soft tanh trim gate of the dICP; the struct grows at its end and 0 keeps the hard gate: additions only, the number stays), mmk_mask_polar_scan, mmk_mask_polar_scan_bwd (+ _ws_bytes) (the Cartesian mask applied to the polar scan, fused; additions only), mmk_conv_first_dgrad (+ _ws_bytes), mmk_input_norm_bwd, mmk_unet_backward_input (gradient of the mask network with respect to its input image; additions only), mmk_icp_backward_points (+ _workspace_bytes), mmk_sample_weights_bwd_pc (gradients with respect to the point clouds), mmk_cfar_mask_bwd, mmk_extract_peaks_bwd (+ _workspace_bytes) (gradients of the radar front end with respect to the scan); 0.5.1: mmk_pose_loss_gt_*, mmk_val_metric, mmk_fft_threshold_*, mmk_bce_fft_threshold_*, mmk_channel_meanstd (the gt_eye=False pose terms, the fft-threshold mask loss and standardisation on the kernels); 0.5.0: mmk_unet_backward_buckets / mmk_unet_grad_bucket (per-bucket completion events for an overlapped gradient all-reduce); 0.4.2: arg-max codes of the poolings (mmk_conv_desc.pool_arg, mmk_maxpool2_fwd_arg / _bwd_arg, mmk_unet_desc.keep_full_res); 0.4.1: mmk_pose_loss_*, mmk_bce_mean_*; 0.4.0: mmk_icp_status / _accumulate / _solve_update; 0.3.1: mmk_host_read_rows_batch; 0.3.0: no float atomics left (first / final layer gradients and the mask-gradient scatter take workspaces; mmk_conv3x3_wgrad + _unpack removed) */
 
 #define MMK_OK 0
 #define MMK_ERR_ARG (-1)
@@ -291,6 +291,30 @@ int mmk_knn_normals(const float *points /*B,M,cols*/, int32_t B, int32_t M, int3
                     const float *viewpoint /*B,3 or NULL = origin*/,
                     float *normals /*B,M,3*/, float *curvature /*B,M or NULL*/, int32_t *count /*B,M or NULL*/,
                     int32_t *nbr_idx /*B,M,k or NULL*/, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Voxel-grid downsampling of a cloud (this build's own, nothing upstream corresponds: upstream the maps
+ * arrive voxel-filtered from vtr3).  points (B,M,cols), dim <= cols <= 8.  A row is valid when all its cols values are
+ * finite and |x_c| < pad_val for c < dim; every other row is padding (voxel_of -1).  Cell of a valid row: i_c = (int)
+ * floorf(x_c * inv), c < dim, inv = (float)(1.0 / (double)voxel) formed once on the host.  One output row per occupied
+ * cell, ordered by the lowest member index (first appearance).  out_count[b] = occupied cells (it may exceed max_out: the
+ * first max_out are kept); voxel_of[b,i] = rank of row i's cell in that order (also when >= max_out); out_n = members,
+ * out_first = lowest member index; rows from min(count, max_out) on are padding: every column pad_val, out_n 0, out_first
+ * -1.  MMK_VOXEL_CENTROID: every column the mean of the members, summed as 64-bit fixed point (one power-of-two scale per
+ * pair, M max|value| scale < 2^62) and closed by (float)((double)sum / scale / n): independent of the arrival order;
+ * normals = 1 (cols >= 6): columns 3..5 are the mean normal divided by its fp64 length, rounded once, exactly 0 when the
+ * length is 0.  MMK_VOXEL_FIRST: every column a bit copy of the lowest-index member.  voxel and pad_val finite and > 0,
+ * pad_val * inv <= 2^20, dim 2|3, normals 0|1, 1 <= max_out, 1 <= M <= 2^28, 1 <= B <= 65535, points / out / out_count not
+ * NULL, workspace of mmk_voxel_downsample_workspace_bytes(B, M, cols, max_out) bytes (0 for refused sizes): anything else
+ * is MMK_ERR_ARG before any launch.  Asynchronous on `stream`, no allocation, nothing read back; every value depends on
+ * the pair's own rows alone; no float atomics.                                                                          */
+#define MMK_VOXEL_CENTROID 0
+#define MMK_VOXEL_FIRST 1
+size_t mmk_voxel_downsample_workspace_bytes(int32_t B, int32_t M, int32_t cols, int32_t max_out);
+int mmk_voxel_downsample(const float *points /*B,M,cols*/, int32_t B, int32_t M, int32_t cols, int32_t dim /*2|3*/,
+                         float voxel, float pad_val, int32_t mode, int32_t normals /*0|1*/, int32_t max_out,
+                         float *out /*B,max_out,cols*/, int32_t *out_count /*B*/,
+                         int32_t *out_n /*B,max_out or NULL*/, int32_t *out_first /*B,max_out or NULL*/,
+                         int32_t *voxel_of /*B,M or NULL*/, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Measurement hook (bench.py): while enabled, every nn_search launch made by this
  * process (inside mmk_icp_forward or mmk_nn_search) is bracketed by HIP events on its

@@ -24,7 +24,8 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 SO_PATH = os.environ.get("MMK_LIB", os.path.join(_HERE, "libmmk_hip.so"))   # MMK_LIB: A/B another build (development)
-SOURCES = ["mmk_api.hip", "mmk_icp.hip", "mmk_radar.hip", "mmk_unet.hip", "mmk_unet_driver.hip", "mmk_loader.hip", "mmk_loss.hip"]
+SOURCES = ["mmk_api.hip", "mmk_icp.hip", "mmk_cloud.hip", "mmk_radar.hip", "mmk_unet.hip", "mmk_unet_driver.hip",
+           "mmk_loader.hip", "mmk_loss.hip"]
 
 _lib = None
 
@@ -125,6 +126,7 @@ ICP_TYPES = _codes("MMK_ICP_", {"pt2pt": "PT2PT", "pt2pl": "PT2PL"})
 LOSSES = _codes("MMK_LOSS_", {None: "NONE", "none": "NONE", "l2": "NONE", "cauchy": "CAUCHY", "huber": "HUBER",
                               "geman_mcclure": "GEMAN_MCCLURE", "welsch": "WELSCH"})
 NN_METHODS = _codes("MMK_NN_", {"brute": "BRUTE", "grid": "GRID"})
+VOXEL_MODES = _codes("MMK_VOXEL_", {"centroid": "CENTROID", "first": "FIRST"})
 
 
 def build(verbose=False):

@@ -63,3 +63,13 @@ __device__ __forceinline__ int wave_sum_i(int v)
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
 }
+
+// Scale of the order-independent fixed-point sums (the dICP's target gradient, the voxel centroids): entry v is added as
+// llrint(v · scale) in a 64-bit integer, scale the power of two with 2^cnt_bits · max|v| · scale < 2^62, so that no partial
+// sum of up to 2^cnt_bits entries can overflow.  mbits = the bits of max|v|; a non-finite maximum gives 0.
+__device__ __forceinline__ double tgt_fixed_scale(unsigned mbits, int cnt_bits)
+{
+    if (mbits >= 0x7f800000u) return 0.0;
+    if (mbits == 0u) return 1.0;
+    return ldexp(1.0, 62 - cnt_bits - ((int)(mbits >> 23) - 126));      // max|v| < 2^((bits >> 23) − 126), subnormals too
+}

@@ -2152,13 +2152,7 @@ __global__ void bwd_final_kernel(const double *__restrict__ Gdir, const double *
 // source row maps to the same one), so the rows are added as FIXED POINT in 64-bit integers, whose sum does not depend on
 // the order of arrival: entry v becomes llrint(v·scale), scale the power of two with K·N·max|v|·scale < 2^62 (no partial
 // sum can overflow) -- a resolution of max|v|·2^(cnt_bits − 62) per entry, cnt_bits = ceil(log2(K·N)).  A non-finite entry
-// (pmax bits >= +inf) makes the pair's target gradient NaN.
-__device__ __forceinline__ double tgt_fixed_scale(unsigned mbits, int cnt_bits)
-{
-    if (mbits >= 0x7f800000u) return 0.0;
-    if (mbits == 0u) return 1.0;
-    return ldexp(1.0, 62 - cnt_bits - ((int)(mbits >> 23) - 126));      // max|v| < 2^((bits >> 23) − 126), subnormals too
-}
+// (pmax bits >= +inf) makes the pair's target gradient NaN.  The scale is tgt_fixed_scale of mmk_common.h.
 
 // One thread per (row, column), L = tgt_acc_cols(C) lanes per row, so that an atomic wave-instruction adds 64 / L whole rows
 // (C·8 contiguous bytes each) instead of 64 scattered words.  A wave whose rows all share one target (the hot target) sums

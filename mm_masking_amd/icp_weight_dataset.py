@@ -140,6 +140,8 @@ class ICPWeightDataset(torch.utils.data.Dataset):
         .../map/<map_stamp>.bin                    float32 x 6 per point, xyz | normal in the robot frame
         .../map/<map_stamp>_xyz.bin                optional, float32 x 3: a map without normals; when <map_stamp>.bin is
                                                    missing it is written once from this file with estimated normals
+        .../map/<map_stamp>_vox<v>.bin             with params["map_voxel"] = v > 0 (metres): the voxel-filtered map, float32 x 6,
+                                                   written once from <map_stamp>.bin and read in its place
 
     The per-item work is the reference's: PNG rows -> load_radar, zero / target_pad_val padding to the largest
     cloud of the set, map filtering by elevation and normal, rotation augmentation, polar -> Cartesian (HIP
@@ -199,7 +201,16 @@ class ICPWeightDataset(torch.utils.data.Dataset):
         self.max_map_pts = int(params.get("max_map_pts", 0))
         scan_max = self.max_loc_pts == 0 or self.max_map_pts == 0
         radar_in = not (map_sensor == "lidar" and loc_sensor == "lidar")
+        # params["map_voxel"] (metres; absent upstream, where the maps arrive voxel-filtered from vtr3): the maps are read from
+        # a voxel-filtered cache beside the export; absent, None or 0: the export's own maps
+        voxel = params.get("map_voxel")
+        self.map_voxel = 0.0 if voxel is None else float(voxel)
+        if not math.isfinite(self.map_voxel) or self.map_voxel < 0:
+            raise ValueError("params['map_voxel'] must be a finite edge length in metres >= 0 (got %r)" % (voxel,))
+        self._map_suffix = "_vox%r" % self.map_voxel if self.map_voxel > 0 else ""
         self._write_map_normals(loc_pairs, sensor_dir_name, radar_in, num_samples, params)
+        if self.map_voxel > 0:
+            self._write_map_voxels(loc_pairs, sensor_dir_name, radar_in, num_samples)
         for pair_idx, (map_seq, loc_seq) in enumerate(loc_pairs):
             pdir = os.path.join(data_dir, "vtr_export", sensor_dir_name, map_seq, loc_seq)
             idx = np.load(os.path.join(pdir, "index.npz"), allow_pickle=False)
@@ -220,7 +231,7 @@ class ICPWeightDataset(torch.utils.data.Dataset):
                         self._write_cfar(radar_path, cfar_path)
                 T_gt_idx = torch.tensor(np.asarray(idx["T_gt"][ii]), dtype=self.float_type)
                 if scan_max:
-                    raw, _, mp, mn = self._read_clouds(pdir, loc_stamp, map_stamp)
+                    raw, _, mp, mn = self._read_clouds(pdir, loc_stamp, map_stamp, self._map_suffix)
                     mps, mns = self._to_sensor_frame(torch.from_numpy(mp), torch.from_numpy(mn), T_msr)
                     kept, _ = filter_map(mps, mns, T_gt_idx, loc_sensor, map_sensor)
                     self.max_loc_pts = max(self.max_loc_pts, raw.shape[0])
@@ -259,7 +270,53 @@ class ICPWeightDataset(torch.utils.data.Dataset):
         maps of the samples this Dataset will use; distinct maps are grouped into padded batches of at most ``max_rows``
         rows, one launch each (the result does not depend on the batch).  Everything downstream reads the cache as an
         ordinary export.  A map with neither file is left to _read_clouds' error."""
-        todo, seen, n = [], set(), 0
+        todo, seen = [], set()
+        for path in self._used_map_paths(loc_pairs, sensor_dir_name, radar_in, num_samples):
+            xyz = path[:-4] + "_xyz.bin"
+            if path not in seen and not os.path.exists(path) and os.path.exists(xyz):
+                seen.add(path)
+                todo.append((path, load_xyz_bin(xyz, 3)))
+        if not todo:
+            return
+        from .dICP.normals import estimate_normals
+        k, radius = int(params.get("map_normal_k", 16)), params.get("map_normal_radius")
+        for group, batch, pad in self._padded_batches(todo, max_rows):
+            if not torch.cuda.is_available():
+                from . import _lib
+                raise _lib.MmkError("ICPWeightDataset: %s holds xyz only and estimating its normals needs an MI355X/HIP "
+                                    "device" % (group[0][0][:-4] + "_xyz.bin"))
+            normals = estimate_normals(torch.from_numpy(batch).cuda(), k=k, dim=3, max_radius=radius, pad_val=pad).cpu().numpy()
+            for j, (path, c) in enumerate(group):
+                self._write_cloud(path, np.concatenate((c, normals[j, :c.shape[0]]), axis=1))
+
+    def _write_map_voxels(self, loc_pairs, sensor_dir_name, radar_in, num_samples, max_rows=1 << 21):
+        """The voxel cache of params["map_voxel"] (metres), built as the normals cache: every map the samples of this
+        Dataset use gets, once, ``map/<map_stamp>_vox<voxel>.bin`` = voxel.voxel_downsample of ``map/<map_stamp>.bin``
+        (dim 3, centroids, normals re-normalised; robot frame, first ``count`` rows), which _read_clouds and
+        _cloud_sources then open in place of the full map.  A map without its ``.bin`` is left to _read_clouds' error."""
+        todo, seen = [], set()
+        for path in self._used_map_paths(loc_pairs, sensor_dir_name, radar_in, num_samples):
+            vox = path[:-4] + self._map_suffix + ".bin"
+            if vox not in seen and not os.path.exists(vox) and os.path.exists(path):
+                seen.add(vox)
+                todo.append((vox, load_xyz_bin(path, 6)))
+        if not todo:
+            return
+        from .dICP.voxel import voxel_downsample
+        for group, batch, pad in self._padded_batches(todo, max_rows):
+            if not torch.cuda.is_available():
+                from . import _lib
+                raise _lib.MmkError("ICPWeightDataset: %s is missing and voxel-filtering its map (map_voxel = %r) needs an "
+                                    "MI355X/HIP device" % (group[0][0], self.map_voxel))
+            out, count = voxel_downsample(torch.from_numpy(batch).cuda(), self.map_voxel, dim=3, pad_val=pad, mode="centroid",
+                                          normals=True, max_out=batch.shape[1])
+            out, count = out.cpu().numpy(), count.cpu().numpy()
+            for j, (vox, _) in enumerate(group):
+                self._write_cloud(vox, out[j, :int(count[j])])
+
+    def _used_map_paths(self, loc_pairs, sensor_dir_name, radar_in, num_samples):
+        """``map/<map_stamp>.bin`` of every sample the constructor's loop will take, in its order (repeats included)."""
+        n = 0
         for map_seq, loc_seq in loc_pairs:
             pdir = os.path.join(self.data_dir, "vtr_export", sensor_dir_name, map_seq, loc_seq)
             idx = np.load(os.path.join(pdir, "index.npz"), allow_pickle=False)
@@ -268,18 +325,14 @@ class ICPWeightDataset(torch.utils.data.Dataset):
                                                                 "%d.png" % int(idx["loc_stamp"][ii]))):
                     continue
                 n += 1
-                path = os.path.join(pdir, "map", "%d.bin" % int(idx["map_stamp"][ii]))
-                xyz = path[:-4] + "_xyz.bin"
-                if path not in seen and not os.path.exists(path) and os.path.exists(xyz):
-                    seen.add(path)
-                    todo.append((path, load_xyz_bin(xyz, 3)))
+                yield os.path.join(pdir, "map", "%d.bin" % int(idx["map_stamp"][ii]))
                 if num_samples > 0 and n >= num_samples:
                     break
-        if not todo:
-            return
-        from .dICP.normals import estimate_normals
-        k, radius = int(params.get("map_normal_k", 16)), params.get("map_normal_radius")
-        todo.sort(key=lambda t: t[1].shape[0])
+
+    def _padded_batches(self, todo, max_rows):
+        """``todo`` = [(path, cloud (n,cols))] grouped, smallest first, into padded batches of at most ``max_rows`` rows:
+        yields (group, batch (len(group),rows,cols) fp32, pad value)."""
+        todo = sorted(todo, key=lambda t: t[1].shape[0])
         while todo:
             rows = max(todo[0][1].shape[0], 1)
             group = [todo.pop(0)]
@@ -288,25 +341,23 @@ class ICPWeightDataset(torch.utils.data.Dataset):
             rows = max(max(c.shape[0] for _, c in group), 1)
             # padding rows sit beyond every real coordinate (target_pad_val unless a map reaches that far)
             pad = max(float(self.target_pad_val), 2.0 * max([float(np.abs(c).max()) for _, c in group if c.size] + [0.0]))
-            batch = np.full((len(group), rows, 3), pad, dtype=np.float32)
+            batch = np.full((len(group), rows, group[0][1].shape[1]), pad, dtype=np.float32)
             for j, (_, c) in enumerate(group):
                 batch[j, :c.shape[0]] = c
-            if not torch.cuda.is_available():
-                from . import _lib
-                raise _lib.MmkError("ICPWeightDataset: %s holds xyz only and estimating its normals needs an MI355X/HIP "
-                                    "device" % (group[0][0][:-4] + "_xyz.bin"))
-            normals = estimate_normals(torch.from_numpy(batch).cuda(), k=k, dim=3, max_radius=radius, pad_val=pad).cpu().numpy()
-            for j, (path, c) in enumerate(group):
-                tmp = "%s.%d.%d.tmp" % (path, os.getpid(), threading.get_ident())
-                with open(tmp, "wb") as f:           # atomically: ranks of a multi-rank job may race for the same file
-                    f.write(np.ascontiguousarray(np.concatenate((c, normals[j, :c.shape[0]]), axis=1), dtype=np.float32).tobytes())
-                os.replace(tmp, path)
+            yield group, batch, pad
 
     @staticmethod
-    def _read_clouds(pdir, loc_stamp, map_stamp):
+    def _write_cloud(path, rows):
+        tmp = "%s.%d.%d.tmp" % (path, os.getpid(), threading.get_ident())
+        with open(tmp, "wb") as f:           # atomically: ranks of a multi-rank job may race for the same file
+            f.write(np.ascontiguousarray(rows, dtype=np.float32).tobytes())
+        os.replace(tmp, path)
+
+    @staticmethod
+    def _read_clouds(pdir, loc_stamp, map_stamp, map_suffix=""):
         raw = load_xyz_bin(os.path.join(pdir, "scan", "%d_raw.bin" % loc_stamp), 3)
         filt = load_xyz_bin(os.path.join(pdir, "scan", "%d_filt.bin" % loc_stamp), 3)
-        m = load_xyz_bin(os.path.join(pdir, "map", "%d.bin" % map_stamp), 6)
+        m = load_xyz_bin(os.path.join(pdir, "map", "%d%s.bin" % (map_stamp, map_suffix)), 6)
         return raw, filt, np.ascontiguousarray(m[:, :3]), np.ascontiguousarray(m[:, 3:6])
 
     def _cloud_sources(self, index):
@@ -314,7 +365,7 @@ class ICPWeightDataset(torch.utils.data.Dataset):
         pair_idx, loc_stamp, map_stamp = self.samples[index]
         pdir = self.pair_dirs[pair_idx]
         return [os.path.join(pdir, "scan", "%d_raw.bin" % loc_stamp), os.path.join(pdir, "scan", "%d_filt.bin" % loc_stamp),
-                os.path.join(pdir, "map", "%d.bin" % map_stamp)]
+                os.path.join(pdir, "map", "%d%s.bin" % (map_stamp, self._map_suffix))]
 
     @staticmethod
     def _to_sensor_frame(map_pts, map_norms, T):
@@ -326,7 +377,7 @@ class ICPWeightDataset(torch.utils.data.Dataset):
     def load_graph_data(self, idx, T_ml_gt):
         """icp_weight_dataset.py:364-400 with the clouds read from the export instead of the pose graph."""
         pair_idx, loc_stamp, map_stamp = self.samples[idx]
-        raw, filt, mp, mn = self._read_clouds(self.pair_dirs[pair_idx], loc_stamp, map_stamp)
+        raw, filt, mp, mn = self._read_clouds(self.pair_dirs[pair_idx], loc_stamp, map_stamp, self._map_suffix)
         scan_pc_raw = pad_scan(torch.from_numpy(raw), self.max_loc_pts, self.float_type)
         scan_pc_filt = pad_scan(torch.from_numpy(filt), self.max_loc_pts, self.float_type)
         mps, mns = self._to_sensor_frame(torch.from_numpy(mp), torch.from_numpy(mn), self.T_map_sensor_robot[pair_idx])
